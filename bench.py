@@ -2,14 +2,24 @@
 """bench.py -- the measurement contract of this repo.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--config 1|3|4|5] [--reflections] [--arith auto|host_sse|ieee] [--scaling strong|weak] [--rank0-share F]
-                  [--camera-path static|orbit|dolly]
+                  [--camera-path static|orbit|dolly] [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times EXACTLY K steps, writes the last step's outputs if `--dump-outputs DIR` is given, and prints the
+result line (metric, value, unit, ms_per_step, config).  Everything else this file measures or checks runs only with `--full`: the
+verification of the timed output (`verified`, `verification`), `cpu_baseline`, `roofline` (with the lone-frame latency, the same K steps
+with one frame per launch and in the other arithmetic), and at N > 1 the lone launch through the whole route and the ranks' self-audit.
+`--dump-outputs DIR` (rank 0): the arrays a caller of the timed path receives from its LAST step, as DIR/<name>.npy in float32 / float64
+-- t, u, v (float32), tri_id (float64) and hit (float32, 1 = hit) of the hit-record frame, a miss's t written as -1 instead of +inf so that
+every value is finite, or rgb (float32, [resy, resx, 3]) of the shaded frame -- at most 64 MB in all: a larger frame is written at a fixed,
+seeded sample of its pixels (pixel_index.npy = their row-major indices).  With the same
+arguments the inputs (scene, cameras) are the same in every run.
 Both forms work for N > 1: started WITHOUT torch.distributed.run (no WORLD_SIZE in the environment), `bench.py --gpus N` starts its own N ranks
 -- `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port <free> bench.py <same arguments>` as a CHILD
 process, before this process has imported torch or touched a GPU -- relays rank 0's JSON line and exits with the child's status.
 The documented multi-GPU sweep: N = 1, 2, 4, 8 with the defaults (throughput; several frames per launch and per collective) and again with
-`--frames-per-launch 1` (latency: one frame per launch and per collective); every N > 1 line carries `roofline`, `frames_in_flight` and the
-measured latency of a lone launch through the whole route (`config.lone_launch_ms`).
+`--frames-per-launch 1` (latency: one frame per launch and per collective); every N > 1 line carries `frames_in_flight`, and with `--full`
+`roofline` and the measured latency of a lone launch through the whole route (`config.lone_launch_ms`).
 
 A "step" is ONE FRAME through the hot path (RayGenerator + SafeInv + packet BVH traversal + ray/triangle
 intersection -> hit records), inputs (BVH, camera) resident in HBM before the timed region.
@@ -295,6 +305,56 @@ def weak_frame_size(n_gpus: int, res):
     return int(round(res[0] * s / 16.0)) * 16, int(round(res[1] * s / 8.0)) * 8
 
 
+DUMP_BYTES_MAX = 64_000_000   # --dump-outputs: at most this many bytes in all (.npy headers included)
+DUMP_SAMPLE_SEED = 20090501
+DUMP_SAMPLE_PIXELS = 1 << 20   # pixels kept of a frame whose arrays exceed DUMP_BYTES_MAX (4K: 1 M of 8.3 M)
+DUMP_MISS_T = -1.0             # t of a miss in the dump (the hit record holds +inf; hit.npy says which pixels hit)
+
+
+def hit_record_arrays(t, u, v, tri_id):
+    """The hit records of a frame as finite float32 / float64 arrays: t, u, v (float32; a miss's t = DUMP_MISS_T instead of +inf), tri_id
+    (float64, exact for every int32) and hit (float32: 1 where t is finite, else 0)."""
+    import numpy as np
+    hit = np.isfinite(t)
+    return {"t": np.where(hit, t, np.float32(DUMP_MISS_T)).astype(np.float32), "u": np.asarray(u, dtype=np.float32), "v": np.asarray(v, dtype=np.float32),
+            "tri_id": np.asarray(tri_id).astype(np.float64), "hit": hit.astype(np.float32)}
+
+
+def last_step_arrays(rnd):
+    """What a caller of the timed path receives from its last step (rank 0, after flush()), as finite numpy arrays in float32 / float64: the
+    hit-record frame (hit_record_arrays) or the shaded RGB8 frame (rgb, float32 [resy, resx, 3])."""
+    import numpy as np
+    if rnd.frame is not None:
+        f = rnd.frame
+        return hit_record_arrays(f.t.cpu().numpy(), f.u.cpu().numpy(), f.v.cpu().numpy(), f.tri_id.cpu().numpy())
+    return {"rgb": rnd.frame_rgb8.cpu().numpy().astype(np.float32)}
+
+
+def write_outputs(arrays, out_dir, max_bytes=DUMP_BYTES_MAX, sample_pixels=DUMP_SAMPLE_PIXELS, seed=DUMP_SAMPLE_SEED):
+    """--dump-outputs: arrays (name -> finite [resy, resx, ...] float32 / float64) as out_dir/<name>.npy.  If the files would exceed max_bytes
+    together, every array keeps the same fixed, seeded sample of `sample_pixels` pixels (sorted row-major indices, written as pixel_index.npy)
+    instead.  Returns {name: shape written}."""
+    import numpy as np
+    for k, a in arrays.items():
+        if a.dtype not in (np.float32, np.float64) or not np.isfinite(a).all():
+            raise ValueError("--dump-outputs: %s must be finite float32 / float64 (%s)" % (k, a.dtype))
+    header = 128                   # bytes of a .npy header (format 1.0) for these shapes
+    first = next(iter(arrays.values()))
+    npix = first.shape[0] * first.shape[1]
+    out = dict(arrays)
+    if sum(a.nbytes + header for a in out.values()) > max_bytes:
+        idx = np.sort(np.random.default_rng(seed).choice(npix, size=min(sample_pixels, npix), replace=False))
+        out = {k: np.ascontiguousarray(a).reshape((npix,) + a.shape[2:])[idx] for k, a in arrays.items()}
+        out["pixel_index"] = idx.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in out.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    written = sum(os.path.getsize(os.path.join(out_dir, k + ".npy")) for k in out)
+    if written > max_bytes:
+        raise ValueError("--dump-outputs: %d bytes written, more than %d" % (written, max_bytes))
+    return {k: list(a.shape) for k, a in out.items()}
+
+
 def cpu_baseline(tv, cam, resx, resy, digest_out=None):
     """Rank 0, N=1 only.  The ONLY place bench.py touches oracle/ -- as the reported CPU baseline: the oracle's primary path written four
     lanes wide with SSE intrinsics (oracle/snail_sse4.inc, one SSE quad per __m128 as the reference's f32x4 code runs; pinned bit-exactly to
@@ -355,7 +415,11 @@ def main():
     ap.add_argument("--arith", default="auto", choices=["auto", "ieee", "host_sse"], help="arithmetic of the path's approximate operations (include/snail_hip.h): host_sse = veclib's SSE definitions as this host's CPU executes them (rcpps / rsqrtps reproduced on the device + Newton), i.e. the reference's x86 results bit for bit -- the arithmetic north_star's parity bar is about; ieee = veclib's scalar definitions (host-independent results, ~2 %% faster); auto (default) = host_sse, or ieee on a host whose instructions cannot be tabulated (config.arith says which ran)")
     ap.add_argument("--arith-tables", default=None, help="with --arith host_sse: compute with the committed rcpps / rsqrtps tables of a NAMED CPU (tests/golden/rcp_tables.npz: xeon_skylake_sp, epyc_9575f; or a .npy file of uint32[3, 4096]) instead of this host's own -- the same bits on any host (snail_arith_set_tables)")
     ap.add_argument("--order-refresh", type=int, default=16, help="frames of a slot between two derivations of its dispatch order while the camera moves (DistributedRenderer order_refresh)")
+    ap.add_argument("--full", action="store_true", help="also verify the timed output and measure everything beside the headline: cpu_baseline, roofline (lone frames, one frame per launch, the other arithmetic), at N > 1 the lone launch and the ranks' self-audit; a plain run does none of it")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write what the timed path computed in its last step as DIR/<name>.npy (rank 0; finite float32 / float64, a miss's t as -1 beside hit.npy; at most 64 MB: a larger frame at a fixed, seeded sample of pixels)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # started as the plain command: become the launcher.  Nothing GPU-related has been imported or initialised in this process.
@@ -475,7 +539,7 @@ def main():
     # and the timed region -- several milliseconds of an almost idle GPU right before a 1.7 ms timed region, which then measured the part's clock ramp: on this
     # round's boxes the driver's 20-step command read 23.2-23.5 Grays/s that way and 26.0-26.3 when timed straight after warm frames)
     acc = pk = None
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and args.full:
         acc = scene.account_primary(cam, resx, resy)                      # single-ray accounting walk, informational
         pk = scene.packet_costs(cam, resx, resy)                          # per-packet {visits, ..., triangle records fetched, ...}
     barrier()
@@ -502,11 +566,13 @@ def main():
         settle_frames = max(rnd.batch, want // rnd.batch * rnd.batch)
         t1 = time.perf_counter()
         for i in range(settle_frames):
-            rnd.render(cam_at(3 * probe + i))
+            rnd.render(cam_at(3 * probe - settle_frames + i))
         rnd.flush()
         torch.cuda.synchronize()
         settle_measured_ms = (time.perf_counter() - t1) * 1e3
-    warm0 = settle_frames + (6 * rnd.nslots * rnd.batch if args.settle_ms > 0 else 0)     # the path goes on where the settle frames stopped
+    # the path goes on where the settle frames stopped, at a point that does not depend on their measured count: with the same arguments
+    # every run times (and dumps) the same views
+    warm0 = 6 * rnd.nslots * rnd.batch if args.settle_ms > 0 else 0
     # (what the timed loop needs is made BEFORE the warm-up steps, so that nothing but the barrier + synchronize stands between them and the timed region)
     every = -(-max(1, args.event_every) // rnd.batch) * rnd.batch
     ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) if i % every == 0 else None for i in range(args.steps)]
@@ -514,8 +580,9 @@ def main():
     for i in range(args.warmup):
         rnd.render(cam_at(warm0 + i))
     rnd.flush()
-    if rank == 0 and not rehearsal:
-        rnd.poison_outputs()      # what verify_outputs() hashes after the timed region was written INSIDE it: the settle / warm-up frames' results are gone
+    poisoned = rank == 0 and not rehearsal and (args.full or args.dump_outputs is not None)
+    if poisoned:
+        rnd.poison_outputs()      # what verify_outputs() hashes / --dump-outputs writes after the timed region was written INSIDE it: the settle / warm-up frames' results are gone
     barrier()
 
     # ---- timed region: EXACTLY K steps (frames are pipelined over the renderer's HIP streams, see DistributedRenderer) ----
@@ -533,16 +600,19 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
     # ---- what the timed region produced (rank 0), before anything else overwrites the renderer's buffers ----
+    dumped = None
+    if rank == 0 and args.dump_outputs is not None:
+        dumped = write_outputs(last_step_arrays(rnd), args.dump_outputs)
     verify = None
-    if len(path) > 1:    # a moving camera: every slot holds another view -- send one more round of the FIXED view through the same renderer (same
+    if args.full and len(path) > 1:    # a moving camera: every slot holds another view -- send one more round of the FIXED view through the same renderer (same
         for _ in range(rnd.nslots * rnd.batch):      # launch form, the dispatch orders it has arrived at) and check that, after the clock has stopped
             rnd.render(cam)
         rnd.flush()
         barrier()
     vkey = "%d%s" % (args.config, "r" if (args.reflections and cfg["lights"]) else "")
-    if rank == 0:
+    if rank == 0 and args.full:
         verify = verify_outputs(rnd, scene_name, resx, resy, vkey, args.arith, cfg["lights"])
-        verify["buffers_poisoned_before_timed_region"] = not rehearsal      # (DistributedRenderer.poison_outputs: nothing a settle / warm-up frame wrote survives into this check)
+        verify["buffers_poisoned_before_timed_region"] = poisoned      # (DistributedRenderer.poison_outputs: nothing a settle / warm-up frame wrote survives into this check)
         verify["what"] = ("one more round of the fixed view through the timed renderer after the timed region (the timed frames each hold another view)" if len(path) > 1
                           else "the last frame each slot traced inside the timed region")
     timed = [e for e in ev if e is not None]
@@ -557,7 +627,7 @@ def main():
     # ---- one launch at a time through the whole route (N > 1): trace -> gather -> scatter of `frames_per_launch` frames with nothing
     # else in flight, host clock of rank 0 between a barrier and the completed frame -- the latency side of the throughput figure ----
     lone_launch_ms = None
-    if world > 1 and args.lone_frames > 0:
+    if args.full and world > 1 and args.lone_frames > 0:
         ts = []
         for _ in range(args.lone_frames):
             barrier()
@@ -574,7 +644,7 @@ def main():
     # collectives use), the GPU each rank sits on (distinct UUIDs unless this is the one-GPU rehearsal), whether every rank's renderer
     # switches streams the fast way, and the collective alone (rank 0's inbound bytes / time) ----
     audit = None
-    if world > 1:
+    if args.full and world > 1:
         one = torch.ones(1, dtype=torch.int64, device="cpu" if rehearsal else torch.device("cuda", local_rank))
         dist.all_reduce(one)
         props = torch.cuda.get_device_properties(local_rank)
@@ -589,7 +659,7 @@ def main():
 
     # ---- one frame at a time (N = 1): the latency a frame has when nothing else is in flight ----
     lone_ms = None
-    if rank == 0 and world == 1 and args.lone_frames > 0:
+    if args.full and rank == 0 and world == 1 and args.lone_frames > 0:
         ts = []
         for _ in range(args.lone_frames):
             torch.cuda.synchronize()
@@ -602,7 +672,7 @@ def main():
 
     # ---- the same K steps with ONE frame per launch (N = 1, when the timed region used several): the rate without the batching ----
     fpl1 = None
-    if rank == 0 and world == 1 and rnd.batch > 1 and args.lone_frames > 0:
+    if args.full and rank == 0 and world == 1 and rnd.batch > 1 and args.lone_frames > 0:
         r1 = DistributedRenderer(scene, resx, resy, 0, 1, slots=rnd.nslots, feedback_order=bool(args.feedback_order),
                                  frames_per_launch=1, order_refresh=args.order_refresh)
         for i in range(max(8, settle_frames + args.warmup)):      # the same settle + warm-up as the timed region had
@@ -620,7 +690,7 @@ def main():
 
     # ---- the same K steps in the OTHER arithmetic (N = 1): both modes' rates in one line ----
     other = None
-    if rank == 0 and world == 1 and args.lone_frames > 0:
+    if args.full and rank == 0 and world == 1 and args.lone_frames > 0:
         other_name = "host_sse" if args.arith == "ieee" else "ieee"
         try:
             scene.set_arith(other_name)
@@ -646,45 +716,47 @@ def main():
         ms_per_step = elapsed * 1e3 / args.steps
         step_s = ms_per_step * 1e-3
         value = total_rays * args.steps / elapsed / 1e6
-        key = "%s_%dx%d_n%d_c%d%s%s" % (scene_name, resx, resy, world, args.config, "r" if (args.reflections and cfg["lights"]) else "", "_sse" if args.arith == "host_sse" else "")
-        tr = pmc_counters(key)
-        shared_note = ""
-        if tr is None and world > 1 and args.scaling == "strong":
-            # N ranks share the SAME frame: its counters are those of the one-GPU pass of this workload (the walk of a packet does not depend
-            # on which rank traces it; the depth-shading epilogue of the tile route adds < 1 % vector instructions), priced against N GPUs' peak
-            tr = pmc_counters("%s_%dx%d_n1_c%d%s%s" % (scene_name, resx, resy, args.config, "r" if (args.reflections and cfg["lights"]) else "", "_sse" if args.arith == "host_sse" else ""))
-            shared_note = " [N = %d: the frame's counters from the one-GPU pass, peak = %d x one GPU's]" % (world, world)
-        valu = tr.get("valu_insts_per_launch") if tr else None
-        traffic = tr.get("bytes_per_launch") if tr else None
-        peak_ginst = VALU_PEAK_GINST * world
-        hbm_peak = HBM_PEAK_GBS * world
-        roof = {"bound": "valu_issue", "achieved": round(valu / step_s / 1e9, 1) if valu else None, "peak": round(peak_ginst, 1), "unit": "Gwaveinst/s",
-                "frac": round(valu / step_s / 1e9 / peak_ginst, 4) if valu else None,
-                "counters_stale": bool(tr.get("_stale")) if tr else None,
-                # what a SIMD of this part sustains on the visit's own instruction mix at 6 waves (tools/micro/visit_rate.hip: 118-121 cycles per
-                # 47-instruction visit; pure v_fma_f32 / v_mul_f32 streams 2.45-2.65 cycles per instruction, tools/micro/valu_banks.hip)
-                "frac_of_measured_issue_rate": round(valu / step_s / 1e9 / (peak_ginst * 2.0 / VALU_CYCLES_MEASURED), 4) if valu else None,
-                "measured_issue_rate_note": "peak above = one wave64 VALU instruction per 2 cycles per SIMD (MI355X_MICROARCH.md); measured on this part: one per %.1f cycles (profiles/r3_valu_microbench.txt)" % VALU_CYCLES_MEASURED,
-                "traffic": traffic * rnd.batch if traffic else None,
-                "traffic_unit": "HBM bytes per launch of %d frame(s) (rocprofv3 PMC of a one-frame launch: 2 x FETCH_SIZE + WRITE_SIZE, x frames per launch)" % rnd.batch,
-                "frames_per_launch": rnd.batch, "traffic_bytes_per_frame": traffic,
-                "hbm_peak_GBs": hbm_peak, "hbm_frac_traffic": round(traffic / step_s / 1e9 / hbm_peak, 4) if traffic else None,
-                "valu_insts_per_launch": valu * rnd.batch if valu else None, "valu_insts_per_frame": valu,
-                "lanes_live_per_valu_inst": tr.get("lanes_live_per_valu_inst") if tr else None, "kernels": tr.get("kernels") if tr else None, "counters_source": (tr.get("source") + shared_note) if tr else "no PMC pass committed for workload key %s" % key,
-                "kernel": tr.get("kernel", "dev::k_primary") if tr else "dev::k_primary", "kernel_ms": round(kern_ms, 5), "kernel_ms_note": "HIP events around one launch (%d frame(s)) on its own stream while %d launches are in flight: overlapped, not a stand-alone duration; every fraction here uses ms_per_step (per frame) and per-frame counters" % (rnd.batch, rnd.nslots),
-                "denominator_ms": round(ms_per_step, 5), "lone_frame_ms": round(lone_ms, 5) if lone_ms is not None else None,
-                "one_frame_per_launch": fpl1, "other_arith": other}
-        if pk is not None:
-            visits, fetched = int(pk[:, 0].sum()), int(pk[:, 4].sum())
-            pbytes = 32 * visits + 64 * fetched + 16 * 256 * len(pk)
-            roof.update({"packet_alg_bytes_per_launch": pbytes * rnd.batch, "packet_alg_bytes_per_frame": pbytes, "packet_node_visits": visits, "packet_tri_records_fetched": fetched,
-                         "hbm_frac_packet_alg": round(pbytes / step_s / 1e9 / hbm_peak, 4),
-                         "compulsory_bytes_per_frame": 32 * hbvh.n_nodes + 64 * hbvh.n_tris + 16 * primary_rays})
-        if acc is not None:
-            b_alg = (32.0 * float(acc[1]) + 64.0 * float(acc[2])) / float(acc[0]) + 16.0
-            roof.update({"alg_single_ray_bytes_per_ray": round(b_alg, 1),
-                         "alg_single_ray_frac_of_hbm_peak": round(primary_rays * b_alg / step_s / 1e9 / hbm_peak, 4),
-                         "alg_single_ray_note": "SURVEY 8(d)'s single-ray cache-less bytes; the packet kernel fetches a node once per 256 rays, so this is informational and may exceed 1"})
+        roof = None
+        if args.full:      # priced with the committed PMC counters of this workload (profiles/traffic.json) and the diagnostic passes above
+            key = "%s_%dx%d_n%d_c%d%s%s" % (scene_name, resx, resy, world, args.config, "r" if (args.reflections and cfg["lights"]) else "", "_sse" if args.arith == "host_sse" else "")
+            tr = pmc_counters(key)
+            shared_note = ""
+            if tr is None and world > 1 and args.scaling == "strong":
+                # N ranks share the SAME frame: its counters are those of the one-GPU pass of this workload (the walk of a packet does not depend
+                # on which rank traces it; the depth-shading epilogue of the tile route adds < 1 % vector instructions), priced against N GPUs' peak
+                tr = pmc_counters("%s_%dx%d_n1_c%d%s%s" % (scene_name, resx, resy, args.config, "r" if (args.reflections and cfg["lights"]) else "", "_sse" if args.arith == "host_sse" else ""))
+                shared_note = " [N = %d: the frame's counters from the one-GPU pass, peak = %d x one GPU's]" % (world, world)
+            valu = tr.get("valu_insts_per_launch") if tr else None
+            traffic = tr.get("bytes_per_launch") if tr else None
+            peak_ginst = VALU_PEAK_GINST * world
+            hbm_peak = HBM_PEAK_GBS * world
+            roof = {"bound": "valu_issue", "achieved": round(valu / step_s / 1e9, 1) if valu else None, "peak": round(peak_ginst, 1), "unit": "Gwaveinst/s",
+                    "frac": round(valu / step_s / 1e9 / peak_ginst, 4) if valu else None,
+                    "counters_stale": bool(tr.get("_stale")) if tr else None,
+                    # what a SIMD of this part sustains on the visit's own instruction mix at 6 waves (tools/micro/visit_rate.hip: 118-121 cycles per
+                    # 47-instruction visit; pure v_fma_f32 / v_mul_f32 streams 2.45-2.65 cycles per instruction, tools/micro/valu_banks.hip)
+                    "frac_of_measured_issue_rate": round(valu / step_s / 1e9 / (peak_ginst * 2.0 / VALU_CYCLES_MEASURED), 4) if valu else None,
+                    "measured_issue_rate_note": "peak above = one wave64 VALU instruction per 2 cycles per SIMD (the part's documented issue rate); measured on this part: one per %.1f cycles (profiles/r3_valu_microbench.txt)" % VALU_CYCLES_MEASURED,
+                    "traffic": traffic * rnd.batch if traffic else None,
+                    "traffic_unit": "HBM bytes per launch of %d frame(s) (rocprofv3 PMC of a one-frame launch: 2 x FETCH_SIZE + WRITE_SIZE, x frames per launch)" % rnd.batch,
+                    "frames_per_launch": rnd.batch, "traffic_bytes_per_frame": traffic,
+                    "hbm_peak_GBs": hbm_peak, "hbm_frac_traffic": round(traffic / step_s / 1e9 / hbm_peak, 4) if traffic else None,
+                    "valu_insts_per_launch": valu * rnd.batch if valu else None, "valu_insts_per_frame": valu,
+                    "lanes_live_per_valu_inst": tr.get("lanes_live_per_valu_inst") if tr else None, "kernels": tr.get("kernels") if tr else None, "counters_source": (tr.get("source") + shared_note) if tr else "no PMC pass committed for workload key %s" % key,
+                    "kernel": tr.get("kernel", "dev::k_primary") if tr else "dev::k_primary", "kernel_ms": round(kern_ms, 5), "kernel_ms_note": "HIP events around one launch (%d frame(s)) on its own stream while %d launches are in flight: overlapped, not a stand-alone duration; every fraction here uses ms_per_step (per frame) and per-frame counters" % (rnd.batch, rnd.nslots),
+                    "denominator_ms": round(ms_per_step, 5), "lone_frame_ms": round(lone_ms, 5) if lone_ms is not None else None,
+                    "one_frame_per_launch": fpl1, "other_arith": other}
+            if pk is not None:
+                visits, fetched = int(pk[:, 0].sum()), int(pk[:, 4].sum())
+                pbytes = 32 * visits + 64 * fetched + 16 * 256 * len(pk)
+                roof.update({"packet_alg_bytes_per_launch": pbytes * rnd.batch, "packet_alg_bytes_per_frame": pbytes, "packet_node_visits": visits, "packet_tri_records_fetched": fetched,
+                             "hbm_frac_packet_alg": round(pbytes / step_s / 1e9 / hbm_peak, 4),
+                             "compulsory_bytes_per_frame": 32 * hbvh.n_nodes + 64 * hbvh.n_tris + 16 * primary_rays})
+            if acc is not None:
+                b_alg = (32.0 * float(acc[1]) + 64.0 * float(acc[2])) / float(acc[0]) + 16.0
+                roof.update({"alg_single_ray_bytes_per_ray": round(b_alg, 1),
+                             "alg_single_ray_frac_of_hbm_peak": round(primary_rays * b_alg / step_s / 1e9 / hbm_peak, 4),
+                             "alg_single_ray_note": "SURVEY 8(d)'s single-ray cache-less bytes; the packet kernel fetches a node once per 256 rays, so this is informational and may exceed 1"})
         if rnd.frame is not None:
             hit_frac = float(torch.isfinite(rnd.frame.t).float().mean().item())
         else:
@@ -716,13 +788,16 @@ def main():
                        "traversal_stack": "VGPR pair per wave (lane i = slot i), at most bvh_depth = %d slots; LDS 0 B/wave in the main kernel (3328 B/wave only in the deferred M_EXACT pass)" % hbvh.depth,
                        "packets_per_rank": [len(p) for p in rnd.plan.packets] if world > 1 else None,
                        "parallelism": par},
-            "roofline": roof,
-            "verified": verify.get("verified") if verify else None, "verification": verify,
+            "full": bool(args.full),
         }
+        if dumped is not None:
+            out["outputs_dumped"] = {"dir": args.dump_outputs, "arrays": dumped, "what": "the last timed step's " + ("hit records" if "t" in dumped else "shaded frame")}
+        if args.full:
+            out.update({"roofline": roof, "verified": verify.get("verified") if verify else None, "verification": verify})
         scalar_digest = {}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(tv, cam, resx, resy, digest_out=scalar_digest)
-        else:
+        elif args.full:
             out["cpu_baseline"] = None
         if verify is not None and not args.no_live_check:
             verify = live_oracle_check(verify, tv, cam, resx, resy, args.arith, args.arith_tables, lights7, bool(args.reflections and cfg["lights"]), scalar_digest or None)

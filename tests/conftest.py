@@ -1,8 +1,6 @@
 import os
 import sys
 
-import pytest
-
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
@@ -15,12 +13,3 @@ def pytest_configure(config):
     if not all(os.path.exists(p) for p in need):
         import __graft_entry__
         __graft_entry__.build()
-
-
-@pytest.fixture(scope="session")
-def reference_scenes():
-    """Directory of the reference's OBJ assets; only present in the build container (never on the GPU box)."""
-    p = "/root/reference/scenes"
-    if not os.path.isdir(p):
-        pytest.skip("reference checkout not present")
-    return p

@@ -322,7 +322,7 @@ def test_bench_checks_itself_on_a_cpu_without_committed_digests(torch_mod, tmp_p
     f = str(tmp_path / "nobody.npy")
     np.save(f, tabs)
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
-    base = [sys.executable, os.path.join(root, "bench.py"), "--steps", "8", "--warmup", "2", "--settle-ms", "0", "--no-cpu-baseline", "--lone-frames", "0", "--arith", "host_sse"]
+    base = [sys.executable, os.path.join(root, "bench.py"), "--steps", "8", "--warmup", "2", "--settle-ms", "0", "--full", "--no-cpu-baseline", "--lone-frames", "0", "--arith", "host_sse"]
     r = subprocess.run(base + ["--arith-tables", f], capture_output=True, text=True, timeout=300, cwd=root, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])

@@ -807,7 +807,7 @@ def test_two_rank_bench_rehearsal(torch_mod, extra, scaling, res):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     full = "FULL" in extra          # the bench's own scene (263 K triangles) instead of the small one: the gathered frame is then checked against the committed digest
     extra = [e for e in extra if e != "FULL"]
-    tail = ["--gpus", "2", "--steps", "6", "--warmup", "2", "--backend", "gloo"] + ([] if full else ["--scene", "atrium:0.05"]) + extra
+    tail = ["--gpus", "2", "--steps", "6", "--warmup", "2", "--backend", "gloo", "--full"] + ([] if full else ["--scene", "atrium:0.05"]) + extra
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     if extra in ([], ["--frames-per-launch", "1"], ["--arith", "ieee"]):
         # the PLAIN command, as the driver's scaling run issues it: bench.py starts its own two ranks (a child torch.distributed.run)
@@ -849,6 +849,56 @@ def test_two_rank_bench_rehearsal(torch_mod, extra, scaling, res):
         assert d["config"]["arith"] == ("ieee" if "--arith" in extra else "host_sse")      # the default arithmetic is the reference's own
     else:
         assert d["verification"].get("committed") is None and "no committed digest" in d["verification"]["note"]
+
+
+def _bench_json(root, args):
+    import json
+    import subprocess
+    import sys
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + args, capture_output=True, text=True, timeout=300, cwd=root, env=env)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    return json.loads(lines[0])
+
+
+def test_bench_plain_run_dumps_the_last_step(torch_mod, tmp_path):
+    """A plain bench.py run (no --full) times exactly --steps steps and reports only the headline; --dump-outputs DIR holds the hit records
+    the last timed step returned (the buffers are poisoned before the timed region), bit-equal to the oracle's frame of that view."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = tmp_path / "dump"
+    d = _bench_json(root, ["--gpus", "1", "--steps", "7", "--warmup", "2", "--scene", "atrium:0.05", "--arith", "ieee", "--dump-outputs", str(out)])
+    assert d["steps"] == 7 and d["warmup"] == 2 and d["n_gpus"] == 1 and d["full"] is False
+    assert d["metric"] == "Mrays/sec (primary)" and d["unit"] == "Mrays/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["ms_per_step"] > 0 and d["value"] == pytest.approx(d["config"]["rays_per_step"] / d["ms_per_step"] / 1e3, rel=0.01)
+    assert not any(k in d for k in ("roofline", "verified", "verification", "cpu_baseline")) and d["config"]["lone_launch_ms"] is None
+    assert sorted(os.listdir(str(out))) == ["hit.npy", "t.npy", "tri_id.npy", "u.npy", "v.npy"]
+    got = {k: np.load(str(out / (k + ".npy"))) for k in ("t", "u", "v", "tri_id", "hit")}
+    assert [got[k].dtype for k in ("t", "u", "v", "tri_id", "hit")] == [np.float32] * 3 + [np.float64, np.float32]
+    assert all(np.isfinite(a).all() for a in got.values())
+    tv = scenes.scene_by_name("atrium:0.05")
+    osc = O.OracleScene(tv)
+    t, u, v, tid, _ = osc.render_primary(util.camera_for("atrium:0.05", tv).as_array13(), 1920, 1080, mode=O.MODE_IEEE, threads=8)
+    hit = np.isfinite(t)
+    assert hit.any() and not hit.all() and np.array_equal(got["hit"], hit.astype(np.float32))
+    util.assert_bit_equal(got["t"], np.where(hit, t, np.float32(-1.0)).astype(np.float32), "dumped t (a miss = -1)")
+    for a, b, n in ((got["u"], u, "u"), (got["v"], v, "v")):
+        util.assert_bit_equal(a, b, "dumped " + n)
+    assert np.array_equal(got["tri_id"], tid.astype(np.float64))
+
+
+def test_bench_dumps_the_same_views_whatever_the_settle_count(torch_mod, tmp_path):
+    """With the same arguments a moving camera's timed views -- and so the dumped last step -- do not depend on how many untimed settle frames
+    the run measured it needed: two runs with different --settle-ms write the same arrays."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    common = ["--gpus", "1", "--steps", "5", "--warmup", "3", "--camera-path", "orbit", "--arith", "ieee"]
+    a = _bench_json(root, common + ["--settle-ms", "2", "--dump-outputs", str(tmp_path / "a")])
+    b = _bench_json(root, common + ["--settle-ms", "40", "--dump-outputs", str(tmp_path / "b")])
+    assert a["config"]["camera_path"] == b["config"]["camera_path"] == "orbit" and a["config"]["settle_frames"] < b["config"]["settle_frames"]
+    for k in ("t", "u", "v", "tri_id", "hit"):
+        x, y = np.load(str(tmp_path / "a" / (k + ".npy"))), np.load(str(tmp_path / "b" / (k + ".npy")))
+        assert x.shape == (1080, 1920) and np.array_equal(x.view(np.uint8), y.view(np.uint8)), k
 
 
 def test_rccl_code_path_single_rank(torch_mod):

@@ -147,8 +147,12 @@ f -5 -4 -1
     assert np.array_equal(sw, want[:, [1, 0, 2]][:, :, [0, 2, 1]])
 
 
-def test_box_restatement_matches_reference_asset(reference_scenes):
-    assert np.array_equal(scenes.load_obj(os.path.join(reference_scenes, "box.obj")), scenes.box_scene())
+def test_box_restatement_matches_reference_asset():
+    # tests/golden/box_tris.npz: the reference's scenes/box.obj as scenes.load_obj reads it (the post-ingest triangle soup, as the
+    # <name>_tris.npz fixtures of tests/golden/make_ref_mesh_fixture.py)
+    tv = np.load(os.path.join(ROOT, "tests", "golden", "box_tris.npz"))["tris"]
+    assert tv.dtype == np.float32 and tv.shape == (12, 3, 3)
+    assert np.array_equal(tv.view(np.uint32), scenes.box_scene().view(np.uint32))
 
 
 def test_tile_plan_partitions_the_frame():
@@ -357,6 +361,54 @@ def test_counters_carry_the_kernel_hash():
     assert re.fullmatch(r"[0-9a-f]{16}", d.get("_kernel_sha16", "")), "tools/make_traffic.py stores _kernel_sha16"
     tr = b.pmc_counters("atrium_1920x1080_n1_c1")
     assert tr is not None and tr["_stale"] == (d["_kernel_sha16"] != b.kernel_source_sha16())
+
+
+def test_bench_dump_outputs_stay_within_budget(tmp_path):
+    """bench.py --dump-outputs writes what the timed path returned as <name>.npy, every value finite (a miss's t = -1 beside a hit mask instead of
+    +inf): a 1080p hit-record frame whole, a 4K one at a fixed, seeded sample of pixels -- the same pixels in every array and in every run --
+    within 64 MB of files; arrays holding a non-finite value are refused."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    rng = np.random.RandomState(5)
+
+    def frame(resx, resy):
+        t = rng.rand(resy, resx).astype(np.float32)
+        t[::7] = np.inf
+        tid = rng.randint(0, 1 << 20, size=(resy, resx)).astype(np.int32)
+        rec = b.hit_record_arrays(t, rng.rand(resy, resx).astype(np.float32), rng.rand(resy, resx).astype(np.float32), tid)
+        assert sorted(rec) == ["hit", "t", "tri_id", "u", "v"] and all(np.isfinite(a).all() for a in rec.values())
+        assert np.array_equal(rec["hit"], np.isfinite(t).astype(np.float32)) and np.all(rec["t"][::7] == b.DUMP_MISS_T)
+        assert np.array_equal(rec["t"][np.isfinite(t)], t[np.isfinite(t)]) and np.array_equal(rec["tri_id"], tid.astype(np.float64))
+        return rec
+
+    def size(d):
+        return sum(os.path.getsize(str(d / n)) for n in os.listdir(str(d)))
+
+    small = frame(1920, 1080)
+    assert b.write_outputs(small, str(tmp_path / "small")) == {k: [1080, 1920] for k in small}
+    assert size(tmp_path / "small") <= 64 * 10 ** 6
+    for k, a in small.items():
+        got = np.load(str(tmp_path / "small" / (k + ".npy")))
+        assert got.dtype == a.dtype and np.array_equal(got, a)
+    big = frame(3840, 2160)
+    shapes = b.write_outputs(big, str(tmp_path / "big"))
+    b.write_outputs(big, str(tmp_path / "again"))
+    names = sorted(os.listdir(str(tmp_path / "big")))
+    assert names == ["hit.npy", "pixel_index.npy", "t.npy", "tri_id.npy", "u.npy", "v.npy"] and shapes["t"] == [b.DUMP_SAMPLE_PIXELS]
+    assert size(tmp_path / "big") <= 64 * 10 ** 6
+    got = {n[:-4]: np.load(str(tmp_path / "big" / n)) for n in names}
+    assert all(np.isfinite(a).all() for a in got.values())
+    idx = got["pixel_index"].astype(np.int64)
+    assert np.array_equal(idx.astype(np.float64), got["pixel_index"]) and idx[0] >= 0 and idx[-1] < 3840 * 2160 and np.all(np.diff(idx) > 0)
+    for k, a in big.items():
+        assert got[k].dtype == a.dtype and np.array_equal(got[k], a.reshape(-1)[idx])
+    for n in names:
+        assert np.array_equal(np.load(str(tmp_path / "again" / n)), got[n[:-4]])
+    bad = dict(small, u=np.where(small["hit"] > 0, small["u"], np.float32(np.nan)).astype(np.float32))
+    with pytest.raises(ValueError):
+        b.write_outputs(bad, str(tmp_path / "bad"))
 
 
 def test_host_sse_tables_reproduce_this_cpus_rcpps_and_rsqrtps():

@@ -20,7 +20,7 @@ run() { # variant, bench arguments...
   local v=$1; shift
   local L="SNAIL_AB=1" F=""
   case $v in product) ;; none) F="--feedback-order 0" ;; *) L="SNAIL_LIB_PATH=$PWD/snail_amd/exp/lib_$v.so" ;; esac
-  env $L timeout -k 10 200 python bench.py $PRE "$@" $F --no-cpu-baseline $TAILFLAGS 2>/dev/null |
+  env $L timeout -k 10 200 python bench.py --full $PRE "$@" $F --no-cpu-baseline $TAILFLAGS 2>/dev/null |
     python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$R $v [$PRE $*]', d['value'], d['ms_per_step'], 'lone', d['roofline'].get('lone_frame_ms'), d['verified'])"
 }
 C3="--config 3 --steps 800"; C3R="--config 3 --reflections --steps 300"; C4="--config 4 --steps 800"; C5="--config 5 --steps 800"

@@ -7,7 +7,7 @@ O=gpurun_out/r5_far; mkdir -p $O
 for v in far0 far1; do
   for c in "--config 1" "--config 5" "--config 3 --reflections"; do
     tag=$(echo $c | tr -d " -")
-    SNAIL_DEBUG_FORCE_DEEP=1 SNAIL_LIB_PATH=$PWD/snail_amd/exp/lib_$v.so timeout -k 10 300 python bench.py $c --steps 400 --warmup 50 --no-cpu-baseline --lone-frames 0 --arith ieee > $O/${v}_$tag.json 2> $O/${v}_$tag.err || echo "FAILED $v $c"
+    SNAIL_DEBUG_FORCE_DEEP=1 SNAIL_LIB_PATH=$PWD/snail_amd/exp/lib_$v.so timeout -k 10 300 python bench.py --full $c --steps 400 --warmup 50 --no-cpu-baseline --lone-frames 0 --arith ieee > $O/${v}_$tag.json 2> $O/${v}_$tag.err || echo "FAILED $v $c"
   done
 done
 python - <<PY

@@ -32,7 +32,7 @@ traffic)
     atrium_1920x1080_n1_c3r=profiles/r5_final_whitted_refl_pmc_summary.txt:frames=6 atrium_1920x1080_n1_c3r_sse=profiles/r5_final_host_sse_whitted_refl_pmc_summary.txt:frames=6
   ;;
 bench)
-  b() { local name=$1; shift; timeout -k 10 400 python bench.py "$@" > $O/bench_$name.json 2> $O/bench_$name.err || { echo "bench $name FAILED"; tail -5 $O/bench_$name.err; }; }
+  b() { local name=$1; shift; timeout -k 10 400 python bench.py --full "$@" > $O/bench_$name.json 2> $O/bench_$name.err || { echo "bench $name FAILED"; tail -5 $O/bench_$name.err; }; }
   for i in 1 2 3; do b steps20_$i --steps 20 --warmup 5; done
   b default
   b ieee --no-cpu-baseline --arith ieee
@@ -60,14 +60,14 @@ prof)
     ( cd /tmp && timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $GRAFT_REPO_ROOT/$O/prof -- "$@" > $GRAFT_REPO_ROOT/$O/prof_$name.log 2>&1 )
     find $O/prof -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $O/r5_final_${name}_kernel_stats.csv; head -6 $O/r5_final_${name}_kernel_stats.csv; rm -rf $O/prof
   }
-  prof default python3 $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline
-  prof steps20 python3 $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --steps 20 --warmup 5
-  prof ieee python3 $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --arith ieee
-  prof orbit python3 $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --camera-path orbit
-  prof dolly python3 $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --camera-path dolly
-  prof stress python3 $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --config 5 --steps 400
-  prof config3 python3 $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --config 3 --steps 400
-  GPU_MAX_HW_QUEUES=16 prof config3_refl python3 $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --config 3 --reflections --steps 200   # (bench.py's own choice for this workload, made before the profiler's library starts HIP)
+  prof default python3 $PWD/bench.py --full --no-cpu-baseline
+  prof steps20 python3 $PWD/bench.py --full --no-cpu-baseline --steps 20 --warmup 5
+  prof ieee python3 $PWD/bench.py --full --no-cpu-baseline --arith ieee
+  prof orbit python3 $PWD/bench.py --full --no-cpu-baseline --camera-path orbit
+  prof dolly python3 $PWD/bench.py --full --no-cpu-baseline --camera-path dolly
+  prof stress python3 $PWD/bench.py --full --no-cpu-baseline --config 5 --steps 400
+  prof config3 python3 $PWD/bench.py --full --no-cpu-baseline --config 3 --steps 400
+  GPU_MAX_HW_QUEUES=16 prof config3_refl python3 $PWD/bench.py --full --no-cpu-baseline --config 3 --reflections --steps 200   # (bench.py's own choice for this workload, made before the profiler's library starts HIP)
   ;;
 *) echo "usage: bash tools/r5_final.sh pmc_ieee|pmc_host_sse|pmc|traffic|bench|prof"; exit 1;;
 esac
