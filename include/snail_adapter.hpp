@@ -16,6 +16,10 @@
 //                                     unit of the reference, after "render.h"), `Render(...)` overloads with EXACTLY the reference's two
 //                                     signatures are declared for Scene<snail::HipBVH<...>>: more specialised than the reference's
 //                                     templates, so existing call sites (src/node.cpp:336-338, src/rtracer.cpp:385-386) pick them.
+//   class snail::HipDBVH           -- the concept's second model, the reference's two-level DBVH (src/dbvh/tree.h): its elements' BLASes
+//                                     uploaded as HipBVH handles, its own nodes / elements passed through snail_instances_create
+//                                     (include/snail_instances.h); the same prefetched / immediate modes as HipBVH, and Render(...) overloads
+//                                     for Scene<snail::HipDBVH<...>> that make depth images on the device.
 //   snail::ShadowBatch / RayBatch  -- the batched form of the immediate path: collect the shadow / secondary packets of a tile,
 //                                     trace them with ONE snail_trace_shadow / snail_trace_rays call (nPackets), results copied back.
 //
@@ -42,12 +46,16 @@
 
 #include <atomic>
 #include <cstdint>
+#include <memory>
+#include <type_traits>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <map>
 #include <vector>
 
 #include "snail_hip.h"
+#include "snail_instances.h"
 
 #ifndef SNAIL_CHECK
 #define SNAIL_CHECK(expr)                                                                              \
@@ -207,6 +215,176 @@ private:
 	mutable bool haveFrame = false;
 	mutable std::atomic<bool> statsPending{false};
 	static inline thread_local long curPacket = -1;   // per render thread (thread_pool workers, src/thread_pool.cpp)
+};
+
+namespace detail {
+// the BLAS type of an instance record (void for any other element type: the overloads below are then never viable, and nothing of them
+// is instantiated for a HipBVH scene)
+template <class E, class = void> struct TreeOf { typedef void type; };
+template <class E> struct TreeOf<E, std::void_t<decltype(std::declval<E>().tree)>> {
+	typedef typename std::remove_cv<typename std::remove_pointer<decltype(std::declval<E>().tree)>::type>::type type;
+};
+} // namespace detail
+
+// The second model of the AccStruct concept: the reference's `DBVH` (src/dbvh/tree.h:97-150) -- rigid `ObjectInstance`s (rotation rows,
+// translation, `const BVH *tree`) under a top-level tree.  Upload() maps each distinct elements[i].tree to an uploaded HipBVH handle and
+// passes the DBVH's own `nodes` and `elements` (in their order: the instance id a hit reports is the element's index) through
+// snail_instances_create; Update() hands the tree the host rebuilt for the next frame (the reference's -instances mode rebuilds it every
+// frame, src/rtracer.cpp:359-386) to snail_instances_update.  The uploaded BLASes live as long as this object.
+template <class RefDBVH>
+class HipDBVH {
+public:
+	typedef typename RefDBVH::CElement CElement;
+	typedef typename RefDBVH::SElement SElement;
+	typedef typename detail::TreeOf<CElement>::type RefBVH;   // the reference's BVH (ObjectInstance::tree, src/dbvh/tree.h:185)
+	enum { isComplex = 1 };
+	enum { isctFlags = RefDBVH::isctFlags };
+	enum { maxDepth = RefDBVH::maxDepth };
+
+	HipDBVH() = default;
+	~HipDBVH() { Release(); }
+	HipDBVH(const HipDBVH &) = delete;
+	HipDBVH &operator=(const HipDBVH &) = delete;
+
+	// Call after the DBVH was constructed (the top-level build stays on the host, src/dbvh/tree.cpp:158-172).
+	void Upload(const RefDBVH &dbvh, int device = 0) {
+		Release();
+		ref = &dbvh;
+		this->device = device;
+		std::vector<float> xf;
+		std::vector<int32_t> bi;
+		Elements(dbvh, xf, bi);
+		std::vector<SnailScene *> hs;
+		for(auto &b : blas) hs.push_back(b->Handle());
+		inst = snail_instances_create(hs.data(), (int)hs.size(), dbvh.nodes.data(), (int)dbvh.nodes.size(), xf.data(), bi.data(), (int)bi.size(), 0);
+		if(!inst) { std::fprintf(stderr, "FATAL: snail_instances_create: %s\n", snail_last_error()); std::abort(); }
+		if(arith != SNAIL_ARITH_IEEE && !SetArith(arith)) { std::fprintf(stderr, "FATAL: HipDBVH::Upload: SetArith(%d): %s\n", arith, snail_last_error()); std::abort(); }
+	}
+	// The DBVH rebuilt over moved instances (same BLAS trees, any count): new transforms and a new top-level tree for the next frame,
+	// ordered after every launch enqueued before it.  A BLAS that was not uploaded before takes a full Upload().
+	void Update(const RefDBVH &dbvh) {
+		for(const auto &e : dbvh.elements)
+			if(index.find(e.tree) == index.end()) { Upload(dbvh, device); return; }
+		ref = &dbvh;
+		std::vector<float> xf;
+		std::vector<int32_t> bi;
+		Elements(dbvh, xf, bi);
+		SNAIL_CHECK(snail_instances_update(inst, dbvh.nodes.data(), (int)dbvh.nodes.size(), xf.data(), bi.data(), (int)bi.size(), 0, nullptr));
+	}
+	// the arithmetic of every BLAS (HipBVH::SetArith); the instanced launches take the BLASes' arithmetic
+	bool SetArith(int a) {
+		std::vector<int> before;
+		for(auto &b : blas) before.push_back(b->Arith());
+		for(size_t k = 0; k < blas.size(); k++)
+			if(!blas[k]->SetArith(a)) {
+				for(size_t g = 0; g < k; g++) (void)blas[g]->SetArith(before[g]);
+				return false;
+			}
+		arith = a;
+		return true;
+	}
+	int Arith() const { return arith; }
+
+	// ---- frame prefetch (as HipBVH) ----
+	template <class CameraT> void BeginFrame(const CameraT &cam, int resx, int resy) const {
+		float c[13] = {cam.pos.x, cam.pos.y, cam.pos.z, cam.right.x, cam.right.y, cam.right.z, cam.up.x, cam.up.y, cam.up.z,
+					   cam.front.x, cam.front.y, cam.front.z, cam.plane_dist};
+		frame.resx = resx; frame.resy = resy;
+		frame.pw = (resx + 15) / 16; frame.ph = (resy + 15) / 16;
+		const size_t n = (size_t)frame.pw * frame.ph * 256;
+		frame.t.resize(n); frame.u.resize(n); frame.v.resize(n); frame.triId.resize(n); frameInst.resize(n);
+		frame.stats[0] = frame.stats[1] = frame.stats[2] = frame.stats[3] = 0;
+		SNAIL_CHECK(snail_instances_trace_frame_packets(inst, c, resx, resy, frame.t.data(), frame.u.data(), frame.v.data(), frameInst.data(), frame.triId.data(),
+														frame.stats));
+		haveFrame = true;
+		statsPending.store(true);
+	}
+	void EndFrame() const { haveFrame = false; }
+	bool HaveFrame() const { return haveFrame; }
+	void SetPacket(int x, int y) const { curPacket = haveFrame ? (long)frame.packetIndex(x, y) : -1; }
+
+	// ---- AccStruct concept ----
+	bool HasShadingData() const { return ref->HasShadingData(); }
+	auto GetSElement(int elem, int sub) const { return ref->GetSElement(elem, sub); }
+	auto GetNormal(int elem, int sub) const { return ref->GetNormal(elem, sub); }
+	int GetMaterialId(int idx, int elem) const { return ref->GetMaterialId(idx, elem); }
+	auto GetBBox() const { return ref->GetBBox(); }
+
+	// DBVH::TraversePrimary<sharedOrigin, hasMask> (src/dbvh/traverse.cpp:136-138): object = instance (element index), element = triId
+	template <class ContextT> void TraversePrimary(ContextT &c) const {
+		using RayGroupT = decltype(c.rays);
+		constexpr bool shared = RayGroupT::sharedOrigin != 0, masked = RayGroupT::hasMask != 0;
+		const int size = c.Size();
+		std::vector<int32_t> elemTmp;
+		int32_t *elem = (int32_t *)c.element;
+		if(!elem) { elemTmp.assign((size_t)size * 4, 0); elem = elemTmp.data(); }
+		if(shared && !masked && size == SNAIL_PACKET_QUADS && curPacket >= 0) {
+			const size_t o = (size_t)curPacket * 256;
+			std::memcpy(c.distance, &frame.t[o], 256 * 4);
+			std::memcpy(c.object, &frameInst[o], 256 * 4);
+			std::memcpy(elem, &frame.triId[o], 256 * 4);
+			if(c.barycentric) {
+				float *b = (float *)c.barycentric;
+				for(int q = 0; q < 64; q++) { std::memcpy(b + q * 8, &frame.u[o + q * 4], 16); std::memcpy(b + q * 8 + 4, &frame.v[o + q * 4], 16); }
+			}
+			curPacket = -1;
+			if(c.stats && statsPending.exchange(false)) {
+				c.stats->Intersection((unsigned)frame.stats[0]); c.stats->LoopIteration((unsigned)frame.stats[1]); c.stats->Skip((unsigned)frame.stats[3]);
+			}
+			return;
+		}
+		uint64_t st[4] = {0, 0, 0, 0};
+		SNAIL_CHECK(snail_instances_trace_rays(inst, 1, size, shared ? 1 : 0, (const float *)c.rays.OriginPtr(), (const float *)c.rays.DirPtr(),
+											   (const float *)c.rays.IDirPtr(), (const uint8_t *)c.MaskPtr(), (float *)c.distance, (int32_t *)c.object, elem,
+											   (float *)c.barycentric, st));
+		if(c.stats) { c.stats->Intersection((unsigned)st[0]); c.stats->LoopIteration((unsigned)st[1]); c.stats->Skip((unsigned)st[3]); }
+	}
+
+	// DBVH::TraverseShadow (src/dbvh/traverse.cpp:76-134, :212)
+	template <class ShadowContextT> void TraverseShadow(ShadowContextT &c) const {
+		const float *o = (const float *)c.rays.OriginPtr();
+		const float org[3] = {o[0], o[4], o[8]};
+		uint64_t st[4] = {0, 0, 0, 0};
+		SNAIL_CHECK(snail_instances_trace_shadow(inst, 1, c.Size(), org, (const float *)c.rays.DirPtr(), (const float *)c.rays.IDirPtr(), (float *)c.distance, st));
+		if(c.stats) { c.stats->Intersection((unsigned)st[0]); c.stats->LoopIteration((unsigned)st[1]); c.stats->Skip((unsigned)st[3]); }
+	}
+
+	SnailInstances *Handle() const { return inst; }
+	const FrameHits &Frame() const { return frame; }                 // t, u, v, triId of the prefetched frame
+	const std::vector<int32_t> &FrameInstances() const { return frameInst; }   // ... and the instance of each record
+	int BlasCount() const { return (int)blas.size(); }
+
+private:
+	// xf12 / BLAS index per element, in the elements' order; new BLASes uploaded on the way
+	void Elements(const RefDBVH &dbvh, std::vector<float> &xf, std::vector<int32_t> &bi) {
+		for(const auto &e : dbvh.elements) {
+			auto it = index.find(e.tree);
+			if(it == index.end()) {
+				blas.emplace_back(new HipBVH<RefBVH>());
+				blas.back()->Upload(*e.tree, device);
+				it = index.emplace(e.tree, (int)blas.size() - 1).first;
+			}
+			for(int r = 0; r < 3; r++) xf.insert(xf.end(), {e.rotation[r].x, e.rotation[r].y, e.rotation[r].z});
+			xf.insert(xf.end(), {e.translation.x, e.translation.y, e.translation.z});
+			bi.push_back(it->second);
+		}
+	}
+	void Release() {
+		if(inst) snail_instances_destroy(inst);   // before the BLASes it reads (include/snail_instances.h, "Lifetime")
+		inst = nullptr;
+		blas.clear(); index.clear();
+	}
+	const RefDBVH *ref = nullptr;
+	int device = 0;
+	int arith = SNAIL_ARITH_IEEE;
+	SnailInstances *inst = nullptr;
+	std::vector<std::unique_ptr<HipBVH<RefBVH>>> blas;
+	std::map<const RefBVH *, int> index;
+	mutable FrameHits frame;
+	mutable std::vector<int32_t> frameInst;
+	mutable bool haveFrame = false;
+	mutable std::atomic<bool> statsPending{false};
+	static inline thread_local long curPacket = -1;
 };
 
 // ---- batched immediate path --------------------------------------------------------------------------------------------------
@@ -419,6 +597,29 @@ inline TreeStats Render(const Scene<snail::HipBVH<RefBVH>> &scene, const Camera 
 	(void)options;
 	mode.antialias = gVals[9] != 0;
 	return snail::RenderImage<TreeStats>(scene, camera, image, mode);
+}
+// Scene<snail::HipDBVH<...>>: the gVals[1] depth image is made on the device (snail_instances_render_depth); every other switch -- and the
+// tile list, whose planar store has no instanced device path -- goes to the reference's renderer over the prefetched frame, whose
+// TraversePrimary calls copy pre-traced packets and whose shadow / secondary packets go to the device one call each.
+template <class RefDBVH>
+inline TreeStats Render(const Scene<snail::HipDBVH<RefDBVH>> &scene, const Camera &camera, uint resx, uint resy, unsigned char *data, const vector<int> &coords,
+						const vector<int> &offsets, const Options options, uint rank, uint threads) {
+	SNAIL_HOST_RENDER("the tile list of an instanced scene", gVals[9] ? 2 : 1, resx, resy,
+					  Render<snail::HipDBVH<RefDBVH>>(scene, camera, resx, resy, data, coords, offsets, options, rank, threads));
+}
+template <class RefDBVH>
+inline TreeStats Render(const Scene<snail::HipDBVH<RefDBVH>> &scene, const Camera &camera, MipmapTexture &image, const Options options, uint threads) {
+	const char *why = snail::UnsupportedSwitch(gVals, scene.geometry.HasShadingData(), false);
+	if(!why && !gVals[1]) why = "shading other than gVals[1] on an instanced scene";
+	if(!why && (gVals[7] || gVals[9])) why = "gVals[7] / gVals[9] on an instanced scene";
+	if(why) SNAIL_HOST_RENDER(why, gVals[9] ? 2 : 1, image.Width(), image.Height(), Render<snail::HipDBVH<RefDBVH>>(scene, camera, image, options, threads));
+	(void)options; (void)threads;
+	float c[13];
+	snail::detail::cam13(camera, c);
+	uint64_t st[4] = {0, 0, 0, 0};
+	SNAIL_CHECK(snail_instances_render_depth(scene.geometry.Handle(), c, (int)image.Width(), (int)image.Height(), (unsigned char *)image.DataPointer(),
+											 (int)image.Pitch(), st));
+	return snail::detail::toStats<TreeStats>(st);
 }
 #undef SNAIL_HOST_RENDER
 #endif

@@ -75,6 +75,23 @@ SIGNATURES = {
     "snail_last_launch": (_I, [_VP, _VP, _VP]),
 }
 
+# include/snail_instances.h (snail_amd/instances.py): a table of its own, because SIGNATURES is the list that
+# tests/c/abi_c.c takes the address of, entry for entry
+INSTANCES_SIGNATURES = {
+    "snail_instances_build": (_I, [_VP, _VP, _I, _VP, _I, _VP, _VP, _VP, _VP]),
+    "snail_instances_create": (_VP, [_VP, _I, _VP, _I, _VP, _VP, _I, _I]),
+    "snail_instances_update": (_I, [_VP, _VP, _I, _VP, _VP, _I, _I, _VP]),
+    "snail_instances_destroy": (None, [_VP]),
+    "snail_instances_trace_primary_dev": (_I, [_VP, _F13, _I, _I, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "snail_instances_trace_packets_dev": (_I, [_VP, _F13, _I, _I, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "snail_instances_trace_rays_dev": (_I, [_VP, _I, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "snail_instances_trace_shadow_dev": (_I, [_VP, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "snail_instances_trace_rays": (_I, [_VP, _I, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "snail_instances_trace_shadow": (_I, [_VP, _I, _I, _VP, _VP, _VP, _VP, _VP]),
+    "snail_instances_trace_frame_packets": (_I, [_VP, _F13, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "snail_instances_render_depth": (_I, [_VP, _F13, _I, _I, _VP, _I, _VP]),
+}
+
 # include/snail_hip_debug.h: the workbench build only (libsnailhip_debug.so, -DSNAIL_DEBUG_API)
 DEBUG_SIGNATURES = {
     "snail_debug_delay_dev": (_I, [C.c_float, _VP]),
@@ -97,7 +114,7 @@ def debug_lib():
         if not os.path.exists(DEBUG_LIB_PATH):
             raise SnailError("workbench library %s is missing: `make -C snail_amd/csrc debug`" % DEBUG_LIB_PATH)
         L = C.CDLL(DEBUG_LIB_PATH)
-        for table in (SIGNATURES, DEBUG_SIGNATURES):
+        for table in (SIGNATURES, INSTANCES_SIGNATURES, DEBUG_SIGNATURES):
             for name, (res, args) in table.items():
                 fn = getattr(L, name)
                 fn.restype = res
@@ -118,10 +135,11 @@ def lib():
             L = C.CDLL(LIB_PATH)
         except OSError as e:  # pragma: no cover - depends on the box
             raise SnailError("cannot load %s: %s" % (LIB_PATH, e)) from e
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(L, name)
-            fn.restype = res
-            fn.argtypes = args
+        for table in (SIGNATURES, INSTANCES_SIGNATURES):
+            for name, (res, args) in table.items():
+                fn = getattr(L, name)
+                fn.restype = res
+                fn.argtypes = args
         for name, (res, args) in DEBUG_SIGNATURES.items():     # present only when SNAIL_LIB_PATH names the workbench build
             fn = getattr(L, name, None)
             if fn is not None:

@@ -1,0 +1,423 @@
+// instances_host.inc -- host side of the two-level instanced scenes (include/snail_instances.h); included at
+// the end of snail_hip.hip.  The build is in dbvh_build.cpp, the kernels in instances.inc.
+
+struct SnailInstances {
+	int device = 0;
+	std::vector<SnailScene *> blas;
+	dev::InstBlas *dBlas = nullptr;
+	uint4 *dTop = nullptr, *dInst = nullptr;   // top-level node records; 4 x 16 B per builder slot
+	int topCap = 0, instCap = 0;
+	int nNodes = 0, n = 0;
+	// mu: the ordering state below and the buffers' identity (held while a call enqueues)
+	std::mutex mu;
+	// snail_instances_update vs launches: the update's stream waits for every launch enqueued since the previous update (one event per stream
+	// that launched), its copies come from pinned staging (reused once the previous update's copies are done), and every launch after it
+	// waits for `ready`
+	hipEvent_t ready = nullptr;
+	bool hasReady = false;
+	struct Use { hipStream_t stream; hipEvent_t ev; };
+	std::vector<Use> uses;
+	void *staging = nullptr;
+	size_t stagingCap = 0;
+	hipEvent_t stagingFree = nullptr;
+	bool stagingUsed = false;
+};
+
+namespace {
+
+// children inside the array and after their parent, leaf ranges inside [0, n), depth <= 64 over the nodes reached from the root
+int validateInstances(const char *fn, const void *nodes32, int nNodes, const float *xf12, const int32_t *blasIdx, int n, int nBlas, int *depthOut) {
+	if(!nodes32 || !xf12 || !blasIdx || nNodes <= 0 || n <= 0 || nNodes > (1 << 30) || n > (1 << 30)) { snail_set_error("%s: bad arguments", fn); return 1; }
+	for(size_t i = 0; i < (size_t)n * 12; i++)
+		if(!std::isfinite(xf12[i])) { snail_set_error("%s: instance slot %d has a non-finite transform", fn, (int)(i / 12)); return 1; }
+	for(int i = 0; i < n; i++)
+		if(blasIdx[i] < 0 || blasIdx[i] >= nBlas) { snail_set_error("%s: instance slot %d names BLAS %d of %d", fn, i, blasIdx[i], nBlas); return 1; }
+	struct N { float b[6]; uint32_t sub; int32_t aux; };
+	const N *nd = (const N *)nodes32;
+	std::vector<int> depth((size_t)nNodes, -1);
+	std::vector<char> reached((size_t)nNodes, 0);
+	reached[0] = 1;
+	for(int i = 0; i < nNodes; i++) {
+		if(!reached[i]) continue;
+		if(nd[i].sub & 0x80000000u) {
+			const long long first = nd[i].sub & 0x7fffffffu, count = nd[i].aux;
+			if(count < 0 || first + count > n) { snail_set_error("%s: leaf %d holds instances %lld..%lld of %d", fn, i, first, first + count - 1, n); return 1; }
+		} else {
+			const long long sub = nd[i].sub;
+			if(sub <= i || sub + 1 >= nNodes) { snail_set_error("%s: node %d has children %lld, %lld (must follow it, inside %d nodes)", fn, i, sub, sub + 1, nNodes); return 1; }
+			reached[sub] = reached[sub + 1] = 1;
+		}
+	}
+	int maxDepth = 0;
+	for(int i = nNodes - 1; i >= 0; i--) {
+		if(!reached[i]) continue;
+		depth[i] = (nd[i].sub & 0x80000000u) ? 0 : 1 + std::max(depth[nd[i].sub], depth[nd[i].sub + 1]);
+		if(depth[i] > SNAIL_INSTANCES_MAX_DEPTH) { snail_set_error("%s: the tree is deeper than %d levels", fn, SNAIL_INSTANCES_MAX_DEPTH); return 2; }
+	}
+	maxDepth = depth[0];
+	if(depthOut) *depthOut = maxDepth;
+	return 0;
+}
+
+void packInstances(const float *xf12, const int32_t *blasIdx, int n, uint32_t *out16) {
+	for(int i = 0; i < n; i++) {
+		uint32_t *o = out16 + (size_t)i * 16;
+		memset(o, 0, 64);
+		for(int r = 0; r < 3; r++) memcpy(o + r * 4, xf12 + (size_t)i * 12 + r * 3, 12);
+		o[3] = (uint32_t)blasIdx[i];
+		memcpy(o + 12, xf12 + (size_t)i * 12 + 9, 12);
+	}
+}
+
+// new records into the handle's buffers, ordered on `stream` after every launch since the previous update (mu held)
+int instancesUpload(SnailInstances *h, const void *nodes32, int nNodes, const float *xf12, const int32_t *blasIdx, int n, hipStream_t stream) {
+	for(auto &u : h->uses) HIP_TRY(hipStreamWaitEvent(stream, u.ev, 0));
+	const size_t topBytes = (size_t)nNodes * 32, instBytes = (size_t)n * 64;
+	if(nNodes > h->topCap || n > h->instCap) { // grown: the old buffers may still be read by launches in flight
+		HIP_TRY(hipStreamSynchronize(stream));
+		HIP_TRY(hipDeviceSynchronize());
+		if(nNodes > h->topCap) {
+			if(h->dTop) (void)hipFree(h->dTop);
+			h->dTop = nullptr; h->topCap = 0;
+			HIP_TRY(hipMalloc((void **)&h->dTop, topBytes));
+			h->topCap = nNodes;
+		}
+		if(n > h->instCap) {
+			if(h->dInst) (void)hipFree(h->dInst);
+			h->dInst = nullptr; h->instCap = 0;
+			HIP_TRY(hipMalloc((void **)&h->dInst, instBytes));
+			h->instCap = n;
+		}
+	}
+	if(h->stagingUsed) HIP_TRY(hipEventSynchronize(h->stagingFree));   // the previous update's copies out of the staging area
+	if(topBytes + instBytes > h->stagingCap) {
+		if(h->staging) (void)hipHostFree(h->staging);
+		h->staging = nullptr; h->stagingCap = 0;
+		HIP_TRY(hipHostMalloc(&h->staging, topBytes + instBytes, hipHostMallocDefault));
+		h->stagingCap = topBytes + instBytes;
+	}
+	char *st = (char *)h->staging;
+	memcpy(st, nodes32, topBytes);
+	packInstances(xf12, blasIdx, n, (uint32_t *)(st + topBytes));
+	HIP_TRY(hipMemcpyAsync(h->dTop, st, topBytes, hipMemcpyHostToDevice, stream));
+	HIP_TRY(hipMemcpyAsync(h->dInst, st + topBytes, instBytes, hipMemcpyHostToDevice, stream));
+	if(!h->stagingFree) HIP_TRY(hipEventCreateWithFlags(&h->stagingFree, hipEventDisableTiming));
+	HIP_TRY(hipEventRecord(h->stagingFree, stream));
+	h->stagingUsed = true;
+	if(!h->ready) HIP_TRY(hipEventCreateWithFlags(&h->ready, hipEventDisableTiming));
+	HIP_TRY(hipEventRecord(h->ready, stream));
+	h->hasReady = true;
+	h->nNodes = nNodes; h->n = n;
+	return 0;
+}
+
+// the launch's argument record (arithmetic and tree flavour of the BLASes) and its ordering against updates (mu held)
+int instancesBegin(SnailInstances *h, const char *fn, dev::InstArgs &A, bool *sse, bool *deep, hipStream_t stream) {
+	memset(&A, 0, sizeof(A));
+	const int arith = h->blas[0]->arith;
+	*deep = false;
+	for(SnailScene *s : h->blas) {
+		if(s->arith != arith) { snail_set_error("%s: the BLAS scenes are set to different arithmetics", fn); return 1; }
+		*deep = *deep || useDeep(s);
+	}
+	*sse = arith == SNAIL_ARITH_HOST_SSE;
+	A.hostTab = *sse ? h->blas[0]->dTab : nullptr;
+	if(*sse) {
+		for(SnailScene *s : h->blas)
+			if(s->dTab != h->blas[0]->dTab && s->tabGen != h->blas[0]->tabGen) { snail_set_error("%s: the BLAS scenes hold different rcpps / rsqrtps tables", fn); return 1; }
+	}
+	A.top = h->dTop; A.inst = h->dInst; A.blas = h->dBlas;
+	if(h->hasReady) HIP_TRY(hipStreamWaitEvent(stream, h->ready, 0));
+	return 0;
+}
+int instancesEnd(SnailInstances *h, hipStream_t stream) {
+	HIP_TRY(hipGetLastError());
+	for(auto &u : h->uses)
+		if(u.stream == stream) { HIP_TRY(hipEventRecord(u.ev, stream)); return 0; }
+	SnailInstances::Use u;
+	u.stream = stream;
+	HIP_TRY(hipEventCreateWithFlags(&u.ev, hipEventDisableTiming));
+	HIP_TRY(hipEventRecord(u.ev, stream));
+	h->uses.push_back(u);
+	return 0;
+}
+
+int checkInstances(const SnailInstances *h, const char *fn) {
+	if(!h || !h->dTop || !h->dInst || !h->dBlas || h->blas.empty()) { snail_set_error("%s: invalid instances handle", fn); return 1; }
+	return 0;
+}
+
+#define SNAIL_INST_LAUNCH(SSE, GRID, STREAM, A, ...) SNAIL_LAUNCH(SSE, InstArgs, GRID, dim3(64), 0, STREAM, A, __VA_ARGS__)
+
+int instancesPrimary(SnailInstances *h, const char *fn, const float cam[13], int resx, int resy, int x0, int y0, int w, int hh, const int32_t *dPacketXY,
+					 int nPackets, float *t, float *u, float *v, int32_t *inst, int32_t *tri, uint64_t *dStats, hipStream_t stream) {
+	if(int rc = checkInstances(h, fn)) return rc;
+	if(!cam || resx <= 0 || resy <= 0) { snail_set_error("%s: bad camera or resolution", fn); return 1; }
+	dev::InstArgs A;
+	bool sse, deep;
+	DeviceGuard guard(h->device);
+	std::lock_guard<std::mutex> lock(h->mu);
+	if(int rc = instancesBegin(h, fn, A, &sse, &deep, stream)) return rc;
+	A.g = makeGen(cam, resx, resy);
+	A.resx = resx; A.resy = resy;
+	if(dPacketXY) {
+		if(nPackets <= 0) return 0;
+		A.packetXY = (const int2 *)dPacketXY;
+		A.nPackets = nPackets;
+	} else {
+		if((x0 & 15) || (y0 & 15) || w <= 0 || hh <= 0 || x0 < 0 || y0 < 0) { snail_set_error("%s: rect origin must be a non-negative multiple of 16 and the size positive", fn); return 1; }
+		A.x0 = x0; A.y0 = y0; A.w = w; A.h = hh;
+		A.pw = (w + 15) / 16;
+		A.nPackets = A.pw * ((hh + 15) / 16);
+	}
+	A.t = t; A.u = u; A.v = v; A.instOut = inst; A.triOut = tri;
+	A.stats = (dev::u64 *)dStats;
+	if(deep) SNAIL_INST_LAUNCH(sse, dim3(A.nPackets), stream, A, k_inst_frame<true>);
+	else SNAIL_INST_LAUNCH(sse, dim3(A.nPackets), stream, A, k_inst_frame<false>);
+	return instancesEnd(h, stream);
+}
+
+template <bool SHARED, bool MASK>
+void instancesRaysKernels(bool sse, bool deep, bool bary, const dev::InstArgs &A, hipStream_t stream) {
+	const dim3 grid(A.nPackets);
+	if(deep && bary) SNAIL_INST_LAUNCH(sse, grid, stream, A, k_inst_trace<SHARED, MASK, true, true>);
+	else if(deep) SNAIL_INST_LAUNCH(sse, grid, stream, A, k_inst_trace<SHARED, MASK, true, false>);
+	else if(bary) SNAIL_INST_LAUNCH(sse, grid, stream, A, k_inst_trace<SHARED, MASK, false, true>);
+	else SNAIL_INST_LAUNCH(sse, grid, stream, A, k_inst_trace<SHARED, MASK, false, false>);
+}
+
+int instancesRays(SnailInstances *h, const char *fn, bool shadow, int nPackets, int size, int sharedOrigin, const float *origin, const float *dir, const float *idir,
+				  const uint8_t *mask, float *distance, int32_t *object, int32_t *element, float *bary, uint64_t *dStats, hipStream_t stream) {
+	if(int rc = checkInstances(h, fn)) return rc;
+	if(nPackets <= 0) return 0;
+	if(size < 1 || size > SNAIL_PACKET_QUADS) { snail_set_error("%s: packet size %d outside 1..%d quads", fn, size, SNAIL_PACKET_QUADS); return 1; }
+	if(!origin || !dir || !idir || !distance || (!shadow && (!object || !element))) { snail_set_error("%s: null ray array", fn); return 1; }
+	dev::InstArgs A;
+	bool sse, deep;
+	DeviceGuard guard(h->device);
+	std::lock_guard<std::mutex> lock(h->mu);
+	if(int rc = instancesBegin(h, fn, A, &sse, &deep, stream)) return rc;
+	A.nPackets = nPackets; A.size = size;
+	A.origin = origin; A.dir = dir; A.idir = idir; A.mask = mask;
+	A.distance = distance; A.object = object; A.element = element; A.bary = bary;
+	A.stats = (dev::u64 *)dStats;
+	if(shadow) {
+		if(deep) SNAIL_INST_LAUNCH(sse, dim3(nPackets), stream, A, k_inst_occl<true>);
+		else SNAIL_INST_LAUNCH(sse, dim3(nPackets), stream, A, k_inst_occl<false>);
+	} else if(sharedOrigin && mask) instancesRaysKernels<true, true>(sse, deep, bary != nullptr, A, stream);
+	else if(sharedOrigin) instancesRaysKernels<true, false>(sse, deep, bary != nullptr, A, stream);
+	else if(mask) instancesRaysKernels<false, true>(sse, deep, bary != nullptr, A, stream);
+	else instancesRaysKernels<false, false>(sse, deep, bary != nullptr, A, stream);
+	return instancesEnd(h, stream);
+}
+
+
+// the whole frame's packets, row-major over the packet grid, through the call's own stream and arena (snail_instances_trace_frame_packets /
+// snail_instances_render_depth): -> device t (and, if asked for, u, v, instance, triId), packet-major
+static int instancesFramePackets(SnailInstances *h, const char *fn, HostCallScope &hc, const float cam[13], int resx, int resy, bool all, void **dXY,
+								 float **dT, float **dU, float **dV, int32_t **dI, int32_t **dTri, int *nPackets) {
+	if(!cam || resx <= 0 || resy <= 0) { snail_set_error("%s: bad camera or resolution", fn); return 1; }
+	const int pw = (resx + 15) / 16, ph = (resy + 15) / 16, np = pw * ph;
+	std::vector<int32_t> xy((size_t)np * 2);
+	for(int y = 0; y < ph; y++)
+		for(int x = 0; x < pw; x++) { xy[((size_t)y * pw + x) * 2] = x * 16; xy[((size_t)y * pw + x) * 2 + 1] = y * 16; }
+	typedef HostCallScope H;
+	const size_t rays = (size_t)np * 256;
+	if(int rc = hc.reserve(H::pad(xy.size() * 4) + (all ? 5 : 1) * H::pad(rays * 4) + H::pad(rays * 3))) return rc;
+	if(int rc = hc.put(dXY, xy.data(), xy.size() * 4)) return rc;
+	*dT = (float *)hc.carve(rays * 4);
+	*dU = *dV = nullptr; *dI = *dTri = nullptr;
+	if(all) { *dU = (float *)hc.carve(rays * 4); *dV = (float *)hc.carve(rays * 4); *dI = (int32_t *)hc.carve(rays * 4); *dTri = (int32_t *)hc.carve(rays * 4); }
+	*nPackets = np;
+	return instancesPrimary(h, fn, cam, resx, resy, 0, 0, 0, 0, (const int32_t *)*dXY, np, *dT, *dU, *dV, *dI, *dTri, hc.stats(), hc.stream());
+}
+} // namespace
+
+extern "C" {
+
+SnailInstances *snail_instances_create(SnailScene *const *blas, int nBlas, const void *nodes32, int nNodes, const float *xf12, const int32_t *blasIdx,
+									   int n, int depth) {
+	const char *fn = "snail_instances_create";
+	if(!blas || nBlas <= 0) { snail_set_error("%s: no BLAS scenes", fn); return nullptr; }
+	int measured = 0;
+	if(validateInstances(fn, nodes32, nNodes, xf12, blasIdx, n, nBlas, &measured)) return nullptr;
+	for(int b = 0; b < nBlas; b++) {
+		if(checkScene(blas[b], fn)) return nullptr;
+		if(blas[b]->device != blas[0]->device) { snail_set_error("%s: BLAS %d lives on device %d, BLAS 0 on device %d", fn, b, blas[b]->device, blas[0]->device); return nullptr; }
+	}
+	(void)depth;   // (the depth that matters -- the stack the kernels need -- is measured above)
+	DeviceGuard guard(blas[0]->device);
+	if(!guard.ok) { snail_set_error("%s: cannot select device %d", fn, blas[0]->device); return nullptr; }
+	SnailInstances *h = new SnailInstances();
+	h->device = blas[0]->device;
+	h->blas.assign(blas, blas + nBlas);
+	std::vector<dev::InstBlas> rec((size_t)nBlas);
+	for(int b = 0; b < nBlas; b++) { rec[b].nodes = blas[b]->dNodes; rec[b].tris = blas[b]->dTris; }
+	hipError_t e = hipMalloc((void **)&h->dBlas, rec.size() * sizeof(dev::InstBlas));
+	if(e == hipSuccess) e = hipMemcpy(h->dBlas, rec.data(), rec.size() * sizeof(dev::InstBlas), hipMemcpyHostToDevice);
+	if(e != hipSuccess) { snail_set_error("%s: %s", fn, hipGetErrorString(e)); snail_instances_destroy(h); return nullptr; }
+	int rc;
+	{
+		std::lock_guard<std::mutex> lock(h->mu);
+		rc = instancesUpload(h, nodes32, nNodes, xf12, blasIdx, n, nullptr);
+	}
+	if(rc == 0 && hipStreamSynchronize(nullptr) != hipSuccess) { snail_set_error("%s: upload failed", fn); rc = 1; }
+	if(rc) { snail_instances_destroy(h); return nullptr; }
+	return h;
+}
+
+int snail_instances_update(SnailInstances *h, const void *nodes32, int nNodes, const float *xf12, const int32_t *blasIdx, int n, int depth, void *stream) {
+	const char *fn = "snail_instances_update";
+	if(int rc = checkInstances(h, fn)) return rc;
+	if(int rc = validateInstances(fn, nodes32, nNodes, xf12, blasIdx, n, (int)h->blas.size(), nullptr)) return rc;
+	(void)depth;
+	DeviceGuard guard(h->device);
+	std::lock_guard<std::mutex> lock(h->mu);
+	return instancesUpload(h, nodes32, nNodes, xf12, blasIdx, n, (hipStream_t)stream);
+}
+
+void snail_instances_destroy(SnailInstances *h) {
+	if(!h) return;
+	DeviceGuard guard(h->device);
+	(void)hipDeviceSynchronize();
+	if(h->dBlas) (void)hipFree(h->dBlas);
+	if(h->dTop) (void)hipFree(h->dTop);
+	if(h->dInst) (void)hipFree(h->dInst);
+	if(h->staging) (void)hipHostFree(h->staging);
+	if(h->ready) (void)hipEventDestroy(h->ready);
+	if(h->stagingFree) (void)hipEventDestroy(h->stagingFree);
+	for(auto &u : h->uses) (void)hipEventDestroy(u.ev);
+	delete h;
+}
+
+int snail_instances_trace_primary_dev(SnailInstances *h, const float cam[13], int resx, int resy, int x0, int y0, int w, int hh, float *t, float *u, float *v,
+									  int32_t *inst, int32_t *tri, uint64_t *dStats, void *stream) {
+	return instancesPrimary(h, "snail_instances_trace_primary_dev", cam, resx, resy, x0, y0, w, hh, nullptr, 0, t, u, v, inst, tri, dStats, (hipStream_t)stream);
+}
+
+int snail_instances_trace_packets_dev(SnailInstances *h, const float cam[13], int resx, int resy, const int32_t *dPacketXY, int nPackets, float *t, float *u,
+									  float *v, int32_t *inst, int32_t *tri, uint64_t *dStats, void *stream) {
+	if(!dPacketXY) { snail_set_error("snail_instances_trace_packets_dev: null packet list"); return 1; }
+	return instancesPrimary(h, "snail_instances_trace_packets_dev", cam, resx, resy, 0, 0, 0, 0, dPacketXY, nPackets, t, u, v, inst, tri, dStats, (hipStream_t)stream);
+}
+
+int snail_instances_trace_rays_dev(SnailInstances *h, int nPackets, int size, int sharedOrigin, const float *origin, const float *dir, const float *idir,
+								   const uint8_t *mask, float *distance, int32_t *object, int32_t *element, float *bary, uint64_t *dStats, void *stream) {
+	return instancesRays(h, "snail_instances_trace_rays_dev", false, nPackets, size, sharedOrigin, origin, dir, idir, mask, distance, object, element, bary,
+						 dStats, (hipStream_t)stream);
+}
+
+int snail_instances_trace_shadow_dev(SnailInstances *h, int nPackets, int size, const float *origin3, const float *dir, const float *idir, float *distance,
+									 uint64_t *dStats, void *stream) {
+	return instancesRays(h, "snail_instances_trace_shadow_dev", true, nPackets, size, 1, origin3, dir, idir, nullptr, distance, nullptr, nullptr, nullptr,
+						 dStats, (hipStream_t)stream);
+}
+
+int snail_instances_trace_rays(SnailInstances *h, int nPackets, int size, int sharedOrigin, const float *origin, const float *dir, const float *idir,
+							   const uint8_t *mask, float *distance, int32_t *object, int32_t *element, float *bary, uint64_t stats[4]) {
+	const char *fn = "snail_instances_trace_rays";
+	if(int rc = checkInstances(h, fn)) return rc;
+	if(nPackets <= 0) return 0;
+	if(size < 1 || size > SNAIL_PACKET_QUADS) { snail_set_error("%s: packet size %d outside 1..%d quads", fn, size, SNAIL_PACKET_QUADS); return 1; }
+	if(!origin || !dir || !idir || !distance || !object || !element) { snail_set_error("%s: null ray array", fn); return 1; }
+	DeviceGuard guard(h->device);
+	HostCallScope hc(h->blas[0], fn);   // (a stream, counters and staging arena of the call's own; the BLAS handle only lends its free list)
+	if(hc.rc) return hc.rc;
+	const size_t nq = (size_t)nPackets * size;
+	const size_t nOrg = (sharedOrigin ? (size_t)nPackets : nq) * 48;
+	typedef HostCallScope H;
+	if(int rc = hc.reserve(H::pad(nOrg) + 2 * H::pad(nq * 48) + H::pad(nq) + 3 * H::pad(nq * 16) + H::pad(nq * 32))) return rc;
+	void *o = nullptr, *d = nullptr, *i = nullptr, *m = nullptr, *ds = nullptr, *ob = nullptr, *el = nullptr, *ba = nullptr;
+	if(int rc = hc.put(&o, origin, nOrg)) return rc;
+	if(int rc = hc.put(&d, dir, nq * 48)) return rc;
+	if(int rc = hc.put(&i, idir, nq * 48)) return rc;
+	if(mask) { if(int rc = hc.put(&m, mask, nq)) return rc; }
+	if(int rc = hc.put(&ds, distance, nq * 16)) return rc;
+	if(int rc = hc.put(&ob, object, nq * 16)) return rc;
+	if(int rc = hc.put(&el, element, nq * 16)) return rc;
+	if(bary) { if(int rc = hc.put(&ba, bary, nq * 32)) return rc; }
+	if(stats) { if(int rc = hc.zeroStats()) return rc; }
+	if(int rc = instancesRays(h, fn, false, nPackets, size, sharedOrigin, (float *)o, (float *)d, (float *)i, (uint8_t *)m, (float *)ds, (int32_t *)ob,
+							  (int32_t *)el, (float *)ba, stats ? hc.stats() : nullptr, hc.stream()))
+		return rc;
+	if(int rc = hc.get(distance, ds, nq * 16)) return rc;
+	if(int rc = hc.get(object, ob, nq * 16)) return rc;
+	if(int rc = hc.get(element, el, nq * 16)) return rc;
+	if(int rc = hc.get(bary, ba, nq * 32)) return rc;
+	return hc.finish(stats);
+}
+
+int snail_instances_trace_shadow(SnailInstances *h, int nPackets, int size, const float *origin3, const float *dir, const float *idir, float *distance,
+								 uint64_t stats[4]) {
+	const char *fn = "snail_instances_trace_shadow";
+	if(int rc = checkInstances(h, fn)) return rc;
+	if(nPackets <= 0) return 0;
+	if(size < 1 || size > SNAIL_PACKET_QUADS) { snail_set_error("%s: packet size %d outside 1..%d quads", fn, size, SNAIL_PACKET_QUADS); return 1; }
+	if(!origin3 || !dir || !idir || !distance) { snail_set_error("%s: null ray array", fn); return 1; }
+	DeviceGuard guard(h->device);
+	HostCallScope hc(h->blas[0], fn);
+	if(hc.rc) return hc.rc;
+	const size_t nq = (size_t)nPackets * size;
+	typedef HostCallScope H;
+	if(int rc = hc.reserve(H::pad((size_t)nPackets * 12) + 2 * H::pad(nq * 48) + H::pad(nq * 16))) return rc;
+	void *o = nullptr, *d = nullptr, *i = nullptr, *ds = nullptr;
+	if(int rc = hc.put(&o, origin3, (size_t)nPackets * 12)) return rc;
+	if(int rc = hc.put(&d, dir, nq * 48)) return rc;
+	if(int rc = hc.put(&i, idir, nq * 48)) return rc;
+	if(int rc = hc.put(&ds, distance, nq * 16)) return rc;
+	if(stats) { if(int rc = hc.zeroStats()) return rc; }
+	if(int rc = instancesRays(h, fn, true, nPackets, size, 1, (float *)o, (float *)d, (float *)i, nullptr, (float *)ds, nullptr, nullptr, nullptr,
+							  stats ? hc.stats() : nullptr, hc.stream()))
+		return rc;
+	if(int rc = hc.get(distance, ds, nq * 16)) return rc;
+	return hc.finish(stats);
+}
+
+
+int snail_instances_trace_frame_packets(SnailInstances *h, const float cam[13], int resx, int resy, float *t, float *u, float *v, int32_t *inst, int32_t *tri,
+										uint64_t stats[4]) {
+	const char *fn = "snail_instances_trace_frame_packets";
+	if(int rc = checkInstances(h, fn)) return rc;
+	if(!t || !u || !v || !inst || !tri) { snail_set_error("%s: null output", fn); return 1; }
+	DeviceGuard guard(h->device);
+	HostCallScope hc(h->blas[0], fn);
+	if(hc.rc) return hc.rc;
+	if(int rc = hc.zeroStats()) return rc;
+	void *xy = nullptr; float *dT, *dU, *dV; int32_t *dI, *dTri; int np = 0;
+	if(int rc = instancesFramePackets(h, fn, hc, cam, resx, resy, true, &xy, &dT, &dU, &dV, &dI, &dTri, &np)) return rc;
+	const size_t bytes = (size_t)np * 256 * 4;
+	if(int rc = hc.get(t, dT, bytes)) return rc;
+	if(int rc = hc.get(u, dU, bytes)) return rc;
+	if(int rc = hc.get(v, dV, bytes)) return rc;
+	if(int rc = hc.get(inst, dI, bytes)) return rc;
+	if(int rc = hc.get(tri, dTri, bytes)) return rc;
+	return hc.finish(stats);
+}
+
+int snail_instances_render_depth(SnailInstances *h, const float cam[13], int resx, int resy, uint8_t *image, int pitch, uint64_t stats[4]) {
+	const char *fn = "snail_instances_render_depth";
+	if(int rc = checkInstances(h, fn)) return rc;
+	if(!image || pitch < resx * 3) { snail_set_error("%s: bad image", fn); return 1; }
+	DeviceGuard guard(h->device);
+	HostCallScope hc(h->blas[0], fn);
+	if(hc.rc) return hc.rc;
+	if(int rc = hc.zeroStats()) return rc;
+	void *xy = nullptr; float *dT, *dU, *dV; int32_t *dI, *dTri; int np = 0;
+	if(int rc = instancesFramePackets(h, fn, hc, cam, resx, resy, false, &xy, &dT, &dU, &dV, &dI, &dTri, &np)) return rc;
+	uint8_t *bgr = (uint8_t *)hc.carve((size_t)np * 256 * 3);
+	if(int rc = snail_shade_depth_arith_dev(dT, np, bgr, h->blas[0]->arith, hc.stream())) return rc;
+	// the image in device memory: a separate allocation of the call (frames are rare next to packets; freed once the copy is done)
+	uint8_t *dImg = nullptr;
+	HIP_TRY(hipMalloc((void **)&dImg, (size_t)pitch * resy));
+	int rc = snail_packets_bgr_to_frame_dev((const int32_t *)xy, np, resx, resy, bgr, dImg, pitch, hc.stream());
+	if(rc == 0 && hipMemcpy2DAsync(image, (size_t)pitch, dImg, (size_t)pitch, (size_t)resx * 3, (size_t)resy, hipMemcpyDeviceToHost, hc.stream()) != hipSuccess) {
+		snail_set_error("%s: copy of the image failed", fn);
+		rc = 1;
+	}
+	if(rc == 0) rc = hc.finish(stats);
+	else (void)hipStreamSynchronize(hc.stream());
+	(void)hipFree(dImg);
+	return rc;
+}
+
+} // extern "C"

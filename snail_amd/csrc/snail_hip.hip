@@ -42,6 +42,7 @@
 #include <vector>
 
 #include "../../include/snail_hip.h"
+#include "../../include/snail_instances.h"
 #include "host_sse.h"
 #ifdef SNAIL_DEBUG_API
 #include "../../include/snail_hip_debug.h"
@@ -74,11 +75,13 @@ void snail_set_error(const char *fmt, ...) {
 #define SNAIL_DEV_NS dev
 #define SNAIL_ARITH_SSE 0
 #include "snail_dev.inc"
+#include "instances.inc"
 #undef SNAIL_DEV_NS
 #undef SNAIL_ARITH_SSE
 #define SNAIL_DEV_NS dev_sse
 #define SNAIL_ARITH_SSE 1
 #include "snail_dev.inc"
+#include "instances.inc"
 #undef SNAIL_DEV_NS
 #undef SNAIL_ARITH_SSE
 
@@ -1612,3 +1615,4 @@ int snail_account_primary(SnailScene *s, const float cam[13], int resx, int resy
 } // extern "C"
 
 #include "render_host.inc"
+#include "instances_host.inc"

@@ -1,0 +1,191 @@
+"""Two-level instanced scenes: the host-side mirror of the reference's second `AccStruct` model, DBVH (src/dbvh/tree.h,
+src/dbvh/tree.cpp, src/dbvh/traverse.cpp), over the C-ABI of include/snail_instances.h.
+
+  InstancedScene(blas, rotations, translations, blas_index)   <-> DBVH(vector<ObjectInstance>)   (host build: snail_instances_build)
+  .update(rotations, translations, blas_index)                <-> rebuilding the DBVH for the next frame (rtracer.cpp's -instances mode)
+  .trace_primary(cam, resx, resy)                              <-> RayGenerator + SafeInv + DBVH::TraversePrimary over 16x16 packets
+  .traverse_primary(ctx, element) / .traverse_shadow(ctx)     <-> DBVH::TraversePrimary<so,mask> / DBVH::TraverseShadow
+
+The instance id a hit reports is the instance's BUILDER SLOT (the DBVH::elements order); .perm()[slot] is the caller's instance."""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from .bvh import NODE_DTYPE
+from .scene import Scene, Context, ShadowContext, HitFrame, _stream_ptr, _torch
+
+
+def _xf12(rotations, translations) -> np.ndarray:
+    r = np.ascontiguousarray(rotations, dtype=np.float32).reshape(-1, 3, 3)
+    t = np.ascontiguousarray(translations, dtype=np.float32).reshape(-1, 3)
+    if len(r) != len(t):
+        raise ValueError("rotations and translations differ in length")
+    return np.ascontiguousarray(np.concatenate([r.reshape(-1, 9), t], axis=1), dtype=np.float32)
+
+
+def build_instances(xf12: np.ndarray, blas_index: np.ndarray, blas_bbox6: np.ndarray):
+    """snail_instances_build -> (nodes NODE_DTYPE [nNodes], depth, perm int32 [n]: builder slot -> caller's instance)."""
+    xf = np.ascontiguousarray(xf12, dtype=np.float32).reshape(-1, 12)
+    bi = np.ascontiguousarray(blas_index, dtype=np.int32).reshape(-1)
+    bb = np.ascontiguousarray(blas_bbox6, dtype=np.float32).reshape(-1, 6)
+    n = len(xf)
+    if len(bi) != n:
+        raise ValueError("blas_index must hold one entry per instance")
+    nodes = np.zeros(max(2 * n, 1), dtype=NODE_DTYPE)
+    perm = np.zeros(n, dtype=np.int32)
+    nn, depth = C.c_int(0), C.c_int(0)
+    _lib.check(_lib.lib().snail_instances_build(_lib.ptr(xf), _lib.ptr(bi), n, _lib.ptr(bb), len(bb), _lib.ptr(nodes), C.addressof(nn),
+                                                C.addressof(depth), _lib.ptr(perm)), "snail_instances_build")
+    return np.ascontiguousarray(nodes[:nn.value]), depth.value, perm
+
+
+class InstancedScene:
+    """Rigid instances of BLAS scenes (snail_amd.scene.Scene, kept alive by this object) under a top-level tree resident on their GPU."""
+
+    def __init__(self, blas_scenes, rotations, translations, blas_index=None):
+        self.blas = list(blas_scenes) if isinstance(blas_scenes, (list, tuple)) else [blas_scenes]
+        if not self.blas:
+            raise ValueError("at least one BLAS scene")
+        self.device = self.blas[0].device
+        self._h = None
+        nodes, depth, xf, bi, perm = self._build(rotations, translations, blas_index)
+        arr = (C.c_void_p * len(self.blas))(*[s._h.value for s in self.blas])
+        h = _lib.lib().snail_instances_create(arr, len(self.blas), _lib.ptr(nodes), len(nodes), _lib.ptr(xf), _lib.ptr(bi), len(xf), depth)
+        if not h:
+            raise _lib.SnailError("snail_instances_create: %s" % _lib.lib().snail_last_error().decode())
+        self._h = C.c_void_p(h)
+        self._set(nodes, depth, xf, bi, perm)
+
+    @classmethod
+    def from_tree(cls, blas_scenes, nodes, xf12_slots, blas_index_slots, depth: int = 0):
+        """A caller's tree (e.g. the reference's own DBVH::nodes with its elements' transforms in slot order), validated by
+        snail_instances_create; perm() is then the identity."""
+        self = cls.__new__(cls)
+        self.blas = list(blas_scenes)
+        self.device = self.blas[0].device
+        self._h = None
+        nodes = np.ascontiguousarray(np.asarray(nodes).view(NODE_DTYPE))
+        xf = np.ascontiguousarray(xf12_slots, dtype=np.float32).reshape(-1, 12)
+        bi = np.ascontiguousarray(blas_index_slots, dtype=np.int32).reshape(-1)
+        arr = (C.c_void_p * len(self.blas))(*[s._h.value for s in self.blas])
+        h = _lib.lib().snail_instances_create(arr, len(self.blas), _lib.ptr(nodes), len(nodes), _lib.ptr(xf), _lib.ptr(bi), len(xf), int(depth))
+        if not h:
+            raise _lib.SnailError("snail_instances_create: %s" % _lib.lib().snail_last_error().decode())
+        self._h = C.c_void_p(h)
+        self._set(nodes, int(depth), xf, bi, np.arange(len(xf), dtype=np.int32))
+        return self
+
+    def _build(self, rotations, translations, blas_index):
+        xf = _xf12(rotations, translations)
+        n = len(xf)
+        bi = np.zeros(n, dtype=np.int32) if blas_index is None else np.ascontiguousarray(blas_index, dtype=np.int32).reshape(-1)
+        bb = np.stack([np.concatenate(s.get_bbox()) for s in self.blas]).astype(np.float32)
+        nodes, depth, perm = build_instances(xf, bi, bb)
+        # the handle takes the records in builder-slot order (DBVH::elements)
+        return nodes, depth, np.ascontiguousarray(xf[perm]), np.ascontiguousarray(bi[perm]), perm
+
+    def _set(self, nodes, depth, xf, bi, perm):
+        self._nodes, self.depth, self._xf, self._bi, self._perm = nodes, depth, xf, bi, perm
+
+    def update(self, rotations, translations, blas_index=None, stream=None) -> None:
+        """New transforms and a new tree for the next frame, ordered on `stream` after every launch enqueued before it."""
+        nodes, depth, xf, bi, perm = self._build(rotations, translations, blas_index)
+        _lib.check(_lib.lib().snail_instances_update(self._h, _lib.ptr(nodes), len(nodes), _lib.ptr(xf), _lib.ptr(bi), len(xf), depth, _stream_ptr(stream)),
+                   "snail_instances_update")
+        self._set(nodes, depth, xf, bi, perm)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            _lib.lib().snail_instances_destroy(self._h)
+            self._h = None
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    # ---- for tests --------------------------------------------------------------------------------
+    def nodes(self) -> np.ndarray:
+        return self._nodes.copy()
+
+    def perm(self) -> np.ndarray:
+        return self._perm.copy()
+
+    def slot_transforms(self):
+        """(xf12 [n,12], blas_index [n]) in builder-slot order, as the handle holds them."""
+        return self._xf.copy(), self._bi.copy()
+
+    # ---- traversal ----------------------------------------------------------------------------------
+    def _dev(self):
+        return _torch().device("cuda", self.device)
+
+    def new_stats(self):
+        return _torch().zeros(4, dtype=_torch().int64, device=self._dev())
+
+    def trace_primary(self, cam, resx: int, resy: int, rect=None, stats=None, stream=None):
+        """-> (t, u, v, instance, tri_id) row-major [resy, resx] tensors; miss = (+inf, 0, 0, 0, 0)."""
+        torch = _torch()
+        x0, y0, w, h = rect if rect is not None else (0, 0, resx, resy)
+        d = self._dev()
+        t = torch.full((resy, resx), float("inf"), dtype=torch.float32, device=d)
+        u = torch.zeros((resy, resx), dtype=torch.float32, device=d)
+        v = torch.zeros((resy, resx), dtype=torch.float32, device=d)
+        inst = torch.zeros((resy, resx), dtype=torch.int32, device=d)
+        tri = torch.zeros((resy, resx), dtype=torch.int32, device=d)
+        cam13 = np.ascontiguousarray(cam.as_array13(), dtype=np.float32)
+        rc = _lib.lib().snail_instances_trace_primary_dev(self._h, _lib.ptr(cam13), resx, resy, x0, y0, w, h, _lib.ptr(t), _lib.ptr(u), _lib.ptr(v),
+                                                         _lib.ptr(inst), _lib.ptr(tri), _lib.ptr(stats), _stream_ptr(stream))
+        _lib.check(rc, "snail_instances_trace_primary_dev")
+        return t, u, v, inst, tri
+
+    def trace_packets(self, cam, resx: int, resy: int, packet_xy, stats=None, stream=None):
+        """Packet-major [n,256] (t, u, v, instance, tri_id) of the packets at int32 [n,2] pixel origins (device tensor)."""
+        torch = _torch()
+        n = int(packet_xy.shape[0])
+        d = self._dev()
+        t = torch.full((n, 256), float("inf"), dtype=torch.float32, device=d)
+        u = torch.zeros((n, 256), dtype=torch.float32, device=d)
+        v = torch.zeros((n, 256), dtype=torch.float32, device=d)
+        inst = torch.zeros((n, 256), dtype=torch.int32, device=d)
+        tri = torch.zeros((n, 256), dtype=torch.int32, device=d)
+        cam13 = np.ascontiguousarray(cam.as_array13(), dtype=np.float32)
+        rc = _lib.lib().snail_instances_trace_packets_dev(self._h, _lib.ptr(cam13), resx, resy, _lib.ptr(packet_xy), n, _lib.ptr(t), _lib.ptr(u), _lib.ptr(v),
+                                                         _lib.ptr(inst), _lib.ptr(tri), _lib.ptr(stats), _stream_ptr(stream))
+        _lib.check(rc, "snail_instances_trace_packets_dev")
+        return t, u, v, inst, tri
+
+    def render_depth(self, cam, resx: int, resy: int, arith=None, stream=None):
+        """The gVals[1] depth-shaded RGB8 frame [resy, resx, 3] (B,G,R) of the instanced scene: packet-major distances, then the existing
+        shade_depth and frame-store kernels."""
+        torch = _torch()
+        from .render import divide_image, tile_packets
+        xy = np.ascontiguousarray(tile_packets(divide_image(resx, resy)), dtype=np.int32).reshape(-1, 2)
+        pxy = torch.from_numpy(xy).to(self._dev())
+        t = self.trace_packets(cam, resx, resy, pxy, stream=stream)[0]
+        a = arith if arith is not None else self.blas[0].arith()
+        bgr = Scene.shade_depth(t, stream=stream, arith=a)
+        frame = torch.zeros((resy, resx, 3), dtype=torch.uint8, device=self._dev())
+        Scene.packets_bgr_to_frame(pxy, bgr, frame, stream=stream)
+        return frame
+
+    def traverse_primary(self, ctx: Context, element, stats=None, stream=None) -> Context:
+        """DBVH::TraversePrimary<shared_origin, mask>: ctx.distance / ctx.object (= instance slot) / element (= triId) / ctx.barycentric
+        (may be None) IN/OUT."""
+        rc = _lib.lib().snail_instances_trace_rays_dev(self._h, ctx.n_packets, ctx.size, int(ctx.shared_origin), _lib.ptr(ctx.origin), _lib.ptr(ctx.dir),
+                                                      _lib.ptr(ctx.idir), _lib.ptr(ctx.mask), _lib.ptr(ctx.distance), _lib.ptr(ctx.object), _lib.ptr(element),
+                                                      _lib.ptr(ctx.barycentric), _lib.ptr(stats), _stream_ptr(stream))
+        _lib.check(rc, "snail_instances_trace_rays_dev")
+        return ctx
+
+    def traverse_shadow(self, ctx: ShadowContext, stats=None, stream=None) -> ShadowContext:
+        rc = _lib.lib().snail_instances_trace_shadow_dev(self._h, ctx.n_packets, ctx.size, _lib.ptr(ctx.origin), _lib.ptr(ctx.dir), _lib.ptr(ctx.idir),
+                                                        _lib.ptr(ctx.distance), _lib.ptr(stats), _stream_ptr(stream))
+        _lib.check(rc, "snail_instances_trace_shadow_dev")
+        return ctx
+
+
+__all__ = ["InstancedScene", "build_instances", "HitFrame"]

@@ -400,3 +400,26 @@ def scene_by_name(name: str, scenes_dir: str | None = None) -> np.ndarray:
     if not os.path.exists(path) and scenes_dir:
         path = os.path.join(scenes_dir, name)
     return load_obj(path)
+
+
+def instance_field(bbox_min, bbox_max, n: int, seed: int = 5, n_blas: int = 1):
+    """A layout of `n` rigid instances in the manner of the reference's -instances mode (MakeDBVH, src/rtracer.cpp:146-178): scale =
+    |bbox size| * 0.015, translations uniform in +-500 * scale, rotations from three angles (R = Rz * Ry * Rx), the identity instance last;
+    BLAS indices cycle over n_blas.  Deterministic from `seed`; not claimed equal to the reference's demo (its Rotate lives in libfwk).
+    -> (rotations float32 [n,3,3] (rows), translations float32 [n,3], blas_index int32 [n])."""
+    lo, hi = np.asarray(bbox_min, dtype=np.float64), np.asarray(bbox_max, dtype=np.float64)
+    scale = float(np.linalg.norm(hi - lo)) * 0.015
+    rng = np.random.default_rng(seed)
+    rot = np.zeros((n, 3, 3), dtype=np.float32)
+    tr = np.zeros((n, 3), dtype=np.float32)
+    for i in range(n):
+        if i == n - 1:
+            rot[i] = np.eye(3, dtype=np.float32)
+            continue
+        a, b, c = rng.uniform(0.0, 2.0 * np.pi, 3)
+        rx = np.array([[1, 0, 0], [0, np.cos(a), -np.sin(a)], [0, np.sin(a), np.cos(a)]])
+        ry = np.array([[np.cos(b), 0, np.sin(b)], [0, 1, 0], [-np.sin(b), 0, np.cos(b)]])
+        rz = np.array([[np.cos(c), -np.sin(c), 0], [np.sin(c), np.cos(c), 0], [0, 0, 1]])
+        rot[i] = (rz @ ry @ rx).astype(np.float32)
+        tr[i] = rng.uniform(-500.0 * scale, 500.0 * scale, 3).astype(np.float32)
+    return rot, tr, (np.arange(n) % max(1, int(n_blas))).astype(np.int32)
