@@ -162,7 +162,8 @@ int snail_trace_packets_shaded_dev(SnailScene *, const float cam[13], int resx, 
  * the launches above plus two optional device arrays of nSlots int32 -- nSlots = snail_primary_slots(w, h) for a rect (>= the
  * number of its packets; some slots hold no packet) and nPackets for a list:
  *   d_slot_cost (out): node visits of each slot's packet in THIS launch (0 for an empty slot);
- *   d_order     (in) : the slot each workgroup takes, a permutation of [0, nSlots); NULL = the built-in order.
+ *   d_order     (in) : the slot each dispatch rank takes, a permutation of [0, nSlots); NULL = the built-in order.  Rank r is
+ *                      workgroup r of a one-frame launch; in a multi-frame launch (below) each rank is taken by nFrames workgroups.
  * snail_order_from_cost_dev turns the costs of one frame into the order of the next (stream-ordered, one small kernel on the CURRENT
  * device, no scratch; costs below zero count as zero and, for inputs of up to 49152 slots, costs above 65535 as 65535).  The order it
  * writes is ALWAYS a permutation of [0, nSlots); which one is the library's choice (round 5): for HEAVY-TAILED costs -- the cost of the
@@ -196,10 +197,12 @@ int snail_order_from_cost_hint_dev(const int32_t *d_slot_cost, int nSlots, int32
  * 20480 slots fall back to that kernel inside the call. */
 /* Multi-frame launches: ONE launch traces nFrames (1..SNAIL_MAX_BATCH) frames of the same rect / packet list, each with its own camera
  * (cams13: HOST array nFrames x 13) and its own output planes (HOST arrays of nFrames DEVICE pointers; a NULL array = that plane is not
- * wanted).  The heaviest packets of all the frames are dispatched first; a frame's tail -- ~0.2 ms whatever the launch holds -- and the
- * launch overheads are paid once per nFrames frames.  What it costs is latency (a frame is complete when its launch is): the choice of
- * a host that renders a camera path for throughput, or whose launches are small (one rank's share of a frame).  Hit records, shaded
- * bytes and counters are those of nFrames single-frame launches; d_slot_cost receives the first frame's costs. */
+ * wanted).  The heaviest packets of all the frames are dispatched first: the launch runs rank by rank, a group of 8 ranks at a time in
+ * every frame, and the nFrames copies of a rank (the same slot of every frame) are consecutive workgroups of one XCD, i.e. of one L2.
+ * A frame's tail -- ~0.2 ms whatever the launch holds -- and the launch overheads are paid once per nFrames frames.  What it costs
+ * is latency (a frame is complete when its launch is): the choice of a host that renders a camera path for throughput, or whose
+ * launches are small (one rank's share of a frame).  Hit records, shaded bytes and counters are those of nFrames single-frame
+ * launches; d_slot_cost receives the first frame's costs. */
 #define SNAIL_MAX_BATCH 8
 int snail_trace_primary_batch_dev(SnailScene *, int nFrames, const float *cams13, int resx, int resy, float *const *d_t, float *const *d_u,
                                   float *const *d_v, int32_t *const *d_triId, uint64_t *d_stats, const int32_t *d_order,

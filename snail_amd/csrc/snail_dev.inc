@@ -1907,7 +1907,9 @@ __device__ __forceinline__ PrimaryArgsK lateArgs() {
 // Blocks are dealt round-robin over the 8 XCDs (each with a private L2): XCD x receives blocks x, x+8, ...
 // Give each XCD whole 4x4-packet REGIONS (64x64 px; its 16 consecutive blocks), regions interleaved over the
 // image: neighbouring packets (same BVH subtrees) share an L2, and every XCD samples the whole frame, so a
-// heavy image band does not land on one XCD.
+// heavy image band does not land on one XCD.  b is the dispatch RANK: the hardware block in a one-frame launch;
+// in a multi-frame launch k_primary maps block B to a rank with the same B & 7 (SNAIL_FRAME_XCD_MAJOR), so
+// XCD group g still gets region set g, now for every frame of the launch.
 __device__ __forceinline__ int interleave16(int b) { // -> logical index; 16 consecutive logical indices per XCD turn
 	const int xcd = b & 7, j = b >> 3;
 	return (((j >> 4) << 3) + xcd) * 16 + (j & 15);
@@ -2075,9 +2077,17 @@ __device__ __forceinline__ void primaryPacket(const PrimaryArgs &A, const int li
 #define SNAIL_PRIMARY_WAVES 6 // occupancy target of the primary kernel (76 VGPRs by itself; 7 = 72 VGPRs measured separately: profiles/README.md)
 #endif
 // SNAIL_BLOCK_WAVES packets per workgroup (one per wave; waves end independently, nothing of the block is shared): the XCD's
-// region turn is kept -- wave w of hardware block B takes entry (B >> 3) * W + w of XCD (B & 7)'s list.
+// region turn is kept -- wave w of hardware block B takes entry (B >> 3) * W + w of XCD (B & 7)'s list.  One-frame launches only
+// (launchPrimaryFrames refuses W > 1 with several frames); W = 1 is the block -> (frame, rank) map of SNAIL_FRAME_XCD_MAJOR below.
 #ifndef SNAIL_BLOCK_WAVES
 #define SNAIL_BLOCK_WAVES 1 // 2 and 4 measured slower (22.65 / 21.80 vs 23.40 Grays/s): residency is not limited by workgroup slots
+#endif
+// Frames of a multi-frame launch (grid = nFrames x the slot count, a multiple of 128): hardware block B runs on XCD group B & 7 and takes frame
+// (B >> 3) % F at rank ((B >> 3) / F) * 8 + (B & 7) -- the F copies of a rank (the same packet of every frame: same subtrees, same triangles) run
+// back to back on ONE XCD, whose L2 then fetches their lines once, and XCD group g keeps its own region set g of interleave16.  F = 1: rank B.
+// 0 = frame-minor (frame B % F at rank B / F): the copies of a rank on F different XCDs, each XCD tied to frame g % F.  DESIGN.md section 2
+#ifndef SNAIL_FRAME_XCD_MAJOR
+#define SNAIL_FRAME_XCD_MAJOR 1
 #endif
 #ifndef SNAIL_PRIO_RANK
 #define SNAIL_PRIO_RANK 0 // round 5: OFF.  Issue priority by dispatch rank (s_setprio 3 / 2 / 1 for the first N / 2N / 4N blocks of an ordered launch; N = 1024 in rounds 2-4)
@@ -2091,7 +2101,15 @@ __global__ __launch_bounds__(64 * SNAIL_BLOCK_WAVES) __attribute__((amdgpu_waves
 	const int wv = SNAIL_BLOCK_WAVES > 1 ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : 0;
 	int b = (int)blockIdx.x * SNAIL_BLOCK_WAVES + wv; // dispatch index of this wave's packet
 	int fi = 0;
-	if(A.nFrames > 1) { fi = b % A.nFrames; b = b / A.nFrames; } // several frames in one launch: frame fi at dispatch rank b
+	if(A.nFrames > 1) { // several frames in one launch: frame fi at dispatch rank b
+#if SNAIL_FRAME_XCD_MAJOR
+		const int t = b >> 3;   // (SNAIL_BLOCK_WAVES == 1 whenever nFrames > 1: b is the hardware block)
+		fi = t % A.nFrames;
+		b = ((t / A.nFrames) << 3) | (b & 7);
+#else
+		fi = b % A.nFrames; b = b / A.nFrames;
+#endif
+	}
 	int li;
 	if(SNAIL_BLOCK_WAVES > 1) {
 		const int xcd = (int)blockIdx.x & 7, j = ((int)blockIdx.x >> 3) * SNAIL_BLOCK_WAVES + wv;   // (single-frame launches only)

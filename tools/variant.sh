@@ -7,5 +7,6 @@ name=$1; shift
 cd "$(dirname "$0")/../snail_amd/csrc"
 mkdir -p ../exp
 FLAGS=$(grep '^FLAGS' Makefile | sed 's/^FLAGS *?= *//')
-/opt/rocm/bin/hipcc --offload-arch=gfx950 $FLAGS "$@" -shared snail_hip.hip bvh_build.cpp host_sse.cpp -o ../exp/lib_$name.so
+CPPS=$(grep '^CPPS' Makefile | sed 's/^CPPS *:= *//')
+/opt/rocm/bin/hipcc --offload-arch=gfx950 $FLAGS "$@" -shared snail_hip.hip $CPPS -o ../exp/lib_$name.so
 echo "built snail_amd/exp/lib_$name.so ($*)"
