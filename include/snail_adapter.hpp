@@ -598,9 +598,10 @@ inline TreeStats Render(const Scene<snail::HipBVH<RefBVH>> &scene, const Camera 
 	mode.antialias = gVals[9] != 0;
 	return snail::RenderImage<TreeStats>(scene, camera, image, mode);
 }
-// Scene<snail::HipDBVH<...>>: the gVals[1] depth image is made on the device (snail_instances_render_depth); every other switch -- and the
-// tile list, whose planar store has no instanced device path -- goes to the reference's renderer over the prefetched frame, whose
-// TraversePrimary calls copy pre-traced packets and whose shadow / secondary packets go to the device one call each.
+// Scene<snail::HipDBVH<...>>: the image is made on the device (snail_instances_render_image: gVals[1] depth shading, or the lit frame of
+// Scene<DBVH>::RayTrace's simple-shading branch with the scene's lights and ambient, gVals[7] = one mirrored bounce).  gVals[9], gVals[5],
+// gVals[8] -- and the tile list, whose planar store has no instanced device path -- go to the reference's renderer over the prefetched
+// frame, whose TraversePrimary calls copy pre-traced packets and whose shadow / secondary packets go to the device one call each.
 template <class RefDBVH>
 inline TreeStats Render(const Scene<snail::HipDBVH<RefDBVH>> &scene, const Camera &camera, uint resx, uint resy, unsigned char *data, const vector<int> &coords,
 						const vector<int> &offsets, const Options options, uint rank, uint threads) {
@@ -610,14 +611,18 @@ inline TreeStats Render(const Scene<snail::HipDBVH<RefDBVH>> &scene, const Camer
 template <class RefDBVH>
 inline TreeStats Render(const Scene<snail::HipDBVH<RefDBVH>> &scene, const Camera &camera, MipmapTexture &image, const Options options, uint threads) {
 	const char *why = snail::UnsupportedSwitch(gVals, scene.geometry.HasShadingData(), false);
-	if(!why && !gVals[1]) why = "shading other than gVals[1] on an instanced scene";
-	if(!why && (gVals[7] || gVals[9])) why = "gVals[7] / gVals[9] on an instanced scene";
+	if(!why && gVals[9]) why = "gVals[9] (4x antialiasing) on an instanced scene";
+	if(!why && gVals[8]) why = "gVals[8] on an instanced scene";
 	if(why) SNAIL_HOST_RENDER(why, gVals[9] ? 2 : 1, image.Width(), image.Height(), Render<snail::HipDBVH<RefDBVH>>(scene, camera, image, options, threads));
-	(void)options; (void)threads;
+	(void)options; (void)threads;   // (the bounce is gated by gVals[7] alone, src/scene_trace.cpp:454)
 	float c[13];
 	snail::detail::cam13(camera, c);
+	const std::vector<float> l = snail::detail::lights7(scene);
+	const float amb[3] = {scene.ambientLight.x, scene.ambientLight.y, scene.ambientLight.z};
+	const snail::RenderMode mode;
 	uint64_t st[4] = {0, 0, 0, 0};
-	SNAIL_CHECK(snail_instances_render_depth(scene.geometry.Handle(), c, (int)image.Width(), (int)image.Height(), (unsigned char *)image.DataPointer(),
+	SNAIL_CHECK(snail_instances_render_image(scene.geometry.Handle(), c, (int)image.Width(), (int)image.Height(), l.data(), (int)(l.size() / 7), amb, mode.color,
+											 (gVals[1] ? SNAIL_RENDER_DEPTH : 0) | (gVals[7] ? SNAIL_RENDER_REFLECTIONS : 0), (unsigned char *)image.DataPointer(),
 											 (int)image.Pitch(), st));
 	return snail::detail::toStats<TreeStats>(st);
 }

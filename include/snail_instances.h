@@ -92,4 +92,6 @@ int snail_instances_trace_shadow(SnailInstances *, int nPackets, int size, const
 #ifdef __cplusplus
 }
 #endif
+/* lit frames of instanced scenes (lights, shadow packets, one mirrored bounce): declared in a header of their own, part of this one */
+#include "snail_instances_shade.h"
 #endif

@@ -92,6 +92,14 @@ INSTANCES_SIGNATURES = {
     "snail_instances_render_depth": (_I, [_VP, _F13, _I, _I, _VP, _I, _VP]),
 }
 
+# include/snail_instances_shade.h (the lit frames of instanced scenes; part of snail_instances.h): a table of its own for the same reason --
+# tests/c/instances_c.c enumerates INSTANCES_SIGNATURES entry for entry, tests/c/instances_shade_c.c this one
+INSTANCES_SHADE_SIGNATURES = {
+    "snail_instances_render_whitted_dev": (_I, [_VP, _F13, _I, _I, _VP, _I, _VP, _VP, _I, _VP, _I, _VP, _VP]),
+    "snail_instances_render_whitted_packets_dev": (_I, [_VP, _F13, _I, _I, _VP, _I, _VP, _I, _VP, _VP, _I, _VP, _VP, _VP]),
+    "snail_instances_render_image": (_I, [_VP, _F13, _I, _I, _VP, _I, _VP, _VP, _I, _VP, _I, _VP]),
+}
+
 # include/snail_hip_debug.h: the workbench build only (libsnailhip_debug.so, -DSNAIL_DEBUG_API)
 DEBUG_SIGNATURES = {
     "snail_debug_delay_dev": (_I, [C.c_float, _VP]),
@@ -114,7 +122,7 @@ def debug_lib():
         if not os.path.exists(DEBUG_LIB_PATH):
             raise SnailError("workbench library %s is missing: `make -C snail_amd/csrc debug`" % DEBUG_LIB_PATH)
         L = C.CDLL(DEBUG_LIB_PATH)
-        for table in (SIGNATURES, INSTANCES_SIGNATURES, DEBUG_SIGNATURES):
+        for table in (SIGNATURES, INSTANCES_SIGNATURES, INSTANCES_SHADE_SIGNATURES, DEBUG_SIGNATURES):
             for name, (res, args) in table.items():
                 fn = getattr(L, name)
                 fn.restype = res
@@ -135,7 +143,7 @@ def lib():
             L = C.CDLL(LIB_PATH)
         except OSError as e:  # pragma: no cover - depends on the box
             raise SnailError("cannot load %s: %s" % (LIB_PATH, e)) from e
-        for table in (SIGNATURES, INSTANCES_SIGNATURES):
+        for table in (SIGNATURES, INSTANCES_SIGNATURES, INSTANCES_SHADE_SIGNATURES):
             for name, (res, args) in table.items():
                 fn = getattr(L, name)
                 fn.restype = res

@@ -21,6 +21,48 @@ struct SnailInstances {
 	size_t stagingCap = 0;
 	hipEvent_t stagingFree = nullptr;
 	bool stagingUsed = false;
+	// intermediates of snail_instances_render_whitted*_dev (hits, shadow distances, mirrored packets and colours), one set per launch in flight:
+	// handed out round-robin, a recycled set's next user waits for the event recorded after its previous user's last kernel
+	struct ShadeBufs {
+		float *hitT = nullptr; int *hitInst = nullptr, *hitTri = nullptr;
+		float *sDist = nullptr;
+		float *rOrg = nullptr, *rDir = nullptr, *rIDir = nullptr, *rDist = nullptr, *rCol = nullptr;
+		int *rInst = nullptr, *rTri = nullptr;
+		unsigned char *rMask = nullptr;
+		static size_t bytes(size_t packets, int lights, bool refl) {
+			const size_t rays = packets * 256;
+			return rays * 12 + rays * 4 * (size_t)lights + (refl ? rays * (36 + 12 + 12) + packets * 64 : 0) + 256;
+		}
+		void carve(char *base, size_t packets, int lights, bool refl) {
+			const size_t rays = packets * 256;
+			hitT = (float *)base; base += rays * 4;
+			hitInst = (int *)base; base += rays * 4;
+			hitTri = (int *)base; base += rays * 4;
+			sDist = (float *)base; base += rays * 4 * (size_t)lights;
+			if(!refl) return;
+			rOrg = (float *)base; base += rays * 12;
+			rDir = (float *)base; base += rays * 12;
+			rIDir = (float *)base; base += rays * 12;
+			rDist = (float *)base; base += rays * 4;
+			rInst = (int *)base; base += rays * 4;
+			rTri = (int *)base; base += rays * 4;
+			rCol = (float *)base; base += rays * 12;
+			rMask = (unsigned char *)base;
+		}
+	};
+	enum { kShadeSets = 8 };
+	struct ShadeSet {
+		ShadeBufs b;
+		char *base = nullptr;
+		size_t packets = 0;
+		bool refl = false;
+		hipEvent_t done = nullptr;
+		bool used = false;
+	} shade[kShadeSets];
+	unsigned shadeCount = 0;
+	// packet lists of whole frames (row-major over the 16x16 packet grid), by grid size; built once each
+	struct FrameList { int pw, ph; int32_t *d; };
+	std::vector<FrameList> frameLists;
 };
 
 namespace {
@@ -231,6 +273,122 @@ static int instancesFramePackets(SnailInstances *h, const char *fn, HostCallScop
 	*nPackets = np;
 	return instancesPrimary(h, fn, cam, resx, resy, 0, 0, 0, 0, (const int32_t *)*dXY, np, *dT, *dU, *dV, *dI, *dTri, hc.stats(), hc.stream());
 }
+
+// ---- Scene<DBVH>::RayTrace, simple-shading configuration (instances_shade.inc) ----
+int checkShadeArgs(const char *fn, const float cam[13], int resx, int resy, const float *lights7, int nLights, const float ambient[3], const float color[3]) {
+	if(!cam || resx <= 0 || resy <= 0 || nLights < 0 || nLights > SNAIL_MAX_LIGHTS || (nLights && !lights7) || !ambient || !color) {
+		snail_set_error("%s: bad arguments (camera, resolution, at most %d lights, ambient, color)", fn, SNAIL_MAX_LIGHTS);
+		return 1;
+	}
+	return 0;
+}
+
+#define SNAIL_INST_SHADE_LAUNCH(SSE, GRID, STREAM, A, ...) SNAIL_LAUNCH(SSE, InstShadeArgs, GRID, dim3(64), 0, STREAM, A, __VA_ARGS__)
+
+// the stages of one lit frame over the packet list dXY into `frame` (or packet-major `bgrPackets`), intermediates in W; mu held
+int instancesShade(SnailInstances *h, const char *fn, const float cam[13], int resx, int resy, const int32_t *dXY, int np, const float *lights7, int nLights,
+				   const float ambient[3], const float color[3], bool refl, uint8_t *frame, int pitch, uint8_t *bgrPackets, const SnailInstances::ShadeBufs &W,
+				   uint64_t *dStats, hipStream_t st) {
+	dev::InstArgs I;
+	bool sse, deep;
+	if(int rc = instancesBegin(h, fn, I, &sse, &deep, st)) return rc;
+	const dim3 grid(np);
+	// primary hits
+	dev::InstArgs P = I;
+	P.g = makeGen(cam, resx, resy);
+	P.resx = resx; P.resy = resy;
+	P.packetXY = (const int2 *)dXY; P.nPackets = np;
+	P.t = W.hitT; P.instOut = W.hitInst; P.triOut = W.hitTri;
+	P.stats = (dev::u64 *)dStats;
+	if(deep) SNAIL_INST_LAUNCH(sse, grid, st, P, k_inst_frame<true>);
+	else SNAIL_INST_LAUNCH(sse, grid, st, P, k_inst_frame<false>);
+
+	dev::InstShadeArgs A;
+	memset(&A, 0, sizeof(A));
+	A.i = I;
+	A.s.hostTab = I.hostTab;
+	A.s.g = P.g;
+	A.s.resx = resx; A.s.resy = resy; A.s.pw = (resx + 15) / 16; A.s.ph = (resy + 15) / 16;
+	A.s.packetXY = (const int2 *)dXY; A.s.nPackets = np; A.s.nBlocks = np;
+	A.s.bgrPackets = bgrPackets; A.s.frame = frame; A.s.pitch = pitch;
+	A.s.nLights = nLights;
+	for(int n = 0; n < nLights; n++) for(int k = 0; k < 7; k++) A.s.lights[n][k] = lights7[n * 7 + k];
+	for(int c = 0; c < 3; c++) { A.s.ambient[c] = ambient[c]; A.s.color[c] = color[c]; }
+	A.s.hitT = W.hitT; A.s.hitId = W.hitTri; A.hitInst = W.hitInst;
+	A.s.rOrg = W.rOrg; A.s.rDir = W.rDir; A.s.rIDir = W.rIDir; A.s.rMask = W.rMask; A.s.rDist = W.rDist; A.s.rObj = W.rTri; A.rInst = W.rInst; A.s.rCol = W.rCol;
+	A.s.sDist = W.sDist;
+	A.s.blend = refl ? 1 : 0;
+	A.s.stats = (dev::u64 *)dStats;
+	const dim3 lgrid(np, nLights > 0 ? nLights : 1);
+	if(refl) { // the nested RayTrace of the mirrored packets
+		SNAIL_INST_SHADE_LAUNCH(sse, grid, st, A, k_inst_final<dev::SRC_PRIMARY, dev::DST_MIRROR>);
+		dev::InstArgs R = I;
+		R.nPackets = np; R.size = 64;
+		R.origin = W.rOrg; R.dir = W.rDir; R.idir = W.rIDir; R.mask = W.rMask;
+		R.distance = W.rDist; R.object = W.rInst; R.element = W.rTri;
+		R.stats = (dev::u64 *)dStats;
+		if(deep) SNAIL_INST_LAUNCH(sse, grid, st, R, k_inst_trace<false, true, true, false>);
+		else SNAIL_INST_LAUNCH(sse, grid, st, R, k_inst_trace<false, true, false, false>);
+		if(nLights) {
+			if(deep) SNAIL_INST_SHADE_LAUNCH(sse, lgrid, st, A, k_inst_light<true, dev::SRC_MIRROR>);
+			else SNAIL_INST_SHADE_LAUNCH(sse, lgrid, st, A, k_inst_light<false, dev::SRC_MIRROR>);
+		}
+		SNAIL_INST_SHADE_LAUNCH(sse, grid, st, A, k_inst_final<dev::SRC_MIRROR, dev::DST_COLOR>);
+	}
+	if(nLights) {
+		if(deep) SNAIL_INST_SHADE_LAUNCH(sse, lgrid, st, A, k_inst_light<true, dev::SRC_PRIMARY>);
+		else SNAIL_INST_SHADE_LAUNCH(sse, lgrid, st, A, k_inst_light<false, dev::SRC_PRIMARY>);
+	}
+	SNAIL_INST_SHADE_LAUNCH(sse, grid, st, A, k_inst_final<dev::SRC_PRIMARY, dev::DST_FRAME>);
+	return instancesEnd(h, st);
+}
+
+// the packet list of a whole frame, cached in the handle by packet-grid size (mu held)
+int instancesFrameList(SnailInstances *h, int resx, int resy, const int32_t **dXY, int *np) {
+	const int pw = (resx + 15) / 16, ph = (resy + 15) / 16;
+	*np = pw * ph;
+	for(auto &f : h->frameLists)
+		if(f.pw == pw && f.ph == ph) { *dXY = f.d; return 0; }
+	if(h->frameLists.size() >= 16) { // (a host that keeps changing its resolution: start over once nothing reads the old lists)
+		HIP_TRY(hipDeviceSynchronize());
+		for(auto &f : h->frameLists) (void)hipFree(f.d);
+		h->frameLists.clear();
+	}
+	std::vector<int32_t> xy((size_t)pw * ph * 2);
+	for(int y = 0; y < ph; y++)
+		for(int x = 0; x < pw; x++) { xy[((size_t)y * pw + x) * 2] = x * 16; xy[((size_t)y * pw + x) * 2 + 1] = y * 16; }
+	SnailInstances::FrameList f = {pw, ph, nullptr};
+	HIP_TRY(hipMalloc((void **)&f.d, xy.size() * 4));
+	if(hipMemcpy(f.d, xy.data(), xy.size() * 4, hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(f.d); snail_set_error("frame packet list: upload failed"); return 1; }
+	h->frameLists.push_back(f);
+	*dXY = f.d;
+	return 0;
+}
+
+// snail_instances_render_whitted_dev / _packets_dev: the next set of intermediates of the handle, grown if need be (mu held)
+int instancesShadeDev(SnailInstances *h, const char *fn, const float cam[13], int resx, int resy, const int32_t *dXY, int np, const float *lights7, int nLights,
+					  const float ambient[3], const float color[3], int flags, uint8_t *frame, int pitch, uint8_t *bgrPackets, uint64_t *dStats, hipStream_t st) {
+	const bool refl = (flags & SNAIL_WHITTED_REFLECTIONS) != 0;
+	if(!dXY) { if(int rc = instancesFrameList(h, resx, resy, &dXY, &np)) return rc; }
+	SnailInstances::ShadeSet &W = h->shade[h->shadeCount++ % SnailInstances::kShadeSets];
+	if(!W.base || W.packets < (size_t)np || (refl && !W.refl)) { // grown (shadow distances sized for SNAIL_MAX_LIGHTS once): its previous user may still be running
+		HIP_TRY(hipDeviceSynchronize());
+		if(W.base) (void)hipFree(W.base);
+		const size_t packets = std::max(W.packets, (size_t)np);
+		const bool r = refl || W.refl;
+		W.base = nullptr; W.packets = 0; W.refl = false; W.used = false;
+		HIP_TRY(hipMalloc((void **)&W.base, SnailInstances::ShadeBufs::bytes(packets, SNAIL_MAX_LIGHTS, r)));
+		W.packets = packets; W.refl = r;
+	}
+	W.b = SnailInstances::ShadeBufs();
+	W.b.carve(W.base, (size_t)np, nLights, refl);
+	if(!W.done) HIP_TRY(hipEventCreateWithFlags(&W.done, hipEventDisableTiming));
+	if(W.used) HIP_TRY(hipStreamWaitEvent(st, W.done, 0));
+	if(int rc = instancesShade(h, fn, cam, resx, resy, dXY, np, lights7, nLights, ambient, color, refl, frame, pitch, bgrPackets, W.b, dStats, st)) return rc;
+	HIP_TRY(hipEventRecord(W.done, st));
+	W.used = true;
+	return 0;
+}
 } // namespace
 
 extern "C" {
@@ -287,6 +445,11 @@ void snail_instances_destroy(SnailInstances *h) {
 	if(h->ready) (void)hipEventDestroy(h->ready);
 	if(h->stagingFree) (void)hipEventDestroy(h->stagingFree);
 	for(auto &u : h->uses) (void)hipEventDestroy(u.ev);
+	for(auto &w : h->shade) {
+		if(w.base) (void)hipFree(w.base);
+		if(w.done) (void)hipEventDestroy(w.done);
+	}
+	for(auto &f : h->frameLists) (void)hipFree(f.d);
 	delete h;
 }
 
@@ -418,6 +581,69 @@ int snail_instances_render_depth(SnailInstances *h, const float cam[13], int res
 	else (void)hipStreamSynchronize(hc.stream());
 	(void)hipFree(dImg);
 	return rc;
+}
+
+int snail_instances_render_whitted_dev(SnailInstances *h, const float cam[13], int resx, int resy, const float *lights7, int nLights, const float ambient[3],
+									   const float color[3], int flags, uint8_t *frame, int pitch, uint64_t *dStats, void *stream) {
+	const char *fn = "snail_instances_render_whitted_dev";
+	if(int rc = checkInstances(h, fn)) return rc;
+	if(int rc = checkShadeArgs(fn, cam, resx, resy, lights7, nLights, ambient, color)) return rc;
+	if((flags & ~SNAIL_WHITTED_REFLECTIONS) || !frame || pitch < resx * 3) { snail_set_error("%s: bad frame, or flags other than SNAIL_WHITTED_REFLECTIONS", fn); return 1; }
+	DeviceGuard guard(h->device);
+	std::lock_guard<std::mutex> lock(h->mu);
+	return instancesShadeDev(h, fn, cam, resx, resy, nullptr, 0, lights7, nLights, ambient, color, flags, frame, pitch, nullptr, dStats, (hipStream_t)stream);
+}
+
+int snail_instances_render_whitted_packets_dev(SnailInstances *h, const float cam[13], int resx, int resy, const int32_t *dPacketXY, int nPackets,
+											   const float *lights7, int nLights, const float ambient[3], const float color[3], int flags, uint8_t *bgrPackets,
+											   uint64_t *dStats, void *stream) {
+	const char *fn = "snail_instances_render_whitted_packets_dev";
+	if(int rc = checkInstances(h, fn)) return rc;
+	if(!dPacketXY && nPackets > 0) { snail_set_error("%s: null packet list", fn); return 1; }
+	if(nPackets <= 0) return 0;
+	if(int rc = checkShadeArgs(fn, cam, resx, resy, lights7, nLights, ambient, color)) return rc;
+	if((flags & ~SNAIL_WHITTED_REFLECTIONS) || !bgrPackets || ((unsigned long long)bgrPackets & 3)) {
+		snail_set_error("%s: null or unaligned output, or flags other than SNAIL_WHITTED_REFLECTIONS", fn);
+		return 1;
+	}
+	DeviceGuard guard(h->device);
+	std::lock_guard<std::mutex> lock(h->mu);
+	return instancesShadeDev(h, fn, cam, resx, resy, dPacketXY, nPackets, lights7, nLights, ambient, color, flags, nullptr, 0, bgrPackets, dStats, (hipStream_t)stream);
+}
+
+int snail_instances_render_image(SnailInstances *h, const float cam[13], int resx, int resy, const float *lights7, int nLights, const float ambient[3],
+								 const float color[3], int flags, uint8_t *image, int pitch, uint64_t stats[4]) {
+	const char *fn = "snail_instances_render_image";
+	if(int rc = checkInstances(h, fn)) return rc;
+	if(flags & SNAIL_RENDER_AA4) { snail_set_error("%s: SNAIL_RENDER_AA4 is not available for instanced scenes", fn); return 1; }
+	if(flags & ~(SNAIL_RENDER_REFLECTIONS | SNAIL_RENDER_DEPTH)) { snail_set_error("%s: unknown flags 0x%x", fn, flags); return 1; }
+	if(!cam || resx <= 0 || resy <= 0 || !image || pitch < resx * 3) { snail_set_error("%s: bad camera, resolution or image", fn); return 1; }
+	if(flags & SNAIL_RENDER_DEPTH) return snail_instances_render_depth(h, cam, resx, resy, image, pitch, stats);
+	if(int rc = checkShadeArgs(fn, cam, resx, resy, lights7, nLights, ambient, color)) return rc;
+	const bool refl = (flags & SNAIL_RENDER_REFLECTIONS) != 0;
+	DeviceGuard guard(h->device);
+	HostCallScope hc(h->blas[0], fn);
+	if(hc.rc) return hc.rc;
+	if(int rc = hc.zeroStats()) return rc;
+	const int pw = (resx + 15) / 16, ph = (resy + 15) / 16, np = pw * ph;
+	std::vector<int32_t> xy((size_t)np * 2);
+	for(int y = 0; y < ph; y++)
+		for(int x = 0; x < pw; x++) { xy[((size_t)y * pw + x) * 2] = x * 16; xy[((size_t)y * pw + x) * 2 + 1] = y * 16; }
+	typedef HostCallScope H;
+	const size_t imgBytes = (size_t)pitch * resy;
+	if(int rc = hc.reserve(H::pad(xy.size() * 4) + H::pad(SnailInstances::ShadeBufs::bytes((size_t)np, nLights, refl)) + H::pad(imgBytes + 4))) return rc;
+	void *dXY = nullptr;
+	if(int rc = hc.put(&dXY, xy.data(), xy.size() * 4)) return rc;
+	SnailInstances::ShadeBufs W;
+	W.carve((char *)hc.carve(SnailInstances::ShadeBufs::bytes((size_t)np, nLights, refl)), (size_t)np, nLights, refl);
+	uint8_t *dImg = (uint8_t *)hc.carve(imgBytes + 4);
+	{
+		std::lock_guard<std::mutex> lock(h->mu);
+		if(int rc = instancesShade(h, fn, cam, resx, resy, (const int32_t *)dXY, np, lights7, nLights, ambient, color, refl, dImg, pitch, nullptr, W, hc.stats(), hc.stream()))
+			return rc;
+	}
+	HIP_TRY(hipMemcpy2DAsync(image, (size_t)pitch, dImg, (size_t)pitch, (size_t)resx * 3, (size_t)resy, hipMemcpyDeviceToHost, hc.stream()));
+	return hc.finish(stats);
 }
 
 } // extern "C"

@@ -76,12 +76,14 @@ void snail_set_error(const char *fmt, ...) {
 #define SNAIL_ARITH_SSE 0
 #include "snail_dev.inc"
 #include "instances.inc"
+#include "instances_shade.inc"
 #undef SNAIL_DEV_NS
 #undef SNAIL_ARITH_SSE
 #define SNAIL_DEV_NS dev_sse
 #define SNAIL_ARITH_SSE 1
 #include "snail_dev.inc"
 #include "instances.inc"
+#include "instances_shade.inc"
 #undef SNAIL_DEV_NS
 #undef SNAIL_ARITH_SSE
 

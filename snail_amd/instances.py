@@ -172,6 +172,55 @@ class InstancedScene:
         Scene.packets_bgr_to_frame(pxy, bgr, frame, stream=stream)
         return frame
 
+    def render_whitted(self, cam, resx: int, resy: int, lights7, ambient=(0.1, 0.1, 0.1), color=(1.0, 1.0, 1.0), out=None, stats=None, stream=None,
+                       reflections: bool = False):
+        """Scene<DBVH>::RayTrace in the simple-shading configuration (Scene.render_whitted for an instanced scene: primary packets, one
+        shadow packet per point light, reflections=True = gVals[7]), staged on the device; returns the interleaved [resy,resx,3] uint8
+        (B,G,R) frame.  snail_instances_render_whitted_dev."""
+        torch = _torch()
+        if out is None:
+            out = torch.zeros((resy, resx, 3), dtype=torch.uint8, device=self._dev())
+        lights = np.ascontiguousarray(lights7 if lights7 is not None else np.zeros((0, 7)), dtype=np.float32).reshape(-1, 7)
+        cam13 = np.ascontiguousarray(cam.as_array13(), dtype=np.float32)
+        amb = np.ascontiguousarray(ambient, dtype=np.float32); col = np.ascontiguousarray(color, dtype=np.float32)
+        rc = _lib.lib().snail_instances_render_whitted_dev(self._h, _lib.ptr(cam13), resx, resy, _lib.ptr(lights) if len(lights) else None, len(lights),
+                                                          _lib.ptr(amb), _lib.ptr(col), 1 if reflections else 0, _lib.ptr(out), resx * 3, _lib.ptr(stats),
+                                                          _stream_ptr(stream))
+        _lib.check(rc, "snail_instances_render_whitted_dev")
+        return out
+
+    def render_whitted_packets(self, cam, resx: int, resy: int, packet_xy, lights7, ambient=(0.1, 0.1, 0.1), color=(1.0, 1.0, 1.0), out=None, stats=None,
+                               stream=None, reflections: bool = False):
+        """render_whitted for an explicit packet list (int32 [n,2] device tensor): packet-major [n,256,3] uint8 (B,G,R)."""
+        torch = _torch()
+        n = int(packet_xy.shape[0])
+        if out is None:
+            out = torch.empty((n, 256, 3), dtype=torch.uint8, device=self._dev())
+        lights = np.ascontiguousarray(lights7 if lights7 is not None else np.zeros((0, 7)), dtype=np.float32).reshape(-1, 7)
+        cam13 = np.ascontiguousarray(cam.as_array13(), dtype=np.float32)
+        amb = np.ascontiguousarray(ambient, dtype=np.float32); col = np.ascontiguousarray(color, dtype=np.float32)
+        rc = _lib.lib().snail_instances_render_whitted_packets_dev(self._h, _lib.ptr(cam13), resx, resy, _lib.ptr(packet_xy), n,
+                                                                  _lib.ptr(lights) if len(lights) else None, len(lights), _lib.ptr(amb), _lib.ptr(col),
+                                                                  1 if reflections else 0, _lib.ptr(out), _lib.ptr(stats), _stream_ptr(stream))
+        _lib.check(rc, "snail_instances_render_whitted_packets_dev")
+        return out
+
+    RENDER_REFLECTIONS, RENDER_DEPTH, RENDER_AA4 = 1, 2, 4     # include/snail_hip.h: flags of the host-pointer image call
+
+    def render_image_host(self, cam, resx: int, resy: int, lights7=None, flags: int = 0, ambient=(0.1, 0.1, 0.1), color=(1.0, 1.0, 1.0)):
+        """snail_instances_render_image = Render(scene, camera, image, options, threads) for an instanced scene: the rgb8 frame
+        [resy, resx, 3] (B,G,R) in host memory and the call's TreeStats.  flags: RENDER_REFLECTIONS (gVals[7]), RENDER_DEPTH (gVals[1]);
+        RENDER_AA4 is refused."""
+        lights = np.ascontiguousarray(lights7 if lights7 is not None else np.zeros((0, 7)), dtype=np.float32).reshape(-1, 7)
+        cam13 = np.ascontiguousarray(cam.as_array13(), dtype=np.float32)
+        amb = np.ascontiguousarray(ambient, dtype=np.float32); col = np.ascontiguousarray(color, dtype=np.float32)
+        img = np.zeros((resy, resx, 3), dtype=np.uint8)
+        stats = np.zeros(4, dtype=np.uint64)
+        rc = _lib.lib().snail_instances_render_image(self._h, _lib.ptr(cam13), resx, resy, _lib.ptr(lights) if len(lights) else None, len(lights),
+                                                    _lib.ptr(amb), _lib.ptr(col), int(flags), _lib.ptr(img), resx * 3, _lib.ptr(stats))
+        _lib.check(rc, "snail_instances_render_image")
+        return img, stats
+
     def traverse_primary(self, ctx: Context, element, stats=None, stream=None) -> Context:
         """DBVH::TraversePrimary<shared_origin, mask>: ctx.distance / ctx.object (= instance slot) / element (= triId) / ctx.barycentric
         (may be None) IN/OUT."""

@@ -4,7 +4,18 @@ beside the plain Scene.trace_primary rate of the same BLAS; and what a per-frame
 top-level tree every frame): the host build (snail_instances_build) and a whole InstancedScene.update() -- build + upload, host wall time --
 for --rebuild-counts instances (default 10 000).  Prints one JSON object.  No target: a measurement.
 
-    python tools/instances_time.py [--res 1920x1080] [--reps 5]"""
+    python tools/instances_time.py [--res 1920x1080] [--reps 5]
+
+--lit: what a LIT instanced frame costs instead (one light, atrium, both arithmetics): ms per frame and Mrays/s (primary rays per second) of
+  device      snail_instances_render_whitted_dev, the whole frame in a handful of launches;
+  per_packet  the path it replaces in a C++ host: snail_instances_trace_frame_packets for the primary frame, then ONE snail_instances_trace_shadow
+              call per packet and light with that packet's shadow rays (prepared beforehand: the host's shading arithmetic between the calls is
+              left out, which flatters this path);
+  plain       Scene.render_whitted of the BLAS alone with the same camera and light, for scale.
+Repeated alternating runs, medians.  --baseline-lib PATH loads another build of libsnailhip.so (e.g. the parent commit's, which has no device
+path) and measures per_packet only.
+
+    python tools/instances_time.py --lit [--baseline-lib PATH] [--reps 5]"""
 import argparse
 import json
 import os
@@ -42,8 +53,12 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--counts", default="1,64,1024")
     ap.add_argument("--rebuild-counts", default="10000")
+    ap.add_argument("--lit", action="store_true")
+    ap.add_argument("--baseline-lib", default=None)
     a = ap.parse_args()
     resx, resy = (int(x) for x in a.res.split("x"))
+    if a.lit:
+        return lit(torch, a, resx, resy)
     rays = resx * resy
     out = {"res": a.res, "unit": "Mrays/s (best of %d launches)" % a.reps, "rows": []}
     meshes = {"atrium": lambda: scenes.atrium(),
@@ -69,6 +84,116 @@ def main():
         if name == "atrium":
             out["rebuild"] = rebuild(torch, sc, [int(c) for c in a.rebuild_counts.split(",")], a.reps)
         sc.close()
+    print(json.dumps(out))
+
+
+def shadow_packets_of(isc, cam13, resx, resy, light, t, inst, tri, tris_plane):
+    """The shadow packets a host renderer would trace for one light (src/scene_trace.cpp:538-558), from the frame's packet-major hits:
+    origin3 [1, 3], dir / idir [np*64, 3, 4], distance [np*64, 4] (-inf = masked).  Plain numpy; not timed."""
+    pw, ph = (resx + 15) // 16, (resy + 15) // 16
+    n = pw * ph
+    q = np.arange(64)
+    px = (np.arange(n) % pw * 16)[:, None, None] + (4 * (q & 3))[None, :, None] + np.arange(4)[None, None, :]
+    py = (np.arange(n) // pw * 16)[:, None, None] + (q >> 2)[None, :, None] + np.zeros(4, dtype=np.int64)[None, None, :]
+    pos, right, up, front, pd = cam13[0:3], cam13[3:6], cam13[6:9], cam13[9:12], cam13[12]
+    sx = (px - resx * 0.5) / resy
+    sy = (py - resy * 0.5) / resy
+    d = right[None, None, None, :] * sx[..., None] + up[None, None, None, :] * sy[..., None] + (front * pd)[None, None, None, :]
+    d /= np.linalg.norm(d, axis=-1, keepdims=True)
+    t = t.reshape(n, 64, 4); inst = inst.reshape(n, 64, 4); tri = tri.reshape(n, 64, 4)
+    hit = np.isfinite(t)
+    p = pos + d * np.where(hit, t, 0.0)[..., None]
+    xs, _ = isc.slot_transforms()
+    rot = xs[inst][..., :9].reshape(n, 64, 4, 3, 3)
+    nrm = np.einsum("...rc,...c->...r", rot, tris_plane[np.where(hit, tri, 0)])
+    lv = p - light[None, None, None, :3]
+    dist = np.linalg.norm(lv, axis=-1)
+    fl = lv / np.maximum(dist, 1e-20)[..., None]
+    cast = hit & ((nrm * fl).sum(-1) > 0)
+    fl = np.where(hit[..., None], fl, 0.0)
+    sdir = np.ascontiguousarray(np.transpose(fl, (0, 1, 3, 2)), dtype=np.float32).reshape(n * 64, 3, 4)
+    with np.errstate(all="ignore"):
+        sidir = np.where(sdir != 0, np.float32(1.0) / (sdir + np.float32(1e-8)), np.float32(0.0)).astype(np.float32)
+    sdist = np.where(cast, dist * 0.9999, -np.inf).astype(np.float32).reshape(n * 64, 4)
+    return np.ascontiguousarray(light[:3], dtype=np.float32).reshape(1, 3), sdir, sidir, sdist, int(cast.sum())
+
+
+def lit(torch, a, resx, resy):
+    import ctypes as C
+    import statistics
+    import time
+    from snail_amd import _lib
+    if a.baseline_lib:      # another build of the library for the whole process (it need not have the lit entry points)
+        L = C.CDLL(os.path.abspath(a.baseline_lib))
+        for table in (_lib.SIGNATURES, _lib.INSTANCES_SIGNATURES):
+            for name, (res, args) in table.items():
+                fn = getattr(L, name)
+                fn.restype, fn.argtypes = res, args
+        _lib._lib = L
+    L = _lib.lib()
+    rays = resx * resy
+    pw, ph = (resx + 15) // 16, (resy + 15) // 16
+    npk = pw * ph
+    tv = scenes.atrium()
+    hb = HostBVH.build(tv)
+    sc = Scene(hb, 0)
+    lo, hi = sc.get_bbox()
+    plane = np.ascontiguousarray(hb.tris.view(np.float32).reshape(-1, 16)[:, 12:15])
+    out = {"res": a.res, "lights": 1, "library": a.baseline_lib or "this build", "unit": "median of %d alternating runs" % a.reps, "rows": []}
+    for arith in ("ieee", "host_sse"):
+        sc.set_arith(arith)
+        for n in (int(c) for c in a.counts.split(",")):
+            rot, tr, bi = scenes.instance_field(lo, hi, n, seed=1)
+            isc = InstancedScene([sc], rot, tr, bi)
+            nd = isc.nodes()[0]
+            cam = survey_camera(tv) if n == 1 else survey_camera(np.concatenate([nd["bmin"], nd["bmax"], nd["bmin"]]).reshape(1, 9))
+            cam13 = np.ascontiguousarray(cam.as_array13(), dtype=np.float32)
+            c, ext = (nd["bmin"] + nd["bmax"]) * 0.5, nd["bmax"] - nd["bmin"]
+            light = np.array([[c[0], c[1] + 0.3 * ext[1], c[2], 1.0, 1.0, 1.0, float(np.linalg.norm(ext))]], dtype=np.float32)
+            # the primary frame's hits, packet-major, and from them the shadow packets of the per-packet path
+            t = np.zeros(npk * 256, np.float32); u = np.zeros_like(t); v = np.zeros_like(t)
+            ins = np.zeros(npk * 256, np.int32); tri = np.zeros_like(ins)
+            st = np.zeros(4, np.uint64)
+
+            def frame_packets():
+                _lib.check(L.snail_instances_trace_frame_packets(isc._h, _lib.ptr(cam13), resx, resy, _lib.ptr(t), _lib.ptr(u), _lib.ptr(v), _lib.ptr(ins), _lib.ptr(tri),
+                                                                 _lib.ptr(st)), "snail_instances_trace_frame_packets")
+            frame_packets()
+            o3, sdir, sidir, sdist, cast = shadow_packets_of(isc, cam13.astype(np.float64), resx, resy, light[0].astype(np.float64), t, ins, tri, plane)
+            work = sdist.copy()
+
+            def per_packet():
+                frame_packets()
+                np.copyto(work, sdist)
+                fn, h, po = L.snail_instances_trace_shadow, isc._h, _lib.ptr(o3)
+                base_d, base_i, base_s = sdir.ctypes.data, sidir.ctypes.data, work.ctypes.data
+                for p in range(npk):
+                    rc = fn(h, 1, 64, po, C.c_void_p(base_d + p * 3072), C.c_void_p(base_i + p * 3072), C.c_void_p(base_s + p * 1024), None)
+                    if rc:
+                        _lib.check(rc, "snail_instances_trace_shadow")
+
+            frame = torch.zeros((resy, resx, 3), dtype=torch.uint8, device="cuda")
+            runs = {"per_packet": per_packet, "plain": lambda: sc.render_whitted(cam, resx, resy, light, out=frame)}
+            if not a.baseline_lib:
+                runs["device"] = lambda: isc.render_whitted(cam, resx, resy, light, out=frame)
+            else:
+                del runs["plain"]
+            ms = {k: [] for k in runs}
+            for k, fn in runs.items():      # warm-up
+                fn(); torch.cuda.synchronize()
+            for _ in range(a.reps):         # alternating
+                for k, fn in runs.items():
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter(); fn(); torch.cuda.synchronize()
+                    ms[k].append((time.perf_counter() - t0) * 1e3)
+            row = {"arith": arith, "instances": n, "packets": npk, "shadow_rays": cast}
+            for k in ms:
+                m = statistics.median(ms[k])
+                row[k + "_ms"] = round(m, 3); row[k + "_mrays"] = round(rays / m / 1e3, 1)
+            out["rows"].append(row)
+            print(json.dumps(row), file=sys.stderr, flush=True)
+            isc.close()
+    sc.close()
     print(json.dumps(out))
 
 
