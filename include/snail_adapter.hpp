@@ -492,6 +492,7 @@ struct RenderMode {
 	bool reflections = false;   // gVals[7]
 	bool antialias = false;     // gVals[9]
 	float color[3] = {1.0f, 1.0f, 1.0f};
+	bool rankTint = false;      // gVals[8]: read by RenderInstancedTiles alone (the tile list of an instanced scene), which is given the rank
 };
 
 namespace detail {
@@ -510,6 +511,17 @@ template <class StatsT> inline StatsT toStats(const uint64_t (&st)[4]) {
 	StatsT s;
 	s.Intersection((unsigned)st[0]); s.LoopIteration((unsigned)st[1]); s.TracingRays((unsigned)st[2]); s.Skip((unsigned)st[3]);
 	return s;
+}
+// the render nodes' tint (colorizeNodes, src/render.cpp:119-129): sixteen colours, taken by rank % 16.  Entry 15's green is 1.7 in the reference.
+inline const float *RankTint(unsigned rank) {
+	static const float ncolors[16][3] = {
+		{0.6f, 0.6f, 0.6f}, {0.6f, 0.6f, 1.0f}, {0.6f, 1.0f, 0.6f}, {0.6f, 1.0f, 1.0f}, {1.0f, 0.6f, 0.6f}, {1.0f, 0.6f, 1.0f}, {1.0f, 1.0f, 0.6f}, {1.0f, 1.0f, 1.0f},
+		{0.3f, 0.3f, 0.3f}, {0.3f, 0.3f, 1.0f}, {0.3f, 0.7f, 0.3f}, {0.3f, 0.7f, 0.7f}, {0.7f, 0.3f, 0.3f}, {0.7f, 0.3f, 0.7f}, {0.7f, 0.7f, 0.3f}, {0.7f, 1.7f, 0.7f},
+	};
+	return ncolors[rank % 16u];
+}
+inline int renderFlags(const RenderMode &mode) {
+	return (mode.depthShading ? SNAIL_RENDER_DEPTH : 0) | (mode.reflections ? SNAIL_RENDER_REFLECTIONS : 0) | (mode.antialias ? SNAIL_RENDER_AA4 : 0);
 }
 } // namespace detail
 
@@ -545,6 +557,34 @@ inline StatsT RenderImage(const SceneT &scene, const CameraT &camera, ImageT &im
 	SNAIL_CHECK(snail_render_image(scene.geometry.Handle(), c, (int)image.Width(), (int)image.Height(), l.data(), (int)(l.size() / 7), amb, mode.color,
 								   (mode.depthShading ? SNAIL_RENDER_DEPTH : 0) | (mode.reflections ? SNAIL_RENDER_REFLECTIONS : 0) | (mode.antialias ? SNAIL_RENDER_AA4 : 0),
 								   (unsigned char *)image.DataPointer(), (int)image.Pitch(), st));
+	return detail::toStats<StatsT>(st);
+}
+
+// The two calls for an instanced scene (Scene<snail::HipDBVH<...>>; what the reference's render node does every frame after MakeDBVH,
+// src/node.cpp:326-338, src/rtracer.cpp:359-361), entirely on the device: snail_instances_render_tiles / snail_instances_render_frame
+// (include/snail_instances_tiles.h).  mode.rankTint = gVals[8]: the tiles tinted by detail::RankTint(rank); the image form has no tint.
+template <class StatsT, class SceneT, class CameraT>
+inline StatsT RenderInstancedTiles(const SceneT &scene, const CameraT &camera, unsigned resx, unsigned resy, unsigned char *data, const std::vector<int> &coords,
+								   const std::vector<int> &offsets, const RenderMode &mode = RenderMode(), unsigned rank = 0) {
+	float c[13];
+	detail::cam13(camera, c);
+	const std::vector<float> l = detail::lights7(scene);
+	std::vector<int64_t> off(offsets.begin(), offsets.end());
+	const float amb[3] = {scene.ambientLight.x, scene.ambientLight.y, scene.ambientLight.z};
+	uint64_t st[4] = {0, 0, 0, 0};
+	SNAIL_CHECK(snail_instances_render_tiles(scene.geometry.Handle(), c, (int)resx, (int)resy, coords.data(), off.data(), (int)(coords.size() / 4), l.data(),
+											 (int)(l.size() / 7), amb, mode.color, detail::renderFlags(mode), mode.rankTint ? detail::RankTint(rank) : nullptr, data, st));
+	return detail::toStats<StatsT>(st);
+}
+template <class StatsT, class SceneT, class CameraT, class ImageT>
+inline StatsT RenderInstancedImage(const SceneT &scene, const CameraT &camera, ImageT &image, const RenderMode &mode = RenderMode()) {
+	float c[13];
+	detail::cam13(camera, c);
+	const std::vector<float> l = detail::lights7(scene);
+	const float amb[3] = {scene.ambientLight.x, scene.ambientLight.y, scene.ambientLight.z};
+	uint64_t st[4] = {0, 0, 0, 0};
+	SNAIL_CHECK(snail_instances_render_frame(scene.geometry.Handle(), c, (int)image.Width(), (int)image.Height(), l.data(), (int)(l.size() / 7), amb, mode.color,
+											 detail::renderFlags(mode), (unsigned char *)image.DataPointer(), (int)image.Pitch(), st));
 	return detail::toStats<StatsT>(st);
 }
 
@@ -602,6 +642,34 @@ inline TreeStats Render(const Scene<snail::HipBVH<RefBVH>> &scene, const Camera 
 // Scene<DBVH>::RayTrace's simple-shading branch with the scene's lights and ambient, gVals[7] = one mirrored bounce).  gVals[9], gVals[5],
 // gVals[8] -- and the tile list, whose planar store has no instanced device path -- go to the reference's renderer over the prefetched
 // frame, whose TraversePrimary calls copy pre-traced packets and whose shadow / secondary packets go to the device one call each.
+//
+// Define SNAIL_ADAPTER_INSTANCED_TILES as well (before the include) and both overloads go to the device instead -- the tile list with
+// gVals[1], [7], [9] and [8] (tint by `rank`), the image with gVals[1], [7], [9]: snail::RenderInstancedTiles / RenderInstancedImage -- and
+// only gVals[5] (and gVals[8] on an image) still takes the reference's renderer.  Opt-in, so that a host built against the overloads above keeps what it has
+// (INTEGRATION.md, section 2c).
+#ifdef SNAIL_ADAPTER_INSTANCED_TILES
+template <class RefDBVH>
+inline TreeStats Render(const Scene<snail::HipDBVH<RefDBVH>> &scene, const Camera &camera, uint resx, uint resy, unsigned char *data, const vector<int> &coords,
+						const vector<int> &offsets, const Options options, uint rank, uint threads) {
+	if(gVals[5])
+		SNAIL_HOST_RENDER("gVals[5] (TreeStats visualisation, src/scene_trace.cpp:513-517)", gVals[9] ? 2 : 1, resx, resy,
+						  Render<snail::HipDBVH<RefDBVH>>(scene, camera, resx, resy, data, coords, offsets, options, rank, threads));
+	(void)options; (void)threads;   // (the bounce is gated by gVals[7] alone, src/scene_trace.cpp:454)
+	snail::RenderMode mode;
+	mode.depthShading = gVals[1] != 0; mode.reflections = gVals[7] != 0; mode.antialias = gVals[9] != 0; mode.rankTint = gVals[8] != 0;
+	return snail::RenderInstancedTiles<TreeStats>(scene, camera, resx, resy, data, coords, offsets, mode, rank);
+}
+template <class RefDBVH>
+inline TreeStats Render(const Scene<snail::HipDBVH<RefDBVH>> &scene, const Camera &camera, MipmapTexture &image, const Options options, uint threads) {
+	if(gVals[5] || gVals[8])   // (the device's image form has no tint: gVals[8] on an image stays where it was)
+		SNAIL_HOST_RENDER(gVals[5] ? "gVals[5] (TreeStats visualisation, src/scene_trace.cpp:513-517)" : "gVals[8] on the image of an instanced scene", gVals[9] ? 2 : 1,
+						  image.Width(), image.Height(), Render<snail::HipDBVH<RefDBVH>>(scene, camera, image, options, threads));
+	(void)options; (void)threads;
+	snail::RenderMode mode;
+	mode.depthShading = gVals[1] != 0; mode.reflections = gVals[7] != 0; mode.antialias = gVals[9] != 0;
+	return snail::RenderInstancedImage<TreeStats>(scene, camera, image, mode);
+}
+#else
 template <class RefDBVH>
 inline TreeStats Render(const Scene<snail::HipDBVH<RefDBVH>> &scene, const Camera &camera, uint resx, uint resy, unsigned char *data, const vector<int> &coords,
 						const vector<int> &offsets, const Options options, uint rank, uint threads) {
@@ -626,5 +694,6 @@ inline TreeStats Render(const Scene<snail::HipDBVH<RefDBVH>> &scene, const Camer
 											 (int)image.Pitch(), st));
 	return snail::detail::toStats<TreeStats>(st);
 }
+#endif
 #undef SNAIL_HOST_RENDER
 #endif

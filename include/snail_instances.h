@@ -94,4 +94,6 @@ int snail_instances_trace_shadow(SnailInstances *, int nPackets, int size, const
 #endif
 /* lit frames of instanced scenes (lights, shadow packets, one mirrored bounce): declared in a header of their own, part of this one */
 #include "snail_instances_shade.h"
+/* the tile renderer of instanced scenes (tile list with planar store, 4x antialiasing, rank tint): likewise */
+#include "snail_instances_tiles.h"
 #endif

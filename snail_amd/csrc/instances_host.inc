@@ -1,6 +1,7 @@
 // instances_host.inc -- host side of the two-level instanced scenes (include/snail_instances.h); included at
 // the end of snail_hip.hip.  The build is in dbvh_build.cpp, the kernels in instances.inc.
 
+namespace { struct InstTileJob; void freeInstTileJob(InstTileJob *); } // instances_tiles_host.inc: the cached lists of snail_instances_render_tiles
 struct SnailInstances {
 	int device = 0;
 	std::vector<SnailScene *> blas;
@@ -27,14 +28,19 @@ struct SnailInstances {
 		float *hitT = nullptr; int *hitInst = nullptr, *hitTri = nullptr;
 		float *sDist = nullptr;
 		float *rOrg = nullptr, *rDir = nullptr, *rIDir = nullptr, *rDist = nullptr, *rCol = nullptr;
+		float *col = nullptr; int32_t *xy2 = nullptr;   // snail_instances_tiles.h: the packets' float colours, the double-resolution packet list
 		int *rInst = nullptr, *rTri = nullptr;
 		unsigned char *rMask = nullptr;
-		static size_t bytes(size_t packets, int lights, bool refl) {
+		static size_t bytes(size_t packets, int lights, bool refl, bool tiles = false) {
 			const size_t rays = packets * 256;
-			return rays * 12 + rays * 4 * (size_t)lights + (refl ? rays * (36 + 12 + 12) + packets * 64 : 0) + 256;
+			return rays * 12 + rays * 4 * (size_t)lights + (tiles ? rays * 12 + packets * 8 + 256 : 0) + (refl ? rays * (36 + 12 + 12) + packets * 64 : 0) + 256;
 		}
-		void carve(char *base, size_t packets, int lights, bool refl) {
+		void carve(char *base, size_t packets, int lights, bool refl, bool tiles = false) {
 			const size_t rays = packets * 256;
+			if(tiles) { // (first: 16-byte aligned whatever follows)
+				col = (float *)base; base += rays * 12;
+				xy2 = (int32_t *)base; base += (packets * 8 + 255) & ~(size_t)255;
+			}
 			hitT = (float *)base; base += rays * 4;
 			hitInst = (int *)base; base += rays * 4;
 			hitTri = (int *)base; base += rays * 4;
@@ -55,7 +61,7 @@ struct SnailInstances {
 		ShadeBufs b;
 		char *base = nullptr;
 		size_t packets = 0;
-		bool refl = false;
+		bool refl = false, tiles = false;
 		hipEvent_t done = nullptr;
 		bool used = false;
 	} shade[kShadeSets];
@@ -63,6 +69,9 @@ struct SnailInstances {
 	// packet lists of whole frames (row-major over the 16x16 packet grid), by grid size; built once each
 	struct FrameList { int pw, ph; int32_t *d; };
 	std::vector<FrameList> frameLists;
+	// snail_instances_render_tiles: ONE cached tile job per handle, whose calls take turns
+	std::mutex renderMu;
+	InstTileJob *tileJob = nullptr;
 };
 
 namespace {
@@ -288,7 +297,7 @@ int checkShadeArgs(const char *fn, const float cam[13], int resx, int resy, cons
 // the stages of one lit frame over the packet list dXY into `frame` (or packet-major `bgrPackets`), intermediates in W; mu held
 int instancesShade(SnailInstances *h, const char *fn, const float cam[13], int resx, int resy, const int32_t *dXY, int np, const float *lights7, int nLights,
 				   const float ambient[3], const float color[3], bool refl, uint8_t *frame, int pitch, uint8_t *bgrPackets, const SnailInstances::ShadeBufs &W,
-				   uint64_t *dStats, hipStream_t st) {
+				   uint64_t *dStats, hipStream_t st, float *colPackets = nullptr) {
 	dev::InstArgs I;
 	bool sse, deep;
 	if(int rc = instancesBegin(h, fn, I, &sse, &deep, st)) return rc;
@@ -311,6 +320,7 @@ int instancesShade(SnailInstances *h, const char *fn, const float cam[13], int r
 	A.s.resx = resx; A.s.resy = resy; A.s.pw = (resx + 15) / 16; A.s.ph = (resy + 15) / 16;
 	A.s.packetXY = (const int2 *)dXY; A.s.nPackets = np; A.s.nBlocks = np;
 	A.s.bgrPackets = bgrPackets; A.s.frame = frame; A.s.pitch = pitch;
+	A.s.colPackets = colPackets;   // the float colours k_inst_store goes on from, instead of bytes
 	A.s.nLights = nLights;
 	for(int n = 0; n < nLights; n++) for(int k = 0; k < 7; k++) A.s.lights[n][k] = lights7[n * 7 + k];
 	for(int c = 0; c < 3; c++) { A.s.ambient[c] = ambient[c]; A.s.color[c] = color[c]; }
@@ -365,25 +375,35 @@ int instancesFrameList(SnailInstances *h, int resx, int resy, const int32_t **dX
 	return 0;
 }
 
-// snail_instances_render_whitted_dev / _packets_dev: the next set of intermediates of the handle, grown if need be (mu held)
+// the next set of intermediates of the handle, grown if need be, its previous user's last kernel waited for on `st` (mu held).  tiles: with the
+// float colours and the double-resolution packet list of snail_instances_tiles.h
+int instancesNextSet(SnailInstances *h, size_t np, bool refl, bool tiles, hipStream_t st, SnailInstances::ShadeSet **out) {
+	SnailInstances::ShadeSet &W = h->shade[h->shadeCount++ % SnailInstances::kShadeSets];
+	if(!W.base || W.packets < np || (refl && !W.refl) || (tiles && !W.tiles)) { // grown (shadow distances sized for SNAIL_MAX_LIGHTS once): its previous user may still be running
+		HIP_TRY(hipDeviceSynchronize());
+		if(W.base) (void)hipFree(W.base);
+		const size_t packets = std::max(W.packets, np);
+		const bool r = refl || W.refl, t = tiles || W.tiles;
+		W.base = nullptr; W.packets = 0; W.refl = W.tiles = false; W.used = false;
+		HIP_TRY(hipMalloc((void **)&W.base, SnailInstances::ShadeBufs::bytes(packets, SNAIL_MAX_LIGHTS, r, t)));
+		W.packets = packets; W.refl = r; W.tiles = t;
+	}
+	if(!W.done) HIP_TRY(hipEventCreateWithFlags(&W.done, hipEventDisableTiming));
+	if(W.used) HIP_TRY(hipStreamWaitEvent(st, W.done, 0));
+	*out = &W;
+	return 0;
+}
+
+// snail_instances_render_whitted_dev / _packets_dev (mu held)
 int instancesShadeDev(SnailInstances *h, const char *fn, const float cam[13], int resx, int resy, const int32_t *dXY, int np, const float *lights7, int nLights,
 					  const float ambient[3], const float color[3], int flags, uint8_t *frame, int pitch, uint8_t *bgrPackets, uint64_t *dStats, hipStream_t st) {
 	const bool refl = (flags & SNAIL_WHITTED_REFLECTIONS) != 0;
 	if(!dXY) { if(int rc = instancesFrameList(h, resx, resy, &dXY, &np)) return rc; }
-	SnailInstances::ShadeSet &W = h->shade[h->shadeCount++ % SnailInstances::kShadeSets];
-	if(!W.base || W.packets < (size_t)np || (refl && !W.refl)) { // grown (shadow distances sized for SNAIL_MAX_LIGHTS once): its previous user may still be running
-		HIP_TRY(hipDeviceSynchronize());
-		if(W.base) (void)hipFree(W.base);
-		const size_t packets = std::max(W.packets, (size_t)np);
-		const bool r = refl || W.refl;
-		W.base = nullptr; W.packets = 0; W.refl = false; W.used = false;
-		HIP_TRY(hipMalloc((void **)&W.base, SnailInstances::ShadeBufs::bytes(packets, SNAIL_MAX_LIGHTS, r)));
-		W.packets = packets; W.refl = r;
-	}
+	SnailInstances::ShadeSet *Wp = nullptr;
+	if(int rc = instancesNextSet(h, (size_t)np, refl, false, st, &Wp)) return rc;
+	SnailInstances::ShadeSet &W = *Wp;
 	W.b = SnailInstances::ShadeBufs();
 	W.b.carve(W.base, (size_t)np, nLights, refl);
-	if(!W.done) HIP_TRY(hipEventCreateWithFlags(&W.done, hipEventDisableTiming));
-	if(W.used) HIP_TRY(hipStreamWaitEvent(st, W.done, 0));
 	if(int rc = instancesShade(h, fn, cam, resx, resy, dXY, np, lights7, nLights, ambient, color, refl, frame, pitch, bgrPackets, W.b, dStats, st)) return rc;
 	HIP_TRY(hipEventRecord(W.done, st));
 	W.used = true;
@@ -450,6 +470,7 @@ void snail_instances_destroy(SnailInstances *h) {
 		if(w.done) (void)hipEventDestroy(w.done);
 	}
 	for(auto &f : h->frameLists) (void)hipFree(f.d);
+	freeInstTileJob(h->tileJob);
 	delete h;
 }
 

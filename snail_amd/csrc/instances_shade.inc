@@ -16,6 +16,12 @@
 // The one difference to a plain scene's sample is the normal: ObjectInstance::GetNormal = TransformVec(blas.GetNormal(elem))
 // (src/dbvh/tree.h:21-26,178-181,216-218).  hitBounds / lightCulled / shadowLane / shadeAndStore are the plain pipeline's, on these samples.
 // Table arithmetic: every look-up in its fully checked form.
+//
+// The tile renderer's switches (include/snail_instances_tiles.h; RenderTask::Work, src/render.cpp:71-190) end in one more pass:
+//   k_inst_store<DEPTH, AA, PLANAR>            float colours of k_inst_final (ShadeArgs::colPackets) or the hit distances of k_inst_frame
+//                                              -> [2x2 reduction of gVals[9]] -> [rank tint of gVals[8]] -> ConvColor -> packet-major B,G,R
+//                                              bytes, or the tile's planes R, G-R, B-R
+// and, for the antialiased frames, k_inst_aa_packets lists the four double-resolution packets of every packet of the call.
 namespace SNAIL_DEV_NS {
 
 struct InstShadeArgs {
@@ -176,6 +182,123 @@ __global__ __launch_bounds__(64) void k_inst_final(InstShadeArgs A) {
 	if(DST == DST_FRAME || DST == DST_COLOR) {
 		const float none[4] = {0.0f, 0.0f, 0.0f, 0.0f};
 		shadeAndStore<SRC, DST, false>(A.s, P, lane, d, S, none);
+	}
+}
+
+// ---- the tail of RenderTask::Work (src/render.cpp:71-163) for the packets of an instanced scene ----
+struct InstStoreArgs {
+	const unsigned *hostTab;     // FIRST: as PrimaryArgs::hostTab (DEPTH: Inv of the handle's arithmetic)
+	const float *in;             // colours [n][256][3] (r, g, b), DEPTH: hit distances [n][256]; AA: n = 4 nPackets, sub-packet k of packet p at 4 p + k
+	int nPackets;                // OUTPUT packets
+	int tinted;                  // gVals[8]: c = (c + 0.1) * tint, after the reduction, before ConvColor (src/render.cpp:118-132)
+	float tint[3];
+	unsigned char *bgrPackets;   // !PLANAR: packet-major B,G,R [nPackets][256][3], 4-byte aligned
+	// PLANAR: packet p belongs to tile packetTile[p], whose packets firstPacket[tile] .. are consecutive, row bands outer, columns inner
+	const int4 *tiles;
+	const int *packetTile, *firstPacket;
+	const long long *outOff;
+	unsigned char *out;
+	int resx, resy;
+};
+
+#if !SNAIL_ARITH_SSE
+// the packets of the double-resolution frame behind packet p: 4 p + k at (2x + 16 (k & 1), 2y + 16 (k >> 1)) (src/render.cpp:72-77)
+__global__ __launch_bounds__(256) void k_inst_aa_packets(const int2 *xy, int nPackets, int2 *xy2) {
+	const int i = (int)(blockIdx.x * 256 + threadIdx.x);
+	if(i >= nPackets * 4) return;
+	const int2 p = xy[i >> 2];
+	const int k = i & 3;
+	xy2[i] = make_int2(p.x * 2 + ((k & 1) ? 16 : 0), p.y * 2 + ((k & 2) ? 16 : 0));
+}
+#endif
+
+// One wave per output packet, lane = output quad (row lane >> 2, pixels 4 (lane & 3) .. + 3).  The reduction is k_aa_reduce's: the same quad
+// mapping, out = ((a0 + b0) * 0.25) + ((a1 + b1) * 0.25); the depth colour is k_shade_depth's Inv(t) * (20, 250, 2); the planes follow
+// k_bgr_to_planar's index rule (byte ty * w + tx of plane k of a w x h tile), clipped to the tile's rect and to the image.
+template <bool DEPTH, bool AA, bool PLANAR>
+__global__ __launch_bounds__(64) void k_inst_store(InstStoreArgs A) {
+	const int p = (int)blockIdx.x, lane = (int)threadIdx.x;
+	if(p >= A.nPackets) return;
+	const int row = lane >> 2, qc = lane & 3;
+	float c[4][3];   // [pixel of the quad][r, g, b]
+	if(AA) {
+		const int k = (row >= 8 ? 2 : 0) + (qc >= 2 ? 1 : 0);     // the quarter of the packet = the sub-packet it comes from
+		const int r = row & 7, h = qc & 1;
+#pragma unroll
+		for(int j = 0; j < 4; j++) {
+			const int i = j >> 1, s2 = (j & 1) * 2;
+			const int qa = 8 * r + 2 * h + i, qb = qa + 4;          // the input quads of rows 2r and 2r + 1
+			const size_t ia = ((size_t)(4 * p + k) * 64 + qa) * 4 + s2, ib = ((size_t)(4 * p + k) * 64 + qb) * 4 + s2;
+			float ta0 = 0.0f, ta1 = 0.0f, tb0 = 0.0f, tb1 = 0.0f;
+			if(DEPTH) { ta0 = InvDiv(A.in[ia]); ta1 = InvDiv(A.in[ia + 1]); tb0 = InvDiv(A.in[ib]); tb1 = InvDiv(A.in[ib + 1]); }
+#pragma unroll
+			for(int ch = 0; ch < 3; ch++) {
+				float a0, a1, b0, b1;
+				if(DEPTH) {
+					const float scale = ch == 0 ? 20.0f : ch == 1 ? 250.0f : 2.0f;
+					a0 = ta0 * scale; a1 = ta1 * scale; b0 = tb0 * scale; b1 = tb1 * scale;
+				} else { a0 = A.in[ia * 3 + ch]; a1 = A.in[(ia + 1) * 3 + ch]; b0 = A.in[ib * 3 + ch]; b1 = A.in[(ib + 1) * 3 + ch]; }
+				c[j][ch] = (a0 + b0) * 0.25f + (a1 + b1) * 0.25f;
+			}
+		}
+	} else {
+		const size_t q = ((size_t)p * 64 + (size_t)lane) * 4;
+		if(DEPTH) {
+			const float4 tv = *(const float4 *)(A.in + q);
+			const float tt[4] = {tv.x, tv.y, tv.z, tv.w};
+#pragma unroll
+			for(int l = 0; l < 4; l++) {
+				const float dist = InvDiv(tt[l]);
+				c[l][0] = dist * 20.0f; c[l][1] = dist * 250.0f; c[l][2] = dist * 2.0f;
+			}
+		} else {
+			const float4 *s = (const float4 *)(A.in + q * 3);
+			const float4 v0 = s[0], v1 = s[1], v2 = s[2];
+			const float f[12] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w, v2.x, v2.y, v2.z, v2.w};
+#pragma unroll
+			for(int l = 0; l < 4; l++) { c[l][0] = f[l * 3]; c[l][1] = f[l * 3 + 1]; c[l][2] = f[l * 3 + 2]; }
+		}
+	}
+	if(A.tinted) {
+#pragma unroll
+		for(int l = 0; l < 4; l++)
+#pragma unroll
+			for(int ch = 0; ch < 3; ch++) c[l][ch] = (c[l][ch] + 0.1f) * A.tint[ch];
+	}
+	unsigned rr[4], gg[4], bb[4];
+#pragma unroll
+	for(int l = 0; l < 4; l++) { rr[l] = (unsigned)convChannelW(c[l][0]); gg[l] = (unsigned)convChannelW(c[l][1]); bb[l] = (unsigned)convChannelW(c[l][2]); }
+	if(!PLANAR) {
+		unsigned bytes[12];
+#pragma unroll
+		for(int l = 0; l < 4; l++) { bytes[l * 3 + 0] = bb[l]; bytes[l * 3 + 1] = gg[l]; bytes[l * 3 + 2] = rr[l]; }
+		unsigned *o = (unsigned *)(A.bgrPackets + ((size_t)p * 256 + (size_t)lane * 4) * 3);
+#pragma unroll
+		for(int w = 0; w < 3; w++) o[w] = bytes[4 * w] | (bytes[4 * w + 1] << 8) | (bytes[4 * w + 2] << 16) | (bytes[4 * w + 3] << 24);
+		return;
+	}
+	const int tile = A.packetTile[p];
+	const int4 T = A.tiles[tile];
+	const int ppr = (T.z + 15) >> 4, lp = p - A.firstPacket[tile];
+	const int ty = (lp / ppr) * 16 + row, tx = (lp % ppr) * 16 + qc * 4;
+	if(ty >= T.w || T.y + ty >= A.resy) return;
+	int nIn = T.z - tx;                                        // pixels of the quad inside the tile and the image
+	if(A.resx - (T.x + tx) < nIn) nIn = A.resx - (T.x + tx);
+	if(nIn <= 0) return;
+	const size_t n = (size_t)T.z * (size_t)T.w, i = (size_t)ty * (size_t)T.z + (size_t)tx;
+	unsigned char *o = A.out + A.outOff[tile] + i;
+	unsigned pl[3][4];
+#pragma unroll
+	for(int l = 0; l < 4; l++) { pl[0][l] = rr[l]; pl[1][l] = (gg[l] - rr[l]) & 255u; pl[2][l] = (bb[l] - rr[l]) & 255u; }
+#pragma unroll
+	for(int k = 0; k < 3; k++) {
+		unsigned char *d = o + (size_t)k * n;
+		if(nIn >= 4 && ((unsigned long long)d & 3) == 0) *(unsigned *)d = pl[k][0] | (pl[k][1] << 8) | (pl[k][2] << 16) | (pl[k][3] << 24);
+		else {
+#pragma unroll
+			for(int l = 0; l < 4; l++)
+				if(l < nIn) d[l] = (unsigned char)pl[k][l];
+		}
 	}
 }
 

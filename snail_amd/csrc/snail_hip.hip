@@ -1618,3 +1618,4 @@ int snail_account_primary(SnailScene *s, const float cam[13], int resx, int resy
 
 #include "render_host.inc"
 #include "instances_host.inc"
+#include "instances_tiles_host.inc"

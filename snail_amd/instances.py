@@ -5,6 +5,7 @@ src/dbvh/tree.cpp, src/dbvh/traverse.cpp), over the C-ABI of include/snail_insta
   .update(rotations, translations, blas_index)                <-> rebuilding the DBVH for the next frame (rtracer.cpp's -instances mode)
   .trace_primary(cam, resx, resy)                              <-> RayGenerator + SafeInv + DBVH::TraversePrimary over 16x16 packets
   .traverse_primary(ctx, element) / .traverse_shadow(ctx)     <-> DBVH::TraversePrimary<so,mask> / DBVH::TraverseShadow
+  .render_tiles_host(cam, resx, resy, tiles, ...)              <-> Render(scene, camera, resx, resy, data, coords, offsets, options, rank, threads)
 
 The instance id a hit reports is the instance's BUILDER SLOT (the DBVH::elements order); .perm()[slot] is the caller's instance."""
 from __future__ import annotations
@@ -219,6 +220,59 @@ class InstancedScene:
         rc = _lib.lib().snail_instances_render_image(self._h, _lib.ptr(cam13), resx, resy, _lib.ptr(lights) if len(lights) else None, len(lights),
                                                     _lib.ptr(amb), _lib.ptr(col), int(flags), _lib.ptr(img), resx * 3, _lib.ptr(stats))
         _lib.check(rc, "snail_instances_render_image")
+        return img, stats
+
+    @staticmethod
+    def _shade_args(cam, lights7, ambient, color, tint):
+        lights = np.ascontiguousarray(lights7 if lights7 is not None else np.zeros((0, 7)), dtype=np.float32).reshape(-1, 7)
+        cam13 = np.ascontiguousarray(cam.as_array13(), dtype=np.float32)
+        amb = np.ascontiguousarray(ambient, dtype=np.float32); col = np.ascontiguousarray(color, dtype=np.float32)
+        tnt = None if tint is None else np.ascontiguousarray(tint, dtype=np.float32).reshape(3)
+        return lights, cam13, amb, col, tnt
+
+    def shade_packets(self, cam, resx: int, resy: int, packet_xy, lights7=None, flags: int = 0, tint=None, ambient=(0.1, 0.1, 0.1), color=(1.0, 1.0, 1.0),
+                      out=None, stats=None, stream=None):
+        """snail_instances_shade_packets_dev: the packets of an explicit list (int32 [n,2] device tensor) with any of RENDER_REFLECTIONS /
+        RENDER_DEPTH / RENDER_AA4 and an optional tint (three factors, gVals[8]): packet-major [n,256,3] uint8 (B,G,R)."""
+        torch = _torch()
+        n = int(packet_xy.shape[0])
+        if out is None:
+            out = torch.empty((n, 256, 3), dtype=torch.uint8, device=self._dev())
+        lights, cam13, amb, col, tnt = self._shade_args(cam, lights7, ambient, color, tint)
+        rc = _lib.lib().snail_instances_shade_packets_dev(self._h, _lib.ptr(cam13), resx, resy, _lib.ptr(packet_xy), n, _lib.ptr(lights) if len(lights) else None,
+                                                         len(lights), _lib.ptr(amb), _lib.ptr(col), int(flags), _lib.ptr(tnt), _lib.ptr(out), _lib.ptr(stats),
+                                                         _stream_ptr(stream))
+        _lib.check(rc, "snail_instances_shade_packets_dev")
+        return out
+
+    def render_tiles_host(self, cam, resx: int, resy: int, tiles, lights7=None, flags: int = 0, tint=None, ambient=(0.1, 0.1, 0.1), color=(1.0, 1.0, 1.0),
+                          offsets=None, data=None):
+        """snail_instances_render_tiles: the tile-list renderer of src/render.h:16-19 for an instanced scene.  tiles = [n, 4] (x, y, w, h);
+        returns (data, offsets, stats) with tile k's planes R, G-R, B-R at data[offsets[k]:offsets[k] + 3 w h], laid out like
+        Scene.render_tiles_host (back to back) unless the caller brings `offsets` and a `data` buffer of its own.  tint = three factors
+        (gVals[8]) or None."""
+        t = np.ascontiguousarray(tiles, dtype=np.int32).reshape(-1, 4)
+        size = 3 * t[:, 2].astype(np.int64) * t[:, 3]
+        if offsets is None:
+            offsets = np.concatenate([[0], np.cumsum(size)[:-1]]).astype(np.int64)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        if data is None:
+            data = np.zeros(int((offsets + size).max()) if len(t) else 0, dtype=np.uint8)
+        lights, cam13, amb, col, tnt = self._shade_args(cam, lights7, ambient, color, tint)
+        stats = np.zeros(4, dtype=np.uint64)
+        rc = _lib.lib().snail_instances_render_tiles(self._h, _lib.ptr(cam13), resx, resy, _lib.ptr(t), _lib.ptr(offsets), len(t), _lib.ptr(lights) if len(lights) else None,
+                                                    len(lights), _lib.ptr(amb), _lib.ptr(col), int(flags), _lib.ptr(tnt), _lib.ptr(data), _lib.ptr(stats))
+        _lib.check(rc, "snail_instances_render_tiles")
+        return data, offsets, stats
+
+    def render_frame_host(self, cam, resx: int, resy: int, lights7=None, flags: int = 0, ambient=(0.1, 0.1, 0.1), color=(1.0, 1.0, 1.0)):
+        """snail_instances_render_frame: render_image_host with RENDER_AA4 accepted (gVals[9]) -> (rgb8 frame [resy, resx, 3] (B,G,R), stats)."""
+        lights, cam13, amb, col, _ = self._shade_args(cam, lights7, ambient, color, None)
+        img = np.zeros((resy, resx, 3), dtype=np.uint8)
+        stats = np.zeros(4, dtype=np.uint64)
+        rc = _lib.lib().snail_instances_render_frame(self._h, _lib.ptr(cam13), resx, resy, _lib.ptr(lights) if len(lights) else None, len(lights), _lib.ptr(amb),
+                                                    _lib.ptr(col), int(flags), _lib.ptr(img), resx * 3, _lib.ptr(stats))
+        _lib.check(rc, "snail_instances_render_frame")
         return img, stats
 
     def traverse_primary(self, ctx: Context, element, stats=None, stream=None) -> Context:

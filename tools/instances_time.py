@@ -15,7 +15,17 @@ for --rebuild-counts instances (default 10 000).  Prints one JSON object.  No ta
 Repeated alternating runs, medians.  --baseline-lib PATH loads another build of libsnailhip.so (e.g. the parent commit's, which has no device
 path) and measures per_packet only.
 
-    python tools/instances_time.py --lit [--baseline-lib PATH] [--reps 5]"""
+    python tools/instances_time.py --lit [--baseline-lib PATH] [--reps 5]
+
+--tiles: what a TILE-LIST frame costs (snail_instances_render_tiles over render.divide_image's 16x64 tiles; one light, atrium, IEEE): host wall ms
+per frame, device-to-host copy and the scatter into the caller's buffer included, of
+  tiles          no antialiasing;
+  tiles_aa       SNAIL_RENDER_AA4;
+  tiles_aa_tint  SNAIL_RENDER_AA4 and the tint of rank 3;
+  image          InstancedScene.render_image_host of the same build (the interleaved frame, no tile list), for scale.
+Repeated alternating runs, medians.
+
+    python tools/instances_time.py --tiles [--reps 9]"""
 import argparse
 import json
 import os
@@ -54,11 +64,14 @@ def main():
     ap.add_argument("--counts", default="1,64,1024")
     ap.add_argument("--rebuild-counts", default="10000")
     ap.add_argument("--lit", action="store_true")
+    ap.add_argument("--tiles", action="store_true")
     ap.add_argument("--baseline-lib", default=None)
     a = ap.parse_args()
     resx, resy = (int(x) for x in a.res.split("x"))
     if a.lit:
         return lit(torch, a, resx, resy)
+    if a.tiles:
+        return tiles(torch, a, resx, resy)
     rays = resx * resy
     out = {"res": a.res, "unit": "Mrays/s (best of %d launches)" % a.reps, "rows": []}
     meshes = {"atrium": lambda: scenes.atrium(),
@@ -193,6 +206,47 @@ def lit(torch, a, resx, resy):
             out["rows"].append(row)
             print(json.dumps(row), file=sys.stderr, flush=True)
             isc.close()
+    sc.close()
+    print(json.dumps(out))
+
+
+def tiles(torch, a, resx, resy):
+    import statistics
+    import time
+    from snail_amd.render import divide_image
+    tv = scenes.atrium()
+    sc = Scene(HostBVH.build(tv), 0)
+    lo, hi = sc.get_bbox()
+    tl = divide_image(resx, resy)
+    tint = np.array([0.6, 1.0, 1.0], dtype=np.float32)      # rank 3 of src/render.cpp:119-128
+    out = {"res": a.res, "lights": 1, "arith": "ieee", "tiles": len(tl), "unit": "host wall ms per frame, median of %d alternating runs" % a.reps, "rows": []}
+    for n in (int(c) for c in a.counts.split(",")):
+        rot, tr, bi = scenes.instance_field(lo, hi, n, seed=1)
+        isc = InstancedScene([sc], rot, tr, bi)
+        nd = isc.nodes()[0]
+        cam = survey_camera(tv) if n == 1 else survey_camera(np.concatenate([nd["bmin"], nd["bmax"], nd["bmin"]]).reshape(1, 9))
+        c, ext = (nd["bmin"] + nd["bmax"]) * 0.5, nd["bmax"] - nd["bmin"]
+        light = np.array([[c[0], c[1] + 0.3 * ext[1], c[2], 1.0, 1.0, 1.0, float(np.linalg.norm(ext))]], dtype=np.float32)
+        data, offsets, _ = isc.render_tiles_host(cam, resx, resy, tl, light)
+        AA = InstancedScene.RENDER_AA4
+        runs = {"tiles": lambda: isc.render_tiles_host(cam, resx, resy, tl, light, offsets=offsets, data=data),
+                "tiles_aa": lambda: isc.render_tiles_host(cam, resx, resy, tl, light, flags=AA, offsets=offsets, data=data),
+                "tiles_aa_tint": lambda: isc.render_tiles_host(cam, resx, resy, tl, light, flags=AA, tint=tint, offsets=offsets, data=data),
+                "image": lambda: isc.render_image_host(cam, resx, resy, light)}
+        ms = {k: [] for k in runs}
+        for k, fn in runs.items():      # warm-up (the cached lists, the handle's sets)
+            fn(); fn()
+        for _ in range(a.reps):         # alternating
+            for k, fn in runs.items():
+                t0 = time.perf_counter(); fn()
+                ms[k].append((time.perf_counter() - t0) * 1e3)
+        row = {"instances": n}
+        for k in ms:
+            row[k + "_ms"] = round(statistics.median(ms[k]), 3)
+            row[k + "_min_ms"] = round(min(ms[k]), 3)
+        out["rows"].append(row)
+        print(json.dumps(row), file=sys.stderr, flush=True)
+        isc.close()
     sc.close()
     print(json.dumps(out))
 
