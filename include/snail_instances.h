@@ -96,4 +96,6 @@ int snail_instances_trace_shadow(SnailInstances *, int nPackets, int size, const
 #include "snail_instances_shade.h"
 /* the tile renderer of instanced scenes (tile list with planar store, 4x antialiasing, rank tint): likewise */
 #include "snail_instances_tiles.h"
+/* the top-level tree rebuilt on the device from transforms in device memory, byte-equal to the host builder's: likewise */
+#include "snail_instances_build.h"
 #endif

@@ -108,6 +108,13 @@ INSTANCES_TILES_SIGNATURES = {
     "snail_instances_render_frame": (_I, [_VP, _F13, _I, _I, _VP, _I, _VP, _VP, _I, _VP, _I, _VP]),
 }
 
+# include/snail_instances_build.h (the top-level tree rebuilt on the device; part of snail_instances.h): a table of its own once more --
+# tests/c/instances_build_c.c enumerates it
+INSTANCES_BUILD_SIGNATURES = {
+    "snail_instances_rebuild_dev": (_I, [_VP, _VP, _VP, _I, _VP, _VP, _VP]),
+    "snail_instances_read_tree": (_I, [_VP, _VP, _I, _VP, _VP, _VP, _I, _VP]),
+}
+
 # include/snail_hip_debug.h: the workbench build only (libsnailhip_debug.so, -DSNAIL_DEBUG_API)
 DEBUG_SIGNATURES = {
     "snail_debug_delay_dev": (_I, [C.c_float, _VP]),
@@ -130,7 +137,7 @@ def debug_lib():
         if not os.path.exists(DEBUG_LIB_PATH):
             raise SnailError("workbench library %s is missing: `make -C snail_amd/csrc debug`" % DEBUG_LIB_PATH)
         L = C.CDLL(DEBUG_LIB_PATH)
-        for table in (SIGNATURES, INSTANCES_SIGNATURES, INSTANCES_SHADE_SIGNATURES, INSTANCES_TILES_SIGNATURES, DEBUG_SIGNATURES):
+        for table in (SIGNATURES, INSTANCES_SIGNATURES, INSTANCES_SHADE_SIGNATURES, INSTANCES_TILES_SIGNATURES, INSTANCES_BUILD_SIGNATURES, DEBUG_SIGNATURES):
             for name, (res, args) in table.items():
                 fn = getattr(L, name)
                 fn.restype = res
@@ -151,7 +158,7 @@ def lib():
             L = C.CDLL(LIB_PATH)
         except OSError as e:  # pragma: no cover - depends on the box
             raise SnailError("cannot load %s: %s" % (LIB_PATH, e)) from e
-        for table in (SIGNATURES, INSTANCES_SIGNATURES, INSTANCES_SHADE_SIGNATURES, INSTANCES_TILES_SIGNATURES):
+        for table in (SIGNATURES, INSTANCES_SIGNATURES, INSTANCES_SHADE_SIGNATURES, INSTANCES_TILES_SIGNATURES, INSTANCES_BUILD_SIGNATURES):
             for name, (res, args) in table.items():
                 fn = getattr(L, name)
                 fn.restype = res

@@ -9,6 +9,14 @@ struct SnailInstances {
 	uint4 *dTop = nullptr, *dInst = nullptr;   // top-level node records; 4 x 16 B per builder slot
 	int topCap = 0, instCap = 0;
 	int nNodes = 0, n = 0;
+	// snail_instances_rebuild_dev (instances_build.inc): the BLAS root boxes (nBlas x 6 floats, from the BLAS scenes' root nodes at create), the
+	// builder's scratch (one allocation, sized by the largest n so far) and {nNodes, n} of the tree the buffers hold, which only the device
+	// knows once a rebuild has been enqueued (curOnDevice; a rebuild that fails leaves the previous values)
+	float *dBlasBox = nullptr;
+	char *buildBase = nullptr;
+	int buildCap = 0;
+	int *dCur = nullptr;
+	bool curOnDevice = false;
 	// mu: the ordering state below and the buffers' identity (held while a call enqueues)
 	std::mutex mu;
 	// snail_instances_update vs launches: the update's stream waits for every launch enqueued since the previous update (one event per stream
@@ -123,6 +131,8 @@ void packInstances(const float *xf12, const int32_t *blasIdx, int n, uint32_t *o
 // new records into the handle's buffers, ordered on `stream` after every launch since the previous update (mu held)
 int instancesUpload(SnailInstances *h, const void *nodes32, int nNodes, const float *xf12, const int32_t *blasIdx, int n, hipStream_t stream) {
 	for(auto &u : h->uses) HIP_TRY(hipStreamWaitEvent(stream, u.ev, 0));
+	if(h->curOnDevice && h->hasReady) HIP_TRY(hipStreamWaitEvent(stream, h->ready, 0));   // a device rebuild still writing the buffers
+	h->curOnDevice = false;
 	const size_t topBytes = (size_t)nNodes * 32, instBytes = (size_t)n * 64;
 	if(nNodes > h->topCap || n > h->instCap) { // grown: the old buffers may still be read by launches in flight
 		HIP_TRY(hipStreamSynchronize(stream));
@@ -433,6 +443,10 @@ SnailInstances *snail_instances_create(SnailScene *const *blas, int nBlas, const
 	for(int b = 0; b < nBlas; b++) { rec[b].nodes = blas[b]->dNodes; rec[b].tris = blas[b]->dTris; }
 	hipError_t e = hipMalloc((void **)&h->dBlas, rec.size() * sizeof(dev::InstBlas));
 	if(e == hipSuccess) e = hipMemcpy(h->dBlas, rec.data(), rec.size() * sizeof(dev::InstBlas), hipMemcpyHostToDevice);
+	// the BLAS root boxes, for the device builder: each scene's own root node (what Scene.get_bbox returns)
+	if(e == hipSuccess) e = hipMalloc((void **)&h->dBlasBox, (size_t)nBlas * 24);
+	for(int b = 0; b < nBlas && e == hipSuccess; b++) e = hipMemcpy((char *)h->dBlasBox + (size_t)b * 24, blas[b]->dNodes, 24, hipMemcpyDeviceToDevice);
+	if(e == hipSuccess) e = hipMalloc((void **)&h->dCur, 2 * sizeof(int));
 	if(e != hipSuccess) { snail_set_error("%s: %s", fn, hipGetErrorString(e)); snail_instances_destroy(h); return nullptr; }
 	int rc;
 	{
@@ -461,6 +475,9 @@ void snail_instances_destroy(SnailInstances *h) {
 	if(h->dBlas) (void)hipFree(h->dBlas);
 	if(h->dTop) (void)hipFree(h->dTop);
 	if(h->dInst) (void)hipFree(h->dInst);
+	if(h->dBlasBox) (void)hipFree(h->dBlasBox);
+	if(h->buildBase) (void)hipFree(h->buildBase);
+	if(h->dCur) (void)hipFree(h->dCur);
 	if(h->staging) (void)hipHostFree(h->staging);
 	if(h->ready) (void)hipEventDestroy(h->ready);
 	if(h->stagingFree) (void)hipEventDestroy(h->stagingFree);
@@ -665,6 +682,141 @@ int snail_instances_render_image(SnailInstances *h, const float cam[13], int res
 	}
 	HIP_TRY(hipMemcpy2DAsync(image, (size_t)pitch, dImg, (size_t)pitch, (size_t)resx * 3, (size_t)resy, hipMemcpyDeviceToHost, hc.stream()));
 	return hc.finish(stats);
+}
+
+} // extern "C"
+
+// ---- snail_instances_build.h: DBVH::Construct on the device (kernels: instances_build.inc) ----
+namespace {
+
+// room for a tree over n instances in the handle's buffers -- their contents KEPT, a rebuild that fails must leave the previous tree --
+// and in the builder's scratch (mu held).  Grown, never shrunk; growing waits for the device, as in instancesUpload
+int buildReserve(SnailInstances *h, int n) {
+	const int needTop = (int)(2LL * n - 1);
+	if(needTop <= h->topCap && n <= h->instCap && n <= h->buildCap) return 0;
+	HIP_TRY(hipDeviceSynchronize());
+	if(needTop > h->topCap) {
+		uint4 *p = nullptr;
+		HIP_TRY(hipMalloc((void **)&p, (size_t)needTop * 32));
+		if(hipMemcpy(p, h->dTop, (size_t)h->topCap * 32, hipMemcpyDeviceToDevice) != hipSuccess) { (void)hipFree(p); snail_set_error("snail_instances_rebuild_dev: copy of the nodes failed"); return 1; }
+		(void)hipFree(h->dTop);
+		h->dTop = p; h->topCap = needTop;
+	}
+	if(n > h->instCap) {
+		uint4 *p = nullptr;
+		HIP_TRY(hipMalloc((void **)&p, (size_t)n * 64));
+		if(hipMemcpy(p, h->dInst, (size_t)h->instCap * 64, hipMemcpyDeviceToDevice) != hipSuccess) { (void)hipFree(p); snail_set_error("snail_instances_rebuild_dev: copy of the records failed"); return 1; }
+		(void)hipFree(h->dInst);
+		h->dInst = p; h->instCap = n;
+	}
+	if(n > h->buildCap) {
+		if(h->buildBase) (void)hipFree(h->buildBase);
+		h->buildBase = nullptr; h->buildCap = 0;
+		const size_t N = (size_t)n;
+		const size_t bytes = 256 * 12 + sizeof(devb::BuildHdr) + N * 24 + 5 * N * 4 + 2 * N * sizeof(devb::TNode) + 2 * (N / 65 + 2) * 4 + (N / 2 + 2) * 4;
+		HIP_TRY(hipMalloc((void **)&h->buildBase, bytes));
+		h->buildCap = n;
+	}
+	return 0;
+}
+
+// the scratch of a build over up to `cap` instances, carved out of the handle's allocation
+void buildCarve(char *base, int cap, devb::BuildArgs &A) {
+	const size_t N = (size_t)cap;
+	auto take = [&](size_t bytes) { char *p = base; base += (bytes + 255) & ~(size_t)255; return p; };
+	A.hdr = (devb::BuildHdr *)take(sizeof(devb::BuildHdr));
+	A.tn = (devb::TNode *)take(2 * N * sizeof(devb::TNode));
+	A.box = (float *)take(N * 24);
+	A.src = (int *)take(N * 4);
+	A.binE = (int *)take(N * 4);
+	A.tmpA = (int *)take(N * 4);
+	A.tmpB = (int *)take(N * 4);
+	A.startCnt = (int *)take(N * 4);
+	A.queue[0] = (int *)take((N / 65 + 2) * 4);
+	A.queue[1] = (int *)take((N / 65 + 2) * 4);
+	A.small = (int *)take((N / 2 + 2) * 4);
+}
+
+} // namespace
+
+extern "C" {
+
+int snail_instances_rebuild_dev(SnailInstances *h, const float *d_xf12, const int32_t *d_blasIdx, int n, int32_t *d_perm, int32_t *d_info, void *stream) {
+	const char *fn = "snail_instances_rebuild_dev";
+	if(n <= 0 || n > (1 << 30)) { snail_set_error("%s: %d instances (1 .. 1 << 30)", fn, n); return 1; }
+	if(!d_xf12) { snail_set_error("%s: null transforms", fn); return 1; }
+	if(int rc = checkInstances(h, fn)) return rc;
+	if(!h->dBlasBox || !h->dCur) { snail_set_error("%s: invalid instances handle", fn); return 1; }
+	hipStream_t st = (hipStream_t)stream;
+	DeviceGuard guard(h->device);
+	std::lock_guard<std::mutex> lock(h->mu);
+	if(int rc = buildReserve(h, n)) return rc;
+	// after every launch enqueued since the previous update (they read the buffers the commit writes) and after the previous update or rebuild
+	// itself (one scratch area per handle)
+	for(auto &u : h->uses) HIP_TRY(hipStreamWaitEvent(st, u.ev, 0));
+	if(h->hasReady) HIP_TRY(hipStreamWaitEvent(st, h->ready, 0));
+	devb::BuildArgs A;
+	memset(&A, 0, sizeof(A));
+	buildCarve(h->buildBase, h->buildCap, A);
+	A.xf = d_xf12; A.blasIdx = d_blasIdx; A.n = n; A.nBlas = (int)h->blas.size(); A.blasBox = h->dBlasBox;
+	A.top = h->dTop; A.inst = h->dInst; A.cur = h->dCur; A.perm = d_perm; A.info = d_info;
+	A.seed = h->curOnDevice ? 0 : 1; A.seedNodes = h->nNodes; A.seedN = h->n;
+	const int perN = (n + 255) / 256;
+	hipLaunchKernelGGL(devb::k_build_init, dim3(perN), dim3(256), 0, st, A);
+	hipLaunchKernelGGL(devb::k_build_boxes, dim3(perN), dim3(256), 0, st, A);
+	hipLaunchKernelGGL(devb::k_build_root, dim3(1), dim3(64), 0, st, A);
+	if(n > devb::kSmall) {
+		// level L holds at most min(2^L, n / 65) nodes of more than 64 instances; how many it does hold only the device knows: sized for the
+		// worst case (capped; the workgroups stride), the surplus leaves at once
+		const int most = n / (devb::kSmall + 1) + 1;
+		const int wide = 16;   // a level per launch up to here (2^16 x 65 instances before a balanced tree has such nodes deeper) ...
+		for(int level = 0; level < wide; level++) {
+			int grid = level < 10 ? (1 << level) : 1024;
+			grid = std::min(grid, most);
+			hipLaunchKernelGGL(devb::k_build_big, dim3(grid), dim3(256), 0, st, A, level, level + 1);
+		}
+		hipLaunchKernelGGL(devb::k_build_big, dim3(1), dim3(256), 0, st, A, wide, (int)devb::kLevels);   // ... the rest in one workgroup, level after level
+	}
+	if(n >= 2) hipLaunchKernelGGL(devb::k_build_small, dim3(std::min(n / 2 + 1, 4096)), dim3(64), 0, st, A);
+	hipLaunchKernelGGL(devb::k_build_scan, dim3(1), dim3(1024), 0, st, A);
+	hipLaunchKernelGGL(devb::k_build_commit, dim3(std::min((2 * (long long)n + 255) / 256, 2048LL)), dim3(256), 0, st, A);
+	HIP_TRY(hipGetLastError());
+	if(!h->ready) HIP_TRY(hipEventCreateWithFlags(&h->ready, hipEventDisableTiming));
+	HIP_TRY(hipEventRecord(h->ready, st));
+	h->hasReady = true;
+	h->curOnDevice = true;
+	return 0;
+}
+
+int snail_instances_read_tree(SnailInstances *h, void *nodes32, int nodeCap, int *nNodes, float *xf12_slots, int32_t *blasIdx_slots, int slotCap, int *n) {
+	const char *fn = "snail_instances_read_tree";
+	if(int rc = checkInstances(h, fn)) return rc;
+	DeviceGuard guard(h->device);
+	std::lock_guard<std::mutex> lock(h->mu);
+	HIP_TRY(hipDeviceSynchronize());
+	int cur[2] = {h->nNodes, h->n};
+	if(h->curOnDevice) HIP_TRY(hipMemcpy(cur, h->dCur, sizeof(cur), hipMemcpyDeviceToHost));
+	if(cur[0] <= 0 || cur[0] > h->topCap || cur[1] <= 0 || cur[1] > h->instCap) { snail_set_error("%s: the handle holds no tree", fn); return 1; }
+	if(nNodes) *nNodes = cur[0];
+	if(n) *n = cur[1];
+	if(nodes32) {
+		if(nodeCap < cur[0]) { snail_set_error("%s: room for %d nodes, the tree has %d", fn, nodeCap, cur[0]); return 1; }
+		HIP_TRY(hipMemcpy(nodes32, h->dTop, (size_t)cur[0] * 32, hipMemcpyDeviceToHost));
+	}
+	if(xf12_slots || blasIdx_slots) {
+		if(slotCap < cur[1]) { snail_set_error("%s: room for %d instances, the handle has %d", fn, slotCap, cur[1]); return 1; }
+		std::vector<uint32_t> rec((size_t)cur[1] * 16);
+		HIP_TRY(hipMemcpy(rec.data(), h->dInst, rec.size() * 4, hipMemcpyDeviceToHost));
+		for(int i = 0; i < cur[1]; i++) {   // packInstances, backwards
+			const uint32_t *o = rec.data() + (size_t)i * 16;
+			if(xf12_slots) {
+				for(int r = 0; r < 3; r++) memcpy(xf12_slots + (size_t)i * 12 + r * 3, o + r * 4, 12);
+				memcpy(xf12_slots + (size_t)i * 12 + 9, o + 12, 12);
+			}
+			if(blasIdx_slots) blasIdx_slots[i] = (int32_t)o[3];
+		}
+	}
+	return 0;
 }
 
 } // extern "C"

@@ -86,6 +86,7 @@ void snail_set_error(const char *fmt, ...) {
 #include "instances_shade.inc"
 #undef SNAIL_DEV_NS
 #undef SNAIL_ARITH_SSE
+#include "instances_build.inc"   // the device top-level builder: plain fp32, once for both arithmetics
 
 // A launch in the scene's arithmetic: dev::K, or dev_sse::K with the same argument record (the two namespaces are the same text, so the
 // records have the same layout; they are distinct types, hence the copy).  K comes last because its template arguments hold commas.

@@ -3,6 +3,7 @@ src/dbvh/tree.cpp, src/dbvh/traverse.cpp), over the C-ABI of include/snail_insta
 
   InstancedScene(blas, rotations, translations, blas_index)   <-> DBVH(vector<ObjectInstance>)   (host build: snail_instances_build)
   .update(rotations, translations, blas_index)                <-> rebuilding the DBVH for the next frame (rtracer.cpp's -instances mode)
+  .update_dev(xf12, blas_index)                                <-> the same rebuild ON THE DEVICE from device tensors (snail_instances_rebuild_dev)
   .trace_primary(cam, resx, resy)                              <-> RayGenerator + SafeInv + DBVH::TraversePrimary over 16x16 packets
   .traverse_primary(ctx, element) / .traverse_shadow(ctx)     <-> DBVH::TraversePrimary<so,mask> / DBVH::TraverseShadow
   .render_tiles_host(cam, resx, resy, tiles, ...)              <-> Render(scene, camera, resx, resy, data, coords, offsets, options, rank, threads)
@@ -89,7 +90,13 @@ class InstancedScene:
         return nodes, depth, np.ascontiguousarray(xf[perm]), np.ascontiguousarray(bi[perm]), perm
 
     def _set(self, nodes, depth, xf, bi, perm):
-        self._nodes, self.depth, self._xf, self._bi, self._perm = nodes, depth, xf, bi, perm
+        self._nodes, self._depth, self._xf, self._bi, self._perm = nodes, depth, xf, bi, perm
+        # update_dev: _dirty = the handle may hold another tree than the fields above; _d_perm = the scene's own device copy of perm, which
+        # every rebuild that stands overwrites and a refused one leaves alone (_perm_seeded: it starts from the fields above)
+        self._dirty = False
+        self._perm_seeded = False
+        if not hasattr(self, "_d_perm"):
+            self._d_perm = None
 
     def update(self, rotations, translations, blas_index=None, stream=None) -> None:
         """New transforms and a new tree for the next frame, ordered on `stream` after every launch enqueued before it."""
@@ -97,6 +104,77 @@ class InstancedScene:
         _lib.check(_lib.lib().snail_instances_update(self._h, _lib.ptr(nodes), len(nodes), _lib.ptr(xf), _lib.ptr(bi), len(xf), depth, _stream_ptr(stream)),
                    "snail_instances_update")
         self._set(nodes, depth, xf, bi, perm)
+
+    def update_dev(self, xf12, blas_index=None, stream=None, perm=None, info=None):
+        """update() on the device (snail_instances_rebuild_dev): xf12 = float32 [n, 12] and blas_index = int32 [n] (None: all 0) are torch
+        tensors on the scene's device in the CALLER's order; nothing waits on the host, except when the scene's buffers grow and on the
+        first call after an update().  The tree, the slot order and the records it leaves are byte-equal to update()'s.
+        -> (perm int32 [n]: slot -> caller's instance, info int32 [4]: {status, nNodes, depth, n}), device tensors filled on `stream`;
+        status 1 (non-finite transform, BLAS index out of range) or 2 (deeper than 64 levels) leaves the scene as it was.  Without `perm`
+        the returned tensor is a view of the scene's own copy, valid until the next update_dev; with `perm` it is copied there on `stream`.
+        xf12 and blas_index are read on `stream` and must stay alive and unchanged until that work has run (keep the tensors, or
+        record_stream them, when `stream` is not the current one).  nodes() / perm() / slot_transforms() / depth read the handle back (and
+        wait for it) when they are next asked."""
+        torch = _torch()
+        d = self._dev()
+        if not (hasattr(xf12, "data_ptr") and xf12.is_cuda and xf12.device == d and xf12.dtype == torch.float32 and xf12.dim() == 2
+                and xf12.shape[1] == 12 and xf12.is_contiguous()):
+            raise ValueError("xf12 must be a contiguous float32 [n, 12] tensor on %s" % d)
+        n = int(xf12.shape[0])
+        if blas_index is not None and not (blas_index.is_cuda and blas_index.device == d and blas_index.dtype == torch.int32
+                                           and blas_index.numel() == n and blas_index.is_contiguous()):
+            raise ValueError("blas_index must be a contiguous int32 [n] tensor on %s" % d)
+        if perm is not None and not (perm.is_cuda and perm.device == d and perm.dtype == torch.int32 and perm.numel() >= n and perm.is_contiguous()):
+            raise ValueError("perm must be a contiguous int32 tensor of at least n entries on %s" % d)
+        cap = 0 if self._d_perm is None else int(self._d_perm.numel())
+        if cap < n or not self._perm_seeded:
+            # (one-off, like the growth of the handle's buffers: the scene's device copy of perm starts from what the host knows)
+            self._refresh()
+            torch.cuda.synchronize(d)
+            if cap < max(n, len(self._perm)):
+                self._d_perm = torch.empty(max(n, len(self._perm), 2 * cap), dtype=torch.int32, device=d)
+            self._d_perm[:len(self._perm)].copy_(torch.from_numpy(np.ascontiguousarray(self._perm, dtype=np.int32)))
+            torch.cuda.synchronize(d)
+            self._perm_seeded = True
+        if info is None:
+            info = torch.empty(4, dtype=torch.int32, device=d)
+            if stream is not None:
+                info.record_stream(stream)
+        _lib.check(_lib.lib().snail_instances_rebuild_dev(self._h, _lib.ptr(xf12), _lib.ptr(blas_index), n, _lib.ptr(self._d_perm), _lib.ptr(info),
+                                                          _stream_ptr(stream)), "snail_instances_rebuild_dev")
+        self._dirty = True
+        if perm is None:
+            return self._d_perm[:n], info
+        with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(d)):
+            perm[:n].copy_(self._d_perm[:n])
+        return perm, info
+
+    def _refresh(self):
+        """what the handle holds after the update_dev calls since the last look: its own tree and records (snail_instances_read_tree,
+        which waits for everything enqueued), the depth of that tree, and the perm of the latest rebuild that stood"""
+        if not self._dirty:
+            return
+        nn, n = C.c_int(0), C.c_int(0)
+        L = _lib.lib()
+        _lib.check(L.snail_instances_read_tree(self._h, None, 0, C.addressof(nn), None, None, 0, C.addressof(n)), "snail_instances_read_tree")
+        nodes = np.zeros(nn.value, dtype=NODE_DTYPE)
+        xf = np.zeros((n.value, 12), dtype=np.float32)
+        bi = np.zeros(n.value, dtype=np.int32)
+        _lib.check(L.snail_instances_read_tree(self._h, _lib.ptr(nodes), len(nodes), None, _lib.ptr(xf), _lib.ptr(bi), len(xf), None),
+                   "snail_instances_read_tree")
+        # depth = the deepest leaf (children follow their parent)
+        sub = nodes["sub"].astype(np.int64)
+        level = np.zeros(len(nodes), dtype=np.int64)
+        for i in np.nonzero((sub & 0x80000000) == 0)[0]:
+            level[sub[i]] = level[sub[i] + 1] = level[i] + 1
+        self._nodes, self._depth, self._xf, self._bi = nodes, int(level.max()), xf, bi
+        self._perm = self._d_perm[:n.value].cpu().numpy().astype(np.int32)
+        self._dirty = False
+
+    @property
+    def depth(self) -> int:
+        self._refresh()
+        return self._depth
 
     def close(self):
         if getattr(self, "_h", None):
@@ -111,13 +189,16 @@ class InstancedScene:
 
     # ---- for tests --------------------------------------------------------------------------------
     def nodes(self) -> np.ndarray:
+        self._refresh()
         return self._nodes.copy()
 
     def perm(self) -> np.ndarray:
+        self._refresh()
         return self._perm.copy()
 
     def slot_transforms(self):
         """(xf12 [n,12], blas_index [n]) in builder-slot order, as the handle holds them."""
+        self._refresh()
         return self._xf.copy(), self._bi.copy()
 
     # ---- traversal ----------------------------------------------------------------------------------

@@ -25,7 +25,15 @@ per frame, device-to-host copy and the scatter into the caller's buffer included
   image          InstancedScene.render_image_host of the same build (the interleaved frame, no tile list), for scale.
 Repeated alternating runs, medians.
 
-    python tools/instances_time.py --tiles [--reps 9]"""
+    python tools/instances_time.py --tiles [--reps 9]
+
+--rebuild-dev: what the per-frame rebuild costs on the device (InstancedScene.update_dev = snail_instances_rebuild_dev, transforms already in
+device memory) beside the host path (InstancedScene.update = snail_instances_build + upload, transforms in host memory), for --rebuild-counts
+instances (default here 1024,10000): host wall ms per frame of each, synchronised, and the device time of update_dev alone between two events.
+Alternating runs (each round: update(), one untimed update_dev, the timed update_dev -- the steady state of a loop that stays on the device),
+medians.
+
+    python tools/instances_time.py --rebuild-dev [--rebuild-counts 1024,10000] [--reps 15]"""
 import argparse
 import json
 import os
@@ -62,12 +70,16 @@ def main():
     ap.add_argument("--res", default="1920x1080")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--counts", default="1,64,1024")
-    ap.add_argument("--rebuild-counts", default="10000")
+    ap.add_argument("--rebuild-counts", default=None)
+    ap.add_argument("--rebuild-dev", action="store_true")
     ap.add_argument("--lit", action="store_true")
     ap.add_argument("--tiles", action="store_true")
     ap.add_argument("--baseline-lib", default=None)
     a = ap.parse_args()
     resx, resy = (int(x) for x in a.res.split("x"))
+    if a.rebuild_dev:
+        return rebuild_dev(torch, [int(c) for c in (a.rebuild_counts or "1024,10000").split(",")], a.reps)
+    a.rebuild_counts = a.rebuild_counts or "10000"
     if a.lit:
         return lit(torch, a, resx, resy)
     if a.tiles:
@@ -273,6 +285,48 @@ def rebuild(torch, sc, counts, reps):
         isc.close()
         rows.append({"instances": n, "build_ms": round(best_b * 1e3, 3), "update_ms": round(best_u * 1e3, 3)})
     return rows
+
+
+def rebuild_dev(torch, counts, reps):
+    import statistics
+    import time
+    tv = scenes.atrium()
+    sc = Scene(HostBVH.build(tv), 0)
+    lo, hi = sc.get_bbox()
+    out = {"unit": "ms per rebuild, median of %d alternating runs" % reps, "rows": []}
+    for n in counts:
+        frames = []
+        for k in range(4):          # a few different fields, so that no run rebuilds what it has just built
+            rot, tr, bi = scenes.instance_field(lo, hi, n, seed=3 + k)
+            xf = np.ascontiguousarray(np.concatenate([rot.reshape(-1, 9), tr], axis=1), dtype=np.float32)
+            frames.append((rot, tr, bi, torch.from_numpy(xf).cuda(), torch.from_numpy(bi).cuda()))
+        isc = InstancedScene([sc], frames[0][0], frames[0][1], frames[0][2])
+        info = torch.empty(4, dtype=torch.int32, device="cuda")
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        ms = {"update_host": [], "update_dev": [], "update_dev_device": []}
+        for k in range(reps + 2):   # (two warm-up rounds: buffer growth, first launches)
+            rot, tr, bi, d_xf, d_bi = frames[k % len(frames)]
+            torch.cuda.synchronize()
+            t0 = time.perf_counter(); isc.update(rot, tr, bi); torch.cuda.synchronize(); t1 = time.perf_counter()
+            isc.update_dev(d_xf, d_bi, info=info)       # (untimed: the first update_dev after an update() re-seeds the scene's device copy of perm)
+            torch.cuda.synchronize()
+            e0.record()
+            t2 = time.perf_counter(); isc.update_dev(d_xf, d_bi, info=info); e1.record(); torch.cuda.synchronize(); t3 = time.perf_counter()
+            if k >= 2:
+                ms["update_host"].append((t1 - t0) * 1e3)
+                ms["update_dev"].append((t3 - t2) * 1e3)
+                ms["update_dev_device"].append(e0.elapsed_time(e1))
+        assert int(info.cpu()[0]) == 0
+        row = {"instances": n}
+        for k, v in ms.items():
+            row[k + "_ms"] = round(statistics.median(v), 4)
+            row[k + "_min_ms"] = round(min(v), 4)
+        row["host_over_dev"] = round(row["update_host_ms"] / row["update_dev_ms"], 2)
+        out["rows"].append(row)
+        print(json.dumps(row), file=sys.stderr, flush=True)
+        isc.close()
+    sc.close()
+    print(json.dumps(out))
 
 
 if __name__ == "__main__":
