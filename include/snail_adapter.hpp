@@ -55,6 +55,7 @@
 #include <vector>
 
 #include "snail_hip.h"
+#include "snail_bvh_fast.h"
 #include "snail_instances.h"
 
 #ifndef SNAIL_CHECK
@@ -114,6 +115,23 @@ public:
 	// One copy of the tree per listed device (the reference's server ships the same arrays to every render node, src/server.cpp:144-164):
 	// the tile-list renderer then deals a frame's tiles over all of them (snail::RenderTiles -> snail_render_tiles_multi); every other
 	// path (prefetched frame, immediate and batched packets, image renderer) runs on the first device.
+	// BVH::Construct(scene, flags) with BVH::fastBuild set (the default of BVH::BVH, -fastRebuild, lm.rebuild == 1), run on the device from
+	// vertices in device memory (include/snail_bvh_fast.h): the handle holds the very tree RefBVH::Construct(scene, fastBuild) builds, triId
+	// included, and Rebuild() repeats the build in place on a stream for a mesh that deforms.  Without fastBuild the sweep builder stays on
+	// the host: Construct there, then Upload().  d_perm / d_info as in snail_scene_create_fast_dev (may be null).
+	void ConstructOnDevice(const float *d_verts9, int nTris, int flags, int device = 0, int32_t *d_perm = nullptr, int32_t *d_info = nullptr, void *stream = nullptr) {
+		if(!(flags & RefBVH::fastBuild)) { std::fprintf(stderr, "FATAL: HipBVH::ConstructOnDevice: only BVH::fastBuild runs on the device\n"); std::abort(); }
+		ref = nullptr;
+		Release();
+		SnailScene *h = snail_scene_create_fast_dev(d_verts9, nTris, device, d_perm, d_info, stream);
+		if(!h) { std::fprintf(stderr, "FATAL: snail_scene_create_fast_dev(device %d): %s\n", device, snail_last_error()); std::abort(); }
+		handles.push_back(h);
+		scene = h;
+		if(arith != SNAIL_ARITH_IEEE && !SetArith(arith)) { std::fprintf(stderr, "FATAL: HipBVH::ConstructOnDevice: SetArith(%d): %s\n", arith, snail_last_error()); std::abort(); }
+	}
+	bool Rebuild(const float *d_verts9, int nTris, int32_t *d_perm = nullptr, int32_t *d_info = nullptr, void *stream = nullptr) {
+		return scene && snail_scene_rebuild_fast_dev(scene, d_verts9, nTris, d_perm, d_info, stream) == 0;
+	}
 	void Upload(const RefBVH &bvh, const std::vector<int> &devices) {
 		if(devices.empty()) { std::fprintf(stderr, "FATAL: HipBVH::Upload: no device\n"); std::abort(); }
 		ref = &bvh;

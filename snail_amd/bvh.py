@@ -46,6 +46,21 @@ class HostBVH:
                                               _lib.ptr(perm)), "snail_bvh_build")
         return HostBVH(tris, np.ascontiguousarray(nodes[:nn.value]), depth.value, perm)
 
+    @staticmethod
+    def build_fast(tri_verts: np.ndarray) -> "HostBVH":
+        """The reference's fast builder, BVH::Construct(scene, fastBuild) / FindSplit (src/bvh/tree.cpp:161-287): 16 bins on the node's longest
+        axis (snail_bvh_build_fast, include/snail_bvh_fast.h).  Same records and conventions as build(); another tree."""
+        tris = HostBVH.triangles(tri_verts)
+        n = len(tris)
+        if n == 0:
+            raise _lib.SnailError("cannot build a BVH over zero triangles")
+        nodes = np.zeros(2 * n + 2, dtype=NODE_DTYPE)
+        perm = np.zeros(n, dtype=np.int32)
+        nn, depth = C.c_int(0), C.c_int(0)
+        _lib.check(_lib.lib().snail_bvh_build_fast(_lib.ptr(tris), n, _lib.ptr(nodes), C.addressof(nn), C.addressof(depth),
+                                                   _lib.ptr(perm)), "snail_bvh_build_fast")
+        return HostBVH(tris, np.ascontiguousarray(nodes[:nn.value]), depth.value, perm)
+
     @property
     def n_tris(self) -> int:
         return len(self.tris)

@@ -12,7 +12,7 @@
 // computed once and carried along with the permutation; recursion is replaced by an explicit stack
 // that reproduces the reference's pre-order node numbering (both children are appended when the parent
 // is split, the left subtree is completed before the right one).
-#include "../../include/snail_hip.h"
+#include "../../include/snail_bvh_fast.h"
 
 #include <algorithm>
 #include <cmath>
@@ -171,6 +171,143 @@ int buildSweep(Tri64 *tris, int nTris, Node32 *nodes, int *outNodes, int *outDep
 	return 0;
 }
 
+// int((c - sub) * mul), defined where the reference is not (include/snail_bvh_fast.h): NaN or below 0 is bin 0, 16 or more is bin 15
+static inline int binOf(float c, float sub, float mul) {
+	const float v = (c - sub) * mul;
+	if(!(v >= 0.0f)) return 0;
+	if(!(v < 16.0f)) return 15;
+	return (int)v;
+}
+
+// BVH::Construct(scene, fastBuild) + BVH::FindSplit (src/bvh/tree.cpp:161-287, :293-314): the 16-bin builder.  Boxes and source indices
+// travel with the partition; the 64-byte records are gathered once at the end (the reference gathers per split, :245-247: same order).
+int buildFast(Tri64 *tris, int nTris, Node32 *nodes, int *outNodes, int *outDepth, int32_t *perm) {
+	enum { nBins = 16 };
+	std::vector<Bounds> box(nTris);
+	std::vector<int32_t> src(nTris);
+	for(int i = 0; i < nTris; i++) { box[i] = boundsOf(tris[i]); src[i] = i; }
+
+	auto putBox = [&](int n, const Bounds &b) {
+		for(int k = 0; k < 3; k++) { nodes[n].bmin[k] = b.lo[k]; nodes[n].bmax[k] = b.hi[k]; }
+		nodes[n].sub = 0; nodes[n].aux = 0;
+	};
+	Bounds root = box[0];
+	for(int i = 1; i < nTris; i++) root.merge(box[i]);
+	putBox(0, root);
+	int nNodes = 1, depth = 0;
+	const float inf = std::numeric_limits<float>::infinity();
+
+	std::vector<Job> todo;
+	todo.push_back(Job{0, 0, nTris, 0});
+	while(!todo.empty()) {
+		const Job j = todo.back();
+		todo.pop_back();
+		const int first = j.first, count = j.count;
+		bool leaf = count <= 4;
+		int axis = 0, minIdx = 1;
+		float sub = 0.0f, mul = 0.0f;
+		Bounds leftBoxes[nBins], rightBoxes[nBins];
+		int leftCounts[nBins], rightCounts[nBins];
+		if(!leaf) {
+			Bounds nb;
+			for(int k = 0; k < 3; k++) { nb.lo[k] = nodes[j.node].bmin[k]; nb.hi[k] = nodes[j.node].bmax[k]; }
+			const float sx = nb.hi[0] - nb.lo[0], sy = nb.hi[1] - nb.lo[1], sz = nb.hi[2] - nb.lo[2];
+			axis = sy > sx ? (sz > sy ? 2 : 1) : (sz > sx ? 2 : 0);                     // MaxAxis, src/rtbase.h:136-138
+			Bounds bins[nBins];
+			int binCount[nBins];
+			for(int b = 0; b < nBins; b++) {
+				for(int k = 0; k < 3; k++) { bins[b].lo[k] = inf; bins[b].hi[k] = -inf; }
+				binCount[b] = 0;
+			}
+			mul = (float)nBins * (1.0f - 0.0001f) / (nb.hi[axis] - nb.lo[axis]);       // constant::epsilon = 0.0001f, veclib/vecbase.h:40
+			sub = nb.lo[axis];
+			for(int n = 0; n < count; n++) {
+				const Bounds &b = box[first + n];
+				const float c = (b.hi[axis] + b.lo[axis]) * 0.5f;
+				const int bin = binOf(c, sub, mul);
+				binCount[bin]++;
+				bins[bin].merge(b);
+			}
+			rightBoxes[nBins - 1] = bins[nBins - 1]; rightCounts[nBins - 1] = binCount[nBins - 1];
+			leftBoxes[0] = bins[0]; leftCounts[0] = binCount[0];
+			for(int b = 1; b < nBins; b++) {
+				leftBoxes[b] = leftBoxes[b - 1]; leftBoxes[b].merge(bins[b]);
+				leftCounts[b] = leftCounts[b - 1] + binCount[b];
+			}
+			for(int b = nBins - 2; b >= 0; b--) {
+				rightBoxes[b] = rightBoxes[b + 1]; rightBoxes[b].merge(bins[b]);
+				rightCounts[b] = rightCounts[b + 1] + binCount[b];
+			}
+			float minCost = inf;
+			const float noSplitCost = 1.0f * count * nb.area();
+			for(int b = 1; b < nBins; b++) {
+				const float cost = (leftCounts[b - 1] ? leftBoxes[b - 1].area() * leftCounts[b - 1] : 0) +
+								   (rightCounts[b] ? rightBoxes[b].area() * rightCounts[b] : 0);
+				if(cost < minCost) { minCost = cost; minIdx = b; }
+			}
+			minCost = 0.0f + 1.0f * minCost;
+			if(noSplitCost < minCost) leaf = true;
+		}
+		if(leaf) {                                                                   // tree.cpp:165-169: the box stays the parent's fold
+			depth = std::max(depth, j.depth);
+			nodes[j.node].sub = (uint32_t)first | 0x80000000u;
+			nodes[j.node].aux = count;
+			continue;
+		}
+		// std::partition(&indices[0], &indices[count], TestTris(...)) as libstdc++ runs it for bidirectional iterators (bits/stl_algo.h
+		// __partition: skip true from the front, skip false from the back, swap, repeat).  TestTris (tree.cpp:28-38) takes the centre from
+		// Min / Max of P1, P2, P3: the two bounds GetBBox holds, added in the other order (fp32 addition commutes)
+		{
+			auto pred = [&](int i) { return binOf((box[i].lo[axis] + box[i].hi[axis]) * 0.5f, sub, mul) < minIdx; };
+			int lo = first, hi = first + count;
+			for(;;) {
+				for(;;) {
+					if(lo == hi) goto PARTITIONED;
+					if(pred(lo)) lo++;
+					else break;
+				}
+				hi--;
+				for(;;) {
+					if(lo == hi) goto PARTITIONED;
+					if(!pred(hi)) hi--;
+					else break;
+				}
+				std::swap(box[lo], box[hi]);
+				std::swap(src[lo], src[hi]);
+				lo++;
+			}
+		PARTITIONED:;
+		}
+		Bounds lb = leftBoxes[minIdx - 1], rb = rightBoxes[minIdx];
+		int leftCount = leftCounts[minIdx - 1], rightCount = rightCounts[minIdx];
+		if(leftCount == 0 || rightCount == 0) {                                      // tree.cpp:260-271
+			const int mid = count / 2;
+			lb = box[first];
+			rb = box[first + count - 1];
+			for(int n = 1; n < mid; n++) lb.merge(box[first + n]);
+			for(int n = mid; n < count; n++) rb.merge(box[first + n]);
+			leftCount = mid;
+			rightCount = count - leftCount;
+		}
+		const int child = nNodes;
+		nodes[j.node].sub = (uint32_t)child;
+		// tree.cpp:277-279: the second assignment to firstNode is the one that counts
+		const int firstNode = lb.lo[axis] == rb.lo[axis] ? (lb.hi[axis] < rb.hi[axis] ? 0 : 1) : 0;
+		nodes[j.node].aux = (axis & 0xffff) | (firstNode << 16);
+		putBox(child, lb); putBox(child + 1, rb);
+		nNodes += 2;
+		todo.push_back(Job{child + 1, first + leftCount, rightCount, j.depth + 1});   // right: after the whole left subtree
+		todo.push_back(Job{child + 0, first, leftCount, j.depth + 1});
+	}
+
+	std::vector<Tri64> tmp(tris, tris + nTris);
+	for(int i = 0; i < nTris; i++) tris[i] = tmp[src[i]];
+	if(perm) for(int i = 0; i < nTris; i++) perm[i] = src[i];
+	*outNodes = nNodes;
+	*outDepth = depth;
+	return 0;
+}
+
 void trisFromVerts(const float *v, int n, Tri64 *out) {
 	for(int i = 0; i < n; i++) {
 		const float *p = v + (size_t)i * 9;
@@ -216,5 +353,14 @@ extern "C" int snail_bvh_build(void *tris64, int nTris, void *nodes32, int *nNod
 	FpEnvGuard fpEnv;
 	int rc = snail::buildSweep((snail::Tri64 *)tris64, nTris, (snail::Node32 *)nodes32, nNodes, depth, perm);
 	if(rc == 0 && *depth > SNAIL_MAX_DEPTH) { snail_set_error("snail_bvh_build: depth %d exceeds %d", *depth, SNAIL_MAX_DEPTH); return 2; }
+	return rc;
+}
+
+// include/snail_bvh_fast.h
+extern "C" int snail_bvh_build_fast(void *tris64, int nTris, void *nodes32, int *nNodes, int *depth, int32_t *perm) {
+	if(nTris <= 0 || !tris64 || !nodes32 || !nNodes || !depth) { snail_set_error("snail_bvh_build_fast: bad arguments"); return 1; }
+	FpEnvGuard fpEnv;
+	int rc = snail::buildFast((snail::Tri64 *)tris64, nTris, (snail::Node32 *)nodes32, nNodes, depth, perm);
+	if(rc == 0 && *depth > SNAIL_MAX_DEPTH) { snail_set_error("snail_bvh_build_fast: depth %d exceeds %d", *depth, SNAIL_MAX_DEPTH); return 2; }
 	return rc;
 }

@@ -189,10 +189,15 @@ int instancesBegin(SnailInstances *h, const char *fn, dev::InstArgs &A, bool *ss
 	}
 	A.top = h->dTop; A.inst = h->dInst; A.blas = h->dBlas;
 	if(h->hasReady) HIP_TRY(hipStreamWaitEvent(stream, h->ready, 0));
+	// a BLAS that is rebuilt on the device (snail_scene_rebuild_fast_dev): this launch reads its tree
+	for(SnailScene *s : h->blas)
+		if(s->fast) { std::lock_guard<std::mutex> lock(s->mu); if(int rc = fastSceneBegin(s, stream)) return rc; }
 	return 0;
 }
 int instancesEnd(SnailInstances *h, hipStream_t stream) {
 	HIP_TRY(hipGetLastError());
+	for(SnailScene *s : h->blas)
+		if(s->fast) { std::lock_guard<std::mutex> lock(s->mu); fastSceneEnd(s, stream); }
 	for(auto &u : h->uses)
 		if(u.stream == stream) { HIP_TRY(hipEventRecord(u.ev, stream)); return 0; }
 	SnailInstances::Use u;
@@ -712,29 +717,11 @@ int buildReserve(SnailInstances *h, int n) {
 	if(n > h->buildCap) {
 		if(h->buildBase) (void)hipFree(h->buildBase);
 		h->buildBase = nullptr; h->buildCap = 0;
-		const size_t N = (size_t)n;
-		const size_t bytes = 256 * 12 + sizeof(devb::BuildHdr) + N * 24 + 5 * N * 4 + 2 * N * sizeof(devb::TNode) + 2 * (N / 65 + 2) * 4 + (N / 2 + 2) * 4;
+		const size_t bytes = buildScratchBytes(n);
 		HIP_TRY(hipMalloc((void **)&h->buildBase, bytes));
 		h->buildCap = n;
 	}
 	return 0;
-}
-
-// the scratch of a build over up to `cap` instances, carved out of the handle's allocation
-void buildCarve(char *base, int cap, devb::BuildArgs &A) {
-	const size_t N = (size_t)cap;
-	auto take = [&](size_t bytes) { char *p = base; base += (bytes + 255) & ~(size_t)255; return p; };
-	A.hdr = (devb::BuildHdr *)take(sizeof(devb::BuildHdr));
-	A.tn = (devb::TNode *)take(2 * N * sizeof(devb::TNode));
-	A.box = (float *)take(N * 24);
-	A.src = (int *)take(N * 4);
-	A.binE = (int *)take(N * 4);
-	A.tmpA = (int *)take(N * 4);
-	A.tmpB = (int *)take(N * 4);
-	A.startCnt = (int *)take(N * 4);
-	A.queue[0] = (int *)take((N / 65 + 2) * 4);
-	A.queue[1] = (int *)take((N / 65 + 2) * 4);
-	A.small = (int *)take((N / 2 + 2) * 4);
 }
 
 } // namespace
@@ -755,16 +742,26 @@ int snail_instances_rebuild_dev(SnailInstances *h, const float *d_xf12, const in
 	// itself (one scratch area per handle)
 	for(auto &u : h->uses) HIP_TRY(hipStreamWaitEvent(st, u.ev, 0));
 	if(h->hasReady) HIP_TRY(hipStreamWaitEvent(st, h->ready, 0));
+	// the root box of a BLAS that can be rebuilt on the device (snail_scene_rebuild_fast_dev) is read again, after any rebuild enqueued so far
+	for(size_t b = 0; b < h->blas.size(); b++) {
+		SnailScene *s = h->blas[b];
+		if(!s->fast) continue;
+		std::lock_guard<std::mutex> blasLock(s->mu);
+		if(int rc = fastSceneBegin(s, st)) return rc;
+		HIP_TRY(hipMemcpyAsync((char *)h->dBlasBox + b * 24, s->dNodes, 24, hipMemcpyDeviceToDevice, st));
+		fastSceneEnd(s, st);
+	}
 	devb::BuildArgs A;
 	memset(&A, 0, sizeof(A));
 	buildCarve(h->buildBase, h->buildCap, A);
-	A.xf = d_xf12; A.blasIdx = d_blasIdx; A.n = n; A.nBlas = (int)h->blas.size(); A.blasBox = h->dBlasBox;
+	A.xf = d_xf12; A.blasIdx = d_blasIdx; A.n = n; A.maxDepth = devb::kMaxDepth; A.nBlas = (int)h->blas.size(); A.blasBox = h->dBlasBox;
 	A.top = h->dTop; A.inst = h->dInst; A.cur = h->dCur; A.perm = d_perm; A.info = d_info;
 	A.seed = h->curOnDevice ? 0 : 1; A.seedNodes = h->nNodes; A.seedN = h->n;
 	const int perN = (n + 255) / 256;
 	hipLaunchKernelGGL(devb::k_build_init, dim3(perN), dim3(256), 0, st, A);
 	hipLaunchKernelGGL(devb::k_build_boxes, dim3(perN), dim3(256), 0, st, A);
-	hipLaunchKernelGGL(devb::k_build_root, dim3(1), dim3(64), 0, st, A);
+	const devb::SplitArgs &SA = A;
+	hipLaunchKernelGGL(devb::k_build_root<devb::SplitDbvh>, dim3(1), dim3(64), 0, st, SA);
 	if(n > devb::kSmall) {
 		// level L holds at most min(2^L, n / 65) nodes of more than 64 instances; how many it does hold only the device knows: sized for the
 		// worst case (capped; the workgroups stride), the surplus leaves at once
@@ -773,12 +770,12 @@ int snail_instances_rebuild_dev(SnailInstances *h, const float *d_xf12, const in
 		for(int level = 0; level < wide; level++) {
 			int grid = level < 10 ? (1 << level) : 1024;
 			grid = std::min(grid, most);
-			hipLaunchKernelGGL(devb::k_build_big, dim3(grid), dim3(256), 0, st, A, level, level + 1);
+			hipLaunchKernelGGL(devb::k_build_big<devb::SplitDbvh>, dim3(grid), dim3(256), 0, st, SA, level, level + 1);
 		}
-		hipLaunchKernelGGL(devb::k_build_big, dim3(1), dim3(256), 0, st, A, wide, (int)devb::kLevels);   // ... the rest in one workgroup, level after level
+		hipLaunchKernelGGL(devb::k_build_big<devb::SplitDbvh>, dim3(1), dim3(256), 0, st, SA, wide, (int)devb::kLevels);   // ... the rest in one workgroup, level after level
 	}
-	if(n >= 2) hipLaunchKernelGGL(devb::k_build_small, dim3(std::min(n / 2 + 1, 4096)), dim3(64), 0, st, A);
-	hipLaunchKernelGGL(devb::k_build_scan, dim3(1), dim3(1024), 0, st, A);
+	if(n >= 2) hipLaunchKernelGGL(devb::k_build_small<devb::SplitDbvh>, dim3(std::min(n / 2 + 1, 4096)), dim3(64), 0, st, SA);
+	hipLaunchKernelGGL(devb::k_build_scan, dim3(1), dim3(1024), 0, st, SA);
 	hipLaunchKernelGGL(devb::k_build_commit, dim3(std::min((2 * (long long)n + 255) / 256, 2048LL)), dim3(256), 0, st, A);
 	HIP_TRY(hipGetLastError());
 	if(!h->ready) HIP_TRY(hipEventCreateWithFlags(&h->ready, hipEventDisableTiming));

@@ -62,35 +62,38 @@ __global__ void k_morton(const float *verts, int n, const unsigned *bounds, u64 
 	keys[i] = ((u64)code << 32) | (unsigned)i;
 }
 
-// triangle records in sorted order: the formulas of Triangle::Triangle + ComputeData (src/triangle.h:16-21,123-131), as in
-// snail_tris_from_verts (this TU is built without FMA contraction, IEEE divide / sqrt)
-__global__ void k_records(const float *verts, int n, const u64 *keys, float *tris /*16 floats each*/, int *perm, Box *leafBox, int *flags) {
-	const int j = (int)(blockIdx.x * blockDim.x + threadIdx.x);
-	if(j >= n) return;
-	const int src = (int)(unsigned)(keys[j] & 0xffffffffull);
-	const float *p = verts + (size_t)src * 9;
+// one triangle record: the formulas of Triangle::Triangle + ComputeData (src/triangle.h:16-21,123-131), as in snail_tris_from_verts (this
+// TU is built without FMA contraction, IEEE divide / sqrt); p = 9 floats of vertices, t = 16 floats.  Returns the sanity conditions of
+// snail_scene_create (fast arithmetic modes need finite records of sane magnitude).  Shared with bvh_fast.inc
+__device__ __forceinline__ bool triRecord(const float *p, float *t) {
 	float a[3], ba[3], ca[3];
-	Box b;
-	for(int k = 0; k < 3; k++) {
-		a[k] = p[k]; ba[k] = p[3 + k] - p[k]; ca[k] = p[6 + k] - p[k];
-		b.mn[k] = fminf(p[k], fminf(p[3 + k], p[6 + k])); b.mx[k] = fmaxf(p[k], fmaxf(p[3 + k], p[6 + k]));
-	}
+	for(int k = 0; k < 3; k++) { a[k] = p[k]; ba[k] = p[3 + k] - p[k]; ca[k] = p[6 + k] - p[k]; }
 	float nx = ba[1] * ca[2] - ba[2] * ca[1];
 	float ny = ba[2] * ca[0] - ba[0] * ca[2];
 	float nz = ba[0] * ca[1] - ba[1] * ca[0];
 	const float len = __builtin_sqrtf(nx * nx + ny * ny + nz * nz);
 	const float inv = 1.0f / len;
 	nx *= inv; ny *= inv; nz *= inv;
-	float *t = tris + (size_t)j * 16;
 	t[0] = a[0]; t[1] = a[1]; t[2] = a[2]; t[3] = ba[0]; t[4] = ba[1]; t[5] = ba[2]; t[6] = ca[0]; t[7] = ca[1]; t[8] = ca[2];
 	t[9] = len; t[10] = 1.0f / len; t[11] = 0.0f;
 	t[12] = nx; t[13] = ny; t[14] = nz; t[15] = nx * a[0] + ny * a[1] + nz * a[2];
-	perm[j] = src;
-	leafBox[j] = b;
-	// the sanity conditions of snail_scene_create (fast arithmetic modes need finite records of sane magnitude)
 	bool ok = len > 0.0f && t[10] <= 1.0e12f && t[10] > 0.0f;
 	for(int k = 0; k < 9; k++) ok = ok && fabsf(t[k]) <= 1.0e9f;
 	for(int k = 12; k < 16; k++) ok = ok && fabsf(t[k]) <= 1.0e18f;
+	return ok;
+}
+
+// triangle records in sorted order
+__global__ void k_records(const float *verts, int n, const u64 *keys, float *tris /*16 floats each*/, int *perm, Box *leafBox, int *flags) {
+	const int j = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+	if(j >= n) return;
+	const int src = (int)(unsigned)(keys[j] & 0xffffffffull);
+	const float *p = verts + (size_t)src * 9;
+	Box b;
+	for(int k = 0; k < 3; k++) { b.mn[k] = fminf(p[k], fminf(p[3 + k], p[6 + k])); b.mx[k] = fmaxf(p[k], fmaxf(p[3 + k], p[6 + k])); }
+	const bool ok = triRecord(p, tris + (size_t)j * 16);
+	perm[j] = src;
+	leafBox[j] = b;
 	if(!ok) atomicAnd(flags, 0);
 }
 

@@ -43,6 +43,7 @@
 
 #include "../../include/snail_hip.h"
 #include "../../include/snail_instances.h"
+#include "../../include/snail_bvh_fast.h"
 #include "host_sse.h"
 #ifdef SNAIL_DEBUG_API
 #include "../../include/snail_hip_debug.h"
@@ -86,7 +87,8 @@ void snail_set_error(const char *fmt, ...) {
 #include "instances_shade.inc"
 #undef SNAIL_DEV_NS
 #undef SNAIL_ARITH_SSE
-#include "instances_build.inc"   // the device top-level builder: plain fp32, once for both arithmetics
+#include "build_common.inc"      // the device builders: plain fp32, once for both arithmetics
+#include "instances_build.inc"   // ... of the top-level tree over instances (bvh_fast.inc, of a plain scene, follows lbvh.inc)
 
 // A launch in the scene's arithmetic: dev::K, or dev_sse::K with the same argument record (the two namespaces are the same text, so the
 // records have the same layout; they are distinct types, hence the copy).  K comes last because its template arguments hold commas.
@@ -104,6 +106,8 @@ void snail_set_error(const char *fmt, ...) {
 // host side of the C-ABI
 // ---------------------------------------------------------------------------------------------------
 namespace { struct TileJob; void freeTileJobs(SnailScene *); } // render_host.inc: cached lists of snail_render_tiles / snail_render_image
+struct SnailSceneFast;   // bvh_fast.inc: what a handle of snail_scene_create_fast_dev carries besides the scene
+namespace { int fastSceneBegin(SnailScene *, hipStream_t); void fastSceneEnd(SnailScene *, hipStream_t); void fastFree(SnailSceneFast *); int fastCurrent(const SnailScene *, int cur[4]); }
 struct SnailScene {
 	int device = 0;
 	int arith = SNAIL_ARITH_IEEE; // snail_scene_set_arith: which of the two kernel sets (dev / dev_sse) every launch of this scene takes
@@ -113,6 +117,7 @@ struct SnailScene {
 	unsigned *dTab = nullptr;
 	unsigned tabGen = 0;
 	TileJob *tileJob = nullptr, *frameJob = nullptr;
+	SnailSceneFast *fast = nullptr;   // snail_scene_create_fast_dev: the tree is rebuilt on the device (nNodes is then the node arrays' capacity)
 	int nNodes = 0, nTris = 0, depth = 0;
 	uint4 *dNodes = nullptr, *dTris = nullptr;   // the caller's records; dTris points INTO dPF (one allocation, see below)
 	// [slot 0: unused][slot i + 1: node i, re-encoded for the record-prefetching loop (dev::pfEncode)] ... [triangle records at trisOff]
@@ -441,6 +446,16 @@ int relUsed(SnailScene *s, int which, hipStream_t stream) {
 	return 0;
 }
 
+// A launch that reads a handle's tree, against snail_scene_rebuild_fast_dev (include/snail_bvh_fast.h): its stream waits for the last rebuild
+// and leaves an event the next rebuild waits for.  Nothing for a handle that is never rebuilt.  (mu held)
+struct SceneUse {
+	SnailScene *s; hipStream_t st; int rc = 0;
+	SceneUse(SnailScene *scene, hipStream_t stream) : s(scene), st(stream) { if(s->fast) rc = fastSceneBegin(s, st); }
+	~SceneUse() { if(s->fast) fastSceneEnd(s, st); }
+	SceneUse(const SceneUse &) = delete;
+	SceneUse &operator=(const SceneUse &) = delete;
+};
+
 int checkScene(const SnailScene *s, const char *fn) {
 	if(!s || !s->dNodes || !s->dPF || !s->dTris) { snail_set_error("%s: invalid scene handle", fn); return 1; }
 	return 0;
@@ -488,6 +503,8 @@ int launchPrimaryFrames(SnailScene *s, const FrameSet &FS, int resx, int resy, i
 	if(resx <= 0 || resy <= 0) { snail_set_error("snail_trace_primary: bad resolution %dx%d", resx, resy); return 1; }
 	if(dNextOrder && !dSlotCost) { snail_set_error("snail_trace_primary: the next dispatch order is derived from d_slot_cost, which is null"); return 1; }
 	if(FS.n < 1 || FS.n > SNAIL_MAX_BATCH || (SNAIL_BLOCK_WAVES > 1 && FS.n > 1)) { snail_set_error("snail_trace_primary: 1..%d frames per launch (got %d)", SNAIL_MAX_BATCH, FS.n); return 1; }
+	SceneUse use(s, stream);
+	if(use.rc) return use.rc;
 	dev::PrimaryArgs A;
 	memset(&A, 0, sizeof(A));
 	A.hostTab = s->arith == SNAIL_ARITH_HOST_SSE ? s->dTab : nullptr;
@@ -648,6 +665,8 @@ int launchRays(SnailScene *s, bool shadow, int nPackets, int size, int sharedOri
 	if(nPackets <= 0) return 0;
 	if(size < 1 || size > SNAIL_PACKET_QUADS) { snail_set_error("packet size %d outside 1..%d quads", size, SNAIL_PACKET_QUADS); return 1; }
 	if(!origin || !dir || !idir || !distance || (!shadow && !object)) { snail_set_error("null ray array"); return 1; }
+	SceneUse use(s, stream);
+	if(use.rc) return use.rc;
 	dev::RaysArgs A;
 	memset(&A, 0, sizeof(A));
 	A.hostTab = s->arith == SNAIL_ARITH_HOST_SSE ? s->dTab : nullptr;
@@ -699,6 +718,8 @@ int launchRays(SnailScene *s, bool shadow, int nPackets, int size, int sharedOri
 template <int SRC>
 int launchLights(SnailScene *s, dev::ShadeArgs A /* a copy: relLight is filled in here */, hipStream_t stream, int32_t *dNextOrder = nullptr, int orderFlags = 0) {
 	if(A.nLights <= 0) return 0;
+	SceneUse use(s, stream);
+	if(use.rc) return use.rc;
 	int relWhich[SNAIL_MAX_LIGHTS];
 	for(int n = 0; n < SNAIL_MAX_LIGHTS; n++) { relWhich[n] = -1; A.relLight[n] = nullptr; }
 	if(SNAIL_NODE_PREFETCH && SNAIL_REL_SHADOW && A.pack && !useDeep(s))
@@ -881,7 +902,13 @@ SnailScene *snail_scene_create_lbvh(const float *tri_verts, int nTris, int devic
 int snail_scene_download(const SnailScene *s, void *nodes32, void *tris64) {
 	if(int rc = checkScene(s, "snail_scene_download")) return rc;
 	DeviceGuard guard(s->device);
-	if(nodes32) HIP_TRY(hipMemcpy(nodes32, s->dNodes, (size_t)s->nNodes * 32, hipMemcpyDeviceToHost));
+	int nNodes = s->nNodes;
+	if(s->fast) {   // the tree of the last rebuild (waits for it; the arrays have room for more nodes than it has)
+		int cur[4];
+		if(int rc = fastCurrent(s, cur)) return rc;
+		nNodes = cur[0];
+	}
+	if(nodes32) HIP_TRY(hipMemcpy(nodes32, s->dNodes, (size_t)nNodes * 32, hipMemcpyDeviceToHost));
 	if(tris64) HIP_TRY(hipMemcpy(tris64, s->dTris, (size_t)s->nTris * 64, hipMemcpyDeviceToHost));
 	return 0;
 }
@@ -893,6 +920,7 @@ void snail_scene_destroy(SnailScene *s) {
 	if(s->dNodes) (void)hipFree(s->dNodes);
 	if(s->dPF) (void)hipFree(s->dPF);   // (dTris points into it)
 	if(s->dTab) (void)hipFree(s->dTab);
+	fastFree(s->fast);
 	for(auto &e : s->rel) {
 		if(e.d) (void)hipFree(e.d);
 		if(e.filled) (void)hipEventDestroy(e.filled);
@@ -917,9 +945,11 @@ void snail_scene_destroy(SnailScene *s) {
 
 int snail_scene_info(const SnailScene *s, int *nNodes, int *nTris, int *depth, int *device) {
 	if(!s) { snail_set_error("snail_scene_info: null scene"); return 1; }
-	if(nNodes) *nNodes = s->nNodes;
+	int cur[4] = {s->nNodes, s->depth, 0, 0};
+	if(s->fast) { if(int rc = fastCurrent(s, cur)) return rc; }   // the tree of the last rebuild (waits for it)
+	if(nNodes) *nNodes = cur[0];
 	if(nTris) *nTris = s->nTris;
-	if(depth) *depth = s->depth;
+	if(depth) *depth = cur[1];
 	if(device) *device = s->device;
 	return 0;
 }
@@ -1236,6 +1266,8 @@ static int renderWhitted(const char *fn, SnailScene *s, const float cam[13], int
 	if(dPacketXY && nPacketsList <= 0) return 0;
 	DeviceGuard guard(s->device);
 	const bool refl = (flags & SNAIL_WHITTED_REFLECTIONS) != 0;
+	SceneUse use(s, (hipStream_t)stream);
+	if(use.rc) return use.rc;
 	dev::ShadeArgs A;
 	memset(&A, 0, sizeof(A));
 	A.hostTab = s->arith == SNAIL_ARITH_HOST_SSE ? s->dTab : nullptr;
@@ -1351,6 +1383,8 @@ int snail_trace_transparency_dev(SnailScene *s, const float cam[13], int resx, i
 	}
 	DeviceGuard guard(s->device);
 	SNAIL_LOCK(s);
+	SceneUse use(s, (hipStream_t)stream);
+	if(use.rc) return use.rc;
 	dev::ShadeArgs A;
 	memset(&A, 0, sizeof(A));
 	A.hostTab = s->arith == SNAIL_ARITH_HOST_SSE ? s->dTab : nullptr;
@@ -1610,13 +1644,19 @@ int snail_account_primary(SnailScene *s, const float cam[13], int resx, int resy
 	A.out = (dev::u64 *)hc.stats();
 	if(int rc = hc.zeroStats()) return rc;
 	const int np = A.pw * A.ph;
-	hipLaunchKernelGGL(dev::k_account, dim3((np + 3) / 4), dim3(256), 0, hc.stream(), A);
-	HIP_TRY(hipGetLastError());
+	{
+		SNAIL_LOCK(s);
+		SceneUse use(s, hc.stream());
+		if(use.rc) return use.rc;
+		hipLaunchKernelGGL(dev::k_account, dim3((np + 3) / 4), dim3(256), 0, hc.stream(), A);
+		HIP_TRY(hipGetLastError());
+	}
 	return hc.finish(out);
 }
 
 } // extern "C"
 
+#include "bvh_fast.inc"
 #include "render_host.inc"
 #include "instances_host.inc"
 #include "instances_tiles_host.inc"

@@ -144,6 +144,100 @@ class Scene:
         self.bvh = HostBVH(tris, nodes, depth.value, perm)
         return self
 
+    @classmethod
+    def from_fast(cls, tri_verts: np.ndarray, device: int | None = None):
+        """The reference's fast (16-bin) builder on the host (HostBVH.build_fast) + snail_scene_create; .perm = triId -> input triangle."""
+        self = cls(HostBVH.build_fast(tri_verts), device)
+        self.perm = self.bvh.perm
+        return self
+
+    @staticmethod
+    def _check_verts(d_verts, d):
+        torch = _torch()
+        if not (hasattr(d_verts, "data_ptr") and d_verts.is_cuda and d_verts.device == d and d_verts.dtype == torch.float32
+                and d_verts.is_contiguous() and d_verts.numel() > 0 and d_verts.numel() % 9 == 0):
+            raise ValueError("d_verts must be a contiguous float32 tensor of n x 9 values on %s" % d)
+        return d_verts.numel() // 9
+
+    @classmethod
+    def from_fast_dev(cls, d_verts, device: int | None = None, stream=None):
+        """The same tree built on the device from vertices in device memory (snail_scene_create_fast_dev): byte-equal to from_fast's nodes,
+        triangle records and perm.  d_verts = float32 torch tensor of n x 9 values on the scene's device.  The scene carries .d_perm and
+        .d_info (device tensors: slot -> input triangle; {status, nNodes, depth, n}); .perm, .bvh and .depth are read back when asked."""
+        torch = _torch()
+        if not torch.cuda.is_available():
+            raise _lib.SnailError("no HIP device available: the traversal path has no CPU fallback")
+        self = cls.__new__(cls)
+        self.device = torch.cuda.current_device() if device is None else int(device)
+        d = self._dev()
+        n = cls._check_verts(d_verts, d)
+        self.d_perm = torch.empty(n, dtype=torch.int32, device=d)
+        self.d_info = torch.zeros(4, dtype=torch.int32, device=d)
+        h = _lib.lib().snail_scene_create_fast_dev(_lib.ptr(d_verts), n, self.device, _lib.ptr(self.d_perm), _lib.ptr(self.d_info), _stream_ptr(stream))
+        if not h:
+            raise _lib.SnailError("snail_scene_create_fast_dev: %s" % _lib.lib().snail_last_error().decode())
+        self._h = C.c_void_p(h)
+        self._fast_dev, self._fast_n, self._stale, self._bvh = True, n, True, None
+        return self
+
+    def rebuild_fast_dev(self, d_verts, stream=None, info=None):
+        """Rebuild a from_fast_dev scene in place from new vertices (snail_scene_rebuild_fast_dev): enqueued on `stream`, no host wait, ordered
+        after every launch enqueued on this scene before and before every one after.  -> info, int32 [4] device tensor {status, nNodes,
+        depth, n}; a status other than 0 (1 non-finite vertex, 2 too deep, 3 outside the fast arithmetic's range: include/snail_bvh_fast.h)
+        leaves the scene as it was.  d_verts is read on `stream` and must stay alive and unchanged until that work has run.  .perm, .bvh,
+        nodes() and .depth read the handle back (and wait for it) when they are next asked."""
+        if not getattr(self, "_fast_dev", False):
+            raise _lib.SnailError("rebuild_fast_dev: the scene was not made by from_fast_dev")
+        torch = _torch()
+        d = self._dev()
+        n = self._check_verts(d_verts, d)
+        if info is None:
+            info = torch.empty(4, dtype=torch.int32, device=d)
+            if stream is not None:
+                info.record_stream(stream)
+        _lib.check(_lib.lib().snail_scene_rebuild_fast_dev(self._h, _lib.ptr(d_verts), n, _lib.ptr(self.d_perm), _lib.ptr(info), _stream_ptr(stream)),
+                   "snail_scene_rebuild_fast_dev")
+        self.d_info = info
+        self._stale = True
+        return info
+
+    def _refresh_fast(self):
+        from .bvh import NODE_DTYPE, TRI_DTYPE
+        nn, nt, depth, dev = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
+        _lib.check(_lib.lib().snail_scene_info(self._h, C.addressof(nn), C.addressof(nt), C.addressof(depth), C.addressof(dev)), "snail_scene_info")
+        nodes = np.zeros(nn.value, dtype=NODE_DTYPE)
+        tris = np.zeros(nt.value, dtype=TRI_DTYPE)
+        _lib.check(_lib.lib().snail_scene_download(self._h, _lib.ptr(nodes), _lib.ptr(tris)), "snail_scene_download")
+        # (a failed rebuild leaves d_perm as it was: the commit is the only writer)
+        self._bvh = HostBVH(tris, nodes, depth.value, self.d_perm.cpu().numpy())
+        self._stale = False
+
+    @property
+    def bvh(self) -> HostBVH:
+        if getattr(self, "_fast_dev", False) and self._stale:
+            self._refresh_fast()
+        return self._bvh
+
+    @bvh.setter
+    def bvh(self, value: HostBVH):
+        self._bvh = value
+
+    @property
+    def perm(self):
+        return self.bvh.perm if getattr(self, "_fast_dev", False) else self._perm
+
+    @perm.setter
+    def perm(self, value):
+        self._perm = value
+
+    @property
+    def depth(self) -> int:
+        return self.bvh.depth
+
+    def nodes(self) -> np.ndarray:
+        """The node records of the tree the scene holds now (NODE_DTYPE)."""
+        return self.bvh.nodes
+
     def close(self):
         if getattr(self, "_h", None):
             _lib.lib().snail_scene_destroy(self._h)
