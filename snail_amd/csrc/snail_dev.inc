@@ -76,18 +76,13 @@ __device__ __forceinline__ float vmax3(float a, float b, float c) { float r; asm
 // (2^-126 <= |x| < 2^126) v_rcp_f32 followed by ONE Newton step in two FMAs is bit-identical to the 11-instruction correctly rounded
 // division sequence -- checked over all 2^32 inputs on the device (tools/micro/recip_check.hip, snail_debug_recip_check): 0 differences
 // inside that range; outside it (denormal or 0 inputs, denormal results, +-inf) the wave takes the full division.
-#ifndef SNAIL_FAST_RECIP
-#define SNAIL_FAST_RECIP 1
-#endif
 __device__ __forceinline__ float recipExact(float x) {
-#if SNAIL_FAST_RECIP
 	const unsigned e = (__float_as_uint(x) & 0x7f800000u) - 0x00800000u;
 	if(__builtin_expect(__builtin_amdgcn_ballot_w64(e >= 0x7e000000u) == 0, 1)) {
 		float r = __builtin_amdgcn_rcpf(x);
 		const float err = __builtin_fmaf(-x, r, 1.0f);
 		return __builtin_fmaf(err, r, r);
 	}
-#endif
 	return 1.0f / x;
 }
 
@@ -247,11 +242,7 @@ __device__ __forceinline__ float waveMax(float v) { return waveReduce<true>(v); 
 // instruction each -- v_min_f32_dpp d, d(shifted), d: a lane without a source keeps its value, which is what the identity operand of the
 // two-instruction form achieves -- and interleaved over the six registers, so that no step waits for the DPP read-after-write hazard
 // (the compiler's form: mov identity, nop, mov_dpp, min = 4 instructions per step and register; 36 instead of 144 per packet)
-#ifndef SNAIL_REDUCE6_ASM
-#define SNAIL_REDUCE6_ASM 1
-#endif
 __device__ __forceinline__ void waveReduce6(float (&mn)[3], float (&mx)[3]) {
-#if SNAIL_REDUCE6_ASM
 #define SNAIL_R6_STEP(CTRL)                                                                                                                 \
 	"v_min_f32_dpp %0, %0, %0 " CTRL "\n v_min_f32_dpp %1, %1, %1 " CTRL "\n v_min_f32_dpp %2, %2, %2 " CTRL "\n"                           \
 	"v_max_f32_dpp %3, %3, %3 " CTRL "\n v_max_f32_dpp %4, %4, %4 " CTRL "\n v_max_f32_dpp %5, %5, %5 " CTRL "\n"
@@ -262,10 +253,6 @@ __device__ __forceinline__ void waveReduce6(float (&mn)[3], float (&mx)[3]) {
 #undef SNAIL_R6_STEP
 #pragma unroll
 	for(int c = 0; c < 3; c++) { mn[c] = readlanef(mn[c], 63); mx[c] = readlanef(mx[c], 63); }
-#else
-#pragma unroll
-	for(int c = 0; c < 3; c++) { mn[c] = waveMin(mn[c]); mx[c] = waveMax(mx[c]); }
-#endif
 }
 
 __device__ __forceinline__ u64 rangeMask(int first, int last) { return ((2ull << last) - 1ull) & ~((1ull << first) - 1ull); }
@@ -374,34 +361,6 @@ __device__ __forceinline__ bool boxTestInterval(const Node &n, const Interval &i
 	return lmax >= 0.0f && lmin <= lmax;
 }
 
-// Triangle::TestInterval (src/triangle.cpp:110-167, shared-origin branch :122-129); each lane its own triangle.
-// Branch-free: (det < 0) | (...) has the same truth value as the reference's early return.
-template <int M>
-__device__ __forceinline__ bool triTestInterval(const Tri &t, const Interval &i) {
-	float det;
-	if(M == M_EXACT)
-		det = (t.n[0] < 0.0f ? i.minDir[0] : i.maxDir[0]) * t.n[0] + (t.n[1] < 0.0f ? i.minDir[1] : i.maxDir[1]) * t.n[1] +
-			  (t.n[2] < 0.0f ? i.minDir[2] : i.maxDir[2]) * t.n[2];
-	else // finite operands, minDir <= maxDir: the selected product is the larger of the two (n < 0 flips the order; n == 0 gives zeros
-		 // whose sign no comparison below observes) -- two multiplies and a max instead of compare -> SGPR -> select -> multiply
-		det = vmax(i.minDir[0] * t.n[0], i.maxDir[0] * t.n[0]) + vmax(i.minDir[1] * t.n[1], i.maxDir[1] * t.n[1]) +
-			  vmax(i.minDir[2] * t.n[2], i.maxDir[2] * t.n[2]);
-	float tv[3] = {i.minOrg[0] - t.a[0], i.minOrg[1] - t.a[1], i.minOrg[2] - t.a[2]};
-	float c1[3] = {t.ba[1] * tv[2] - t.ba[2] * tv[1], t.ba[2] * tv[0] - t.ba[0] * tv[2], t.ba[0] * tv[1] - t.ba[1] * tv[0]};
-	float c2[3] = {tv[1] * t.ca[2] - tv[2] * t.ca[1], tv[2] * t.ca[0] - tv[0] * t.ca[2], tv[0] * t.ca[1] - tv[1] * t.ca[0]};
-	float c1a[3], c1b[3], c2a[3], c2b[3];
-#pragma unroll
-	for(int k = 0; k < 3; k++) {
-		c1a[k] = i.minDir[k] * c1[k]; c1b[k] = i.maxDir[k] * c1[k];
-		c2a[k] = i.minDir[k] * c2[k]; c2b[k] = i.maxDir[k] * c2[k];
-	}
-	float u0 = Min<M>(c1a[0], c1b[0]) + Min<M>(c1a[1], c1b[1]) + Min<M>(c1a[2], c1b[2]);
-	float u1 = Max<M>(c1a[0], c1b[0]) + Max<M>(c1a[1], c1b[1]) + Max<M>(c1a[2], c1b[2]);
-	float v0 = Min<M>(c2a[0], c2b[0]) + Min<M>(c2a[1], c2b[1]) + Min<M>(c2a[2], c2b[2]);
-	float v1 = Max<M>(c2a[0], c2b[0]) + Max<M>(c2a[1], c2b[1]) + Max<M>(c2a[2], c2b[2]);
-	return (det < 0.0f) | ((Min<M>(u1, v1) >= 0.0f) & (u0 + v0 <= det * t.t0));
-}
-
 // shared-origin terms of Triangle::Collide (src/triangle.cpp:13-18 / :76-80)
 struct TriTerms {
 	float t0v[3], t1v[3], tmul;
@@ -426,8 +385,8 @@ __device__ __forceinline__ float selLanes(float a, float b, u64 lanesOfB) {
 }
 __device__ __forceinline__ float xbar(int byteAddr, float x) { return __int_as_float(__builtin_amdgcn_ds_bpermute(byteAddr, __float_as_int(x))); }
 // ---- the packet-level triangle cull + shared-origin terms, FOUR LANES PER TRIANGLE -----------------------------------------------------
-// triTestInterval() and triTerms() above are ~95 VALU instructions that run with one lane per triangle -- at most 4 of 64 lanes in an
-// ordinary leaf.  Here lane 4q + c (c = 0, 1, 2) works on COMPONENT c of triangle q (leaves of at most 16 triangles): it loads
+// Triangle::TestInterval (src/triangle.cpp:110-167, shared-origin branch :122-129) and triTerms() above are ~95 VALU instructions when they run
+// with one lane per triangle -- at most 4 of 64 lanes in an ordinary leaf.  Here lane 4q + c (c = 0, 1, 2) works on COMPONENT c of triangle q (leaves of at most 16 triangles): it loads
 // a[c], ba[c], ca[c], n[c] and t0 / it0, forms tv[c] = o[c] - a[c], reads the other two components of tv, ba, ca from its quad neighbours
 // through DPP (quad_perm: no LDS, no extra instruction where the read folds into the multiply), and computes component c of both cross
 // products, of the scaled terms and of every per-axis product of the interval test; the three-term sums (dot products, u / v bounds)
@@ -435,9 +394,6 @@ __device__ __forceinline__ float xbar(int byteAddr, float x) { return __int_as_f
 // same bits -- at ~50 instructions per leaf instead of ~95, and a lane keeps 4 registers of triangle data (n[c], tvec0[c], tvec1[c];
 // tmul in lane 4q) instead of 10.  Returns the lanes 4q whose triangle passes the cull (bit 4q); the survivor's terms are read by
 // crossbar from lanes 4q, 4q + 1, 4q + 2.
-#ifndef SNAIL_CULL_QUAD
-#define SNAIL_CULL_QUAD 7 // bit 0: narrow closest-hit leaves, bit 1: narrow any-hit leaves, bit 2: wide leaves; 0 = one lane per triangle everywhere (A/B measurements)
-#endif
 template <int CTRL> __device__ __forceinline__ float quadRot(float v) { // lane c of a quad <- lane (c + 1) % 3 [0xC9] or (c + 2) % 3 [0xD2]; lane 3 keeps its own
 	return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, false));
 }
@@ -492,15 +448,7 @@ __device__ __forceinline__ u64 cullQuad(const uint4 *__restrict__ tris, int coun
 // packets and not for leaves of more than 64 triangles (they keep the wide form).
 // (Control flow: the early return and the unconditional write-back are what this compiler can place beside the hand-written node
 // loop; a flag-guarded gather or a "nothing was hit" early-out end in "illegal VGPR to SGPR copy" on the loop's operands.)
-#ifndef SNAIL_LEAF_COMPACT_SHADOW
-#define SNAIL_LEAF_COMPACT_SHADOW 1 // the narrow-range form for any-hit packets too
-#endif
-#ifndef SNAIL_LEAF_COMPACT_PERRAY
-#define SNAIL_LEAF_COMPACT_PERRAY 1 // the narrow-range form for per-ray-origin packets (mirrored / continuation rays)
-#endif
-#ifndef SNAIL_LEAF_COMPACT
-#define SNAIL_LEAF_COMPACT 1 // 0 = every leaf in the wide form (A/B measurements)
-#endif
+// Any-hit packets and per-ray-origin packets (mirrored / continuation rays) have narrow-range forms of their own below.
 // a hit's triangle index, stored into the caller's per-lane record: an int, or -- inside the hand-written walks -- the same bits in a float: a
 // 32-bit INTEGER VGPR value that lives across the loop statements can end up sharing its undefined register (the instruction selector keeps one
 // per type and path) with the statements' scalar in / out operands, which this compiler reports as "illegal VGPR to SGPR copy"
@@ -525,21 +473,8 @@ __device__ __forceinline__ void leafSharedNarrow(const uint4 *__restrict__ tris,
 	const bool live = lane < width * LPQ;           // this lane holds rays of the range
 	st.leaves++;
 	st.fetched += (unsigned)count;
-	constexpr bool quadCull = (SNAIL_CULL_QUAD & 1) != 0;   // (the caller sends leaves of more than 16 triangles to the wide form then)
-	Tri t = {};
-	TriTerms tt = {};
 	QuadTerms qt = {};
-	u64 keep;
-	if(quadCull) keep = cullQuad<M>(tris, count, firstTri, lane, org, iv, qt);
-	else {
-		bool pass = false;
-		if(lane < count) {
-			t = loadTriVector(tris, firstTri + lane);
-			tt = triTerms(t, org[0][0], org[1][0], org[2][0]);
-			pass = triTestInterval<M>(t, iv);
-		}
-		keep = __builtin_amdgcn_ballot_w64(pass);
-	}
+	u64 keep = cullQuad<M>(tris, count, firstTri, lane, org, iv, qt);   // (the caller sends leaves of more than 16 triangles to the wide form)
 	if(keep == 0) return;
 	NarrowRays<R> N;
 	const int srcAddr = (first + lane / LPQ) * 4;   // lanes past the range read some quad's rays and never accept
@@ -551,22 +486,11 @@ __device__ __forceinline__ void leafSharedNarrow(const uint4 *__restrict__ tris,
 	do {
 		const int kb = __builtin_ctzll(keep);
 		keep &= keep - 1;
-		float nx, ny, nz, ax, ay, az, bx, by, bz, tmul;
-		int k;
-		if(quadCull) {
-			k = kb >> 2;
-			nx = xbar(kb * 4, qt.n); ny = xbar(kb * 4 + 4, qt.n); nz = xbar(kb * 4 + 8, qt.n);
-			ax = xbar(kb * 4, qt.t0v); ay = xbar(kb * 4 + 4, qt.t0v); az = xbar(kb * 4 + 8, qt.t0v);
-			bx = xbar(kb * 4, qt.t1v); by = xbar(kb * 4 + 4, qt.t1v); bz = xbar(kb * 4 + 8, qt.t1v);
-			tmul = xbar(kb * 4, qt.tmul);
-		} else {
-			k = kb;
-			nx = xbar(k * 4, t.n[0]); ny = xbar(k * 4, t.n[1]); nz = xbar(k * 4, t.n[2]);
-			ax = xbar(k * 4, tt.t0v[0]); ay = xbar(k * 4, tt.t0v[1]); az = xbar(k * 4, tt.t0v[2]);
-			bx = xbar(k * 4, tt.t1v[0]); by = xbar(k * 4, tt.t1v[1]); bz = xbar(k * 4, tt.t1v[2]);
-			tmul = xbar(k * 4, tt.tmul);
-		}
-		const int idx = firstTri + k;
+		const float nx = xbar(kb * 4, qt.n), ny = xbar(kb * 4 + 4, qt.n), nz = xbar(kb * 4 + 8, qt.n);
+		const float ax = xbar(kb * 4, qt.t0v), ay = xbar(kb * 4 + 4, qt.t0v), az = xbar(kb * 4 + 8, qt.t0v);
+		const float bx = xbar(kb * 4, qt.t1v), by = xbar(kb * 4 + 4, qt.t1v), bz = xbar(kb * 4 + 8, qt.t1v);
+		const float tmul = xbar(kb * 4, qt.tmul);
+		const int idx = firstTri + (kb >> 2);
 #if SNAIL_ARITH_SSE
 		if(R > 1) { // the lane's rays' table look-ups in one batch (rcpHostN): the same operations, a ray that fails the inside test looks up 1.0
 			if(live) {
@@ -633,18 +557,8 @@ __device__ __forceinline__ void leafSharedNarrowShadow(const uint4 *__restrict__
 	const bool live = lane < width * LPQ;
 	st.leaves++;
 	st.fetched += (unsigned)count;
-	constexpr bool quadCull = (SNAIL_CULL_QUAD & 2) != 0;
-	Tri t = {};
-	TriTerms tt = {};
 	QuadTerms qt = {};
-	u64 keep;
-	if(quadCull) keep = cullQuad<M>(tris, count, firstTri, lane, org, iv, qt);
-	else {
-		const bool mine = lane < count;
-		t = loadTriVector(tris, firstTri + (mine ? lane : 0));
-		tt = triTerms(t, org[0][0], org[1][0], org[2][0]);
-		keep = __builtin_amdgcn_ballot_w64(mine & triTestInterval<M>(t, iv));
-	}
+	u64 keep = cullQuad<M>(tris, count, firstTri, lane, org, iv, qt);
 	if(keep == 0) return;
 	float nd[3][R], ndist[R];
 	const int srcAddr = (first + lane / LPQ) * 4;
@@ -654,19 +568,10 @@ __device__ __forceinline__ void leafSharedNarrowShadow(const uint4 *__restrict__
 	do {
 		const int kb = __builtin_ctzll(keep);
 		keep &= keep - 1;
-		float nx, ny, nz, ax, ay, az, bx, by, bz, tmul;
-		if(quadCull) {
-			nx = xbar(kb * 4, qt.n); ny = xbar(kb * 4 + 4, qt.n); nz = xbar(kb * 4 + 8, qt.n);
-			ax = xbar(kb * 4, qt.t0v); ay = xbar(kb * 4 + 4, qt.t0v); az = xbar(kb * 4 + 8, qt.t0v);
-			bx = xbar(kb * 4, qt.t1v); by = xbar(kb * 4 + 4, qt.t1v); bz = xbar(kb * 4 + 8, qt.t1v);
-			tmul = xbar(kb * 4, qt.tmul);
-		} else {
-			const int k = kb;
-			nx = xbar(k * 4, t.n[0]); ny = xbar(k * 4, t.n[1]); nz = xbar(k * 4, t.n[2]);
-			ax = xbar(k * 4, tt.t0v[0]); ay = xbar(k * 4, tt.t0v[1]); az = xbar(k * 4, tt.t0v[2]);
-			bx = xbar(k * 4, tt.t1v[0]); by = xbar(k * 4, tt.t1v[1]); bz = xbar(k * 4, tt.t1v[2]);
-			tmul = xbar(k * 4, tt.tmul);
-		}
+		const float nx = xbar(kb * 4, qt.n), ny = xbar(kb * 4 + 4, qt.n), nz = xbar(kb * 4 + 8, qt.n);
+		const float ax = xbar(kb * 4, qt.t0v), ay = xbar(kb * 4 + 4, qt.t0v), az = xbar(kb * 4 + 8, qt.t0v);
+		const float bx = xbar(kb * 4, qt.t1v), by = xbar(kb * 4 + 4, qt.t1v), bz = xbar(kb * 4 + 8, qt.t1v);
+		const float tmul = xbar(kb * 4, qt.tmul);
 #pragma unroll
 		for(int i = 0; i < R; i++) { // src/triangle.cpp:91-98
 			const float det = nd[0][i] * nx + nd[1][i] * ny + nd[2][i] * nz;
@@ -686,12 +591,9 @@ __device__ __forceinline__ void leafSharedNarrowShadow(const uint4 *__restrict__
 	}
 }
 
-// ---- leaf, shared origin (src/bvh/traverse.cpp:34-56 / :98-124): lanes 0..chunk-1 each take one triangle (packet-level
-// cull + shared-origin terms in parallel), survivors are broadcast one by one to the whole packet.  Returns true when a
-// shadow packet is fully occluded (the walk ends, src/bvh/traverse.cpp:117-121).
-#ifndef SNAIL_LEAF_MASK
-#define SNAIL_LEAF_MASK 1 // 0 = every lane computes everything in the leaf (A/B measurements)
-#endif
+// ---- leaf, shared origin (src/bvh/traverse.cpp:34-56 / :98-124): the packet-level cull + shared-origin terms of 16 triangles at a
+// time (cullQuad), survivors are broadcast one by one to the whole packet.  Returns true when a shadow packet is fully occluded
+// (the walk ends, src/bvh/traverse.cpp:117-121).
 template <bool MASK, bool SHADOW, int M, bool BARY, class TID>
 __device__ __forceinline__ bool leafShared(const uint4 *__restrict__ tris, int count, int firstTri, int size, int lane, int first, int last,
 										   const float (&org)[3][4], Quad &Q, unsigned mask4, TID (&tid)[4], float (&bu)[4], float (&bv)[4],
@@ -699,25 +601,22 @@ __device__ __forceinline__ bool leafShared(const uint4 *__restrict__ tris, int c
 	const float inf = __builtin_inff();
 	const bool inRange = lane >= first && lane <= last;
 	const int width = last - first + 1;
-	if(SNAIL_LEAF_COMPACT && !SHADOW && !MASK && !BARY) {
+	if(!SHADOW && !MASK && !BARY) {
 		// (first / last come out of an asm statement with vector outputs too, which makes them divergent in the compiler's eyes: a branch
 		// on them would drag every counter into VGPRs)
 		const int widthU = __builtin_amdgcn_readfirstlane(width);
 		const int countU = __builtin_amdgcn_readfirstlane(count);
-		if(widthU <= 32 && countU <= ((SNAIL_CULL_QUAD & 1) ? 16 : 64)) {
+		if(widthU <= 32 && countU <= 16) {
 			const int firstU = __builtin_amdgcn_readfirstlane(first);
 			if(widthU <= 16) leafSharedNarrow<1, M>(tris, countU, firstTri, lane, firstU, firstU + widthU - 1, org, Q, tid, iv, st);
 			else leafSharedNarrow<2, M>(tris, countU, firstTri, lane, firstU, firstU + widthU - 1, org, Q, tid, iv, st);
 			return false;
 		}
 	}
-	if(SNAIL_LEAF_COMPACT_SHADOW && SHADOW && !MASK && !BARY) {
+	if(SHADOW && !MASK && !BARY) {
 		const int widthU = __builtin_amdgcn_readfirstlane(width);
 		const int countU = __builtin_amdgcn_readfirstlane(count);
-#ifndef SNAIL_SHADOW_NARROW2
-#define SNAIL_SHADOW_NARROW2 1 // ranges of 17..32 quads with two rays per lane (fits since the four-lane cull: 76 VGPRs)
-#endif
-		if(widthU <= (SNAIL_SHADOW_NARROW2 ? 32 : 16) && widthU < size && countU <= ((SNAIL_CULL_QUAD & 2) ? 16 : 64)) {
+		if(widthU <= 32 && widthU < size && countU <= 16) {   // (ranges of 17..32 quads with two rays per lane: fits since the four-lane cull, 76 VGPRs)
 			const int firstU = __builtin_amdgcn_readfirstlane(first);
 			if(widthU <= 16) leafSharedNarrowShadow<1, M>(tris, countU, firstTri, lane, firstU, firstU + widthU - 1, org, Q, iv, st);
 			else leafSharedNarrowShadow<2, M>(tris, countU, firstTri, lane, firstU, firstU + widthU - 1, org, Q, iv, st);
@@ -726,7 +625,10 @@ __device__ __forceinline__ bool leafShared(const uint4 *__restrict__ tris, int c
 	}
 	const u64 curRange = rangeMask(first, last);
 	st.leaves++;
-	constexpr bool LANE_MASK = SNAIL_LEAF_MASK && !SHADOW;
+	// Closest-hit packets: only the quads of the range [first, last] intersect a survivor (EXEC off: the instruction count is the same,
+	// the switched lanes are not -- this part is power-limited, profiles/README.md).  Any-hit packets keep every lane on: their test
+	// is three compares shorter and the masks cost more than they save.
+	constexpr bool LANE_MASK = !SHADOW;
 	// one surviving triangle against the packet's quads (src/triangle.cpp:44-60 / :91-98); returns true when a shadow packet is fully occluded
 	auto collide = [&](const float nx, const float ny, const float nz, const float ax, const float ay, const float az, const float bx, const float by, const float bz,
 					   const float tmul, const int idx) -> bool {
@@ -795,68 +697,24 @@ __device__ __forceinline__ bool leafShared(const uint4 *__restrict__ tris, int c
 		st.intersects += width;
 		return false;
 	};
-	if(SNAIL_CULL_QUAD & 4) {
-		// cull and shared-origin terms with four lanes per triangle (cullQuad), 16 triangles at a time (an ordinary leaf holds <= 4);
-		// survivors broadcast from lanes 4k .. 4k + 2, in triangle order
-		const int countU = __builtin_amdgcn_readfirstlane(count);
-		st.fetched += (unsigned)countU;
-		for(int base = 0; base < countU; base += 16) {
-			QuadTerms qt;
-			u64 keep = cullQuad<M>(tris, countU - base < 16 ? countU - base : 16, firstTri + base, lane, org, iv, qt);
-			while(keep) {
-				const int kb = __builtin_ctzll(keep);
-				keep &= keep - 1;
-				const float nx = xbar(kb * 4, qt.n), ny = xbar(kb * 4 + 4, qt.n), nz = xbar(kb * 4 + 8, qt.n);
-				const float ax = xbar(kb * 4, qt.t0v), ay = xbar(kb * 4 + 4, qt.t0v), az = xbar(kb * 4 + 8, qt.t0v);
-				const float bx = xbar(kb * 4, qt.t1v), by = xbar(kb * 4 + 4, qt.t1v), bz = xbar(kb * 4 + 8, qt.t1v);
-				const float tmul = xbar(kb * 4, qt.tmul);
-				if(collide(nx, ny, nz, ax, ay, az, bx, by, bz, tmul, firstTri + base + (kb >> 2))) return true;
-			}
-		}
-		return false;
-	}
-	for(int base = 0; base < count; base += 64) {
-		const int chunk = count - base < 64 ? count - base : 64;
-		st.fetched += (unsigned)chunk;
-		const bool mine = lane < chunk;
-		// Leaves of more than 16 triangles: one lane per triangle.  Closest-hit packets: only the lanes that own a triangle fetch it and
-		// evaluate the cull and the shared-origin terms, and only the quads of the range [first, last] intersect a survivor (EXEC off: the
-		// instruction count is the same, the switched lanes are not -- this part is power-limited, profiles/README.md).  Any-hit packets
-		// keep every lane on: their test is three compares shorter and the masks cost more than they save.
-		Tri t = {};
-		TriTerms tt = {};
-		bool pass = false;
-		if(LANE_MASK) {
-			if(mine) {
-				t = loadTriVector(tris, firstTri + base + lane);
-				tt = triTerms(t, org[0][0], org[1][0], org[2][0]);
-				pass = triTestInterval<M>(t, iv);
-			}
-		} else {
-			t = loadTriVector(tris, firstTri + base + (mine ? lane : 0));
-			tt = triTerms(t, org[0][0], org[1][0], org[2][0]);
-			pass = mine & triTestInterval<M>(t, iv);
-		}
-		u64 keep = __builtin_amdgcn_ballot_w64(pass);
-
+	// cull and shared-origin terms with four lanes per triangle (cullQuad), 16 triangles at a time (an ordinary leaf holds <= 4);
+	// survivors broadcast from lanes 4k .. 4k + 2, in triangle order, through the LDS crossbar (ds_bpermute_b32, no LDS memory) into
+	// VGPRs: ten v_readlane_b32 into SGPRs cost 4 VALU issue cycles each plus the SGPR-write -> VALU-read hazard (measured with one lane
+	// per triangle, tools/history/exp_leaf.sh: atrium 23.5 vs 22.1 Grays/s, stress-1M 10.2 vs 10.4 -- there the ~100 cycles of crossbar
+	// latency per survivor show; issuing the next survivor's broadcast ahead of the current intersection costs more than it hides: 21.0 / 9.5).
+	const int countU = __builtin_amdgcn_readfirstlane(count);
+	st.fetched += (unsigned)countU;
+	for(int base = 0; base < countU; base += 16) {
+		QuadTerms qt;
+		u64 keep = cullQuad<M>(tris, countU - base < 16 ? countU - base : 16, firstTri + base, lane, org, iv, qt);
 		while(keep) {
-			const int k = __builtin_ctzll(keep);
+			const int kb = __builtin_ctzll(keep);
 			keep &= keep - 1;
-			// broadcast of lane k's triangle through the LDS crossbar (ds_bpermute_b32, no LDS memory) into VGPRs: ten v_readlane_b32
-			// into SGPRs cost 4 VALU issue cycles each plus the SGPR-write -> VALU-read hazard.  Same box, tools/history/exp_leaf.sh: atrium
-			// 23.5 vs 22.1 Grays/s, stress-1M 10.2 vs 10.4 (there the ~100 cycles of crossbar latency per survivor show); issuing the
-			// next survivor's broadcast ahead of the current intersection (two register sets) costs more than it hides: 21.0 / 9.5.
-#ifdef SNAIL_EXP_LEAF_READLANE // experiment hook (tools/history/exp_leaf.sh)
-#define BCAST(x) readlanef(x, k)
-#else
-#define BCAST(x) __int_as_float(__builtin_amdgcn_ds_bpermute(k * 4, __float_as_int(x)))
-#endif
-			const float nx = BCAST(t.n[0]), ny = BCAST(t.n[1]), nz = BCAST(t.n[2]);
-			const float ax = BCAST(tt.t0v[0]), ay = BCAST(tt.t0v[1]), az = BCAST(tt.t0v[2]);
-			const float bx = BCAST(tt.t1v[0]), by = BCAST(tt.t1v[1]), bz = BCAST(tt.t1v[2]);
-			const float tmul = BCAST(tt.tmul);
-#undef BCAST
-			if(collide(nx, ny, nz, ax, ay, az, bx, by, bz, tmul, firstTri + base + k)) return true;
+			const float nx = xbar(kb * 4, qt.n), ny = xbar(kb * 4 + 4, qt.n), nz = xbar(kb * 4 + 8, qt.n);
+			const float ax = xbar(kb * 4, qt.t0v), ay = xbar(kb * 4 + 4, qt.t0v), az = xbar(kb * 4 + 8, qt.t0v);
+			const float bx = xbar(kb * 4, qt.t1v), by = xbar(kb * 4 + 4, qt.t1v), bz = xbar(kb * 4 + 8, qt.t1v);
+			const float tmul = xbar(kb * 4, qt.tmul);
+			if(collide(nx, ny, nz, ax, ay, az, bx, by, bz, tmul, firstTri + base + (kb >> 2))) return true;
 		}
 	}
 	return false;
@@ -919,17 +777,14 @@ __device__ __forceinline__ void leafPerRayNarrow(const uint4 *__restrict__ tris,
 		if(inRange && nt >= 0) { Q.dist[l] = d; tid[l] = nt; }
 	}
 }
-#ifndef SNAIL_PERRAY_NARROW2
-#define SNAIL_PERRAY_NARROW2 1 // per-ray-origin leaves of ranges of 17..32 quads with two rays per lane (94 instead of 188 vector instructions per triangle)
-#endif
 template <bool MASK, int M, bool BARY>
 __device__ __forceinline__ void leafPerRay(const uint4 *__restrict__ tris, int count, int firstTri, int lane, int first, int last, const float (&org)[3][4],
 										   Quad &Q, unsigned mask4, int (&tid)[4], float (&bu)[4], float (&bv)[4], Counters &st) {
 	const bool inRange = lane >= first && lane <= last;
 	const int width = last - first + 1;
-	if(SNAIL_LEAF_COMPACT_PERRAY && !BARY) {
+	if(!BARY) {
 		const int widthU = __builtin_amdgcn_readfirstlane(width);
-		if(widthU <= (SNAIL_PERRAY_NARROW2 ? 32 : 16)) {
+		if(widthU <= 32) {   // (ranges of 17..32 quads with two rays per lane: 94 instead of 188 vector instructions per triangle)
 			const int firstU = __builtin_amdgcn_readfirstlane(first);
 			if(widthU <= 16) leafPerRayNarrow<1, MASK, M>(tris, __builtin_amdgcn_readfirstlane(count), firstTri, lane, firstU, firstU + widthU - 1, org, Q, mask4, tid, st);
 			else leafPerRayNarrow<2, MASK, M>(tris, __builtin_amdgcn_readfirstlane(count), firstTri, lane, firstU, firstU + widthU - 1, org, Q, mask4, tid, st);
@@ -965,9 +820,6 @@ __device__ __forceinline__ void leafPerRay(const uint4 *__restrict__ tris, int c
 	}
 }
 
-#ifndef SNAIL_FAR_PRETEST
-#define SNAIL_FAR_PRETEST 0 // experiment hook (round 5): the C++ walk tests the far child at push time and drops pushes that cannot pass (tools/r5_far_child.sh)
-#endif
 // ---- the packet walk -------------------------------------------------------------------------------
 // SHARED : one origin per packet (primary / shadow)   MASK : per-lane 4-bit masks (secondary rays)
 // SHADOW : any-hit TraverseShadow                      M    : arithmetic mode (above)
@@ -1024,7 +876,8 @@ __device__ __forceinline__ void walk(const uint4 *__restrict__ nodes, const uint
 		const int farIdx = (int)n.sub + (firstNode ^ 1);
 		const Node nn = loadNode(nodes, nearIdx);
 
-		// the FAST / COH slab test as a function of the record (SNAIL_FAR_PRETEST evaluates it for the far child as well): the quads with a lane that passes
+		// the FAST / COH slab test of the record: the quads with a lane that passes.  (Testing the far child too at push time, to drop pushes
+		// that cannot pass, was measured and lost: profiles/r5_far_child.txt.)
 		auto fastPass = [&](const Node &n) -> u64 {
 			// finite inputs: lane passes  <=>  lmax >= 0  &&  lmin <= lmax  &&  lmin <= dist   (both flavours)
 			float tn[4], tf[4];
@@ -1120,16 +973,6 @@ __device__ __forceinline__ void walk(const uint4 *__restrict__ nodes, const uint
 			first = __builtin_ctzll(alive);
 			last = 63 - __builtin_clzll(alive);
 			if(!isLeaf) {
-#if SNAIL_FAR_PRETEST
-				// EXPERIMENT (round 5, profiles/r5_far_child.txt): a reject-only test of the FAR child with the distances of the push.  No lane of the pushed
-				// range passes now => none passes when the entry is popped (distances only shrink, the range is the pushed one): the reference would pop it,
-				// count one LoopIteration and fail its box test (src/bvh/traverse.cpp:26-33,:57-58) -- so the push is dropped and that iteration counted.
-				if(!EXACT && !SHADOW) {   // (closest-hit walks only: an any-hit walk may end before the dropped entry would have been popped, and its count with it)
-					const Node fnode = loadNode(nodes, farIdx);
-					const u64 farAlive = fastPass(fnode) & __builtin_amdgcn_ballot_w64((unsigned)(lane - first) <= (unsigned)(last - first));
-					if(farAlive == 0) { st.iters++; n = nn; continue; }
-				}
-#endif
 				const int fl = first | (last << 8);
 				// push: v_writelane_b32 (no clang builtin).  Both the value and the lane select are SALU-produced SGPRs,
 				// so none of the VALU->v_writelane hazards of the ISA applies.
@@ -1177,9 +1020,6 @@ __device__ __forceinline__ void walk(const uint4 *__restrict__ nodes, const uint
 //                sign16 = signBits << 16, so bit 16 of (sign16 >> axis) ^ aux is that XOR (aux = axis | firstNode << 16)
 //   iters        every chain of visits starts with a pop (the root is pushed by the caller) and every push is popped, so
 //                visits = 2 * pops - 1: only the pops are counted
-#ifndef SNAIL_EXP_PAD
-#define SNAIL_EXP_PAD "" // experiment hook: extra instructions per node visit (tools/history/exp_pad.sh)
-#endif
 // slab products of ray L -> tn in t0, tf in t3.  COH: near/far planes known (pn*, pf*); FAST: planes bmin-o / bmax-o, min/max per axis
 #define SNAIL_SLAB_COH(L, NX, FX, NY, FY, NZ, FZ)                                                                                           \
 	"v_mul_f32 %[t0], %[ix" L "], %[pnx]\n v_mul_f32 %[t1], %[iy" L "], %[pny]\n v_mul_f32 %[t2], %[iz" L "], %[pnz]\n"                    \
@@ -1230,22 +1070,16 @@ __device__ __forceinline__ void walk(const uint4 *__restrict__ nodes, const uint
 // min(min(tf,dist) - tn, tf)
 #define SNAIL_TAIL_POS(L, S) "v_max_f32 %[t0], 0, %[t0]\n v_min_f32 %[t3], %[t3], %[d" L "]\n v_sub_f32 %[" S "], %[t3], %[t0]\n"
 #define SNAIL_TAIL_ANY(L, S) "v_min_f32 %[t4], %[t3], %[d" L "]\n v_sub_f32 %[t4], %[t4], %[t0]\n v_min_f32 %[" S "], %[t4], %[t3]\n"
-// the traversal stack inside the loop.  2W: two words per entry (node; first | last << 8) in two VGPRs.  1W: one word, node | first << 20
-// | last << 26, for trees of at most 2^20 node slots: one lane read per pop and one lane write per push instead of two (these are
-// the most expensive instructions of the loop, ~4 cycles each against 1.6 for a multiply)
+// the traversal stack inside this loop: two words per entry (node; first | last << 8) in two VGPRs.  (The prefetching loop below keeps ONE
+// word, node | first << 20 | last << 26, for trees of at most 2^20 node slots: one lane read per pop and one lane write per push instead
+// of two -- these are the most expensive instructions of the loop, ~4 cycles each against 1.6 for a multiply.)
 #define SNAIL_POP_2W                                                                                                                       \
 	" v_readlane_b32 %[cur], %[stkN], %[sp]\n v_readlane_b32 %[fl], %[stkF], %[sp]\n"                                                      \
 	" s_and_b32 %[first], %[fl], 0xff\n s_lshr_b32 %[last], %[fl], 8\n"
-#define SNAIL_POP_1W                                                                                                                       \
-	" v_readlane_b32 %[fl], %[stkN], %[sp]\n"                                                                                              \
-	" s_and_b32 %[cur], %[fl], 0xfffff\n s_bfe_u32 %[first], %[fl], 0x60014\n s_lshr_b32 %[last], %[fl], 26\n"
 // push (far child in %[fl]; %[off] is free)
 #define SNAIL_PUSH_2W                                                                                                                      \
 	" s_lshl_b32 %[off], %[last], 8\n s_or_b32 %[off], %[off], %[first]\n"                                                                 \
 	" s_mov_b32 m0, %[sp]\n v_writelane_b32 %[stkN], %[fl], m0\n v_writelane_b32 %[stkF], %[off], m0\n"
-#define SNAIL_PUSH_1W                                                                                                                      \
-	" s_lshl_b32 %[off], %[last], 6\n s_or_b32 %[off], %[off], %[first]\n s_lshl_b32 %[off], %[off], 20\n s_or_b32 %[off], %[off], %[fl]\n" \
-	" s_mov_b32 m0, %[sp]\n v_writelane_b32 %[stkN], %[off], m0\n"
 #define SNAIL_COUNT " s_add_u32 %[cnt], %[cnt], 1\n"
 // Every statement of the loop starts by waiting for the scalar loads the COMPILER may still have in flight: it does not wait for a load whose
 // result turned out dead (the per-ray-origin leaf fetches a triangle record with s_load_dwordx16 and may leave the loop before using it), such a
@@ -1254,13 +1088,11 @@ __device__ __forceinline__ void walk(const uint4 *__restrict__ nodes, const uint
 // own scalar loads target s4..s67, and no such overwrite has been observed.)
 #define SNAIL_DRAIN_SMEM " s_waitcnt lgkmcnt(0)\n"
 #define SNAIL_DESCEND_ASM(PRE, ORGOPS, SLAB, TAIL, CNTPOP, CNTVISIT, NX, FX, NY, FY, NZ, FZ)                                                 \
-	SNAIL_DESCEND_ASM_S(SNAIL_POP_2W, SNAIL_PUSH_2W, PRE, ORGOPS, SLAB, TAIL, CNTPOP, CNTVISIT, NX, FX, NY, FY, NZ, FZ)
-#define SNAIL_DESCEND_ASM_S(POP, PUSH, PRE, ORGOPS, SLAB, TAIL, CNTPOP, CNTVISIT, NX, FX, NY, FY, NZ, FZ)                                                            \
 	asm volatile(SNAIL_DRAIN_SMEM                                                                                                          \
 				 "L_pop_%=:\n"                                                                                                             \
 				 " s_cmp_eq_u32 %[sp], 0\n s_cbranch_scc1 L_done_%=\n"                                                                     \
 				 " s_sub_u32 %[sp], %[sp], 1\n" CNTPOP                                                                                     \
-				 POP                                                                                                                       \
+				 SNAIL_POP_2W                                                                                                              \
 				 " s_lshl_b32 %[off], %[cur], 5\n s_load_dwordx8 s[84:91], %[base], %[off]\n"                                              \
 				 " s_sub_u32 %[width], %[last], %[first]\n"                                                                                \
 				 " s_bfm_b64 exec, %[width], %[first]\n s_bitset1_b64 exec, %[last]\n"                                                     \
@@ -1270,7 +1102,6 @@ __device__ __forceinline__ void walk(const uint4 *__restrict__ nodes, const uint
 				 SLAB("0", NX, FX, NY, FY, NZ, FZ) TAIL("0", "s0") SLAB("1", NX, FX, NY, FY, NZ, FZ) TAIL("1", "s1")                       \
 				 SLAB("2", NX, FX, NY, FY, NZ, FZ) TAIL("2", "s2") SLAB("3", NX, FX, NY, FY, NZ, FZ) TAIL("3", "s3")                       \
 				 " v_max_f32 %[s2], %[s2], %[s3]\n v_max3_f32 %[s0], %[s0], %[s1], %[s2]\n"                                                \
-				 SNAIL_EXP_PAD                                                                                                             \
 				 " v_cmp_le_f32 vcc, 0, %[s0]\n"                                                                                           \
 				 " s_and_b64 %[alive], vcc, exec\n s_cbranch_scc0 L_pop_%=\n"                                                              \
 				 " s_ff1_i32_b64 %[first], %[alive]\n s_flbit_i32_b64 %[last], %[alive]\n s_xor_b32 %[last], %[last], 63\n"                \
@@ -1281,7 +1112,7 @@ __device__ __forceinline__ void walk(const uint4 *__restrict__ nodes, const uint
 				 " s_add_u32 %[fl], s90, 1\n s_sub_u32 %[fl], %[fl], %[cur]\n"                                                             \
 				 " s_add_u32 %[cur], s90, %[cur]\n s_lshl_b32 %[off], %[cur], 5\n"                                                         \
 				 " s_load_dwordx8 s[84:91], %[base], %[off]\n"                                                                             \
-				 PUSH                                                                                                                      \
+				 SNAIL_PUSH_2W                                                                                                             \
 				 " s_add_u32 %[sp], %[sp], 1\n"                                                                                            \
 				 " s_waitcnt lgkmcnt(0)\n s_branch L_visit_%=\n"                                                                           \
 				 "L_leaf_%=:\n s_mov_b32 %[leafSub], s90\n s_mov_b32 %[leafAux], s91\n s_branch L_end_%=\n"                                \
@@ -1328,120 +1159,19 @@ __device__ __forceinline__ void walk(const uint4 *__restrict__ nodes, const uint
 #define SNAIL_MOV_REC(D0, D1, D2, D3, S0, S1, S2, S3)                                                                                       \
 	" s_mov_b64 " D0 ", " S0 "\n s_mov_b64 " D1 ", " S1 "\n s_mov_b64 " D2 ", " S2 "\n s_mov_b64 " D3 ", " S3 "\n"
 #define SNAIL_A_FROM_T SNAIL_MOV_REC("s[84:85]", "s[86:87]", "s[88:89]", "s[90:91]", "s[68:69]", "s[70:71]", "s[72:73]", "s[74:75]")
-// One visit of the loop with the tested record in register set X (planes NX..FZ, SUB = subNode | leaf bit, AUX) and the near child
-// requested into the OTHER set: a descent is a jump to the other copy of the body, not a copy of eight registers.  Inside the
-// body EXEC = the lanes that survived the node (a lane that fails a box fails every box inside it -- each operation of the slab test
-// rounds monotonically -- so first / last come out as with the whole range); a pop rebuilds EXEC from the popped range.
-// SNAIL_PF_LEAFREQ: what a LEAF record's "near child" request fetches.  The loop's own copy of the tree holds the triangle records behind
-// the nodes: the leaf flag is cleared and the request is the leaf's first triangle record (ahead of the leaf code).  A camera-relative
-// node array (below) holds nodes only: the request becomes slot 0.
-// SNAIL_PF_LEAFREQ_RELTRI (round 5, SNAIL_REL_TRI_PREFETCH): a camera- or light-relative node array with the leaf's request going to the triangle records all
-// the same -- they live in the loop's own copy of the tree, whose address is a second base (%[tbase] = tris - 2^25: a leaf record's offset counts from there):
-// the base is picked per visit on the scalar side (two more scalar instructions than SLOT0, which issue beside the visit's vector ones).
-#ifndef SNAIL_TRI_PREFETCH
-#define SNAIL_TRI_PREFETCH 1 // 0 = a leaf's request is slot 0 in the walks over the loop's own copy too (experiment, profiles/r5_tri_prefetch.txt)
-#endif
-#if SNAIL_TRI_PREFETCH
+// What a LEAF record's "near child" request fetches (LEAFREQ).  The loop's own copy of the tree holds the triangle records behind the
+// nodes: the leaf flag is cleared and the request is the leaf's first triangle record, ahead of the leaf code (_TRI; against slot 0
+// there too: profiles/r5_tri_prefetch.txt).  A camera- or light-relative node array (below) holds nodes only: the request becomes slot 0
+// (_SLOT0; picking the triangle records' base per visit on the scalar side instead was measured and lost: profiles/r5_tri_prefetch.txt).
 #define SNAIL_PF_LEAFREQ_TRI(OTHERSET) " s_bitset0_b32 %[cur], 31\n s_load_dwordx8 " OTHERSET ", %[base], %[cur]\n"
-#else
-#define SNAIL_PF_LEAFREQ_TRI(OTHERSET) " s_max_i32 %[cur], %[cur], 0\n s_load_dwordx8 " OTHERSET ", %[base], %[cur]\n"
-#endif
 #define SNAIL_PF_LEAFREQ_SLOT0(OTHERSET) " s_max_i32 %[cur], %[cur], 0\n s_load_dwordx8 " OTHERSET ", %[base], %[cur]\n"
-#define SNAIL_PF_LEAFREQ_RELTRI(OTHERSET)                                                                                                   \
-	" s_cmp_lt_i32 %[cur], 0\n s_cselect_b64 s[92:93], %[tbase], %[base]\n s_bitset0_b32 %[cur], 31\n s_load_dwordx8 " OTHERSET ", s[92:93], %[cur]\n"
-// what a variant adds to the statement's clobbers and input operands (pasted from the variant's name, as SNAIL_PREVARS_of)
-#define SNAIL_LRCLOB_SNAIL_PF_LEAFREQ_TRI
-#define SNAIL_LRCLOB_SNAIL_PF_LEAFREQ_SLOT0
-#define SNAIL_LRCLOB_SNAIL_PF_LEAFREQ_RELTRI , "s92", "s93"
-#define SNAIL_LRCLOB_of(L) SNAIL_LRCLOB_##L
-#define SNAIL_LROPS_SNAIL_PF_LEAFREQ_TRI
-#define SNAIL_LROPS_SNAIL_PF_LEAFREQ_SLOT0
-#define SNAIL_LROPS_SNAIL_PF_LEAFREQ_RELTRI [tbase] "s"(triBase),
-#define SNAIL_LROPS_of(L) SNAIL_LROPS_##L
-#define SNAIL_PF_VISIT(X, Y, OTHERSET, SUB, AUX, PRE, SLAB, TAIL, CNTVISIT, LEAFREQ, NX, FX, NY, FY, NZ, FZ)                                          \
-				 "L_visit" X "_%=:\n" CNTVISIT                                                                                              \
-				 " s_and_b32 %[cur], " AUX ", %[sign16]\n s_cselect_b32 %[cur], 32, 0\n" /* sign[axis] of lane 0 -> 32 or 0 */               \
-				 " s_xor_b32 %[cur], " SUB ", %[cur]\n" /* near child's byte offset (a leaf: its first triangle's, maybe + 32) */             \
-				 " s_xor_b32 %[fl], %[cur], 32\n" /* far child's: the other half of the pair's 64-B line */                                  \
-				 LEAFREQ(OTHERSET)                                                                                                         \
-				 PRE(NX, FX, NY, FY, NZ, FZ)                                                                                               \
-				 SLAB("0", NX, FX, NY, FY, NZ, FZ) TAIL("0", "s0") SLAB("1", NX, FX, NY, FY, NZ, FZ) TAIL("1", "s1")                       \
-				 SLAB("2", NX, FX, NY, FY, NZ, FZ) TAIL("2", "s2") SLAB("3", NX, FX, NY, FY, NZ, FZ) TAIL("3", "s3")                       \
-				 " v_max_f32 %[s2], %[s2], %[s3]\n v_max3_f32 %[s0], %[s0], %[s1], %[s2]\n"                                                \
-				 SNAIL_EXP_PAD                                                                                                             \
-				 " v_cmp_le_f32 vcc, 0, %[s0]\n" /* EXEC = the parent's survivors: VCC has no bit outside them, VCC IS the new survivor set */ \
-				 " s_cbranch_vccz L_fail_%=\n"                                                                                             \
-				 " s_ff1_i32_b64 %[first], vcc\n s_flbit_i32_b64 %[last], vcc\n s_xor_b32 %[last], %[last], 63\n"                          \
-				 " s_mov_b64 exec, vcc\n"                                                                                                  \
-				 " s_cmp_lt_i32 " SUB ", 0\n s_cbranch_scc1 L_leaf" X "_%=\n"                                                               \
-				 " s_lshl_b32 %[off], %[last], 6\n s_or_b32 %[off], %[off], %[first]\n s_lshl_b32 %[off], %[off], 20\n"                    \
-				 " s_lshr_b32 %[topw], %[fl], 5\n s_or_b32 %[topw], %[topw], %[off]\n" /* stack word: record slot | first << 20 | last << 26 */ \
-				 " v_writelane_b32 %[stkN], %[topw], m0\n" /* m0 = sp throughout this statement */                                                           \
-				 " s_add_u32 m0, m0, 1\n"                                                                                            \
-				 " s_waitcnt lgkmcnt(0)\n"                                                                                                 \
-				 " s_load_dwordx8 s[68:75], %[base], %[fl]\n" /* the far child is the new top entry */                                    \
-				 " s_branch L_visit" Y "_%=\n"                                                                                              \
-				 "L_leaf" X "_%=:\n s_bfe_u32 %[leafSub], " SUB ", 0x190006\n s_sub_u32 %[leafSub], %[leafSub], 0x80000\n s_bitset1_b32 %[leafSub], 31\n" /* 0x80000000 | first triangle: (offset - 2^25) / 64 */ \
-				 " s_mov_b32 %[leafAux], " AUX "\n s_waitcnt lgkmcnt(0)\n s_branch L_end_%=\n"
-// set A = s[84:91] (planes NXA.., sub s90, aux s91), set B = s[76:83] (planes NXB.., sub s82, aux s83)
-#define SNAIL_DESCEND_PF(PRE, ORGOPS, SLAB, TAIL, CNTPOP, CNTVISIT, LEAFREQ, NXA, FXA, NYA, FYA, NZA, FZA, NXB, FXB, NYB, FYB, NZB, FZB)                 \
-	asm volatile(SNAIL_DRAIN_SMEM " s_mov_b32 m0, %[sp]\n"                                                                                \
-				 "L_entry_%=:\n"                                                                                                           \
-				 " s_cmp_eq_u32 m0, 0\n s_cbranch_scc1 L_done_%=\n"                                                                     \
-				 " s_sub_u32 %[off], m0, 1\n"                                                                                           \
-				 " v_readlane_b32 %[topw], %[stkN], %[off]\n"                                                                              \
-				 " s_and_b32 %[cur], %[topw], 0xfffff\n s_lshl_b32 %[off], %[cur], 5\n"                                                    \
-				 " s_load_dwordx8 s[68:75], %[base], %[off]\n"                                                                             \
-				 "L_pop_%=:\n" /* sp > 0, topw = the top entry, T = its record (requested) */                                              \
-				 " s_sub_u32 m0, m0, 1\n" CNTPOP                                                                                     \
-				 " s_bfe_u32 %[first], %[topw], 0x60014\n s_lshr_b32 %[last], %[topw], 26\n"                                               \
-				 " s_sub_u32 %[width], %[last], %[first]\n"                                                                                \
-				 " s_bfm_b64 exec, %[width], %[first]\n s_bitset1_b64 exec, %[last]\n"                                                     \
-				 " s_cmp_eq_u32 m0, 0\n s_cbranch_scc1 L_last_%=\n"                                                                     \
-				 " s_sub_u32 %[off], m0, 1\n"                                                                                           \
-				 " v_readlane_b32 %[topw], %[stkN], %[off]\n"                                                                              \
-				 " s_and_b32 %[cur], %[topw], 0xfffff\n s_lshl_b32 %[off], %[cur], 5\n"                                                    \
-				 " s_waitcnt lgkmcnt(0)\n" SNAIL_A_FROM_T                                                                                  \
-				 " s_load_dwordx8 s[68:75], %[base], %[off]\n" /* the new top entry's record */                                            \
-				 " s_branch L_visitA_%=\n"                                                                                                 \
-				 "L_last_%=:\n"                                                                                                            \
-				 " s_waitcnt lgkmcnt(0)\n" SNAIL_A_FROM_T                                                                                  \
-				 SNAIL_PF_VISIT("A", "B", "s[76:83]", "s90", "s91", PRE, SLAB, TAIL, CNTVISIT, LEAFREQ, NXA, FXA, NYA, FYA, NZA, FZA)                \
-				 SNAIL_PF_VISIT("B", "A", "s[84:91]", "s82", "s83", PRE, SLAB, TAIL, CNTVISIT, LEAFREQ, NXB, FXB, NYB, FYB, NZB, FZB)                \
-				 "L_fail_%=:\n"                                                                                                            \
-				 " s_cmp_eq_u32 m0, 0\n s_cbranch_scc0 L_pop_%=\n"                                                                      \
-				 "L_done_%=:\n s_mov_b32 %[leafSub], 0\n s_mov_b32 %[leafAux], 0\n s_waitcnt lgkmcnt(0)\n"                                  \
-				 "L_end_%=:\n s_mov_b64 exec, -1\n s_mov_b32 %[sp], m0\n"                                                                                        \
-				 : [sp] "+s"(sp), [first] "+s"(first), [last] "+s"(last), [cnt] "+s"(cnt), [stkN] "+v"(stkN), [stkF] "+v"(stkF),           \
-				   [leafSub] "=&s"(leafSub), [leafAux] "=&s"(leafAux), [cur] "=&s"(sCur), [fl] "=&s"(sFl), [off] "=&s"(sOff),              \
-				   [width] "=&s"(sWidth), [topw] "=&s"(sTopw), [alive] "=&s"(sAlive), [pnx] "=&v"(vt[0]), [pny] "=&v"(vt[1]),              \
-				   [pnz] "=&v"(vt[2]), [pfx] "=&v"(vt[3]), [pfy] "=&v"(vt[4]), [pfz] "=&v"(vt[5]), [t0] "=&v"(vt[6]), [t1] "=&v"(vt[7]),   \
-				   [t2] "=&v"(vt[8]), [t3] "=&v"(vt[9]), [t4] "=&v"(vt[10]), [t5] "=&v"(vt[11]), [s0] "=&v"(vt[12]), [s1] "=&v"(vt[13]),   \
-				   [s2] "=&v"(vt[14]), [s3] "=&v"(vt[15]), [u0] "=&v"(vt[16])                                                              \
-				 : [base] "s"(nodeBase), SNAIL_LROPS_of(LEAFREQ) [sign16] "s"(sign16), [lane] "v"(lane), ORGOPS(), [ix0] "v"(Q.id[0][0]), [ix1] "v"(Q.id[0][1]), [ix2] "v"(Q.id[0][2]), [ix3] "v"(Q.id[0][3]),        \
-				   [iy0] "v"(Q.id[1][0]), [iy1] "v"(Q.id[1][1]), [iy2] "v"(Q.id[1][2]), [iy3] "v"(Q.id[1][3]), [iz0] "v"(Q.id[2][0]),      \
-				   [iz1] "v"(Q.id[2][1]), [iz2] "v"(Q.id[2][2]), [iz3] "v"(Q.id[2][3]), [d0] "v"(Q.dist[0]), [d1] "v"(Q.dist[1]),          \
-				   [d2] "v"(Q.dist[2]), [d3] "v"(Q.dist[3])                                                                                \
-				 : "s68", "s69", "s70", "s71", "s72", "s73", "s74", "s75", "s76", "s77", "s78", "s79", "s80", "s81", "s82", "s83", "s84", "s85", "s86", "s87", \
-				   "s88", "s89", "s90", "s91", "vcc", "scc", "m0" SNAIL_LRCLOB_of(LEAFREQ));                                               \
-	asm volatile("" ::"s"(sp), "s"(first), "s"(last), "s"(cnt), "v"(stkN), "v"(stkF), "s"(leafSub), "s"(leafAux), "s"(sCur), "s"(sFl), "s"(sOff),    \
-				 "s"(sWidth), "s"(sTopw), "s"(sAlive), "v"(vt[0]), "v"(vt[1]), "v"(vt[2]), "v"(vt[3]), "v"(vt[4]), "v"(vt[5]), "v"(vt[6]), "v"(vt[7]), \
-				 "v"(vt[8]), "v"(vt[9]), "v"(vt[10]), "v"(vt[11]), "v"(vt[12]), "v"(vt[13]), "v"(vt[14]), "v"(vt[15]), "v"(vt[16]))
-#define SNAIL_DESCEND_PF_PLAIN(PRE, ORGOPS, SLAB, TAIL, CNTPOP, CNTVISIT, LEAFREQ)                                                                     \
-	SNAIL_DESCEND_PF(PRE, ORGOPS, SLAB, TAIL, CNTPOP, CNTVISIT, LEAFREQ, "s84", "s87", "s85", "s88", "s86", "s89", "s76", "s79", "s77", "s80", "s78", "s81")
-#define SNAIL_DESCEND_PF_OCT(PRE, ORGOPS, SLAB, TAIL, CNTPOP, CNTVISIT, LEAFREQ, OCT)                                                                \
-	switch(OCT) {                                                                                                                          \
-	case 0: SNAIL_DESCEND_PF(PRE, ORGOPS, SLAB, TAIL, CNTPOP, CNTVISIT, LEAFREQ, "s84", "s87", "s85", "s88", "s86", "s89", "s76", "s79", "s77", "s80", "s78", "s81"); break; \
-	case 1: SNAIL_DESCEND_PF(PRE, ORGOPS, SLAB, TAIL, CNTPOP, CNTVISIT, LEAFREQ, "s87", "s84", "s85", "s88", "s86", "s89", "s79", "s76", "s77", "s80", "s78", "s81"); break; \
-	case 2: SNAIL_DESCEND_PF(PRE, ORGOPS, SLAB, TAIL, CNTPOP, CNTVISIT, LEAFREQ, "s84", "s87", "s88", "s85", "s86", "s89", "s76", "s79", "s80", "s77", "s78", "s81"); break; \
-	case 3: SNAIL_DESCEND_PF(PRE, ORGOPS, SLAB, TAIL, CNTPOP, CNTVISIT, LEAFREQ, "s87", "s84", "s88", "s85", "s86", "s89", "s79", "s76", "s80", "s77", "s78", "s81"); break; \
-	case 4: SNAIL_DESCEND_PF(PRE, ORGOPS, SLAB, TAIL, CNTPOP, CNTVISIT, LEAFREQ, "s84", "s87", "s85", "s88", "s89", "s86", "s76", "s79", "s77", "s80", "s81", "s78"); break; \
-	case 5: SNAIL_DESCEND_PF(PRE, ORGOPS, SLAB, TAIL, CNTPOP, CNTVISIT, LEAFREQ, "s87", "s84", "s85", "s88", "s89", "s86", "s79", "s76", "s77", "s80", "s81", "s78"); break; \
-	case 6: SNAIL_DESCEND_PF(PRE, ORGOPS, SLAB, TAIL, CNTPOP, CNTVISIT, LEAFREQ, "s84", "s87", "s88", "s85", "s89", "s86", "s76", "s79", "s80", "s77", "s81", "s78"); break; \
-	default: SNAIL_DESCEND_PF(PRE, ORGOPS, SLAB, TAIL, CNTPOP, CNTVISIT, LEAFREQ, "s87", "s84", "s88", "s85", "s89", "s86", "s79", "s76", "s80", "s77", "s81", "s78"); break; \
-	}
 
-// ---- the prefetching loop with the PUSH DEFERRED into the next visit (primary packets over camera-relative records) -----------------
+// ---- the prefetching loop, with the PUSH DEFERRED into the next visit -----------------------------------------------------------------
+// Two copies of a visit's body, one per record set: the tested record in set X (A = s[84:91]: sub s90, aux s91; B = s[76:83]: sub s82,
+// aux s83), the near child requested into the OTHER set: a descent is a jump to the other copy of the body, not a copy of eight
+// registers.  Inside the body EXEC = the lanes that survived the node (a lane that fails a box fails every box inside it -- each
+// operation of the slab test rounds monotonically -- so first / last come out as with the whole range); a pop rebuilds EXEC from the
+// popped range.
 // A wave issues in order, so the scalar tail of a visit -- survivors -> first / last, pack the stack word, write the lane, bump the stack
 // pointer, wait, request the far child's record, branch: ~17 instructions that depend on each other -- is time in which the wave issues
 // nothing to the vector pipe (a fifth of a visit; the scalar and vector pipes run side by side only for DIFFERENT instructions of a wave's
@@ -1450,8 +1180,9 @@ __device__ __forceinline__ void walk(const uint4 *__restrict__ nodes, const uint
 // computation BETWEEN its slab products, where scalar instructions issue beside vector ones; a pop likewise leaves the fetch of the new
 // top entry's word and record to the popped node's visit.  Three copies of the visit: after a pop (record set A), pending in B, pending
 // in A; the far child's offset lives in a register of its own per set (A: %[fl], B: %[width]),
-// so that a visit's own near / far computation does not overwrite the pending one.  Invariants are those of SNAIL_DESCEND_PF
-// (a register set never has two requests in flight; m0 = sp; topw = the top entry's word, T = its record).
+// so that a visit's own near / far computation does not overwrite the pending one.  Invariants: a register set never has two requests
+// in flight; m0 = sp; topw = the top entry's word, T = its record.  (The loop with the push at the end of the pusher's own visit was
+// measured and lost: profiles/README.md.)
 #define SNAIL_PF2_NEARFAR(SUB, AUX, FARX, OTHERSET, LEAFREQ)                                                                                          \
 				 " s_and_b32 %[cur], " AUX ", %[sign16]\n s_cselect_b32 %[cur], 32, 0\n"                                                       \
 				 " s_xor_b32 %[cur], " SUB ", %[cur]\n s_xor_b32 " FARX ", %[cur], 32\n"                                                       \
@@ -1528,12 +1259,12 @@ __device__ __forceinline__ void walk(const uint4 *__restrict__ nodes, const uint
 				   [width] "=&s"(sWidth), [topw] "=&s"(sTopw), [alive] "=&s"(sAlive), PREVARS() [t0] "=&v"(vt[6]), [t1] "=&v"(vt[7]),   \
 				   [t2] "=&v"(vt[8]), [t3] "=&v"(vt[9]), [t4] "=&v"(vt[10]), [t5] "=&v"(vt[11]), [s0] "=&v"(vt[12]), [s1] "=&v"(vt[13]),   \
 				   [s2] "=&v"(vt[14]), [s3] "=&v"(vt[15]), [u0] "=&v"(vt[16])                                                              \
-				 : [base] "s"(nodeBase), SNAIL_LROPS_of(LEAFREQ) [sign16] "s"(sign16), [lane] "v"(lane), ORGOPS(), [ix0] "v"(Q.id[0][0]), [ix1] "v"(Q.id[0][1]), [ix2] "v"(Q.id[0][2]), [ix3] "v"(Q.id[0][3]),        \
+				 : [base] "s"(nodeBase), [sign16] "s"(sign16), [lane] "v"(lane), ORGOPS(), [ix0] "v"(Q.id[0][0]), [ix1] "v"(Q.id[0][1]), [ix2] "v"(Q.id[0][2]), [ix3] "v"(Q.id[0][3]),        \
 				   [iy0] "v"(Q.id[1][0]), [iy1] "v"(Q.id[1][1]), [iy2] "v"(Q.id[1][2]), [iy3] "v"(Q.id[1][3]), [iz0] "v"(Q.id[2][0]),      \
 				   [iz1] "v"(Q.id[2][1]), [iz2] "v"(Q.id[2][2]), [iz3] "v"(Q.id[2][3]), [d0] "v"(Q.dist[0]), [d1] "v"(Q.dist[1]),          \
 				   [d2] "v"(Q.dist[2]), [d3] "v"(Q.dist[3])                                                                                \
 				 : "s68", "s69", "s70", "s71", "s72", "s73", "s74", "s75", "s76", "s77", "s78", "s79", "s80", "s81", "s82", "s83", "s84", "s85", "s86", "s87", \
-				   "s88", "s89", "s90", "s91", "vcc", "scc", "m0" EXTRACLOB SNAIL_LRCLOB_of(LEAFREQ));                                                                        \
+				   "s88", "s89", "s90", "s91", "vcc", "scc", "m0" EXTRACLOB);                                                                        \
 	asm volatile("" ::"s"(sp), "s"(first), "s"(last), "s"(cnt), "v"(stkN), "v"(stkF), "s"(leafSub), "s"(leafAux), "s"(sCur), "s"(sFl), "s"(sOff),    \
 				 "s"(sWidth), "s"(sTopw), "s"(sAlive), "v"(vt[6]), "v"(vt[7]), \
 				 "v"(vt[8]), "v"(vt[9]), "v"(vt[10]), "v"(vt[11]), "v"(vt[12]), "v"(vt[13]), "v"(vt[14]), "v"(vt[15]), "v"(vt[16]))
@@ -1574,71 +1305,25 @@ __device__ __forceinline__ void walk(const uint4 *__restrict__ nodes, const uint
 	}
 
 // near/far plane registers by sign octant (bit k set = idir negative on axis k: near plane = bmax[k]); s[84:86] = bmin, s[87:89] = bmax
-#define SNAIL_DESCEND_OCT(PRE, ORGOPS, SLAB, TAIL, CNTPOP, CNTVISIT, OCT) SNAIL_DESCEND_OCT_S(SNAIL_POP_2W, SNAIL_PUSH_2W, PRE, ORGOPS, SLAB, TAIL, CNTPOP, CNTVISIT, OCT)
-#define SNAIL_DESCEND_OCT_S(POP, PUSH, PRE, ORGOPS, SLAB, TAIL, CNTPOP, CNTVISIT, OCT)                                                                               \
+#define SNAIL_DESCEND_OCT(PRE, ORGOPS, SLAB, TAIL, CNTPOP, CNTVISIT, OCT)                                                                     \
 	switch(OCT) {                                                                                                                          \
-	case 0: SNAIL_DESCEND_ASM_S(POP, PUSH, PRE, ORGOPS, SLAB, TAIL, CNTPOP, CNTVISIT, "s84", "s87", "s85", "s88", "s86", "s89"); break;                              \
-	case 1: SNAIL_DESCEND_ASM_S(POP, PUSH, PRE, ORGOPS, SLAB, TAIL, CNTPOP, CNTVISIT, "s87", "s84", "s85", "s88", "s86", "s89"); break;                              \
-	case 2: SNAIL_DESCEND_ASM_S(POP, PUSH, PRE, ORGOPS, SLAB, TAIL, CNTPOP, CNTVISIT, "s84", "s87", "s88", "s85", "s86", "s89"); break;                              \
-	case 3: SNAIL_DESCEND_ASM_S(POP, PUSH, PRE, ORGOPS, SLAB, TAIL, CNTPOP, CNTVISIT, "s87", "s84", "s88", "s85", "s86", "s89"); break;                              \
-	case 4: SNAIL_DESCEND_ASM_S(POP, PUSH, PRE, ORGOPS, SLAB, TAIL, CNTPOP, CNTVISIT, "s84", "s87", "s85", "s88", "s89", "s86"); break;                              \
-	case 5: SNAIL_DESCEND_ASM_S(POP, PUSH, PRE, ORGOPS, SLAB, TAIL, CNTPOP, CNTVISIT, "s87", "s84", "s85", "s88", "s89", "s86"); break;                              \
-	case 6: SNAIL_DESCEND_ASM_S(POP, PUSH, PRE, ORGOPS, SLAB, TAIL, CNTPOP, CNTVISIT, "s84", "s87", "s88", "s85", "s89", "s86"); break;                              \
-	default: SNAIL_DESCEND_ASM_S(POP, PUSH, PRE, ORGOPS, SLAB, TAIL, CNTPOP, CNTVISIT, "s87", "s84", "s88", "s85", "s89", "s86"); break;                             \
+	case 0: SNAIL_DESCEND_ASM(PRE, ORGOPS, SLAB, TAIL, CNTPOP, CNTVISIT, "s84", "s87", "s85", "s88", "s86", "s89"); break;                              \
+	case 1: SNAIL_DESCEND_ASM(PRE, ORGOPS, SLAB, TAIL, CNTPOP, CNTVISIT, "s87", "s84", "s85", "s88", "s86", "s89"); break;                              \
+	case 2: SNAIL_DESCEND_ASM(PRE, ORGOPS, SLAB, TAIL, CNTPOP, CNTVISIT, "s84", "s87", "s88", "s85", "s86", "s89"); break;                              \
+	case 3: SNAIL_DESCEND_ASM(PRE, ORGOPS, SLAB, TAIL, CNTPOP, CNTVISIT, "s87", "s84", "s88", "s85", "s86", "s89"); break;                              \
+	case 4: SNAIL_DESCEND_ASM(PRE, ORGOPS, SLAB, TAIL, CNTPOP, CNTVISIT, "s84", "s87", "s85", "s88", "s89", "s86"); break;                              \
+	case 5: SNAIL_DESCEND_ASM(PRE, ORGOPS, SLAB, TAIL, CNTPOP, CNTVISIT, "s87", "s84", "s85", "s88", "s89", "s86"); break;                              \
+	case 6: SNAIL_DESCEND_ASM(PRE, ORGOPS, SLAB, TAIL, CNTPOP, CNTVISIT, "s84", "s87", "s88", "s85", "s89", "s86"); break;                              \
+	default: SNAIL_DESCEND_ASM(PRE, ORGOPS, SLAB, TAIL, CNTPOP, CNTVISIT, "s87", "s84", "s88", "s85", "s89", "s86"); break;                             \
 	}
 
-// Issue priority by work done (wave-uniform, at every leaf): packet costs are heavy-tailed and a frame ends with its heaviest
-// packets; a wave that has already popped more entries than most packets ever do is one of them.  s_setprio makes the SIMD's
-// arbiter prefer it over its co-resident waves (priority, then age: MI355X_MICROARCH.md, "Two waves per SIMD"), so the long
-// packets run at the speed of a lone wave while the short ones fill the gaps -- work-conserving, results untouched.
-#ifndef SNAIL_PRIO_T1
-#define SNAIL_PRIO_T1 0 // pops; 0 = off
-#define SNAIL_PRIO_T2 0
-#define SNAIL_PRIO_T3 0
-#endif
-#if SNAIL_PRIO_T1 > 0
-#define SNAIL_PRIO_BY_WORK(cnt)                                                                                                            \
-	do {                                                                                                                                   \
-		if((cnt) >= SNAIL_PRIO_T3) __builtin_amdgcn_s_setprio(3);                                                                          \
-		else if((cnt) >= SNAIL_PRIO_T2) __builtin_amdgcn_s_setprio(2);                                                                     \
-		else if((cnt) >= SNAIL_PRIO_T1) __builtin_amdgcn_s_setprio(1);                                                                     \
-	} while(0)
-#else
-#define SNAIL_PRIO_BY_WORK(cnt) do { } while(0)
-#endif
 // SHADOW=false: closest hit of a primary packet (distances >= 0; visits = 2 * pops - 1: every chain of visits starts with a pop,
 // the root is pushed here, and every push is popped).  SHADOW=true: any hit of a shadow packet (masked lanes -inf; the walk ends
 // when a triangle occludes the whole packet, so every visit is counted).  COH: one asm statement per sign octant, picked by a
 // wave-uniform switch at every (re-)entry, i.e. once per leaf; the leaf code exists once.
-#ifndef SNAIL_NODE_PREFETCH
-#define SNAIL_NODE_PREFETCH 1 // 0 = the loop without record prefetch for one-word stacks too (A/B measurements)
-#endif
-#ifndef SNAIL_DEFER_PUSH
-#define SNAIL_DEFER_PUSH 1 // the prefetching loop with the push of a descent done inside the next visit (SNAIL_DESCEND_PF2); 0 = SNAIL_DESCEND_PF (A/B measurements)
-#endif
-#if SNAIL_DEFER_PUSH
-#define SNAIL_WALK_PF_OCT SNAIL_DESCEND_PF2_OCT
-#define SNAIL_WALK_PF_PLAIN SNAIL_DESCEND_PF2_PLAIN
-#else
-#define SNAIL_WALK_PF_OCT SNAIL_DESCEND_PF_OCT
-#define SNAIL_WALK_PF_PLAIN SNAIL_DESCEND_PF_PLAIN
-#endif
-#ifndef SNAIL_REL_NODES
-#define SNAIL_REL_NODES 1 // primary packets walk camera-relative node records (no plane offsets to compute per visit); 0 = the loop's plain copy
-#endif
-#ifndef SNAIL_REL_TRI_PREFETCH
-#define SNAIL_REL_TRI_PREFETCH 0 // walks over origin-relative node arrays request a leaf's first triangle line ahead of the leaf code, as the walks over the loop's own copy do (SNAIL_PF_LEAFREQ_RELTRI)
-#endif
-#if SNAIL_REL_TRI_PREFETCH
-#define SNAIL_PF_LEAFREQ_REL SNAIL_PF_LEAFREQ_RELTRI
-#else
-#define SNAIL_PF_LEAFREQ_REL SNAIL_PF_LEAFREQ_SLOT0
-#endif
-#ifndef SNAIL_REL_SHADOW
-#define SNAIL_REL_SHADOW 1 // shadow packets of k_light walk records relative to their light's position (ShadeArgs::relLight), as primary packets do for the camera
-#endif
-// the node array a PACK instantiation of the hand-written walks is given: the prefetching loop's own copy of the tree
-#define SNAIL_PACK_NODES(A) (SNAIL_NODE_PREFETCH ? (A).pf : (A).nodes)
+// PACK: one-word stack entries and the prefetching loop over its own copy of the tree (the kernel arguments' `pf`); primary packets walk camera-relative
+// node records there and shadow packets of k_light records relative to their light's position (ShadeArgs::relLight): no plane offsets
+// to compute per visit.  Issue priority by work done (s_setprio by pops, at every leaf) measured +-0: profiles/README.md.
 template <bool SHADOW, bool COH, bool PACK, bool MASK, bool BARY, bool POSDIST, bool REL = true /* PACK: `nodes` holds records relative to the packet's origin (else the loop's plain copy) */>
 __device__ __forceinline__ void walkSharedAsm(const uint4 *__restrict__ nodes /* PACK: the prefetching loop's copy, SnailScene::dPF */, const uint4 *__restrict__ tris, int size, int lane,
 											  const float (&org)[3][4], Quad &Q, unsigned mask4, int (&tid)[4], float (&bu)[4], float (&bv)[4], float *lds,
@@ -1660,57 +1345,41 @@ __device__ __forceinline__ void walkSharedAsm(const uint4 *__restrict__ nodes /*
 	float tidBits[4];   // the caller's tid[] as float bits while the loop statements are around (setId)
 #pragma unroll
 	for(int l = 0; l < 4; l++) tidBits[l] = __int_as_float(tid[l]);
-	constexpr bool PF = PACK && SNAIL_NODE_PREFETCH;   // the record-prefetching loop over its own copy of the tree
-	const int sign16 = PF ? signBits : signBits << 16; // (PF: sign bit k against an inner record's 1 << axis)
+	const int sign16 = PACK ? signBits : signBits << 16; // (PACK: sign bit k against an inner record's 1 << axis)
 	const u64 nodeBase = (u64)nodes;
-	const u64 triBase = (u64)tris - (1u << 25);   // SNAIL_PF_LEAFREQ_RELTRI: the base a leaf record's byte offset counts from (SnailScene::dPF; pfTrisOffset)
-	(void)triBase;
-	// stack slot 0 = the root (PF: record slot 1) with the full quad range.  (float-typed: the only 32-bit INTEGER values that go in and out of the loop
+	// stack slot 0 = the root (PACK: record slot 1) with the full quad range.  (float-typed: the only 32-bit INTEGER values that go in and out of the loop
 	// statements are then scalar ones -- the instruction selector shares one undefined register among all undefined values of a type on a path, and an
 	// undefined VGPR feeding a scalar operand's PHI is this compiler's "illegal VGPR to SGPR copy")
-	float stkN = __int_as_float(PACK ? (int)((unsigned)(size - 1) << 26) | (PF ? 1 : 0) : 0), stkF = __int_as_float((size - 1) << 8);
+	float stkN = __int_as_float(PACK ? (int)((unsigned)(size - 1) << 26) | 1 : 0), stkF = __int_as_float((size - 1) << 8);
 	int sp = 1, first = 0, last = size - 1, cnt = 0;
 	for(;;) {
 		int leafSub, leafAux, sCur, sFl, sOff, sWidth;
 		u64 sRng, sAlive;
 		float vt[17];
-#define SNAIL_SHARED_VARIANTS(POP, PUSH)                                                                                                   \
-		if(COH) {                                                                                                                          \
-			if(SHADOW) { SNAIL_DESCEND_OCT_S(POP, PUSH, SNAIL_PRE_SHARED, SNAIL_ORG_SHARED, SNAIL_SLAB_COH, SNAIL_TAIL_ANY, "", SNAIL_COUNT, oct) } \
-			else if(POSDIST) { SNAIL_DESCEND_OCT_S(POP, PUSH, SNAIL_PRE_SHARED, SNAIL_ORG_SHARED, SNAIL_SLAB_COH, SNAIL_TAIL_POS, SNAIL_COUNT, "", oct) } \
-			else { SNAIL_DESCEND_OCT_S(POP, PUSH, SNAIL_PRE_SHARED, SNAIL_ORG_SHARED, SNAIL_SLAB_COH, SNAIL_TAIL_ANY, SNAIL_COUNT, "", oct) }      \
-		} else {                                                                                                                           \
-			if(SHADOW) { SNAIL_DESCEND_ASM_S(POP, PUSH, SNAIL_PRE_SHARED, SNAIL_ORG_SHARED, SNAIL_SLAB_FAST, SNAIL_TAIL_ANY, "", SNAIL_COUNT, "s84", "s87", "s85", "s88", "s86", "s89"); } \
-			else if(POSDIST) { SNAIL_DESCEND_ASM_S(POP, PUSH, SNAIL_PRE_SHARED, SNAIL_ORG_SHARED, SNAIL_SLAB_FAST, SNAIL_TAIL_POS, SNAIL_COUNT, "", "s84", "s87", "s85", "s88", "s86", "s89"); } \
-			else { SNAIL_DESCEND_ASM_S(POP, PUSH, SNAIL_PRE_SHARED, SNAIL_ORG_SHARED, SNAIL_SLAB_FAST, SNAIL_TAIL_ANY, SNAIL_COUNT, "", "s84", "s87", "s85", "s88", "s86", "s89"); } \
-		}
-		if(PF) {
+		if(PACK) {
 			int sTopw;
 			// primary packets (POSDIST) read camera-relative records: no plane offsets to form, a leaf's request is slot 0
 			if(COH) {
-				if(SHADOW && REL && SNAIL_REL_SHADOW) { SNAIL_WALK_PF_OCT(SNAIL_PRE_NONE_X, SNAIL_ORG_SHARED, SNAIL_SLAB_COH_R, SNAIL_TAIL_ANY, "", SNAIL_COUNT, SNAIL_PF_LEAFREQ_REL, oct) }
-				else if(SHADOW) { SNAIL_WALK_PF_OCT(SNAIL_PRE_SHARED, SNAIL_ORG_SHARED, SNAIL_SLAB_COH, SNAIL_TAIL_ANY, "", SNAIL_COUNT, SNAIL_PF_LEAFREQ_TRI, oct) }
-#if SNAIL_REL_NODES
-				else if(POSDIST) { SNAIL_WALK_PF_OCT(SNAIL_PRE_NONE_X, SNAIL_ORG_SHARED, SNAIL_SLAB_COH_R, SNAIL_TAIL_POS, SNAIL_COUNT, "", SNAIL_PF_LEAFREQ_REL, oct) }
-#else
-				else if(POSDIST) { SNAIL_WALK_PF_OCT(SNAIL_PRE_SHARED, SNAIL_ORG_SHARED, SNAIL_SLAB_COH, SNAIL_TAIL_POS, SNAIL_COUNT, "", SNAIL_PF_LEAFREQ_TRI, oct) }
-#endif
-				else { SNAIL_WALK_PF_OCT(SNAIL_PRE_SHARED, SNAIL_ORG_SHARED, SNAIL_SLAB_COH, SNAIL_TAIL_ANY, SNAIL_COUNT, "", SNAIL_PF_LEAFREQ_TRI, oct) }
+				if(SHADOW && REL) { SNAIL_DESCEND_PF2_OCT(SNAIL_PRE_NONE_X, SNAIL_ORG_SHARED, SNAIL_SLAB_COH_R, SNAIL_TAIL_ANY, "", SNAIL_COUNT, SNAIL_PF_LEAFREQ_SLOT0, oct) }
+				else if(SHADOW) { SNAIL_DESCEND_PF2_OCT(SNAIL_PRE_SHARED, SNAIL_ORG_SHARED, SNAIL_SLAB_COH, SNAIL_TAIL_ANY, "", SNAIL_COUNT, SNAIL_PF_LEAFREQ_TRI, oct) }
+				else if(POSDIST) { SNAIL_DESCEND_PF2_OCT(SNAIL_PRE_NONE_X, SNAIL_ORG_SHARED, SNAIL_SLAB_COH_R, SNAIL_TAIL_POS, SNAIL_COUNT, "", SNAIL_PF_LEAFREQ_SLOT0, oct) }
+				else { SNAIL_DESCEND_PF2_OCT(SNAIL_PRE_SHARED, SNAIL_ORG_SHARED, SNAIL_SLAB_COH, SNAIL_TAIL_ANY, SNAIL_COUNT, "", SNAIL_PF_LEAFREQ_TRI, oct) }
 			} else {
-				if(SHADOW && REL && SNAIL_REL_SHADOW) { SNAIL_WALK_PF_PLAIN(SNAIL_PRE_NONE_X, SNAIL_ORG_SHARED, SNAIL_SLAB_FAST_R, SNAIL_TAIL_ANY, "", SNAIL_COUNT, SNAIL_PF_LEAFREQ_REL); }
-				else if(SHADOW) { SNAIL_WALK_PF_PLAIN(SNAIL_PRE_SHARED, SNAIL_ORG_SHARED, SNAIL_SLAB_FAST, SNAIL_TAIL_ANY, "", SNAIL_COUNT, SNAIL_PF_LEAFREQ_TRI); }
-#if SNAIL_REL_NODES
-				else if(POSDIST) { SNAIL_WALK_PF_PLAIN(SNAIL_PRE_NONE_X, SNAIL_ORG_SHARED, SNAIL_SLAB_FAST_R, SNAIL_TAIL_POS, SNAIL_COUNT, "", SNAIL_PF_LEAFREQ_REL); }
-#else
-				else if(POSDIST) { SNAIL_WALK_PF_PLAIN(SNAIL_PRE_SHARED, SNAIL_ORG_SHARED, SNAIL_SLAB_FAST, SNAIL_TAIL_POS, SNAIL_COUNT, "", SNAIL_PF_LEAFREQ_TRI); }
-#endif
-				else { SNAIL_WALK_PF_PLAIN(SNAIL_PRE_SHARED, SNAIL_ORG_SHARED, SNAIL_SLAB_FAST, SNAIL_TAIL_ANY, SNAIL_COUNT, "", SNAIL_PF_LEAFREQ_TRI); }
+				if(SHADOW && REL) { SNAIL_DESCEND_PF2_PLAIN(SNAIL_PRE_NONE_X, SNAIL_ORG_SHARED, SNAIL_SLAB_FAST_R, SNAIL_TAIL_ANY, "", SNAIL_COUNT, SNAIL_PF_LEAFREQ_SLOT0); }
+				else if(SHADOW) { SNAIL_DESCEND_PF2_PLAIN(SNAIL_PRE_SHARED, SNAIL_ORG_SHARED, SNAIL_SLAB_FAST, SNAIL_TAIL_ANY, "", SNAIL_COUNT, SNAIL_PF_LEAFREQ_TRI); }
+				else if(POSDIST) { SNAIL_DESCEND_PF2_PLAIN(SNAIL_PRE_NONE_X, SNAIL_ORG_SHARED, SNAIL_SLAB_FAST_R, SNAIL_TAIL_POS, SNAIL_COUNT, "", SNAIL_PF_LEAFREQ_SLOT0); }
+				else { SNAIL_DESCEND_PF2_PLAIN(SNAIL_PRE_SHARED, SNAIL_ORG_SHARED, SNAIL_SLAB_FAST, SNAIL_TAIL_ANY, SNAIL_COUNT, "", SNAIL_PF_LEAFREQ_TRI); }
 			}
-		} else if(PACK) { SNAIL_SHARED_VARIANTS(SNAIL_POP_1W, SNAIL_PUSH_1W) }
-		else { SNAIL_SHARED_VARIANTS(SNAIL_POP_2W, SNAIL_PUSH_2W) }
-#undef SNAIL_SHARED_VARIANTS
+		} else if(COH) {
+			if(SHADOW) { SNAIL_DESCEND_OCT(SNAIL_PRE_SHARED, SNAIL_ORG_SHARED, SNAIL_SLAB_COH, SNAIL_TAIL_ANY, "", SNAIL_COUNT, oct) }
+			else if(POSDIST) { SNAIL_DESCEND_OCT(SNAIL_PRE_SHARED, SNAIL_ORG_SHARED, SNAIL_SLAB_COH, SNAIL_TAIL_POS, SNAIL_COUNT, "", oct) }
+			else { SNAIL_DESCEND_OCT(SNAIL_PRE_SHARED, SNAIL_ORG_SHARED, SNAIL_SLAB_COH, SNAIL_TAIL_ANY, SNAIL_COUNT, "", oct) }
+		} else {
+			if(SHADOW) { SNAIL_DESCEND_ASM(SNAIL_PRE_SHARED, SNAIL_ORG_SHARED, SNAIL_SLAB_FAST, SNAIL_TAIL_ANY, "", SNAIL_COUNT, "s84", "s87", "s85", "s88", "s86", "s89"); }
+			else if(POSDIST) { SNAIL_DESCEND_ASM(SNAIL_PRE_SHARED, SNAIL_ORG_SHARED, SNAIL_SLAB_FAST, SNAIL_TAIL_POS, SNAIL_COUNT, "", "s84", "s87", "s85", "s88", "s86", "s89"); }
+			else { SNAIL_DESCEND_ASM(SNAIL_PRE_SHARED, SNAIL_ORG_SHARED, SNAIL_SLAB_FAST, SNAIL_TAIL_ANY, SNAIL_COUNT, "", "s84", "s87", "s85", "s88", "s86", "s89"); }
+		}
 		if(leafSub == 0) break;
-		SNAIL_PRIO_BY_WORK(cnt);
 		if(leafShared<MASK, SHADOW, COH ? M_COH : M_FAST, BARY>(tris, leafAux, (int)((unsigned)leafSub & 0x7fffffffu), size, lane, first, last, org, Q, mask4,
 																 tidBits, bu, bv, iv, st))
 			break;
@@ -1722,34 +1391,27 @@ __device__ __forceinline__ void walkSharedAsm(const uint4 *__restrict__ nodes /*
 
 // closest hit of a packet with per-ray origins (TraversePrimaryN<0,mask>), node loop in assembly as in walkSharedAsm; any
 // distance on entry (masked lanes -inf), `size` quads
-#ifndef SNAIL_SHADOW_ENTRY_PF
-#define SNAIL_SHADOW_ENTRY_PF 1 // the packets of snail_trace_shadow and of snail_trace_rays with shared origins through the prefetching loop (0 = the plain two-word loop, as before round 3)
-#endif
-#ifndef SNAIL_PERRAY_COH_PF
-#define SNAIL_PERRAY_COH_PF SNAIL_DEFER_PUSH // coherent per-ray-origin packets (most mirrored packets) through the prefetching loop as well (SNAIL_DESCEND_PF2_SEL)
-#endif
 template <bool MASK, bool COH, bool BARY, bool PACK>
-__device__ __forceinline__ void walkPerRayAsm(const uint4 *__restrict__ nodes /* PACK and not COH: the prefetching loop's copy */, const uint4 *__restrict__ tris, int size, int lane, const float (&org)[3][4],
+__device__ __forceinline__ void walkPerRayAsm(const uint4 *__restrict__ nodes /* PACK: the prefetching loop's copy */, const uint4 *__restrict__ tris, int size, int lane, const float (&org)[3][4],
 											  Quad &Q, unsigned mask4, int (&tid)[4], float (&bu)[4], float (&bv)[4], Counters &st, const int oct) {
 	const int signBits = __builtin_amdgcn_readfirstlane((Q.d[0][0] < 0.0f ? 1 : 0) | (Q.d[1][0] < 0.0f ? 2 : 0) | (Q.d[2][0] < 0.0f ? 4 : 0));
-	constexpr bool PF = PACK && SNAIL_NODE_PREFETCH && (SNAIL_PERRAY_COH_PF || !COH);   // (SNAIL_PERRAY_COH_PF 0: coherent packets keep the plain two-word loop over the caller's records)
-	// PF: bits 0..2 = the signs of lane 0's first ray (child order, as the reference takes it); bits 8..10 = the packet's sign octant (plane selection of SNAIL_PRE_SEL)
-	const int sign16 = PF ? (COH ? signBits | __builtin_amdgcn_readfirstlane(oct) << 8 : signBits) : signBits << 16;
+	// PACK: bits 0..2 = the signs of lane 0's first ray (child order, as the reference takes it); bits 8..10 = the packet's sign octant (plane selection of SNAIL_PRE_SEL)
+	const int sign16 = PACK ? (COH ? signBits | __builtin_amdgcn_readfirstlane(oct) << 8 : signBits) : signBits << 16;
 	const u64 nodeBase = (u64)nodes;
-	float stkN = __int_as_float(PF ? (int)((unsigned)(size - 1) << 26) | 1 : 0), stkF = __int_as_float((size - 1) << 8); // stack slot 0 = the root (PF: record slot 1) with the full quad range; float-typed as in walkSharedAsm
+	float stkN = __int_as_float(PACK ? (int)((unsigned)(size - 1) << 26) | 1 : 0), stkF = __int_as_float((size - 1) << 8); // stack slot 0 = the root (PACK: record slot 1) with the full quad range; float-typed as in walkSharedAsm
 	int sp = 1, first = 0, last = size - 1, cnt = 0;
 	for(;;) {
 		int leafSub, leafAux, sCur, sFl, sOff, sWidth;
 		u64 sRng, sAlive;
 		float vt[17];
-		if(PF) {
+		if(PACK) {
 			// one-word stack entries + node records fetched ahead.  Non-coherent packets: the plain form of the loop.  Coherent packets would need the
 			// loop once per sign octant, and this compiler cannot place eight (or even two) copies of it beside the per-ray leaf code ("illegal VGPR
 			// to SGPR copy": the scalar-register pressure of the 16-SGPR triangle record plus three node record sets): they take ONE statement in
 			// which the near / far planes are picked per visit on the scalar side (SNAIL_DESCEND_PF2_SEL).
 			int sTopw;
 			if(COH) { SNAIL_DESCEND_PF2_SEL(SNAIL_ORG_PERRAY, SNAIL_SLABO_SEL, SNAIL_TAIL_ANY, SNAIL_COUNT, "", SNAIL_PF_LEAFREQ_TRI); }
-			else { SNAIL_WALK_PF_PLAIN(SNAIL_PRE_NONE, SNAIL_ORG_PERRAY, SNAIL_SLABO_FAST, SNAIL_TAIL_ANY, SNAIL_COUNT, "", SNAIL_PF_LEAFREQ_TRI); }
+			else { SNAIL_DESCEND_PF2_PLAIN(SNAIL_PRE_NONE, SNAIL_ORG_PERRAY, SNAIL_SLABO_FAST, SNAIL_TAIL_ANY, SNAIL_COUNT, "", SNAIL_PF_LEAFREQ_TRI); }
 		} else if(COH) { SNAIL_DESCEND_OCT(SNAIL_PRE_NONE, SNAIL_ORG_PERRAY, SNAIL_SLABO_COH, SNAIL_TAIL_ANY, SNAIL_COUNT, "", oct) }
 		else { SNAIL_DESCEND_ASM(SNAIL_PRE_NONE, SNAIL_ORG_PERRAY, SNAIL_SLABO_FAST, SNAIL_TAIL_ANY, SNAIL_COUNT, "", "s84", "s87", "s85", "s88", "s86", "s89"); }
 		if(leafSub == 0) break;
@@ -1908,7 +1570,7 @@ __device__ __forceinline__ PrimaryArgsK lateArgs() {
 // Give each XCD whole 4x4-packet REGIONS (64x64 px; its 16 consecutive blocks), regions interleaved over the
 // image: neighbouring packets (same BVH subtrees) share an L2, and every XCD samples the whole frame, so a
 // heavy image band does not land on one XCD.  b is the dispatch RANK: the hardware block in a one-frame launch;
-// in a multi-frame launch k_primary maps block B to a rank with the same B & 7 (SNAIL_FRAME_XCD_MAJOR), so
+// in a multi-frame launch k_primary maps block B to a rank with the same B & 7 (below), so
 // XCD group g still gets region set g, now for every frame of the launch.
 __device__ __forceinline__ int interleave16(int b) { // -> logical index; 16 consecutive logical indices per XCD turn
 	const int xcd = b & 7, j = b >> 3;
@@ -2012,7 +1674,7 @@ __device__ __forceinline__ void primaryPacket(const PrimaryArgs &A, const int li
 		else walk<true, false, false, M_FAST, false, DEEP, true>(A.nodes, A.tris, 64, lane, org, Q, 15u, tid, bu, bv, lds, st);
 	} else if(A.pack && !DIAG) { // (the counting build walks with the plain loop: same visits, same tests -- and this compiler cannot place the
 		// record-prefetching loop's three record sets beside the extra counters: "illegal VGPR to SGPR copy")
-		const uint4 *pn = (SNAIL_NODE_PREFETCH && SNAIL_REL_NODES) ? A.rel[fi] : SNAIL_PACK_NODES(A);   // this frame's camera-relative records
+		const uint4 *pn = A.rel[fi];   // this frame's camera-relative records
 		if(mode == M_COH) walkSharedAsm<false, true, true, false, false, true>(pn, A.tris, 64, lane, org, Q, 15u, tid, bu, bv, lds, st, oct);
 		else walkSharedAsm<false, false, true, false, false, true>(pn, A.tris, 64, lane, org, Q, 15u, tid, bu, bv, lds, st, 0);
 	} else if(mode == M_COH) walkSharedAsm<false, true, false, false, false, true>(A.nodes, A.tris, 64, lane, org, Q, 15u, tid, bu, bv, lds, st, oct);
@@ -2076,58 +1738,30 @@ __device__ __forceinline__ void primaryPacket(const PrimaryArgs &A, const int li
 #ifndef SNAIL_PRIMARY_WAVES
 #define SNAIL_PRIMARY_WAVES 6 // occupancy target of the primary kernel (76 VGPRs by itself; 7 = 72 VGPRs measured separately: profiles/README.md)
 #endif
-// SNAIL_BLOCK_WAVES packets per workgroup (one per wave; waves end independently, nothing of the block is shared): the XCD's
-// region turn is kept -- wave w of hardware block B takes entry (B >> 3) * W + w of XCD (B & 7)'s list.  One-frame launches only
-// (launchPrimaryFrames refuses W > 1 with several frames); W = 1 is the block -> (frame, rank) map of SNAIL_FRAME_XCD_MAJOR below.
-#ifndef SNAIL_BLOCK_WAVES
-#define SNAIL_BLOCK_WAVES 1 // 2 and 4 measured slower (22.65 / 21.80 vs 23.40 Grays/s): residency is not limited by workgroup slots
-#endif
+// One packet per workgroup: 2 and 4 waves per block measured slower (22.65 / 21.80 vs 23.40 Grays/s): residency is not limited by workgroup slots.
 // Frames of a multi-frame launch (grid = nFrames x the slot count, a multiple of 128): hardware block B runs on XCD group B & 7 and takes frame
 // (B >> 3) % F at rank ((B >> 3) / F) * 8 + (B & 7) -- the F copies of a rank (the same packet of every frame: same subtrees, same triangles) run
 // back to back on ONE XCD, whose L2 then fetches their lines once, and XCD group g keeps its own region set g of interleave16.  F = 1: rank B.
-// 0 = frame-minor (frame B % F at rank B / F): the copies of a rank on F different XCDs, each XCD tied to frame g % F.  DESIGN.md section 2
-#ifndef SNAIL_FRAME_XCD_MAJOR
-#define SNAIL_FRAME_XCD_MAJOR 1
-#endif
-#ifndef SNAIL_PRIO_RANK
-#define SNAIL_PRIO_RANK 0 // round 5: OFF.  Issue priority by dispatch rank (s_setprio 3 / 2 / 1 for the first N / 2N / 4N blocks of an ordered launch; N = 1024 in rounds 2-4)
-						  // measures nothing when the order is exact (static view: 27.30 vs 27.28, stress-1M 16.13 vs 16.23, bounce 10.83 vs 10.74 Grays/s) and costs
-						  // 6-10 % when it is a stale prediction (a turning camera: config 3 23.6 vs 25.2, stress-1M 14.3 vs 15.9): the wrong packets outrank the
-						  // heavy ones.  profiles/r5_prio_and_order.txt
-#endif
+// (Frame-minor -- frame B % F at rank B / F: the copies of a rank on F different XCDs, each XCD tied to frame g % F -- was measured and lost:
+// profiles/xcd_ab.txt, DESIGN.md section 2.)
 template <bool DEEP>
-__global__ __launch_bounds__(64 * SNAIL_BLOCK_WAVES) __attribute__((amdgpu_waves_per_eu(SNAIL_PRIMARY_WAVES))) void k_primary(PrimaryArgs A) {
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SNAIL_PRIMARY_WAVES))) void k_primary(PrimaryArgs A) {
 	__shared__ float lds[LDS_FLOATS_PER_WAVE];
-	const int wv = SNAIL_BLOCK_WAVES > 1 ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : 0;
-	int b = (int)blockIdx.x * SNAIL_BLOCK_WAVES + wv; // dispatch index of this wave's packet
+	int b = (int)blockIdx.x; // dispatch index of this block's packet
 	int fi = 0;
 	if(A.nFrames > 1) { // several frames in one launch: frame fi at dispatch rank b
-#if SNAIL_FRAME_XCD_MAJOR
-		const int t = b >> 3;   // (SNAIL_BLOCK_WAVES == 1 whenever nFrames > 1: b is the hardware block)
+		const int t = b >> 3;
 		fi = t % A.nFrames;
 		b = ((t / A.nFrames) << 3) | (b & 7);
-#else
-		fi = b % A.nFrames; b = b / A.nFrames;
-#endif
 	}
-	int li;
-	if(SNAIL_BLOCK_WAVES > 1) {
-		const int xcd = (int)blockIdx.x & 7, j = ((int)blockIdx.x >> 3) * SNAIL_BLOCK_WAVES + wv;   // (single-frame launches only)
-		li = (((j >> 4) << 3) + xcd) * 16 + (j & 15);
-	} else li = interleave16(b);
+	int li = interleave16(b);
 	if(A.order) { // fed-back dispatch order (snail_order_from_cost_dev): heaviest packets of the previous frame first
 		if(b >= A.nSlots) return;
 		li = __builtin_amdgcn_readfirstlane(A.order[b]);
 		if((unsigned)li >= (unsigned)A.nSlots) return;
-		// issue priority by rank in the fed-back order: the heaviest 1024 packets (one per SIMD) outrank whatever shares their SIMD, the
-		// next 1024 come second, the next 2048 third -- the frame ends with its heaviest packets, so they should never wait for an issue
-		// slot (priority, then age: MI355X_MICROARCH.md "Two waves per SIMD").  Same box, 4 frames in flight: 23.64 vs 23.10 Grays/s,
-		// lone frame 0.231 vs 0.234 ms (profiles/README.md, round 2); 0 = off
-#if SNAIL_PRIO_RANK > 0
-		if(b < SNAIL_PRIO_RANK) __builtin_amdgcn_s_setprio(3);
-		else if(b < 2 * SNAIL_PRIO_RANK) __builtin_amdgcn_s_setprio(2);
-		else if(b < 4 * SNAIL_PRIO_RANK) __builtin_amdgcn_s_setprio(1);
-#endif
+		// (Issue priority by rank in the fed-back order -- s_setprio 3 / 2 / 1 for the first N / 2N / 4N blocks, N = 1024 in rounds 2-4 -- measures nothing
+		// when the order is exact and costs 6-10 % when it is a stale prediction (a turning camera): the wrong packets outrank the heavy ones.
+		// profiles/r5_prio_and_order.txt)
 	}
 	primaryPacket<DEEP, false>(A, li, fi, lds);
 }
@@ -2159,9 +1793,6 @@ __global__ __launch_bounds__(256) void k_hostsse_sums(const unsigned *tables /* 
 // Needs n * 2 bytes of dynamic LDS (the costs as 16-bit words) beside its static 16.4 KB; n <= ORDER_LDS_MAX_SLOTS, cost 16-byte aligned.
 #define ORDER_THREADS_LDS 256
 #define ORDER_LDS_MAX_SLOTS 49152
-#ifndef SNAIL_ORDER_HEAVY_SHIFT
-#define SNAIL_ORDER_HEAVY_SHIFT 0 // experiment hook (round 5, profiles/r5_order_tiers.txt): k > 0 = a TIERED order -- only the heaviest n >> k slots sorted, the rest in the built-in dispatch order; 0 = the fully sorted order (what ships: best on the static heavy-tailed workloads)
-#endif
 #ifndef SNAIL_ORDER_ADAPTIVE
 #define SNAIL_ORDER_ADAPTIVE 3 // round 5: the derived order is the SORTED one only when the costs are heavy-tailed -- the 99th-percentile cost class at least this many times the
 							   // mean cost -- and the BUILT-IN order otherwise (0 = always sorted, rounds 2-4).  Sorting scatters neighbouring packets (same subtrees, same XCD's L2)
@@ -2225,15 +1856,11 @@ __device__ __forceinline__ void orderSortBlock(const int *__restrict__ cost /* 1
 	__syncthreads();
 	int run = incl - sum;
 	for(int w = 0; w < wv; w++) run += waveSum[w];
-	// TIERED ORDER (an experiment of round 5, SNAIL_ORDER_HEAVY_SHIFT > 0; off in the product).  Sorting the whole frame by cost scatters neighbouring
-	// packets -- which walk the same subtrees out of the same XCD's L2 -- over the whole dispatch, and on the atrium a STALE fully sorted order (a turning
-	// camera) is worse than no order at all (26.7 vs 27.4 Grays/s).  The idea: only the heaviest classes that together hold at least n >> SNAIL_ORDER_HEAVY_SHIFT
-	// slots go first, in descending class order; every other slot follows in the BUILT-IN dispatch order (block b -> slot interleave16(b): 4x4-packet regions
-	// dealt over the XCDs).  Measured (profiles/r5_order_tiers.txt): +0.5 % for the turning camera on the atrium, +2 % on stress-1M -- but -2..-5 % on the
-	// static stress-1M frame and -1..-3 % with the mirrored bounce, where the full sort's tail matters more than the locality.  cutClass = the first class
-	// of the second tier, heavyCount = the slots before it (0: every slot is in the first tier).
+	// Two tiers: the classes before cutClass go first, sorted, in descending class order; every other slot follows in the BUILT-IN dispatch order (block b ->
+	// slot interleave16(b): 4x4-packet regions dealt over the XCDs).  The sorted order is the one with every slot in the first tier (cutClass = one past the
+	// last populated class, heavyCount = n); the adaptive rule below emits the built-in order as the one with every slot in the second (cut = 0, heavy = 0).
+	// (A first tier of only the heaviest n >> k slots was measured and lost on the static heavy-tailed workloads: profiles/r5_order_tiers.txt.)
 	__shared__ int cutClass, heavyCount;
-	const int heavyWant = SNAIL_ORDER_HEAVY_SHIFT > 0 ? max(n >> SNAIL_ORDER_HEAVY_SHIFT, 1) : n;
 	const int p99Want = max(n / 100, 1);
 	if(tid == 0) { cutClass = 4096; heavyCount = n; }
 	__syncthreads();
@@ -2241,7 +1868,7 @@ __device__ __forceinline__ void orderSortBlock(const int *__restrict__ cost /* 1
 	for(int k = 0; k < BPT; k++) {
 		const int cnt = bins[tid * BPT + k];
 		bins[tid * BPT + k] = run;
-		if(run < heavyWant && run + cnt >= heavyWant) { cutClass = tid * BPT + k + 1; heavyCount = run + cnt; }   // (exactly one class crosses the mark)
+		if(run < n && run + cnt >= n) { cutClass = tid * BPT + k + 1; heavyCount = run + cnt; }   // (exactly one class crosses the mark)
 		if(run < p99Want && run + cnt >= p99Want) p99Class = tid * BPT + k;                                          // the class of the slot at the 99th percentile
 		run += cnt;
 	}
@@ -2384,16 +2011,11 @@ __device__ __forceinline__ void loadQuad3(const float *base, size_t quad, float 
 // k_final<SRC_PRIMARY, DST_FRAME> then blends diffuse += (colour - diffuse) * 0.3 (:462-465).  Samples and shadow rays are
 // recomputed (the same operations on the same operands, hence the same bits) wherever they are needed: a few hundred VALU
 // instructions per packet against the thousands of a walk, and no kernel carries state across a walk that the walk does not use.
-// block -> slot under a fed-back dispatch order, with the issue priority by rank that k_primary gives its heaviest packets; -1 = no slot
+// block -> slot under a fed-back dispatch order; -1 = no slot
 __device__ __forceinline__ int orderedSlot(const int *order, int nSlots, int b) {
 	if(b >= nSlots) return -1;
 	const int li = __builtin_amdgcn_readfirstlane(order[b]);
 	if((unsigned)li >= (unsigned)nSlots) return -1;
-#if SNAIL_PRIO_RANK > 0
-	if(b < SNAIL_PRIO_RANK) __builtin_amdgcn_s_setprio(3);
-	else if(b < 2 * SNAIL_PRIO_RANK) __builtin_amdgcn_s_setprio(2);
-	else if(b < 4 * SNAIL_PRIO_RANK) __builtin_amdgcn_s_setprio(1);
-#endif
 	return li;
 }
 enum { SRC_PRIMARY = 0, SRC_MIRROR = 1 };
@@ -2711,9 +2333,6 @@ __device__ __forceinline__ void shadeAndStore(const ShadeArgs &A, const PacketPo
 	}
 }
 
-#ifndef SNAIL_LIGHT_SCHED_BARRIER
-#define SNAIL_LIGHT_SCHED_BARRIER 0
-#endif
 // ---- one (packet, light): the shadow packet and its walk ----
 // EXACTPASS=false: the main kernel, walks in M_COH / M_FAST; a shadow packet that needs M_EXACT (a non-finite value: practically
 // never) is appended to A.defer untouched -- nothing has been written or counted for it -- and traced by the second, tiny
@@ -2772,9 +2391,6 @@ __device__ __forceinline__ void lightPacket(const ShadeArgs &A, const int li, co
 				for(int c = 0; c < 3; c++) Q.id[c][l] = S.hit[l] ? r[c] : 0.0f;
 				// the input of the epilogue's FastInv (shadeAndStore: 16 a^2, a = distance * iRadius, for the lanes whose distance is still positive after the walk -- a subset of these)
 				if(!CHK && A.fuse) { const float a = distance * iRadius; special |= Q.dist[l] > 0.0f && specialRcp(16.0f * a * a); }
-#if SNAIL_LIGHT_SCHED_BARRIER
-				__builtin_amdgcn_sched_barrier(0);   // (one lane's set-up at a time: the scheduler otherwise interleaves the four and spills around them)
-#endif
 			}
 			if(!CHK && __builtin_amdgcn_ballot_w64(special) != 0) { deferPacket(); return; }
 		}
@@ -2810,7 +2426,7 @@ __device__ __forceinline__ void lightPacket(const ShadeArgs &A, const int li, co
 			if(mode == M_COH) walk<true, false, true, M_COH, false, DEEP, false>(A.nodes, A.tris, 64, lane, lorg, Q, 15u, stid, bu, bv, lds, st, oct);
 			else walk<true, false, true, M_FAST, false, DEEP, false>(A.nodes, A.tris, 64, lane, lorg, Q, 15u, stid, bu, bv, lds, st);
 		} else if(A.pack) {
-			const uint4 *pn = (SNAIL_NODE_PREFETCH && SNAIL_REL_SHADOW) ? A.relLight[n] : SNAIL_PACK_NODES(A);   // this light's relative records
+			const uint4 *pn = A.relLight[n];   // this light's relative records
 			if(mode == M_COH) walkSharedAsm<true, true, true, false, false, false>(pn, A.tris, 64, lane, lorg, Q, 15u, stid, bu, bv, lds, st, oct);
 			else walkSharedAsm<true, false, true, false, false, false>(pn, A.tris, 64, lane, lorg, Q, 15u, stid, bu, bv, lds, st, 0);
 		} else if(mode == M_COH) walkSharedAsm<true, true, false, false, false, false>(A.nodes, A.tris, 64, lane, lorg, Q, 15u, stid, bu, bv, lds, st, oct);
@@ -3085,13 +2701,13 @@ __device__ __forceinline__ void raysPacket(const RaysArgs &A, const int p, float
 		}
 		if(!SHARED && !DEEP) { // per-ray origins: the hand-written node loop
 			if(A.pack) {
-				if(mode == M_COH) walkPerRayAsm<MASK, true, BARY, true>(SNAIL_PERRAY_COH_PF ? SNAIL_PACK_NODES(A) : A.nodes, A.tris, size, lane, org, Q, mask4, tid, bu, bv, st, oct);
-				else walkPerRayAsm<MASK, false, BARY, true>(SNAIL_PACK_NODES(A), A.tris, size, lane, org, Q, mask4, tid, bu, bv, st, 0);
+				if(mode == M_COH) walkPerRayAsm<MASK, true, BARY, true>(A.pf, A.tris, size, lane, org, Q, mask4, tid, bu, bv, st, oct);
+				else walkPerRayAsm<MASK, false, BARY, true>(A.pf, A.tris, size, lane, org, Q, mask4, tid, bu, bv, st, 0);
 			} else if(mode == M_COH) walkPerRayAsm<MASK, true, BARY, false>(A.nodes, A.tris, size, lane, org, Q, mask4, tid, bu, bv, st, oct);
 			else walkPerRayAsm<MASK, false, BARY, false>(A.nodes, A.tris, size, lane, org, Q, mask4, tid, bu, bv, st, 0);
-		} else if(SHARED && !DEEP && A.pack && SNAIL_SHADOW_ENTRY_PF) { // shared origin, any distances on entry: the prefetching loop over its plain copy of the tree
-			if(mode == M_COH) walkSharedAsm<false, true, true, MASK, BARY, false, false>(SNAIL_PACK_NODES(A), A.tris, size, lane, org, Q, mask4, tid, bu, bv, lds, st, oct);
-			else walkSharedAsm<false, false, true, MASK, BARY, false, false>(SNAIL_PACK_NODES(A), A.tris, size, lane, org, Q, mask4, tid, bu, bv, lds, st, 0);
+		} else if(SHARED && !DEEP && A.pack) { // shared origin, any distances on entry: the prefetching loop over its plain copy of the tree
+			if(mode == M_COH) walkSharedAsm<false, true, true, MASK, BARY, false, false>(A.pf, A.tris, size, lane, org, Q, mask4, tid, bu, bv, lds, st, oct);
+			else walkSharedAsm<false, false, true, MASK, BARY, false, false>(A.pf, A.tris, size, lane, org, Q, mask4, tid, bu, bv, lds, st, 0);
 		} else if(SHARED && !DEEP) {
 			if(mode == M_COH) walkSharedAsm<false, true, false, MASK, BARY, false>(A.nodes, A.tris, size, lane, org, Q, mask4, tid, bu, bv, lds, st, oct);
 			else walkSharedAsm<false, false, false, MASK, BARY, false>(A.nodes, A.tris, size, lane, org, Q, mask4, tid, bu, bv, lds, st, 0);
@@ -3178,9 +2794,9 @@ __device__ __forceinline__ void shadowPacket(const RaysArgs &A, const int p, flo
 		if(DEEP) {
 			if(mode == M_COH) walk<true, false, true, M_COH, false, DEEP, false>(A.nodes, A.tris, size, lane, org, Q, 15u, tid, bu, bv, lds, st, oct);
 			else walk<true, false, true, M_FAST, false, DEEP, false>(A.nodes, A.tris, size, lane, org, Q, 15u, tid, bu, bv, lds, st);
-		} else if(A.pack && SNAIL_SHADOW_ENTRY_PF) { // the prefetching loop over its plain copy of the tree (origins differ from packet to packet: no relative records)
-			if(mode == M_COH) walkSharedAsm<true, true, true, false, false, false, false>(SNAIL_PACK_NODES(A), A.tris, size, lane, org, Q, 15u, tid, bu, bv, lds, st, oct);
-			else walkSharedAsm<true, false, true, false, false, false, false>(SNAIL_PACK_NODES(A), A.tris, size, lane, org, Q, 15u, tid, bu, bv, lds, st, 0);
+		} else if(A.pack) { // the prefetching loop over its plain copy of the tree (origins differ from packet to packet: no relative records)
+			if(mode == M_COH) walkSharedAsm<true, true, true, false, false, false, false>(A.pf, A.tris, size, lane, org, Q, 15u, tid, bu, bv, lds, st, oct);
+			else walkSharedAsm<true, false, true, false, false, false, false>(A.pf, A.tris, size, lane, org, Q, 15u, tid, bu, bv, lds, st, 0);
 		} else if(mode == M_COH) walkSharedAsm<true, true, false, false, false, false>(A.nodes, A.tris, size, lane, org, Q, 15u, tid, bu, bv, lds, st, oct);
 		else walkSharedAsm<true, false, false, false, false, false>(A.nodes, A.tris, size, lane, org, Q, 15u, tid, bu, bv, lds, st, 0);
 	}
@@ -3357,7 +2973,7 @@ __global__ __launch_bounds__(256) void k_recip_check(unsigned base, unsigned lon
 __global__ void k_nop(int *sink) { if(sink && threadIdx.x == 0 && blockIdx.x == 0x7fffffff) *sink = 1; }
 #endif // SNAIL_DEBUG_API
 
-// ---- the record-prefetching loop's copy of the node records (SNAIL_PF_VISIT): slot i + 1 <- node i, words 6 / 7 re-encoded ----
+// ---- the record-prefetching loop's copy of the node records (SNAIL_DESCEND_PF2X): slot i + 1 <- node i, words 6 / 7 re-encoded ----
 // (one thread per node; used for trees that were built on the device -- snail_scene_create encodes on the host, same function)
 __host__ __device__ inline void pfEncode(const unsigned (&in)[8], unsigned (&out)[8], unsigned trisOff) {
 	for(int k = 0; k < 6; k++) out[k] = in[k];

@@ -11,7 +11,7 @@
 // kept exactly -- and they map onto a CDNA4 wavefront without any divergence:
 //   * control flow is wave-uniform: node index, stack pointer, first/last live in SGPRs;
 //   * a 32-B node record is ONE scalar load (s_load_dwordx8) through the scalar cache, requested ahead of
-//     its use from a copy of the tree laid out for that (child pairs on one 64-B line, see SNAIL_PF_VISIT);
+//     its use from a copy of the tree laid out for that (child pairs on one 64-B line, see SNAIL_DESCEND_PF2X);
 //   * the traversal stack is a VGPR pair (lane i = stack slot i): pop = v_readlane, push = lane-predicated move;
 //   * "scan for the first/last quad with a surviving lane" is one __ballot + s_ff1/s_flbit;
 //   * per-leaf, the packet-level Triangle::TestInterval cull and the shared-origin terms tvec0/tvec1/tmul
@@ -502,7 +502,7 @@ int launchPrimaryFrames(SnailScene *s, const FrameSet &FS, int resx, int resy, i
 						int32_t *dNextOrder = nullptr, int orderFlags = 0) {
 	if(resx <= 0 || resy <= 0) { snail_set_error("snail_trace_primary: bad resolution %dx%d", resx, resy); return 1; }
 	if(dNextOrder && !dSlotCost) { snail_set_error("snail_trace_primary: the next dispatch order is derived from d_slot_cost, which is null"); return 1; }
-	if(FS.n < 1 || FS.n > SNAIL_MAX_BATCH || (SNAIL_BLOCK_WAVES > 1 && FS.n > 1)) { snail_set_error("snail_trace_primary: 1..%d frames per launch (got %d)", SNAIL_MAX_BATCH, FS.n); return 1; }
+	if(FS.n < 1 || FS.n > SNAIL_MAX_BATCH) { snail_set_error("snail_trace_primary: 1..%d frames per launch (got %d)", SNAIL_MAX_BATCH, FS.n); return 1; }
 	SceneUse use(s, stream);
 	if(use.rc) return use.rc;
 	dev::PrimaryArgs A;
@@ -545,7 +545,7 @@ int launchPrimaryFrames(SnailScene *s, const FrameSet &FS, int resx, int resy, i
 	A.order = dOrder; A.slotCost = dSlotCost;
 	// the frames' origin-relative node records (only the record-prefetching loop reads them: not the DEEP kernels' C++ walk); after every
 	// early return above, so that a fill is always followed by its reader's event (relUsed below)
-	if(A.pack && SNAIL_REL_NODES && SNAIL_NODE_PREFETCH && !useDeep(s)) {
+	if(A.pack && !useDeep(s)) {
 		RelPending pend;
 		pend.fill.n = 0;
 		for(int k = 0; k < FS.n; k++)
@@ -574,8 +574,7 @@ int launchPrimaryFrames(SnailScene *s, const FrameSet &FS, int resx, int resy, i
 	static const int dynLds = debugEnvInt("SNAIL_DEBUG_DYNLDS");
 	// a scene with sane records defers (practically) nothing: a handful of blocks suffices; an unsafe scene defers every packet
 	const int exactBlocks = A.fastOK ? (blocks < 8 ? blocks : 8) : (blocks < 2048 ? blocks : 2048);
-	static_assert(128 % SNAIL_BLOCK_WAVES == 0, "the slot count is a multiple of 128");
-	const dim3 grid(gridBlocks / SNAIL_BLOCK_WAVES), block(64 * SNAIL_BLOCK_WAVES);
+	const dim3 grid(gridBlocks), block(64);
 	const ExactPass EP = exactPassFor(exactBlocks, dSlotCost, A.nSlots, dCost ? nullptr : dNextOrder, orderFlags);
 	A.nextOrder = EP.nextOrder; A.nextOrderFlags = EP.orderFlags;
 	const bool sse = s->arith == SNAIL_ARITH_HOST_SSE;
@@ -722,7 +721,7 @@ int launchLights(SnailScene *s, dev::ShadeArgs A /* a copy: relLight is filled i
 	if(use.rc) return use.rc;
 	int relWhich[SNAIL_MAX_LIGHTS];
 	for(int n = 0; n < SNAIL_MAX_LIGHTS; n++) { relWhich[n] = -1; A.relLight[n] = nullptr; }
-	if(SNAIL_NODE_PREFETCH && SNAIL_REL_SHADOW && A.pack && !useDeep(s))
+	if(A.pack && !useDeep(s))
 		for(int n = 0; n < A.nLights; n++)
 			if(int rc = relFor(s, A.lights[n], stream, &A.relLight[n], &relWhich[n])) return rc;   // lights[n][0..2] = the light's position
 	const dim3 grid(A.nBlocks, A.nLights);
@@ -760,7 +759,7 @@ int snail_device_count(void) {
 }
 
 // byte offset of the triangle records in SnailScene::dPF: a CONSTANT (2^25 = room for 2^20 record slots), so that the prefetching loop
-// turns a leaf record's triangle offset back into an index with immediates (SNAIL_PF_VISIT, L_leaf)
+// turns a leaf record's triangle offset back into an index with immediates (SNAIL_PF2_LEAF)
 static size_t pfTrisOffset(int) { return (size_t)1 << 25; }
 
 SnailScene *snail_scene_create(const void *nodes32, int nNodes, const void *tris64, int nTris, int depth, int device) {
@@ -1582,7 +1581,7 @@ int snail_debug_anyorder(SnailScene *s, const float cam[13], int resx, int resy,
 	hipStream_t st;
 	HIP_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
 	int relWhich = -1;
-	if(A.pack && SNAIL_REL_NODES && SNAIL_NODE_PREFETCH && !useDeep(s)) {
+	if(A.pack && !useDeep(s)) {
 		if(int rc = relFor(s, cam, st, &A.rel[0], &relWhich)) return rc;
 	}
 	hipEvent_t e0, e1;
@@ -1590,7 +1589,7 @@ int snail_debug_anyorder(SnailScene *s, const float cam[13], int resx, int resy,
 	HIP_TRY(hipDeviceSynchronize());
 	HIP_TRY(hipEventRecord(e0, st));
 	for(int f = 0; f < frames; f++)
-		hipExtLaunchKernelGGL(dev::k_primary<false>, dim3(blocks / SNAIL_BLOCK_WAVES), dim3(64 * SNAIL_BLOCK_WAVES), 0, st, nullptr, nullptr, (unsigned)flags, A);
+		hipExtLaunchKernelGGL(dev::k_primary<false>, dim3(blocks), dim3(64), 0, st, nullptr, nullptr, (unsigned)flags, A);
 	HIP_TRY(hipGetLastError());
 	HIP_TRY(hipEventRecord(e1, st));
 	HIP_TRY(hipStreamSynchronize(st));
@@ -1604,10 +1603,10 @@ int snail_debug_occupancy(int out[4]) {
 	int dev = 0;
 	HIP_TRY(hipGetDevice(&dev));
 	int perCU = 0, maxBlocks = 0, cus = 0;
-	HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, (const void *)dev::k_primary<false>, 64 * SNAIL_BLOCK_WAVES, 0));
+	HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, (const void *)dev::k_primary<false>, 64, 0));
 	HIP_TRY(hipDeviceGetAttribute(&maxBlocks, hipDeviceAttributeMaxBlocksPerMultiProcessor, dev));
 	HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-	out[0] = perCU; out[1] = maxBlocks; out[2] = cus; out[3] = SNAIL_BLOCK_WAVES;
+	out[0] = perCU; out[1] = maxBlocks; out[2] = cus; out[3] = 1;   // waves per block of k_primary
 	return 0;
 }
 

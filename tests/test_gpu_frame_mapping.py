@@ -1,7 +1,7 @@
 """Multi-frame primary launches against single-frame launches (run with -m gpu on an MI355X).
 
 A launch of F frames maps its F x nSlots workgroups onto (frame, dispatch rank) pairs so that the F copies of a rank run on one XCD
-(k_primary, SNAIL_FRAME_XCD_MAJOR).  Whatever the map, every frame must come out bit for bit as its own one-frame launch, the TreeStats
+(k_primary's XCD-major block -> (frame, rank) map).  Whatever the map, every frame must come out bit for bit as its own one-frame launch, the TreeStats
 as their sum and d_slot_cost as the first frame's.  F = 3, 5 catch a non-power-of-two slip in the map; the rect's packet grid (21 x 13)
 is not a multiple of the 4 x 4 regions, and the packet list (300 packets) is not a multiple of 128."""
 from __future__ import annotations
