@@ -57,6 +57,7 @@
 #include "snail_hip.h"
 #include "snail_bvh_fast.h"
 #include "snail_instances.h"
+#include "snail_heatmap.h"
 
 #ifndef SNAIL_CHECK
 #define SNAIL_CHECK(expr)                                                                              \
@@ -496,11 +497,21 @@ private:
 // prefetched HipBVH path (the reference's RenderTask::Work then does its 4x antialiasing, full shading, tints ... itself, and its
 // TraversePrimary calls copy pre-traced packets), or abort with this message when SNAIL_ADAPTER_NO_HOST_RENDERER is defined.
 //   gVals[6]  full shading (materials, textures, transparency selection) when the scene carries shading data   src/scene_trace.cpp:145
-//   gVals[5]  TreeStats visualisation   src/scene_trace.cpp:513-517
+//   gVals[5]  TreeStats visualisation   src/scene_trace.cpp:513-517 -- unless the host opts in to the device heat-map (below)
 //   gVals[8]  per-rank tint of the render nodes' tiles (colorizeNodes: the tile-list Render only)   src/render.cpp:118-132
-inline const char *UnsupportedSwitch(const int *gv, bool hasShadingData, bool tileList) {
+// gVals[5] on the device (include/snail_heatmap.h): define SNAIL_ADAPTER_DEVICE_HEATMAP before the include and the Render(...) overloads send
+// gVals[5] to snail_render_heat_tiles / snail_render_heat_image (and, together with SNAIL_ADAPTER_INSTANCED_TILES, an instanced scene's to
+// snail_instances_render_heat_tiles / _heat_frame) -- RenderMode::statsHeat.  With gVals[1] as well the frame is the depth frame, as in the
+// reference (depth shading returns before the heat colour).  A tree uploaded to several devices keeps the host path for gVals[5] on a tile
+// list (no multi-device heat tiles).  Opt-in, so that hosts and mocks built without it keep today's routing.
+#ifdef SNAIL_ADAPTER_DEVICE_HEATMAP
+enum { kDeviceHeatmap = 1 };
+#else
+enum { kDeviceHeatmap = 0 };
+#endif
+inline const char *UnsupportedSwitch(const int *gv, bool hasShadingData, bool tileList, bool deviceHeatmap = false) {
 	if(gv[6] && hasShadingData) return "gVals[6] (full shading: materials / textures, src/scene_trace.cpp:145)";
-	if(gv[5]) return "gVals[5] (TreeStats visualisation, src/scene_trace.cpp:513-517)";
+	if(gv[5] && !deviceHeatmap) return "gVals[5] (TreeStats visualisation, src/scene_trace.cpp:513-517)";
 	if(gv[8] && tileList) return "gVals[8] (per-rank tint of the tiles, src/render.cpp:118-132)";
 	return nullptr;
 }
@@ -511,6 +522,7 @@ struct RenderMode {
 	bool antialias = false;     // gVals[9]
 	float color[3] = {1.0f, 1.0f, 1.0f};
 	bool rankTint = false;      // gVals[8]: read by RenderInstancedTiles alone (the tile list of an instanced scene), which is given the rank
+	bool statsHeat = false;     // gVals[5]: the TreeStats heat-map (include/snail_heatmap.h); without effect under depthShading, as in the reference
 };
 
 namespace detail {
@@ -541,6 +553,7 @@ inline const float *RankTint(unsigned rank) {
 inline int renderFlags(const RenderMode &mode) {
 	return (mode.depthShading ? SNAIL_RENDER_DEPTH : 0) | (mode.reflections ? SNAIL_RENDER_REFLECTIONS : 0) | (mode.antialias ? SNAIL_RENDER_AA4 : 0);
 }
+inline bool heat(const RenderMode &mode) { return mode.statsHeat && !mode.depthShading; }
 } // namespace detail
 
 // Render(scene, camera, resx, resy, data, coords, offsets, ...) of src/render.h:16-19: coords = x, y, w, h per tile, offsets = byte
@@ -555,7 +568,10 @@ inline StatsT RenderTiles(const SceneT &scene, const CameraT &camera, unsigned r
 	const float amb[3] = {scene.ambientLight.x, scene.ambientLight.y, scene.ambientLight.z};
 	uint64_t st[4] = {0, 0, 0, 0};
 	const int flags = (mode.depthShading ? SNAIL_RENDER_DEPTH : 0) | (mode.reflections ? SNAIL_RENDER_REFLECTIONS : 0) | (mode.antialias ? SNAIL_RENDER_AA4 : 0);
-	if(scene.geometry.DeviceCount() > 1)   // the tiles dealt over every device the tree was uploaded to
+	if(detail::heat(mode))   // (one device: the overloads keep gVals[5] on a several-device tile list with the host path)
+		SNAIL_CHECK(snail_render_heat_tiles(scene.geometry.Handle(), c, (int)resx, (int)resy, coords.data(), off.data(), (int)(coords.size() / 4), l.data(), (int)(l.size() / 7),
+											flags, data, st));
+	else if(scene.geometry.DeviceCount() > 1)   // the tiles dealt over every device the tree was uploaded to
 		SNAIL_CHECK(snail_render_tiles_multi(scene.geometry.Handles(), scene.geometry.DeviceCount(), c, (int)resx, (int)resy, coords.data(), off.data(), (int)(coords.size() / 4),
 											 l.data(), (int)(l.size() / 7), amb, mode.color, flags, data, st));
 	else
@@ -572,6 +588,11 @@ inline StatsT RenderImage(const SceneT &scene, const CameraT &camera, ImageT &im
 	const std::vector<float> l = detail::lights7(scene);
 	const float amb[3] = {scene.ambientLight.x, scene.ambientLight.y, scene.ambientLight.z};
 	uint64_t st[4] = {0, 0, 0, 0};
+	if(detail::heat(mode)) {
+		SNAIL_CHECK(snail_render_heat_image(scene.geometry.Handle(), c, (int)image.Width(), (int)image.Height(), l.data(), (int)(l.size() / 7), detail::renderFlags(mode),
+											(unsigned char *)image.DataPointer(), (int)image.Pitch(), st));
+		return detail::toStats<StatsT>(st);
+	}
 	SNAIL_CHECK(snail_render_image(scene.geometry.Handle(), c, (int)image.Width(), (int)image.Height(), l.data(), (int)(l.size() / 7), amb, mode.color,
 								   (mode.depthShading ? SNAIL_RENDER_DEPTH : 0) | (mode.reflections ? SNAIL_RENDER_REFLECTIONS : 0) | (mode.antialias ? SNAIL_RENDER_AA4 : 0),
 								   (unsigned char *)image.DataPointer(), (int)image.Pitch(), st));
@@ -590,6 +611,11 @@ inline StatsT RenderInstancedTiles(const SceneT &scene, const CameraT &camera, u
 	std::vector<int64_t> off(offsets.begin(), offsets.end());
 	const float amb[3] = {scene.ambientLight.x, scene.ambientLight.y, scene.ambientLight.z};
 	uint64_t st[4] = {0, 0, 0, 0};
+	if(detail::heat(mode)) {
+		SNAIL_CHECK(snail_instances_render_heat_tiles(scene.geometry.Handle(), c, (int)resx, (int)resy, coords.data(), off.data(), (int)(coords.size() / 4), l.data(),
+													  (int)(l.size() / 7), detail::renderFlags(mode), mode.rankTint ? detail::RankTint(rank) : nullptr, data, st));
+		return detail::toStats<StatsT>(st);
+	}
 	SNAIL_CHECK(snail_instances_render_tiles(scene.geometry.Handle(), c, (int)resx, (int)resy, coords.data(), off.data(), (int)(coords.size() / 4), l.data(),
 											 (int)(l.size() / 7), amb, mode.color, detail::renderFlags(mode), mode.rankTint ? detail::RankTint(rank) : nullptr, data, st));
 	return detail::toStats<StatsT>(st);
@@ -601,6 +627,11 @@ inline StatsT RenderInstancedImage(const SceneT &scene, const CameraT &camera, I
 	const std::vector<float> l = detail::lights7(scene);
 	const float amb[3] = {scene.ambientLight.x, scene.ambientLight.y, scene.ambientLight.z};
 	uint64_t st[4] = {0, 0, 0, 0};
+	if(detail::heat(mode)) {
+		SNAIL_CHECK(snail_instances_render_heat_frame(scene.geometry.Handle(), c, (int)image.Width(), (int)image.Height(), l.data(), (int)(l.size() / 7),
+													  detail::renderFlags(mode), (unsigned char *)image.DataPointer(), (int)image.Pitch(), st));
+		return detail::toStats<StatsT>(st);
+	}
 	SNAIL_CHECK(snail_instances_render_frame(scene.geometry.Handle(), c, (int)image.Width(), (int)image.Height(), l.data(), (int)(l.size() / 7), amb, mode.color,
 											 detail::renderFlags(mode), (unsigned char *)image.DataPointer(), (int)image.Pitch(), st));
 	return detail::toStats<StatsT>(st);
@@ -634,10 +665,11 @@ inline StatsT RenderInstancedImage(const SceneT &scene, const CameraT &camera, I
 template <class RefBVH>
 inline TreeStats Render(const Scene<snail::HipBVH<RefBVH>> &scene, const Camera &camera, uint resx, uint resy, unsigned char *data, const vector<int> &coords,
 						const vector<int> &offsets, const Options options, uint rank, uint threads) {
-	if(const char *why = snail::UnsupportedSwitch(gVals, scene.geometry.HasShadingData(), true))
+	if(const char *why = snail::UnsupportedSwitch(gVals, scene.geometry.HasShadingData(), true, snail::kDeviceHeatmap && scene.geometry.DeviceCount() <= 1))
 		SNAIL_HOST_RENDER(why, gVals[9] ? 2 : 1, resx, resy, Render<snail::HipBVH<RefBVH>>(scene, camera, resx, resy, data, coords, offsets, options, rank, threads));
 	(void)rank; (void)threads; // (no tint requested; the host thread pool has no device counterpart)
 	snail::RenderMode mode;
+	mode.statsHeat = gVals[5] != 0;
 	mode.depthShading = gVals[1] != 0;
 	mode.reflections = gVals[7] != 0;   // the bounce is gated by gVals[7] alone (src/scene_trace.cpp:454); Options::reflections is stored and never read (src/render.cpp:24,37)
 	(void)options;
@@ -646,10 +678,11 @@ inline TreeStats Render(const Scene<snail::HipBVH<RefBVH>> &scene, const Camera 
 }
 template <class RefBVH>
 inline TreeStats Render(const Scene<snail::HipBVH<RefBVH>> &scene, const Camera &camera, MipmapTexture &image, const Options options, uint threads) {
-	if(const char *why = snail::UnsupportedSwitch(gVals, scene.geometry.HasShadingData(), false))
+	if(const char *why = snail::UnsupportedSwitch(gVals, scene.geometry.HasShadingData(), false, snail::kDeviceHeatmap != 0))
 		SNAIL_HOST_RENDER(why, gVals[9] ? 2 : 1, image.Width(), image.Height(), Render<snail::HipBVH<RefBVH>>(scene, camera, image, options, threads));
 	(void)threads;
 	snail::RenderMode mode;
+	mode.statsHeat = gVals[5] != 0;
 	mode.depthShading = gVals[1] != 0;
 	mode.reflections = gVals[7] != 0;   // the bounce is gated by gVals[7] alone (src/scene_trace.cpp:454); Options::reflections is stored and never read (src/render.cpp:24,37)
 	(void)options;
@@ -663,27 +696,30 @@ inline TreeStats Render(const Scene<snail::HipBVH<RefBVH>> &scene, const Camera 
 //
 // Define SNAIL_ADAPTER_INSTANCED_TILES as well (before the include) and both overloads go to the device instead -- the tile list with
 // gVals[1], [7], [9] and [8] (tint by `rank`), the image with gVals[1], [7], [9]: snail::RenderInstancedTiles / RenderInstancedImage -- and
-// only gVals[5] (and gVals[8] on an image) still takes the reference's renderer.  Opt-in, so that a host built against the overloads above keeps what it has
-// (INTEGRATION.md, section 2c).
+// only gVals[5] (and gVals[8] on an image) still takes the reference's renderer -- gVals[5] too goes to the device when SNAIL_ADAPTER_DEVICE_HEATMAP is
+// defined as well (snail_instances_render_heat_tiles, tinted by `rank` under gVals[8]; snail_instances_render_heat_frame).  Opt-in, so that a host built
+// against the overloads above keeps what it has.
 #ifdef SNAIL_ADAPTER_INSTANCED_TILES
 template <class RefDBVH>
 inline TreeStats Render(const Scene<snail::HipDBVH<RefDBVH>> &scene, const Camera &camera, uint resx, uint resy, unsigned char *data, const vector<int> &coords,
 						const vector<int> &offsets, const Options options, uint rank, uint threads) {
-	if(gVals[5])
+	if(gVals[5] && !snail::kDeviceHeatmap)
 		SNAIL_HOST_RENDER("gVals[5] (TreeStats visualisation, src/scene_trace.cpp:513-517)", gVals[9] ? 2 : 1, resx, resy,
 						  Render<snail::HipDBVH<RefDBVH>>(scene, camera, resx, resy, data, coords, offsets, options, rank, threads));
 	(void)options; (void)threads;   // (the bounce is gated by gVals[7] alone, src/scene_trace.cpp:454)
 	snail::RenderMode mode;
+	mode.statsHeat = gVals[5] != 0;
 	mode.depthShading = gVals[1] != 0; mode.reflections = gVals[7] != 0; mode.antialias = gVals[9] != 0; mode.rankTint = gVals[8] != 0;
 	return snail::RenderInstancedTiles<TreeStats>(scene, camera, resx, resy, data, coords, offsets, mode, rank);
 }
 template <class RefDBVH>
 inline TreeStats Render(const Scene<snail::HipDBVH<RefDBVH>> &scene, const Camera &camera, MipmapTexture &image, const Options options, uint threads) {
-	if(gVals[5] || gVals[8])   // (the device's image form has no tint: gVals[8] on an image stays where it was)
-		SNAIL_HOST_RENDER(gVals[5] ? "gVals[5] (TreeStats visualisation, src/scene_trace.cpp:513-517)" : "gVals[8] on the image of an instanced scene", gVals[9] ? 2 : 1,
+	if((gVals[5] && !snail::kDeviceHeatmap) || gVals[8])   // (the device's image form has no tint: gVals[8] on an image stays where it was)
+		SNAIL_HOST_RENDER(gVals[5] && !snail::kDeviceHeatmap ? "gVals[5] (TreeStats visualisation, src/scene_trace.cpp:513-517)" : "gVals[8] on the image of an instanced scene", gVals[9] ? 2 : 1,
 						  image.Width(), image.Height(), Render<snail::HipDBVH<RefDBVH>>(scene, camera, image, options, threads));
 	(void)options; (void)threads;
 	snail::RenderMode mode;
+	mode.statsHeat = gVals[5] != 0;
 	mode.depthShading = gVals[1] != 0; mode.reflections = gVals[7] != 0; mode.antialias = gVals[9] != 0;
 	return snail::RenderInstancedImage<TreeStats>(scene, camera, image, mode);
 }

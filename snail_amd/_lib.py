@@ -122,6 +122,18 @@ BVH_FAST_SIGNATURES = {
     "snail_scene_rebuild_fast_dev": (_I, [_VP, _VP, _I, _VP, _VP, _VP]),
 }
 
+# include/snail_heatmap.h: per-packet TreeStats and the gVals[5] heat-map of plain and instanced scenes (tests/c/heatmap_c.c enumerates this table)
+HEATMAP_SIGNATURES = {
+    "snail_packet_stats_dev": (_I, [_VP, _F13, _I, _I, _VP, _I, _VP, _I, _I, _VP, _VP, _VP]),
+    "snail_render_heat_packets_dev": (_I, [_VP, _F13, _I, _I, _VP, _I, _VP, _I, _I, _VP, _VP, _VP, _VP]),
+    "snail_render_heat_tiles": (_I, [_VP, _F13, _I, _I, _VP, _VP, _I, _VP, _I, _I, _VP, _VP]),
+    "snail_render_heat_image": (_I, [_VP, _F13, _I, _I, _VP, _I, _I, _VP, _I, _VP]),
+    "snail_instances_packet_stats_dev": (_I, [_VP, _F13, _I, _I, _VP, _I, _VP, _I, _I, _VP, _VP, _VP]),
+    "snail_instances_heat_packets_dev": (_I, [_VP, _F13, _I, _I, _VP, _I, _VP, _I, _I, _VP, _VP, _VP, _VP, _VP]),
+    "snail_instances_render_heat_tiles": (_I, [_VP, _F13, _I, _I, _VP, _VP, _I, _VP, _I, _I, _VP, _VP, _VP]),
+    "snail_instances_render_heat_frame": (_I, [_VP, _F13, _I, _I, _VP, _I, _I, _VP, _I, _VP]),
+}
+
 # include/snail_hip_debug.h: the workbench build only (libsnailhip_debug.so, -DSNAIL_DEBUG_API)
 DEBUG_SIGNATURES = {
     "snail_debug_delay_dev": (_I, [C.c_float, _VP]),
@@ -144,7 +156,7 @@ def debug_lib():
         if not os.path.exists(DEBUG_LIB_PATH):
             raise SnailError("workbench library %s is missing: `make -C snail_amd/csrc debug`" % DEBUG_LIB_PATH)
         L = C.CDLL(DEBUG_LIB_PATH)
-        for table in (SIGNATURES, INSTANCES_SIGNATURES, INSTANCES_SHADE_SIGNATURES, INSTANCES_TILES_SIGNATURES, INSTANCES_BUILD_SIGNATURES, BVH_FAST_SIGNATURES, DEBUG_SIGNATURES):
+        for table in (SIGNATURES, INSTANCES_SIGNATURES, INSTANCES_SHADE_SIGNATURES, INSTANCES_TILES_SIGNATURES, INSTANCES_BUILD_SIGNATURES, BVH_FAST_SIGNATURES, HEATMAP_SIGNATURES, DEBUG_SIGNATURES):
             for name, (res, args) in table.items():
                 fn = getattr(L, name)
                 fn.restype = res
@@ -165,7 +177,7 @@ def lib():
             L = C.CDLL(LIB_PATH)
         except OSError as e:  # pragma: no cover - depends on the box
             raise SnailError("cannot load %s: %s" % (LIB_PATH, e)) from e
-        for table in (SIGNATURES, INSTANCES_SIGNATURES, INSTANCES_SHADE_SIGNATURES, INSTANCES_TILES_SIGNATURES, INSTANCES_BUILD_SIGNATURES, BVH_FAST_SIGNATURES):
+        for table in (SIGNATURES, INSTANCES_SIGNATURES, INSTANCES_SHADE_SIGNATURES, INSTANCES_TILES_SIGNATURES, INSTANCES_BUILD_SIGNATURES, BVH_FAST_SIGNATURES, HEATMAP_SIGNATURES):
             for name, (res, args) in table.items():
                 fn = getattr(L, name)
                 fn.restype = res

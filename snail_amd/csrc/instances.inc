@@ -30,6 +30,7 @@ struct InstArgs {
 	int *object, *element;
 	float *bary;
 	u64 *stats;
+	unsigned *pstats; // per-packet TreeStats [nPackets][4] (bookPacket: k_inst_frame, k_inst_trace<.., PSTATS>; the heat-map launches) or null
 };
 
 __device__ __forceinline__ float instShfl(float x, int src) { return __int_as_float(__builtin_amdgcn_ds_bpermute(src << 2, __float_as_int(x))); }
@@ -273,6 +274,7 @@ __global__ __launch_bounds__(64) void k_inst_frame(InstArgs A) {
 	Counters st = {0, 0, 0, 0, 0};
 	instWalk<true, false, false, true, DEEP>(A, 64, lane, org, d, id, 15u, dist, obj, elem, bu, bv, lds, st);
 	flushStats(A.stats, st, 256u, lane);
+	bookPacket(A.pstats, (size_t)p, st, 256u, lane);
 
 	if(A.packetXY) { // packet-major (Context layout)
 		const size_t o = (size_t)p * 256 + (size_t)lane * 4;
@@ -300,7 +302,9 @@ __global__ __launch_bounds__(64) void k_inst_frame(InstArgs A) {
 }
 
 // ---- generic packets: DBVH::TraversePrimary<SHARED,MASK>(Context&) ----
-template <bool SHARED, bool MASK, bool DEEP, bool BARY>
+// PSTATS: the heat-map launches' instantiation, which also books per packet (a template argument as in snail_dev.inc: a pointer test here cost the
+// other launches' kernel scalar spills and, in one instantiation, a wave)
+template <bool SHARED, bool MASK, bool DEEP, bool BARY, bool PSTATS = false>
 __global__ __launch_bounds__(64) void k_inst_trace(InstArgs A) {
 	__shared__ float lds[LDS_FLOATS_PER_WAVE];
 	const int lane = threadIdx.x & 63;
@@ -332,6 +336,7 @@ __global__ __launch_bounds__(64) void k_inst_trace(InstArgs A) {
 	Counters st = {0, 0, 0, 0, 0};
 	instWalk<SHARED, MASK, false, BARY, DEEP>(A, size, lane, org, d, id, mask4, dist, obj, elem, bu, bv, lds, st);
 	flushStats(A.stats, st, 0u, lane);
+	if(PSTATS) bookPacket(A.pstats, (size_t)p, st, 0u, lane);
 	if(live) {
 		*(float4 *)(A.distance + q * 4) = make_float4(dist[0], dist[1], dist[2], dist[3]);
 		*(int4 *)(A.object + q * 4) = make_int4(obj[0], obj[1], obj[2], obj[3]);

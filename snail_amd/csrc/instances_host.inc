@@ -37,17 +37,19 @@ struct SnailInstances {
 		float *sDist = nullptr;
 		float *rOrg = nullptr, *rDir = nullptr, *rIDir = nullptr, *rDist = nullptr, *rCol = nullptr;
 		float *col = nullptr; int32_t *xy2 = nullptr;   // snail_instances_tiles.h: the packets' float colours, the double-resolution packet list
+		uint32_t *pstats = nullptr;                     // snail_heatmap.h: the launch's per-packet TreeStats [packets][4] when the caller keeps none of its own
 		int *rInst = nullptr, *rTri = nullptr;
 		unsigned char *rMask = nullptr;
 		static size_t bytes(size_t packets, int lights, bool refl, bool tiles = false) {
 			const size_t rays = packets * 256;
-			return rays * 12 + rays * 4 * (size_t)lights + (tiles ? rays * 12 + packets * 8 + 256 : 0) + (refl ? rays * (36 + 12 + 12) + packets * 64 : 0) + 256;
+			return rays * 12 + rays * 4 * (size_t)lights + (tiles ? rays * 12 + packets * 8 + 256 + packets * 16 + 256 : 0) + (refl ? rays * (36 + 12 + 12) + packets * 64 : 0) + 256;
 		}
 		void carve(char *base, size_t packets, int lights, bool refl, bool tiles = false) {
 			const size_t rays = packets * 256;
 			if(tiles) { // (first: 16-byte aligned whatever follows)
 				col = (float *)base; base += rays * 12;
 				xy2 = (int32_t *)base; base += (packets * 8 + 255) & ~(size_t)255;
+				pstats = (uint32_t *)base; base += (packets * 16 + 255) & ~(size_t)255;
 			}
 			hitT = (float *)base; base += rays * 4;
 			hitInst = (int *)base; base += rays * 4;
@@ -312,7 +314,9 @@ int checkShadeArgs(const char *fn, const float cam[13], int resx, int resy, cons
 // the stages of one lit frame over the packet list dXY into `frame` (or packet-major `bgrPackets`), intermediates in W; mu held
 int instancesShade(SnailInstances *h, const char *fn, const float cam[13], int resx, int resy, const int32_t *dXY, int np, const float *lights7, int nLights,
 				   const float ambient[3], const float color[3], bool refl, uint8_t *frame, int pitch, uint8_t *bgrPackets, const SnailInstances::ShadeBufs &W,
-				   uint64_t *dStats, hipStream_t st, float *colPackets = nullptr) {
+				   uint64_t *dStats, hipStream_t st, float *colPackets = nullptr, uint32_t *pstats = nullptr) {
+	// pstats (a heat-map launch, heatmap_host.inc): every walking stage also books its counters per packet there (cleared by the caller) and the stages that
+	// only make colours -- k_inst_final<.., DST_COLOR / DST_FRAME> -- are left out: the caller stores the counters' colours instead
 	dev::InstArgs I;
 	bool sse, deep;
 	if(int rc = instancesBegin(h, fn, I, &sse, &deep, st)) return rc;
@@ -324,6 +328,7 @@ int instancesShade(SnailInstances *h, const char *fn, const float cam[13], int r
 	P.packetXY = (const int2 *)dXY; P.nPackets = np;
 	P.t = W.hitT; P.instOut = W.hitInst; P.triOut = W.hitTri;
 	P.stats = (dev::u64 *)dStats;
+	P.pstats = pstats;
 	if(deep) SNAIL_INST_LAUNCH(sse, grid, st, P, k_inst_frame<true>);
 	else SNAIL_INST_LAUNCH(sse, grid, st, P, k_inst_frame<false>);
 
@@ -344,6 +349,7 @@ int instancesShade(SnailInstances *h, const char *fn, const float cam[13], int r
 	A.s.sDist = W.sDist;
 	A.s.blend = refl ? 1 : 0;
 	A.s.stats = (dev::u64 *)dStats;
+	A.s.pstats = pstats;
 	const dim3 lgrid(np, nLights > 0 ? nLights : 1);
 	if(refl) { // the nested RayTrace of the mirrored packets
 		SNAIL_INST_SHADE_LAUNCH(sse, grid, st, A, k_inst_final<dev::SRC_PRIMARY, dev::DST_MIRROR>);
@@ -352,19 +358,29 @@ int instancesShade(SnailInstances *h, const char *fn, const float cam[13], int r
 		R.origin = W.rOrg; R.dir = W.rDir; R.idir = W.rIDir; R.mask = W.rMask;
 		R.distance = W.rDist; R.object = W.rInst; R.element = W.rTri;
 		R.stats = (dev::u64 *)dStats;
-		if(deep) SNAIL_INST_LAUNCH(sse, grid, st, R, k_inst_trace<false, true, true, false>);
+		R.pstats = pstats;
+		if(pstats) {
+			if(deep) SNAIL_INST_LAUNCH(sse, grid, st, R, k_inst_trace<false, true, true, false, true>);
+			else SNAIL_INST_LAUNCH(sse, grid, st, R, k_inst_trace<false, true, false, false, true>);
+		} else if(deep) SNAIL_INST_LAUNCH(sse, grid, st, R, k_inst_trace<false, true, true, false>);
 		else SNAIL_INST_LAUNCH(sse, grid, st, R, k_inst_trace<false, true, false, false>);
-		if(nLights) {
+		if(nLights && pstats) {
+			if(deep) SNAIL_INST_SHADE_LAUNCH(sse, lgrid, st, A, k_inst_light<true, dev::SRC_MIRROR, true>);
+			else SNAIL_INST_SHADE_LAUNCH(sse, lgrid, st, A, k_inst_light<false, dev::SRC_MIRROR, true>);
+		} else if(nLights) {
 			if(deep) SNAIL_INST_SHADE_LAUNCH(sse, lgrid, st, A, k_inst_light<true, dev::SRC_MIRROR>);
 			else SNAIL_INST_SHADE_LAUNCH(sse, lgrid, st, A, k_inst_light<false, dev::SRC_MIRROR>);
 		}
-		SNAIL_INST_SHADE_LAUNCH(sse, grid, st, A, k_inst_final<dev::SRC_MIRROR, dev::DST_COLOR>);
+		if(!pstats) SNAIL_INST_SHADE_LAUNCH(sse, grid, st, A, k_inst_final<dev::SRC_MIRROR, dev::DST_COLOR>);
 	}
-	if(nLights) {
+	if(nLights && pstats) {
+		if(deep) SNAIL_INST_SHADE_LAUNCH(sse, lgrid, st, A, k_inst_light<true, dev::SRC_PRIMARY, true>);
+		else SNAIL_INST_SHADE_LAUNCH(sse, lgrid, st, A, k_inst_light<false, dev::SRC_PRIMARY, true>);
+	} else if(nLights) {
 		if(deep) SNAIL_INST_SHADE_LAUNCH(sse, lgrid, st, A, k_inst_light<true, dev::SRC_PRIMARY>);
 		else SNAIL_INST_SHADE_LAUNCH(sse, lgrid, st, A, k_inst_light<false, dev::SRC_PRIMARY>);
 	}
-	SNAIL_INST_SHADE_LAUNCH(sse, grid, st, A, k_inst_final<dev::SRC_PRIMARY, dev::DST_FRAME>);
+	if(!pstats) SNAIL_INST_SHADE_LAUNCH(sse, grid, st, A, k_inst_final<dev::SRC_PRIMARY, dev::DST_FRAME>);
 	return instancesEnd(h, st);
 }
 

@@ -89,7 +89,7 @@ __device__ __forceinline__ void instLoadSamples(const InstShadeArgs &A, const Pa
 }
 
 // ---- one (packet, light): the shadow packet (src/scene_trace.cpp:538-558) and DBVH::TraverseShadow ----
-template <bool DEEP, int SRC>
+template <bool DEEP, int SRC, bool PSTATS = false>
 __global__ __launch_bounds__(64) void k_inst_light(InstShadeArgs A) {
 	__shared__ float lds[LDS_FLOATS_PER_WAVE];
 	const int lane = threadIdx.x & 63;
@@ -127,6 +127,7 @@ __global__ __launch_bounds__(64) void k_inst_light(InstShadeArgs A) {
 	Counters st = {0, 0, 0, 0, 0};
 	instWalk<true, false, true, false, DEEP>(A.i, 64, lane, lorg, Q.d, Q.id, 15u, Q.dist, obj, elem, bu, bv, lds, st);
 	flushStats(A.s.stats, st, rays, lane);
+	if(PSTATS) bookPacket(A.s.pstats, P.pidx, st, rays, lane);   // (a culled light has returned above: it books nothing)
 	*(float4 *)(A.s.sDist + ((size_t)n * (size_t)A.s.nPackets + P.pidx) * 256 + (size_t)lane * 4) = make_float4(Q.dist[0], Q.dist[1], Q.dist[2], Q.dist[3]);
 }
 
@@ -177,6 +178,7 @@ __global__ __launch_bounds__(64) void k_inst_final(InstShadeArgs A) {
 		for(int l = 0; l < 4; l++) cnt += (unsigned)__builtin_popcountll(__builtin_amdgcn_ballot_w64(S.hit[l]));
 		const Counters none = {0, 0, 0, 0, 0};
 		flushStats(A.s.stats, none, cnt, lane);
+		bookPacket(A.s.pstats, P.pidx, none, cnt, lane);
 		return;
 	}
 	if(DST == DST_FRAME || DST == DST_COLOR) {

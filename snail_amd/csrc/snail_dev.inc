@@ -1505,6 +1505,18 @@ __device__ __forceinline__ void flushStats(u64 *stats, const Counters &st, unsig
 		atomicAdd(&stats[3], (u64)st.skips);
 	}
 }
+// Per-packet TreeStats (include/snail_heatmap.h): the same counters once more, into the four words {intersects, iterations, rays, skips} of the
+// packet the wave works for -- `packet` is the packet's index in the intermediates (list position, or cy * pw + cx), never the block's.  Atomic:
+// the shadow packets of several lights of one packet may be in flight together.  Only the PSTATS instantiations of the kernels call it.
+__device__ __forceinline__ void bookPacket(unsigned *pstats, size_t packet, const Counters &st, unsigned rays, int lane) {
+	if(pstats && lane == 0) {
+		unsigned *w = pstats + packet * 4;
+		atomicAdd(&w[0], st.intersects);
+		atomicAdd(&w[1], st.iters);
+		atomicAdd(&w[2], rays);
+		atomicAdd(&w[3], st.skips);
+	}
+}
 
 // Trunc(Clamp(c * 255, 0, 255)) of ConvColor (src/render.cpp:11-17); Clamp = Min(Max(v, lo), hi), veclib/vecbase.h:75-77
 __device__ __forceinline__ int convChannelW(float c) {
@@ -1512,6 +1524,16 @@ __device__ __forceinline__ int convChannelW(float c) {
 	v = v > 0.0f ? v : 0.0f;
 	v = v < 255.0f ? v : 255.0f;
 	return (int)v;
+}
+
+// ... with the array's address read where it is used, through an opaque copy of the kernel-argument pointer (ARGS = the kernel's ONE by-value argument,
+// at offset 0 of the segment; as lateArgs() of the primary kernel): read from the argument record itself, the address is loaded at the top of the kernel
+// and an SGPR pair more stays live across the walk -- spilled, in the deferred passes, for a feature most launches do not use
+template <class ARGS>
+__device__ __forceinline__ void bookPacketLate(size_t packet, const Counters &st, unsigned rays, int lane) {
+	const ARGS __attribute__((address_space(4))) *E = (const ARGS __attribute__((address_space(4))) *)__builtin_amdgcn_kernarg_segment_ptr();
+	asm volatile("" : "+s"(E));
+	bookPacket(E->pstats, packet, st, rays, lane);
 }
 
 // ---- primary kernel: RayGenerator::Generate + SafeInv + TraversePrimary<1,0> ----------------------
@@ -1551,6 +1573,7 @@ struct PrimaryArgs {
 	int *defer;		// [0] = count, [1] = finished blocks of the M_EXACT pass, [2..] = frame * nSlots + logical index of deferred packets
 	int *nextOrder; // out or null: the NEXT dispatch order, derived from slotCost by the last workgroup of the deferred-packet launch (orderSortBlock; that launch then has 256-thread blocks)
 	int nextOrderFlags; // SNAIL_ORDER_* of the caller (include/snail_hip.h)
+	unsigned *pstats;   // per-packet TreeStats [nPackets][4] (bookPacket; frame 0 only) or null
 };
 
 typedef const PrimaryArgs __attribute__((address_space(4))) *PrimaryArgsK;
@@ -1581,7 +1604,9 @@ __device__ __forceinline__ int interleave16(int b) { // -> logical index; 16 con
 // a packet that needs M_EXACT (a non-finite reciprocal: practically never for camera rays) is appended to A.defer and
 // left to the second, tiny kernel (EXACTPASS=true).  Keeping the select-based M_EXACT walk out of the main kernel
 // takes its register allocation from 128 to 84-96 VGPRs, i.e. from 4 to 5 waves per SIMD.
-template <bool DEEP, bool EXACTPASS, bool DIAG = false>
+// PSTATS (here and in the light and generic-packet kernels): the heat-map launches' instantiation, which also books the packet's counters per packet
+// (bookPacket).  A template argument, not a null test: the other launches' kernels stay the code they were, register for register.
+template <bool DEEP, bool EXACTPASS, bool DIAG = false, bool PSTATS = false>
 __device__ __forceinline__ void primaryPacket(const PrimaryArgs &A, const int li, const int fi, float *lds) {
 	const int lane = threadIdx.x & 63;
 	const GenConst &G = A.g[fi];
@@ -1686,6 +1711,7 @@ __device__ __forceinline__ void primaryPacket(const PrimaryArgs &A, const int li
 	if(F->u || F->v) finalBarycentrics(E->tris, org, Q, tid, bu, bv); // (the staged shading pipeline asks for t and triId only)
 
 	flushStats(E->stats, st, 256u, lane);
+	if(PSTATS && fi == 0) bookPacket(E->pstats, (size_t)pidx, st, 256u, lane);
 	if(E->slotCost && fi == 0 && lane == 0) E->slotCost[li] = (int)st.iters;
 	if(DIAG && E->cost && lane == 0) {
 		const u64 tEnd = __builtin_amdgcn_s_memtime();
@@ -1744,7 +1770,7 @@ __device__ __forceinline__ void primaryPacket(const PrimaryArgs &A, const int li
 // back to back on ONE XCD, whose L2 then fetches their lines once, and XCD group g keeps its own region set g of interleave16.  F = 1: rank B.
 // (Frame-minor -- frame B % F at rank B / F: the copies of a rank on F different XCDs, each XCD tied to frame g % F -- was measured and lost:
 // profiles/xcd_ab.txt, DESIGN.md section 2.)
-template <bool DEEP>
+template <bool DEEP, bool PSTATS = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SNAIL_PRIMARY_WAVES))) void k_primary(PrimaryArgs A) {
 	__shared__ float lds[LDS_FLOATS_PER_WAVE];
 	int b = (int)blockIdx.x; // dispatch index of this block's packet
@@ -1763,7 +1789,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SNAIL_PRIMAR
 		// when the order is exact and costs 6-10 % when it is a stale prediction (a turning camera): the wrong packets outrank the heavy ones.
 		// profiles/r5_prio_and_order.txt)
 	}
-	primaryPacket<DEEP, false>(A, li, fi, lds);
+	primaryPacket<DEEP, false, false, PSTATS>(A, li, fi, lds);
 }
 // the diagnostic build of the same packet code (snail_account_packets): per-packet cost records; never on a product path
 template <bool DEEP>
@@ -1972,7 +1998,7 @@ __device__ __forceinline__ bool exactPassSortOrIdle(const int *slotCost, int nSl
 	if((int)blockIdx.x == *blocks) { orderSortBlock(slotCost, nSlots, nextOrder, nextOrderFlags); return true; }
 	return threadIdx.x >= 64;
 }
-template <bool DEEP>
+template <bool DEEP, bool PSTATS = false>
 __global__ __launch_bounds__(ORDER_THREADS_LDS) void k_primary_exact(PrimaryArgs A) {
 	__shared__ float lds[LDS_FLOATS_PER_WAVE];
 	int blocks;
@@ -1981,7 +2007,7 @@ __global__ __launch_bounds__(ORDER_THREADS_LDS) void k_primary_exact(PrimaryArgs
 	if(n == 0) return; // nothing was deferred (the rule): the list is armed as it stands, no fence, no counter
 	for(int i = (int)blockIdx.x; i < n; i += blocks) {
 		const int e = __builtin_amdgcn_readfirstlane(A.defer[2 + i]);
-		primaryPacket<DEEP, true>(A, e % A.nSlots, e / A.nSlots, lds);
+		primaryPacket<DEEP, true, false, PSTATS>(A, e % A.nSlots, e / A.nSlots, lds);
 	}
 	__threadfence();
 	if((threadIdx.x & 63) == 0 && atomicAdd(&A.defer[1], 1) == blocks - 1) { A.defer[0] = 0; A.defer[1] = 0; }
@@ -2060,6 +2086,7 @@ struct ShadeArgs {
 	int nSlots;
 	int *nextOrder; // as PrimaryArgs::nextOrder (k_light_exact)
 	int nextOrderFlags;
+	unsigned *pstats; // per-packet TreeStats [nPackets][4] (bookPacket) or null
 };
 
 
@@ -2338,7 +2365,7 @@ __device__ __forceinline__ void shadeAndStore(const ShadeArgs &A, const PacketPo
 // never) is appended to A.defer untouched -- nothing has been written or counted for it -- and traced by the second, tiny
 // launch (EXACTPASS=true; M_EXACT is valid for any packet).  As in the primary kernel this keeps the select-based walk out
 // of the main kernel's register allocation.
-template <bool DEEP, int SRC, bool EXACTPASS>
+template <bool DEEP, int SRC, bool EXACTPASS, bool PSTATS = false>
 __device__ __forceinline__ void lightPacket(const ShadeArgs &A, const int li, const int n, float *lds) {
 	const int lane = threadIdx.x & 63;
 	const PacketPos P = packetOf(A, li);
@@ -2433,6 +2460,7 @@ __device__ __forceinline__ void lightPacket(const ShadeArgs &A, const int li, co
 		else walkSharedAsm<true, false, false, false, false, false>(A.nodes, A.tris, 64, lane, lorg, Q, 15u, stid, bu, bv, lds, st, 0);
 	}
 	flushStats(A.stats, st, rays, lane);
+	if(PSTATS) bookPacketLate<ShadeArgs>(P.pidx, st, rays, lane);
 	if(wantCost()) A.slotCost[li] = (int)st.iters;
 	} // !culled
 	if(A.fuse) { // the only light: the tail of Scene::TraceLight and the packet's colour, here (the samples are derived again: same operations, same bits)
@@ -2453,14 +2481,14 @@ __device__ __forceinline__ void lightPacket(const ShadeArgs &A, const int li, co
 #ifndef SNAIL_LIGHT_WAVES
 #define SNAIL_LIGHT_WAVES 6 // occupancy target of k_light (80 VGPRs; what does not fit is spilled around the walk, not inside it: tests/test_host_side.py budget)
 #endif
-template <bool DEEP, int SRC>
+template <bool DEEP, int SRC, bool PSTATS = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SNAIL_LIGHT_WAVES))) void k_light(ShadeArgs A) {
 	__shared__ float lds[LDS_FLOATS_PER_WAVE];
 	int li = interleave16((int)blockIdx.x);
 	if(A.order) { li = orderedSlot(A.order, A.nSlots, (int)blockIdx.x); if(li < 0) return; }
-	lightPacket<DEEP, SRC, false>(A, li, (int)blockIdx.y, lds);
+	lightPacket<DEEP, SRC, false, PSTATS>(A, li, (int)blockIdx.y, lds);
 }
-template <bool DEEP, int SRC>
+template <bool DEEP, int SRC, bool PSTATS = false>
 __global__ __launch_bounds__(ORDER_THREADS_LDS) void k_light_exact(ShadeArgs A) {
 	__shared__ float lds[LDS_FLOATS_PER_WAVE];
 	int blocks;
@@ -2469,14 +2497,14 @@ __global__ __launch_bounds__(ORDER_THREADS_LDS) void k_light_exact(ShadeArgs A) 
 	if(cnt == 0) return;
 	for(int i = (int)blockIdx.x; i < cnt; i += blocks) {
 		const int e = __builtin_amdgcn_readfirstlane(A.defer[16 + i]);
-		lightPacket<DEEP, SRC, true>(A, e % A.nBlocks, e / A.nBlocks, lds);
+		lightPacket<DEEP, SRC, true, PSTATS>(A, e % A.nBlocks, e / A.nBlocks, lds);
 	}
 	__threadfence();
 	if((threadIdx.x & 63) == 0 && atomicAdd(&A.defer[1], 1) == blocks - 1) { A.defer[0] = 0; A.defer[1] = 0; }
 }
 
 // ---- one packet: samples -> mirrored rays (DST_MIRROR), or samples + the lights' contributions -> colour ----
-template <int SRC, int DST>
+template <int SRC, int DST, bool PSTATS = false>
 __global__ __launch_bounds__(64) void k_final(ShadeArgs A) {
 	const int lane = threadIdx.x & 63;
 	const PacketPos P = packetOf(A, interleave16((int)blockIdx.x));
@@ -2582,6 +2610,7 @@ __global__ __launch_bounds__(64) void k_final(ShadeArgs A) {
 		for(int l = 0; l < 4; l++) cnt += (unsigned)__builtin_popcountll(__builtin_amdgcn_ballot_w64(S.hit[l]));
 		const Counters none = {0, 0, 0, 0, 0};
 		flushStats(A.stats, none, cnt, lane);
+		if(PSTATS) bookPacketLate<ShadeArgs>(P.pidx, none, cnt, lane);
 		return;
 	}
 
@@ -2648,6 +2677,7 @@ struct RaysArgs {
 	int nSlots;     // entries of order / slotCost (>= nPackets; the grid holds at least this many blocks)
 	int *nextOrder; // as PrimaryArgs::nextOrder (k_rays_exact)
 	int nextOrderFlags;
+	unsigned *pstats; // per-packet TreeStats [nPackets][4] (bookPacket; k_rays only) or null
 };
 
 
@@ -2655,7 +2685,7 @@ struct RaysArgs {
 // One wave per block (packet costs are heavy-tailed, see k_primary), blocks dealt to the XCDs 16 consecutive packets at a time.
 // EXACTPASS as in the primary kernel: the main launch walks in M_COH / M_FAST and appends a packet that needs M_EXACT to A.defer
 // untouched (its distances / objects in memory are still the caller's); the second, small launch walks those in M_EXACT.
-template <bool SHARED, bool MASK, bool DEEP, bool BARY, bool EXACTPASS>
+template <bool SHARED, bool MASK, bool DEEP, bool BARY, bool EXACTPASS, bool PSTATS = false>
 __device__ __forceinline__ void raysPacket(const RaysArgs &A, const int p, float *lds) {
 	const int lane = threadIdx.x & 63;
 	if(p >= A.nPackets) {
@@ -2715,6 +2745,7 @@ __device__ __forceinline__ void raysPacket(const RaysArgs &A, const int p, float
 		else walk<SHARED, MASK, false, M_FAST, BARY, DEEP, false>(A.nodes, A.tris, size, lane, org, Q, mask4, tid, bu, bv, lds, st);
 	}
 	flushStats(A.stats, st, 0u, lane);
+	if(PSTATS) bookPacketLate<RaysArgs>((size_t)p, st, 0u, lane);
 	if(!EXACTPASS && A.slotCost && lane == 0) A.slotCost[p] = (int)st.iters;
 
 	if(live) {
@@ -2735,21 +2766,21 @@ __device__ __forceinline__ void raysPacket(const RaysArgs &A, const int p, float
 #else
 #define SNAIL_RAYS_OCCUPANCY
 #endif
-template <bool SHARED, bool MASK, bool DEEP, bool BARY>
+template <bool SHARED, bool MASK, bool DEEP, bool BARY, bool PSTATS = false>
 __global__ __launch_bounds__(64) SNAIL_RAYS_OCCUPANCY void k_rays(RaysArgs A) {
 	__shared__ float lds[LDS_FLOATS_PER_WAVE];
 	int p = interleave16((int)blockIdx.x);
 	if(A.order) { p = orderedSlot(A.order, A.nSlots, (int)blockIdx.x); if(p < 0) return; }
-	raysPacket<SHARED, MASK, DEEP, BARY, false>(A, p, lds);
+	raysPacket<SHARED, MASK, DEEP, BARY, false, PSTATS>(A, p, lds);
 }
-template <bool SHARED, bool MASK, bool DEEP, bool BARY>
+template <bool SHARED, bool MASK, bool DEEP, bool BARY, bool PSTATS = false>
 __global__ __launch_bounds__(ORDER_THREADS_LDS) void k_rays_exact(RaysArgs A) {
 	__shared__ float lds[LDS_FLOATS_PER_WAVE];
 	int blocks;
 	if(exactPassSortOrIdle(A.slotCost, A.nSlots, A.nextOrder, A.nextOrderFlags, &blocks)) return;
 	const int n = __builtin_amdgcn_readfirstlane(A.defer[0]);
 	if(n == 0) return;
-	for(int i = (int)blockIdx.x; i < n; i += blocks) raysPacket<SHARED, MASK, DEEP, BARY, true>(A, __builtin_amdgcn_readfirstlane(A.defer[16 + i]), lds);
+	for(int i = (int)blockIdx.x; i < n; i += blocks) raysPacket<SHARED, MASK, DEEP, BARY, true, PSTATS>(A, __builtin_amdgcn_readfirstlane(A.defer[16 + i]), lds);
 	__threadfence();
 	if((threadIdx.x & 63) == 0 && atomicAdd(&A.defer[1], 1) == blocks - 1) { A.defer[0] = 0; A.defer[1] = 0; }
 }

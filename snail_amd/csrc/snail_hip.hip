@@ -87,6 +87,7 @@ void snail_set_error(const char *fmt, ...) {
 #include "instances_shade.inc"
 #undef SNAIL_DEV_NS
 #undef SNAIL_ARITH_SSE
+#include "heatmap.inc"           // the heat-map store stage: plain fp32, once for both arithmetics (its C-ABI: heatmap_host.inc)
 #include "build_common.inc"      // the device builders: plain fp32, once for both arithmetics
 #include "instances_build.inc"   // ... of the top-level tree over instances (bvh_fast.inc, of a plain scene, follows lbvh.inc)
 
@@ -166,6 +167,8 @@ struct SnailScene {
 		unsigned char *rMask = nullptr;
 		int *defer = nullptr;
 		float *sDist = nullptr;
+		unsigned *pstats = nullptr;   // heat-map launches (heatmap.inc): per-packet TreeStats [packets][4] when the caller keeps none of its own ...
+		int *heatXY = nullptr;        // ... and the double-resolution packet list of an antialiased one [packets][2]
 		hipEvent_t done = nullptr;
 		bool used = false;
 	} shade[kDeferSlots];
@@ -499,7 +502,7 @@ ExactPass exactPassFor(int exactBlocks, const int32_t *dSlotCost, int nSlots, in
 
 int launchPrimaryFrames(SnailScene *s, const FrameSet &FS, int resx, int resy, int x0, int y0, int w, int h, const int32_t *dPacketXY, int nPackets, uint64_t *dStats,
 						hipStream_t stream, unsigned *dCost = nullptr, bool packetMajor = false, const int32_t *dOrder = nullptr, int32_t *dSlotCost = nullptr,
-						int32_t *dNextOrder = nullptr, int orderFlags = 0) {
+						int32_t *dNextOrder = nullptr, int orderFlags = 0, uint32_t *dPacketStats = nullptr) {
 	if(resx <= 0 || resy <= 0) { snail_set_error("snail_trace_primary: bad resolution %dx%d", resx, resy); return 1; }
 	if(dNextOrder && !dSlotCost) { snail_set_error("snail_trace_primary: the next dispatch order is derived from d_slot_cost, which is null"); return 1; }
 	if(FS.n < 1 || FS.n > SNAIL_MAX_BATCH) { snail_set_error("snail_trace_primary: 1..%d frames per launch (got %d)", SNAIL_MAX_BATCH, FS.n); return 1; }
@@ -519,6 +522,7 @@ int launchPrimaryFrames(SnailScene *s, const FrameSet &FS, int resx, int resy, i
 	A.resx = resx; A.resy = resy;
 	A.stats = (dev::u64 *)dStats;
 	A.cost = dCost;
+	A.pstats = dPacketStats;
 	A.packetMajor = packetMajor ? 1 : 0;
 	A.pack = stackPack(s);
 	int relWhich[SNAIL_MAX_BATCH];
@@ -581,6 +585,9 @@ int launchPrimaryFrames(SnailScene *s, const FrameSet &FS, int resx, int resy, i
 	if(dCost) { // diagnostic launch (snail_account_packets)
 		if(useDeep(s)) SNAIL_LAUNCH(sse, PrimaryArgs, dim3(blocks), dim3(64), 0, stream, A, k_primary_diag<true>);
 		else SNAIL_LAUNCH(sse, PrimaryArgs, dim3(blocks), dim3(64), 0, stream, A, k_primary_diag<false>);
+	} else if(A.pstats) { // a heat-map launch: the instantiation that books per packet as well
+		if(useDeep(s)) SNAIL_LAUNCH(sse, PrimaryArgs, grid, block, dynLds, stream, A, k_primary<true, true>);
+		else SNAIL_LAUNCH(sse, PrimaryArgs, grid, block, dynLds, stream, A, k_primary<false, true>);
 	} else if(useDeep(s)) SNAIL_LAUNCH(sse, PrimaryArgs, grid, block, dynLds, stream, A, k_primary<true>);
 	else SNAIL_LAUNCH(sse, PrimaryArgs, grid, block, dynLds, stream, A, k_primary<false>);
 	// workbench build, SNAIL_DEBUG_NO_EXACT_PASS=1: what the dependent second launch costs (an experiment: deferred packets are then never traced and their
@@ -588,7 +595,10 @@ int launchPrimaryFrames(SnailScene *s, const FrameSet &FS, int resx, int resy, i
 	// order sort; in the table arithmetic the list would grow frame by frame and overflow: round 5 read "2 x the frame rate" off such a run)
 	static const bool noExact = debugEnvInt("SNAIL_DEBUG_NO_EXACT_PASS") != 0;
 	if(noExact && s->arith == SNAIL_ARITH_IEEE && !EP.nextOrder && !EP.sortAfter) { }
-	else if(useDeep(s)) SNAIL_LAUNCH(sse, PrimaryArgs, EP.grid, EP.block, EP.lds, stream, A, k_primary_exact<true>);
+	else if(A.pstats) {
+		if(useDeep(s)) SNAIL_LAUNCH(sse, PrimaryArgs, EP.grid, EP.block, EP.lds, stream, A, k_primary_exact<true, true>);
+		else SNAIL_LAUNCH(sse, PrimaryArgs, EP.grid, EP.block, EP.lds, stream, A, k_primary_exact<false, true>);
+	} else if(useDeep(s)) SNAIL_LAUNCH(sse, PrimaryArgs, EP.grid, EP.block, EP.lds, stream, A, k_primary_exact<true>);
 	else SNAIL_LAUNCH(sse, PrimaryArgs, EP.grid, EP.block, EP.lds, stream, A, k_primary_exact<false>);
 	HIP_TRY(hipGetLastError());
 	if(EP.sortAfter) { if(int rc = snail_order_from_cost_hint_dev(dSlotCost, A.nSlots, dNextOrder, EP.orderFlags, stream)) return rc; }
@@ -602,11 +612,12 @@ int launchPrimaryFrames(SnailScene *s, const FrameSet &FS, int resx, int resy, i
 // one frame per launch (every entry point but the *_batch_dev ones)
 int launchPrimary(SnailScene *s, const float cam[13], int resx, int resy, int x0, int y0, int w, int h, const int32_t *dPacketXY,
 				  int nPackets, float *t, float *u, float *v, int32_t *id, uint64_t *dStats, hipStream_t stream, unsigned *dCost = nullptr,
-				  bool packetMajor = false, uint8_t *dBgr = nullptr, const int32_t *dOrder = nullptr, int32_t *dSlotCost = nullptr, int32_t *dNextOrder = nullptr, int orderFlags = 0) {
+				  bool packetMajor = false, uint8_t *dBgr = nullptr, const int32_t *dOrder = nullptr, int32_t *dSlotCost = nullptr, int32_t *dNextOrder = nullptr, int orderFlags = 0,
+				  uint32_t *dPacketStats = nullptr) {
 	FrameSet FS;
 	FS.n = 1; FS.cam[0] = cam;
 	FS.out[0].t = t; FS.out[0].u = u; FS.out[0].v = v; FS.out[0].id = (int *)id; FS.out[0].bgr = dBgr;
-	return launchPrimaryFrames(s, FS, resx, resy, x0, y0, w, h, dPacketXY, nPackets, dStats, stream, dCost, packetMajor, dOrder, dSlotCost, dNextOrder, orderFlags);
+	return launchPrimaryFrames(s, FS, resx, resy, x0, y0, w, h, dPacketXY, nPackets, dStats, stream, dCost, packetMajor, dOrder, dSlotCost, dNextOrder, orderFlags, dPacketStats);
 }
 
 // scratch of one staged frame: ONE allocation, carved (hitT is its base); grown synchronously when a larger frame or the first
@@ -620,7 +631,7 @@ int shadeScratch(SnailScene *s, SnailScene::ShadeScratch &W, size_t packets, siz
 	W.done = keep;
 	const size_t rays = packets * 256, quads = packets * 64;
 	const size_t deferInts = blocks * SNAIL_MAX_LIGHTS + 16;
-	size_t bytes = rays * 8 + deferInts * 4 + rays * 4 * SNAIL_MAX_LIGHTS; // hitT, hitId, defer list, sDist
+	size_t bytes = rays * 8 + deferInts * 4 + rays * 4 * SNAIL_MAX_LIGHTS + packets * 32; // hitT, hitId, defer list, sDist, pstats, heatXY
 	if(refl) bytes += quads * 12 * 4 * 3 + rays * 4 * 2 + rays * 12 + quads; // rOrg, rDir, rIDir; rDist, rObj; rCol; rMask
 	char *base = nullptr;
 	HIP_TRY(hipMalloc((void **)&base, bytes));
@@ -631,6 +642,8 @@ int shadeScratch(SnailScene *s, SnailScene::ShadeScratch &W, size_t packets, siz
 	HIP_TRY(hipMemset(W.defer, 0, 16 * sizeof(int)));
 	HIP_TRY(hipDeviceSynchronize());   // (ordered on the null stream only, see launchPrimaryFrames)
 	W.sDist = (float *)base; base += rays * 4 * SNAIL_MAX_LIGHTS;
+	W.pstats = (unsigned *)base; base += packets * 16;
+	W.heatXY = (int *)base; base += packets * 16;   // (8 used: what follows stays 16-byte aligned)
 	if(refl) {
 		W.rOrg = (float *)base; base += quads * 48;
 		W.rDir = (float *)base; base += quads * 48;
@@ -660,7 +673,8 @@ void launchRaysKernels(const SnailScene *s, const dev::RaysArgs &A, int blocks, 
 
 int launchRays(SnailScene *s, bool shadow, int nPackets, int size, int sharedOrigin, const float *origin, const float *dir,
 					  const float *idir, const uint8_t *mask, float *distance, int32_t *object, float *bary, uint64_t *dStats, hipStream_t stream,
-					  const int32_t *dOrder = nullptr, int32_t *dSlotCost = nullptr, int nSlots = 0, int32_t *dNextOrder = nullptr, int orderFlags = 0) {
+					  const int32_t *dOrder = nullptr, int32_t *dSlotCost = nullptr, int nSlots = 0, int32_t *dNextOrder = nullptr, int orderFlags = 0,
+					  uint32_t *dPacketStats = nullptr) {
 	if(nPackets <= 0) return 0;
 	if(size < 1 || size > SNAIL_PACKET_QUADS) { snail_set_error("packet size %d outside 1..%d quads", size, SNAIL_PACKET_QUADS); return 1; }
 	if(!origin || !dir || !idir || !distance || (!shadow && !object)) { snail_set_error("null ray array"); return 1; }
@@ -674,6 +688,7 @@ int launchRays(SnailScene *s, bool shadow, int nPackets, int size, int sharedOri
 	A.origin = origin; A.dir = dir; A.idir = idir; A.mask = mask;
 	A.distance = distance; A.object = object; A.bary = bary;
 	A.stats = (dev::u64 *)dStats;
+	A.pstats = shadow ? nullptr : dPacketStats;
 	int blocks = ((nPackets + 127) / 128) * 128;
 	if(!shadow && (dOrder || dSlotCost) && nSlots >= nPackets) { // dispatch-order feedback of the staged pipeline (k_rays): one block per slot
 		A.order = dOrder; A.slotCost = dSlotCost; A.nSlots = nSlots;
@@ -703,6 +718,16 @@ int launchRays(SnailScene *s, bool shadow, int nPackets, int size, int sharedOri
 			hipLaunchKernelGGL(dev::k_shadow<false>, dim3(blocks), dim3(64), 0, stream, A);
 			hipLaunchKernelGGL(dev::k_shadow_exact<false>, dim3(exactBlocks), dim3(64), 0, stream, A);
 		}
+	} else if(A.pstats) { // the mirrored packets of a heat-map launch (per-ray origins, masks, no barycentrics): the instantiations that book per packet as well
+		if(sharedOrigin || !mask || bary) { snail_set_error("per-packet counters: mirrored packets only"); return 1; }
+		const bool sse = s->arith == SNAIL_ARITH_HOST_SSE;
+		if(useDeep(s)) {
+			SNAIL_LAUNCH(sse, RaysArgs, dim3(blocks), dim3(64), 0, stream, A, k_rays<false, true, true, false, true>);
+			SNAIL_LAUNCH(sse, RaysArgs, EP.grid, EP.block, EP.lds, stream, A, k_rays_exact<false, true, true, false, true>);
+		} else {
+			SNAIL_LAUNCH(sse, RaysArgs, dim3(blocks), dim3(64), 0, stream, A, k_rays<false, true, false, false, true>);
+			SNAIL_LAUNCH(sse, RaysArgs, EP.grid, EP.block, EP.lds, stream, A, k_rays_exact<false, true, false, false, true>);
+		}
 	} else if(sharedOrigin && mask) launchRaysKernels<true, true>(s, A, blocks, EP, stream);
 	else if(sharedOrigin) launchRaysKernels<true, false>(s, A, blocks, EP, stream);
 	else if(mask) launchRaysKernels<false, true>(s, A, blocks, EP, stream);
@@ -730,7 +755,15 @@ int launchLights(SnailScene *s, dev::ShadeArgs A /* a copy: relLight is filled i
 	const bool sse = s->arith == SNAIL_ARITH_HOST_SSE;
 	const ExactPass EP = exactPassFor(exactBlocks, A.slotCost, A.nSlots, dNextOrder, orderFlags);
 	A.nextOrder = EP.nextOrder; A.nextOrderFlags = EP.orderFlags;
-	if(useDeep(s)) {
+	if(A.pstats) { // a heat-map launch
+		if(useDeep(s)) {
+			SNAIL_LAUNCH(sse, ShadeArgs, grid, dim3(64), 0, stream, A, k_light<true, SRC, true>);
+			SNAIL_LAUNCH(sse, ShadeArgs, EP.grid, EP.block, EP.lds, stream, A, k_light_exact<true, SRC, true>);
+		} else {
+			SNAIL_LAUNCH(sse, ShadeArgs, grid, dim3(64), 0, stream, A, k_light<false, SRC, true>);
+			SNAIL_LAUNCH(sse, ShadeArgs, EP.grid, EP.block, EP.lds, stream, A, k_light_exact<false, SRC, true>);
+		}
+	} else if(useDeep(s)) {
 		SNAIL_LAUNCH(sse, ShadeArgs, grid, dim3(64), 0, stream, A, k_light<true, SRC>);
 		SNAIL_LAUNCH(sse, ShadeArgs, EP.grid, EP.block, EP.lds, stream, A, k_light_exact<true, SRC>);
 	} else {
@@ -1252,19 +1285,35 @@ int snail_trace_shadow(SnailScene *s, int nPackets, int size, const float *origi
 	return hc.finish(stats);
 }
 
+// What a heat-map launch (include/snail_heatmap.h; heatmap.inc) asks of renderWhitted instead of colours: the per-packet TreeStats of the frame's
+// RayTrace calls, and optionally their colours as packet-major bytes.
+struct HeatOut {
+	uint32_t *dPacketStats = nullptr;   // the caller's [packets][4] (antialiased: [nPackets][4][4]) or null: the launch's own scratch
+	uint8_t *dBgr = nullptr;            // packet-major B,G,R [nPackets][256][3] or null (counters only)
+	bool aa = false;                    // SNAIL_RENDER_AA4: the list's (or grid's) packets are traced as their four double-resolution packets
+};
 static int renderWhitted(const char *fn, SnailScene *s, const float cam[13], int resx, int resy, const int32_t *dPacketXY, int nPacketsList, const float *lights7,
 						 int nLights, const float ambient[3], const float color[3], int flags, uint8_t *frame, int pitch, uint8_t *bgrPackets, uint64_t *dStats,
-						 void *stream, float *colPackets = nullptr, const int32_t *dOrder = nullptr, int32_t *dSlotCost = nullptr, int32_t *dNextOrder = nullptr, int orderFlags = 0) {
+						 void *stream, float *colPackets = nullptr, const int32_t *dOrder = nullptr, int32_t *dSlotCost = nullptr, int32_t *dNextOrder = nullptr, int orderFlags = 0,
+						 const HeatOut *heat = nullptr) {
 	if(int rc = checkScene(s, fn)) return rc;
 	if(dNextOrder && !dSlotCost) { snail_set_error("%s: the next dispatch orders are derived from d_slot_cost, which is null", fn); return 1; }
 	if(resx <= 0 || resy <= 0 || nLights < 0 || nLights > SNAIL_MAX_LIGHTS || (nLights && !lights7) || !ambient || !color || (flags & ~SNAIL_WHITTED_REFLECTIONS) ||
-	   (dPacketXY ? (colPackets ? false : (!bgrPackets || ((unsigned long long)bgrPackets & 3))) : (!frame || pitch < resx * 3 || colPackets))) {
+	   (heat ? (frame || bgrPackets || colPackets || dOrder || dSlotCost) :
+	    dPacketXY ? (colPackets ? false : (!bgrPackets || ((unsigned long long)bgrPackets & 3))) : (!frame || pitch < resx * 3 || colPackets))) {
 		snail_set_error("%s: bad arguments (at most %d lights; flags = SNAIL_WHITTED_REFLECTIONS or 0; 4-byte aligned output)", fn, SNAIL_MAX_LIGHTS);
 		return 1;
 	}
 	if(dPacketXY && nPacketsList <= 0) return 0;
 	DeviceGuard guard(s->device);
 	const bool refl = (flags & SNAIL_WHITTED_REFLECTIONS) != 0;
+	// an antialiased heat-map launch: the frame is the double-resolution one, its packets the four sub-packets of every packet of the caller's list / grid
+	const int nHeatBase = heat ? (dPacketXY ? nPacketsList : ((resx + 15) / 16) * ((resy + 15) / 16)) : 0;
+	const int basePw = (resx + 15) / 16;
+	if(heat && heat->aa) {
+		if(nHeatBase > 0x7fffffff / 4) { snail_set_error("%s: too many packets for 4x antialiasing", fn); return 1; }
+		resx *= 2; resy *= 2;
+	}
 	SceneUse use(s, (hipStream_t)stream);
 	if(use.rc) return use.rc;
 	dev::ShadeArgs A;
@@ -1281,7 +1330,10 @@ static int renderWhitted(const char *fn, SnailScene *s, const float cam[13], int
 	A.frame = frame; A.pitch = pitch; A.stats = (dev::u64 *)dStats;
 	A.packetXY = (const int2 *)dPacketXY; A.bgrPackets = bgrPackets; A.colPackets = colPackets;
 	int packets, blocks;
-	if(dPacketXY) {
+	if(heat && heat->aa) {
+		packets = nHeatBase * 4;
+		blocks = ((packets + 127) / 128) * 128;
+	} else if(dPacketXY) {
 		packets = nPacketsList;
 		blocks = ((packets + 127) / 128) * 128;
 	} else {
@@ -1291,7 +1343,7 @@ static int renderWhitted(const char *fn, SnailScene *s, const float cam[13], int
 	}
 	A.nPackets = packets;
 	A.nBlocks = blocks;
-	A.fuse = nLights == 1 ? 1 : 0;   // one light: its k_light waves finish the packets themselves (no sDist round trip, no k_final launch)
+	A.fuse = nLights == 1 && !heat ? 1 : 0;   // one light: its k_light waves finish the packets themselves (no sDist round trip, no k_final launch)
 	// dispatch-order feedback, frame grid only: SNAIL_WHITTED_STAGES arrays of `blocks` entries, back to back -- the primary packets, the shadow
 	// packets of the primary hits (first light), the mirrored packets, the shadow packets of the mirrored hits (include/snail_hip.h)
 	const int32_t *ord[SNAIL_WHITTED_STAGES] = {};
@@ -1313,22 +1365,42 @@ static int renderWhitted(const char *fn, SnailScene *s, const float cam[13], int
 	const hipStream_t st = (hipStream_t)stream;
 	const dim3 grid(blocks), wave(64);
 	const bool sse = s->arith == SNAIL_ARITH_HOST_SSE;
+	uint32_t *pst = nullptr;
+	if(heat) { // the launch set's per-packet counters, cleared on its stream; an antialiased launch walks the double-resolution list made here
+		pst = heat->dPacketStats ? heat->dPacketStats : W.pstats;
+		A.pstats = pst;
+		HIP_TRY(hipMemsetAsync(pst, 0, (size_t)packets * 16, st));
+		if(heat->aa) {
+			hipLaunchKernelGGL(dev_heat::k_heat_aa_packets, dim3((unsigned)((packets + 255) / 256)), dim3(256), 0, st, (const int2 *)dPacketXY, basePw, nHeatBase, (int2 *)W.heatXY);
+			HIP_TRY(hipGetLastError());
+			dPacketXY = W.heatXY;
+			A.packetXY = (const int2 *)dPacketXY;
+		}
+	}
 	// the primary packets (the bench kernel), hit records packet-major
 	if(dPacketXY) {
-		if(int rc = launchPrimary(s, cam, resx, resy, 0, 0, 0, 0, dPacketXY, packets, W.hitT, nullptr, nullptr, W.hitId, dStats, st)) return rc;
-	} else if(int rc = launchPrimary(s, cam, resx, resy, 0, 0, resx, resy, nullptr, 0, W.hitT, nullptr, nullptr, W.hitId, dStats, st, nullptr, true, nullptr, ord[0], cst[0], nxt[0], orderFlags)) return rc;
+		if(int rc = launchPrimary(s, cam, resx, resy, 0, 0, 0, 0, dPacketXY, packets, W.hitT, nullptr, nullptr, W.hitId, dStats, st, nullptr, false, nullptr, nullptr, nullptr, nullptr, 0, pst)) return rc;
+	} else if(int rc = launchPrimary(s, cam, resx, resy, 0, 0, resx, resy, nullptr, 0, W.hitT, nullptr, nullptr, W.hitId, dStats, st, nullptr, true, nullptr, ord[0], cst[0], nxt[0], orderFlags, pst)) return rc;
 	if(refl) { // the nested RayTrace of the mirrored packets
-		SNAIL_LAUNCH(sse, ShadeArgs, grid, wave, 0, st, A, k_final<dev::SRC_PRIMARY, dev::DST_MIRROR>);
+		if(heat) SNAIL_LAUNCH(sse, ShadeArgs, grid, wave, 0, st, A, k_final<dev::SRC_PRIMARY, dev::DST_MIRROR, true>);
+		else SNAIL_LAUNCH(sse, ShadeArgs, grid, wave, 0, st, A, k_final<dev::SRC_PRIMARY, dev::DST_MIRROR>);
 		HIP_TRY(hipGetLastError());
-		if(int rc = launchRays(s, false, packets, 64, 0, W.rOrg, W.rDir, W.rIDir, W.rMask, W.rDist, W.rObj, nullptr, dStats, st, ord[2], cst[2], dPacketXY ? 0 : blocks, nxt[2], orderFlags)) return rc;
+		if(int rc = launchRays(s, false, packets, 64, 0, W.rOrg, W.rDir, W.rIDir, W.rMask, W.rDist, W.rObj, nullptr, dStats, st, ord[2], cst[2], dPacketXY ? 0 : blocks, nxt[2], orderFlags, pst)) return rc;
 		A.order = ord[3]; A.slotCost = cst[3]; A.nSlots = blocks;
 		if(int rc = launchLights<dev::SRC_MIRROR>(s, A, st, nxt[3], orderFlags)) return rc;
-		if(!A.fuse) SNAIL_LAUNCH(sse, ShadeArgs, grid, wave, 0, st, A, k_final<dev::SRC_MIRROR, dev::DST_COLOR>);
+		if(!A.fuse && !heat) SNAIL_LAUNCH(sse, ShadeArgs, grid, wave, 0, st, A, k_final<dev::SRC_MIRROR, dev::DST_COLOR>);
 		HIP_TRY(hipGetLastError());
 	}
 	A.order = ord[1]; A.slotCost = cst[1]; A.nSlots = blocks;
 	if(int rc = launchLights<dev::SRC_PRIMARY>(s, A, st, nxt[1], orderFlags)) return rc;
-	if(!A.fuse) SNAIL_LAUNCH(sse, ShadeArgs, grid, wave, 0, st, A, k_final<dev::SRC_PRIMARY, dev::DST_FRAME>);
+	// a heat-map launch has walked everything the lit frame walks; no stage of it needs a colour (the mirrored packets' and the frame's k_final are
+	// stores only), so those are left out and the counters' colours stored instead
+	if(heat) {
+		if(heat->dBgr) {
+			if(heat->aa) hipLaunchKernelGGL(dev_heat::k_heat_store<true>, dim3((unsigned)nHeatBase), wave, 0, st, (const unsigned *)pst, nHeatBase, heat->dBgr);
+			else hipLaunchKernelGGL(dev_heat::k_heat_store<false>, dim3((unsigned)nHeatBase), wave, 0, st, (const unsigned *)pst, nHeatBase, heat->dBgr);
+		}
+	} else if(!A.fuse) SNAIL_LAUNCH(sse, ShadeArgs, grid, wave, 0, st, A, k_final<dev::SRC_PRIMARY, dev::DST_FRAME>);
 	HIP_TRY(hipGetLastError());
 	HIP_TRY(hipEventRecord(W.done, st));
 	W.used = true;
@@ -1659,3 +1731,4 @@ int snail_account_primary(SnailScene *s, const float cam[13], int resx, int resy
 #include "render_host.inc"
 #include "instances_host.inc"
 #include "instances_tiles_host.inc"
+#include "heatmap_host.inc"

@@ -356,6 +356,62 @@ class InstancedScene:
         _lib.check(rc, "snail_instances_render_frame")
         return img, stats
 
+    # ---- include/snail_heatmap.h: per-packet TreeStats and the reference's gVals[5] heat-map ------------------------------------------
+    def _heat_args(self, cam, lights7, tint):
+        lights, cam13, _, _, tnt = self._shade_args(cam, lights7, (0, 0, 0), (0, 0, 0), tint)
+        return lights, (_lib.ptr(lights) if len(lights) else None), cam13, tnt
+
+    def packet_stats(self, cam, resx: int, resy: int, packet_xy=None, lights7=None, reflections: bool = False, out=None, stats=None, stream=None, flags: int = 0):
+        """snail_instances_packet_stats_dev: the TreeStats {intersects, iterations, rays, skips} of every packet's RayTrace call as an int32
+        device tensor [n, 4] holding uint32 words.  packet_xy = int32 device tensor [n, 2], or None = the frame's grid, row-major."""
+        torch = _torch()
+        n = int(packet_xy.shape[0]) if packet_xy is not None else ((resx + 15) // 16) * ((resy + 15) // 16)
+        if out is None:
+            out = torch.zeros((n, 4), dtype=torch.int32, device=self._dev())
+        lights, lp, cam13, _ = self._heat_args(cam, lights7, None)
+        rc = _lib.lib().snail_instances_packet_stats_dev(self._h, _lib.ptr(cam13), resx, resy, _lib.ptr(packet_xy), n, lp, len(lights),
+                                                        int(flags) | (self.RENDER_REFLECTIONS if reflections else 0), _lib.ptr(out), _lib.ptr(stats), _stream_ptr(stream))
+        _lib.check(rc, "snail_instances_packet_stats_dev")
+        return out
+
+    def render_heat_packets(self, cam, resx: int, resy: int, packet_xy=None, lights7=None, flags: int = 0, tint=None, out=None, packet_stats=None, stats=None,
+                            stream=None):
+        """snail_instances_heat_packets_dev: the heat-map of the packets, packet-major [n, 256, 3] uint8 (B,G,R).  flags: RENDER_REFLECTIONS,
+        RENDER_AA4; tint = three factors (gVals[8]) or None; packet_stats (optional) int32 device tensor [n, 4] ([n, 4, 4] with RENDER_AA4)."""
+        torch = _torch()
+        n = int(packet_xy.shape[0]) if packet_xy is not None else ((resx + 15) // 16) * ((resy + 15) // 16)
+        if out is None:
+            out = torch.empty((n, 256, 3), dtype=torch.uint8, device=self._dev())
+        lights, lp, cam13, tnt = self._heat_args(cam, lights7, tint)
+        rc = _lib.lib().snail_instances_heat_packets_dev(self._h, _lib.ptr(cam13), resx, resy, _lib.ptr(packet_xy), n, lp, len(lights), int(flags), _lib.ptr(tnt),
+                                                        _lib.ptr(out), _lib.ptr(packet_stats), _lib.ptr(stats), _stream_ptr(stream))
+        _lib.check(rc, "snail_instances_heat_packets_dev")
+        return out
+
+    def render_heat_tiles_host(self, cam, resx: int, resy: int, tiles, lights7=None, flags: int = 0, tint=None):
+        """snail_instances_render_heat_tiles: render_tiles_host with gVals[5] -> (data, offsets, stats)."""
+        t = np.ascontiguousarray(tiles, dtype=np.int32).reshape(-1, 4)
+        size = 3 * t[:, 2].astype(np.int64) * t[:, 3]
+        offsets = np.concatenate([[0], np.cumsum(size)[:-1]]).astype(np.int64)
+        data = np.zeros(int(size.sum()), dtype=np.uint8)
+        lights, lp, cam13, tnt = self._heat_args(cam, lights7, tint)
+        stats = np.zeros(4, dtype=np.uint64)
+        rc = _lib.lib().snail_instances_render_heat_tiles(self._h, _lib.ptr(cam13), resx, resy, _lib.ptr(t), _lib.ptr(offsets), len(t), lp, len(lights), int(flags),
+                                                         _lib.ptr(tnt), _lib.ptr(data), _lib.ptr(stats))
+        _lib.check(rc, "snail_instances_render_heat_tiles")
+        return data, offsets, stats
+
+    def render_heat_frame_host(self, cam, resx: int, resy: int, lights7=None, flags: int = 0, pitch: int | None = None, fill: int = 0):
+        """snail_instances_render_heat_frame: render_frame_host with gVals[5] -> (rgb8 frame [resy, resx, 3], or the rows [resy, pitch] when a
+        pitch is given -- the bytes between rows keep `fill` --, stats)."""
+        lights, lp, cam13, _ = self._heat_args(cam, lights7, None)
+        p = resx * 3 if pitch is None else int(pitch)
+        img = np.full((resy, max(p, 0)), fill, dtype=np.uint8)
+        stats = np.zeros(4, dtype=np.uint64)
+        rc = _lib.lib().snail_instances_render_heat_frame(self._h, _lib.ptr(cam13), resx, resy, lp, len(lights), int(flags), _lib.ptr(img), p, _lib.ptr(stats))
+        _lib.check(rc, "snail_instances_render_heat_frame")
+        return (img if pitch is not None else img.reshape(resy, resx, 3)), stats
+
     def traverse_primary(self, ctx: Context, element, stats=None, stream=None) -> Context:
         """DBVH::TraversePrimary<shared_origin, mask>: ctx.distance / ctx.object (= instance slot) / element (= triId) / ctx.barycentric
         (may be None) IN/OUT."""

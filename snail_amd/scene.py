@@ -567,6 +567,73 @@ class Scene:
             _lib.check(rc, "snail_render_tiles")
         return data, offsets, stats
 
+    # ---- include/snail_heatmap.h: per-packet TreeStats and the reference's gVals[5] heat-map ------------------------------------------
+    @staticmethod
+    def _heat_flags(flags: int, reflections: bool, aa4: bool) -> int:
+        return int(flags) | (Scene.RENDER_REFLECTIONS if reflections else 0) | (Scene.RENDER_AA4 if aa4 else 0)
+
+    @staticmethod
+    def _heat_lights(lights7):
+        lights = np.ascontiguousarray(lights7 if lights7 is not None else np.zeros((0, 7)), dtype=np.float32).reshape(-1, 7)
+        return lights, (_lib.ptr(lights) if len(lights) else None)
+
+    def packet_stats(self, cam: Camera, resx: int, resy: int, packet_xy=None, lights7=None, reflections: bool = False, out=None, stats=None, stream=None,
+                     flags: int = 0):
+        """snail_packet_stats_dev: the TreeStats {intersects, iterations, rays, skips} of every packet's RayTrace call (primary walk, the
+        lights' shadow packets, with reflections the nested call of the mirrored packet) as an int32 device tensor [n, 4] holding
+        uint32 words.  packet_xy = int32 device tensor [n, 2], or None = the frame's grid (packet cy * ceil(resx / 16) + cx)."""
+        torch = _torch()
+        n = int(packet_xy.shape[0]) if packet_xy is not None else ((resx + 15) // 16) * ((resy + 15) // 16)
+        if out is None:
+            out = torch.zeros((n, 4), dtype=torch.int32, device=self._dev())
+        lights, lp = self._heat_lights(lights7)
+        cam13 = np.ascontiguousarray(cam.as_array13(), dtype=np.float32)
+        rc = _lib.lib().snail_packet_stats_dev(self._h, _lib.ptr(cam13), resx, resy, _lib.ptr(packet_xy), n, lp, len(lights), self._heat_flags(flags, reflections, False),
+                                               _lib.ptr(out), _lib.ptr(stats), _stream_ptr(stream))
+        _lib.check(rc, "snail_packet_stats_dev")
+        return out
+
+    def render_heat_packets(self, cam: Camera, resx: int, resy: int, packet_xy=None, lights7=None, reflections: bool = False, aa4: bool = False, out=None,
+                            packet_stats=None, stats=None, stream=None, flags: int = 0):
+        """snail_render_heat_packets_dev: the heat-map of the packets as packet-major [n, 256, 3] uint8 (B,G,R).  packet_stats (optional):
+        int32 device tensor [n, 4] -- [n, 4, 4] with aa4 -- that receives the counters the colours were made from."""
+        torch = _torch()
+        n = int(packet_xy.shape[0]) if packet_xy is not None else ((resx + 15) // 16) * ((resy + 15) // 16)
+        if out is None:
+            out = torch.empty((n, 256, 3), dtype=torch.uint8, device=self._dev())
+        lights, lp = self._heat_lights(lights7)
+        cam13 = np.ascontiguousarray(cam.as_array13(), dtype=np.float32)
+        rc = _lib.lib().snail_render_heat_packets_dev(self._h, _lib.ptr(cam13), resx, resy, _lib.ptr(packet_xy), n, lp, len(lights),
+                                                      self._heat_flags(flags, reflections, aa4), _lib.ptr(out), _lib.ptr(packet_stats), _lib.ptr(stats), _stream_ptr(stream))
+        _lib.check(rc, "snail_render_heat_packets_dev")
+        return out
+
+    def render_heat_tiles_host(self, cam: Camera, resx: int, resy: int, tiles, lights7=None, flags: int = 0):
+        """snail_render_heat_tiles: render_tiles_host with gVals[5]; returns (data, offsets, stats).  flags: RENDER_REFLECTIONS, RENDER_AA4."""
+        t = np.ascontiguousarray(tiles, dtype=np.int32).reshape(-1, 4)
+        size = 3 * t[:, 2].astype(np.int64) * t[:, 3]
+        offsets = np.concatenate([[0], np.cumsum(size)[:-1]]).astype(np.int64)
+        data = np.zeros(int(size.sum()), dtype=np.uint8)
+        lights, lp = self._heat_lights(lights7)
+        cam13 = np.ascontiguousarray(cam.as_array13(), dtype=np.float32)
+        stats = np.zeros(4, dtype=np.uint64)
+        rc = _lib.lib().snail_render_heat_tiles(self._h, _lib.ptr(cam13), resx, resy, _lib.ptr(t), _lib.ptr(offsets), len(t), lp, len(lights), int(flags), _lib.ptr(data),
+                                                _lib.ptr(stats))
+        _lib.check(rc, "snail_render_heat_tiles")
+        return data, offsets, stats
+
+    def render_heat_image_host(self, cam: Camera, resx: int, resy: int, lights7=None, flags: int = 0, pitch: int | None = None, fill: int = 0):
+        """snail_render_heat_image: render_image_host with gVals[5]; returns (image rows [resy, pitch] uint8 when `pitch` is given, else the
+        [resy, resx, 3] frame, stats).  The bytes between rows keep `fill`."""
+        lights, lp = self._heat_lights(lights7)
+        cam13 = np.ascontiguousarray(cam.as_array13(), dtype=np.float32)
+        p = resx * 3 if pitch is None else int(pitch)
+        img = np.full((resy, max(p, 0)), fill, dtype=np.uint8)
+        stats = np.zeros(4, dtype=np.uint64)
+        rc = _lib.lib().snail_render_heat_image(self._h, _lib.ptr(cam13), resx, resy, lp, len(lights), int(flags), _lib.ptr(img), p, _lib.ptr(stats))
+        _lib.check(rc, "snail_render_heat_image")
+        return (img if pitch is not None else img.reshape(resy, resx, 3)), stats
+
     def trace_primary_host(self, cam: Camera, resx: int, resy: int, rect=None):
         """Host-buffer entry point (what a C++ host would call): numpy planes in, numpy planes out."""
         x0, y0, w, h = rect if rect is not None else (0, 0, resx, resy)
