@@ -113,7 +113,7 @@ int validateInstances(const char *fn, const void *nodes32, int nNodes, const flo
 	for(int i = nNodes - 1; i >= 0; i--) {
 		if(!reached[i]) continue;
 		depth[i] = (nd[i].sub & 0x80000000u) ? 0 : 1 + std::max(depth[nd[i].sub], depth[nd[i].sub + 1]);
-		if(depth[i] > SNAIL_INSTANCES_MAX_DEPTH) { snail_set_error("%s: the tree is deeper than %d levels", fn, SNAIL_INSTANCES_MAX_DEPTH); return 2; }
+		if(depth[i] > SNAIL_INSTANCES_MAX_DEPTH) { snail_set_error("%s: the tree is deeper than %d levels (depth limit SNAIL_INSTANCES_MAX_DEPTH)", fn, SNAIL_INSTANCES_MAX_DEPTH); return 2; }
 	}
 	maxDepth = depth[0];
 	if(depthOut) *depthOut = maxDepth;

@@ -249,6 +249,11 @@ def _box_test(node, org, idir, dist, first, last, shared, shadow):
 class Ref:
     """The instanced scene for the restatement: BLAS oracle scenes, top-level nodes, xf12 / blas index in builder-slot order."""
 
+    # instrumentation of traverse() for the tests (it enters no result): the longest top-level stack any packet has held, and the
+    # (axis, firstNode, sign[axis]) triples met at inner nodes; a test resets them before the walks it wants to look at
+    max_stack = 0
+    orders_seen = set()
+
     def __init__(self, blas_oracles, nodes, xf12_slots, blas_index_slots):
         self.blas = list(blas_oracles)
         self.nodes = np.asarray(nodes).view(NODE_DTYPE)
@@ -333,11 +338,27 @@ class Ref:
                     break
                 fn = ((aux >> 16) & 0xffff) ^ sign[aux & 0xffff]
                 stack.append((sub + (fn ^ 1), first, last))
+                Ref.max_stack = max(Ref.max_stack, len(stack))
+                Ref.orders_seen.add((aux & 0xffff, (aux >> 16) & 0xffff, sign[aux & 0xffff]))
                 nn = sub + fn
         return stats
 
-    def render_primary(self, cam13, resx, resy, mode=O.MODE_IEEE):
-        """Frame layout (t, u, v, instance, tri, stats) of the whole image, as snail_instances_trace_primary_dev."""
+    def _primary_packet(self, cam, resx, resy, px, py, mode):
+        """The 16x16 primary packet at pixel origin (px, py): (dist [64,4], bary [64,8], obj [64,4], elem [64,4], TreeStats)."""
+        org = np.repeat(cam[:3].reshape(1, 3, 1), 4, axis=2).astype(np.float32)
+        dd, ii = O.gen_packet(cam, resx, resy, px, py, mode)
+        d = dd.reshape(64, 3, 4).copy(); idir = ii.reshape(64, 3, 4).copy()
+        dist = np.full((64, 4), np.inf, dtype=np.float32)
+        obj = np.zeros((64, 4), dtype=np.int32); elem = np.zeros((64, 4), dtype=np.int32)
+        bary = np.zeros((64, 8), dtype=np.float32)
+        stats = self.traverse(org, d, idir, None, dist, obj, elem, bary, True, False, mode)
+        stats[2] += 256
+        return dist, bary, obj, elem, stats
+
+    def render_primary(self, cam13, resx, resy, mode=O.MODE_IEEE, rect=None):
+        """Frame layout (t, u, v, instance, tri, stats) of the whole image, as snail_instances_trace_primary_dev.  rect = (x0, y0, w, h):
+        only the packets at (x0 + 16 i, y0 + 16 j), i < (w + 15) // 16, j < (h + 15) // 16, are traced (stats are theirs) and only the
+        pixels x < min(resx, x0 + w), y < min(resy, y0 + h) are stored; every other pixel keeps the miss."""
         t = np.full((resy, resx), np.inf, dtype=np.float32)
         u = np.zeros((resy, resx), dtype=np.float32)
         v = np.zeros((resy, resx), dtype=np.float32)
@@ -345,21 +366,34 @@ class Ref:
         tri = np.zeros((resy, resx), dtype=np.int32)
         stats = np.zeros(4, dtype=np.uint64)
         cam = np.asarray(cam13, dtype=np.float32)
-        org = np.repeat(cam[:3].reshape(1, 3, 1), 4, axis=2).astype(np.float32)
-        for py in range(0, resy, 16):
-            for px in range(0, resx, 16):
-                dd, ii = O.gen_packet(cam, resx, resy, px, py, mode)
-                d = dd.reshape(64, 3, 4).copy(); idir = ii.reshape(64, 3, 4).copy()
-                dist = np.full((64, 4), np.inf, dtype=np.float32)
-                obj = np.zeros((64, 4), dtype=np.int32); elem = np.zeros((64, 4), dtype=np.int32)
-                bary = np.zeros((64, 8), dtype=np.float32)
-                stats += self.traverse(org, d, idir, None, dist, obj, elem, bary, True, False, mode)
-                stats[2] += 256
+        x0, y0, w, h = rect if rect is not None else (0, 0, resx, resy)
+        xlim, ylim = min(resx, x0 + w), min(resy, y0 + h)
+        for py in range(y0, y0 + 16 * ((h + 15) // 16), 16):
+            for px in range(x0, x0 + 16 * ((w + 15) // 16), 16):
+                dist, bary, obj, elem, st = self._primary_packet(cam, resx, resy, px, py, mode)
+                stats += st
                 for q in range(64):
                     y = py + (q >> 2)
                     for l in range(4):
                         x = px + 4 * (q & 3) + l
-                        if x < resx and y < resy:
+                        if x < xlim and y < ylim:
                             t[y, x], u[y, x], v[y, x] = dist[q, l], bary[q, l], bary[q, 4 + l]
                             inst[y, x], tri[y, x] = obj[q, l], elem[q, l]
+        return t, u, v, inst, tri, stats
+
+    def render_packets(self, cam13, resx, resy, packet_xy, mode=O.MODE_IEEE):
+        """Packet-major [n, 256] planes (t, u, v, instance, tri) and the summed stats of the packets at the pixel origins packet_xy [n, 2],
+        as snail_instances_trace_packets_dev: entry 4 q + l of a packet is lane l of quad q (pixel (px + 4 (q & 3) + l, py + (q >> 2)), the
+        order render_primary unpacks), all 256 written, rays beyond the frame's edge included."""
+        xy = np.asarray(packet_xy, dtype=np.int64).reshape(-1, 2)
+        n = len(xy)
+        t = np.zeros((n, 256), dtype=np.float32); u = np.zeros((n, 256), dtype=np.float32); v = np.zeros((n, 256), dtype=np.float32)
+        inst = np.zeros((n, 256), dtype=np.int32); tri = np.zeros((n, 256), dtype=np.int32)
+        stats = np.zeros(4, dtype=np.uint64)
+        cam = np.asarray(cam13, dtype=np.float32)
+        for i in range(n):
+            dist, bary, obj, elem, st = self._primary_packet(cam, resx, resy, int(xy[i, 0]), int(xy[i, 1]), mode)
+            stats += st
+            t[i], u[i], v[i] = dist.reshape(256), bary[:, :4].reshape(256), bary[:, 4:].reshape(256)
+            inst[i], tri[i] = obj.reshape(256), elem.reshape(256)
         return t, u, v, inst, tri, stats

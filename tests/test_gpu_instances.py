@@ -12,6 +12,7 @@ from snail_amd import HostBVH, scenes, survey_camera
 from snail_amd.instances import InstancedScene
 from snail_amd.scene import Context, Scene, ShadowContext
 from tests import dbvh_ref as R
+from tests import instances_edges as E
 from tests import oracle_lib as O
 from tests import util as U
 
@@ -33,13 +34,8 @@ _blas_cache = {}
 def blas(name):
     """(HostBVH-built device Scene, OracleScene) of a BLAS: box, lancia (the reference's own mesh), chain (depth 63: the DEEP walk)"""
     if name not in _blas_cache:
-        if name == "lancia":
-            tv = np.load(os.path.join(GOLD, "lancia_tris.npz"))["tris"].reshape(-1, 9).astype(np.float32)
-        elif name == "chain":
-            tv = scenes.chain()
-        else:
-            tv = scenes.scene_by_name(name)
-        _blas_cache[name] = (Scene(HostBVH.build(tv), 0), O.OracleScene(tv), tv)
+        tv = E.blas_tris(name)     # (the triangles and the oracle scene live in tests/instances_edges.py, which the host tests share)
+        _blas_cache[name] = (Scene(HostBVH.build(tv), 0), E.oracle(name), tv)
     return _blas_cache[name]
 
 
