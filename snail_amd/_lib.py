@@ -134,6 +134,19 @@ HEATMAP_SIGNATURES = {
     "snail_instances_render_heat_frame": (_I, [_VP, _F13, _I, _I, _VP, _I, _I, _VP, _I, _VP]),
 }
 
+# include/snail_materials.h: full shading of plain scenes (snail_amd/materials.py; tests/c/materials_c.c enumerates this table)
+MATERIALS_SIGNATURES = {
+    "snail_shtris_pack": (_I, [_VP, _VP, _VP, _VP, _I, _VP, _VP]),
+    "snail_texture_size": (C.c_int64, [_I, _I, _VP]),
+    "snail_texture_build": (_I, [_VP, _I, _I, _VP, C.c_int64, _VP]),
+    "snail_materials_create": (_VP, [_VP, _VP, _I, _VP, _I, _VP, _I, _VP, _I]),
+    "snail_materials_destroy": (None, [_VP]),
+    "snail_materials_shade_packets_dev": (_I, [_VP, _F13, _I, _I, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "snail_render_materials_dev": (_I, [_VP, _F13, _I, _I, _VP, _I, _VP, _I, _VP, _I, _VP, _VP]),
+    "snail_render_materials_packets_dev": (_I, [_VP, _F13, _I, _I, _VP, _I, _VP, _I, _VP, _I, _VP, _VP, _VP]),
+    "snail_render_materials_image": (_I, [_VP, _F13, _I, _I, _VP, _I, _VP, _I, _VP, _I, _VP]),
+}
+
 # include/snail_hip_debug.h: the workbench build only (libsnailhip_debug.so, -DSNAIL_DEBUG_API)
 DEBUG_SIGNATURES = {
     "snail_debug_delay_dev": (_I, [C.c_float, _VP]),
@@ -156,7 +169,7 @@ def debug_lib():
         if not os.path.exists(DEBUG_LIB_PATH):
             raise SnailError("workbench library %s is missing: `make -C snail_amd/csrc debug`" % DEBUG_LIB_PATH)
         L = C.CDLL(DEBUG_LIB_PATH)
-        for table in (SIGNATURES, INSTANCES_SIGNATURES, INSTANCES_SHADE_SIGNATURES, INSTANCES_TILES_SIGNATURES, INSTANCES_BUILD_SIGNATURES, BVH_FAST_SIGNATURES, HEATMAP_SIGNATURES, DEBUG_SIGNATURES):
+        for table in (SIGNATURES, INSTANCES_SIGNATURES, INSTANCES_SHADE_SIGNATURES, INSTANCES_TILES_SIGNATURES, INSTANCES_BUILD_SIGNATURES, BVH_FAST_SIGNATURES, HEATMAP_SIGNATURES, MATERIALS_SIGNATURES, DEBUG_SIGNATURES):
             for name, (res, args) in table.items():
                 fn = getattr(L, name)
                 fn.restype = res
@@ -177,7 +190,7 @@ def lib():
             L = C.CDLL(LIB_PATH)
         except OSError as e:  # pragma: no cover - depends on the box
             raise SnailError("cannot load %s: %s" % (LIB_PATH, e)) from e
-        for table in (SIGNATURES, INSTANCES_SIGNATURES, INSTANCES_SHADE_SIGNATURES, INSTANCES_TILES_SIGNATURES, INSTANCES_BUILD_SIGNATURES, BVH_FAST_SIGNATURES, HEATMAP_SIGNATURES):
+        for table in (SIGNATURES, INSTANCES_SIGNATURES, INSTANCES_SHADE_SIGNATURES, INSTANCES_TILES_SIGNATURES, INSTANCES_BUILD_SIGNATURES, BVH_FAST_SIGNATURES, HEATMAP_SIGNATURES, MATERIALS_SIGNATURES):
             for name, (res, args) in table.items():
                 fn = getattr(L, name)
                 fn.restype = res

@@ -1,0 +1,427 @@
+// materials.inc -- full shading of the primary packets of a plain scene (include/snail_materials.h): the gVals[6] && HasShadingData() branch of
+// Scene::RayTrace (src/scene_trace.cpp:145-358) and, on its samples, the lights of the simple-shading pipeline.  Included once per arithmetic
+// after instances_shade.inc, into the same namespace (dev / dev_sse).  Always over an explicit packet list, one wave per packet or per
+// (packet, light), lane q = quad q, the reference's block of 4 quads = lanes 4b .. 4b + 3:
+//   k_mat_sample           hit records (t, u, v, triId) + ShTriangle records + materials + textures -> 9 floats per ray (normal, diffuse,
+//                          specular), component-major [packet][component][quad][lane]: every store instruction writes one contiguous KB
+//   k_mat_light<DEEP>      one wave per (packet, light): position + the sample's normal -> light cull -> shadow packet -> TraverseShadow ->
+//                          the surviving distances [light][packet][256]                         Scene::TraceLight, src/scene_trace.cpp:523-566
+//   k_mat_final            the tail of TraceLight per light, outColor = diffuse * lDiffuse + specular * lSpecular, ConvColor, store  :567-601, :484-512
+// hitBounds / lightCulled / shadowLane and the shadow walks are the plain pipeline's device functions, called on these samples; what differs is
+// that N.L takes the interpolated normal and that diffuse and specular are two buffers.  Table look-ups in their fully checked form.
+namespace SNAIL_DEV_NS {
+
+enum { MAT_SIMPLE = 0, MAT_TEX = 1, MAT_UBER = 2 };
+struct MatRec {            // 48 bytes, read as three dwordx4
+	int kind, ndotr;
+	float col[3], spec[3];
+	int tex, pad[3];
+};
+struct TexRec {            // 96 bytes
+	unsigned long long base;   // first byte of level 0 in MatArgs::texels
+	int w, h, mips, pad;
+	unsigned lvl[16];          // byte offset of level m from base
+	unsigned pad2[2];
+};
+struct MatArgs {
+	ShadeArgs s;               // FIRST: its hostTab opens the kernel-argument segment.  hitT / hitId = the primary hits; nodes / tris / pf / relLight: the shadow walks
+	const float *hitU, *hitV;  // barycentric.x / .y of the primary hits, packet-major
+	const uint4 *shtris;       // ShTriangle records, 4 x uint4 each, triId order
+	int nTris;
+	const int *matMap;
+	int nMap;
+	const MatRec *mats;
+	int nMats;
+	const TexRec *tex;
+	const unsigned char *texels;
+	float *samples;            // [packet][9][64][4]
+};
+
+// RayGenerator::Generate for the lane's quad, exactly as in loadSamples (checked look-ups)
+__device__ __forceinline__ void matRays(const ShadeArgs &A, const PacketPos &P, int lane, float (&d)[3][4]) {
+	const int ty = lane >> 2, k4 = lane & 3;
+#pragma unroll
+	for(int l = 0; l < 4; l++) {
+		const float xoff = (float)(P.px + (l >= 2 ? 2 : 0)), yoff = (float)(P.py - (l >= 2 ? 1 : 0));
+		const float tposx = (float)(4 * k4) + xoff, tposy = (float)ty + yoff;
+		const float p0 = A.g.tright[0] * tposx + (A.g.tup[0] * tposy + A.g.txyz[0][l]);
+		const float p1 = A.g.tright[1] * tposx + (A.g.tup[1] * tposy + A.g.txyz[1][l]);
+		const float p2 = A.g.tright[2] * tposx + (A.g.tup[2] * tposy + A.g.txyz[2][l]);
+		const float rs = RSqrt(p0 * p0 + p1 * p1 + p2 * p2);
+		d[0][l] = p0 * rs; d[1][l] = p1 * rs; d[2][l] = p2 * rs;
+	}
+}
+
+struct ShTri {
+	float uv[3][2], nrm[3][3];
+	int matId;
+};
+__device__ __forceinline__ ShTri loadShTri(const MatArgs &A, int idx) {
+	const uint4 *r = A.shtris + (size_t)idx * 4;
+	const uint4 a = r[0], b = r[1], c = r[2], e = r[3];
+	ShTri T;
+	T.uv[0][0] = asf(a.x); T.uv[0][1] = asf(a.y); T.uv[1][0] = asf(a.z); T.uv[1][1] = asf(a.w);
+	T.uv[2][0] = asf(b.x); T.uv[2][1] = asf(b.y);
+	T.nrm[0][0] = asf(b.z); T.nrm[0][1] = asf(b.w); T.nrm[0][2] = asf(c.x);
+	T.nrm[1][0] = asf(c.y); T.nrm[1][1] = asf(c.z); T.nrm[1][2] = asf(c.w);
+	T.nrm[2][0] = asf(e.x); T.nrm[2][1] = asf(e.y); T.nrm[2][2] = asf(e.z);
+	T.matId = (int)e.w;
+	return T;
+}
+// BVH::GetMaterialId(shTri.MatId()) = materials[idx].id (src/bvh/tree.h:82-84); -1 = defaultMat.  (The set's creation has checked every record and
+// entry; the tests here only keep a corrupted table from turning into an address.)
+__device__ __forceinline__ int matIdOf(const MatArgs &A, int shMatId) {
+	const int idx = shMatId & 0x7fffffff;
+	if(idx >= A.nMap) return -1;
+	const int m = A.matMap[idx];
+	return (unsigned)m < (unsigned)A.nMats ? m : -1;
+}
+
+// PointSampler::Sample for one ray (src/sampling/point_sampler.cpp:126-210): every operation rounded separately, in the order written
+__device__ __forceinline__ void matSampleTex(const MatArgs &A, int texIdx, float cu, float cv, float tdx, float tdy, float (&out)[3]) {
+	const TexRec *T = A.tex + texIdx;
+	const int w = T->w, h = T->h, mips = T->mips;
+	const float wMul = (float)(w - 1), hMul = (float)(h - 1);
+	// ClampTexCoord: coord - float(int(coord)), + 1 if negative
+	float ux = cu - (float)(int)cu, uy = cv - (float)(int)cv;
+	ux = ux < 0.0f ? ux + 1.0f : ux;
+	uy = uy < 0.0f ? uy + 1.0f : uy;
+	const float px = ux * wMul, py = uy * hMul;
+	// the mip: texDiff is the quad's (broadcast), so Minimize over the quad is the value itself
+	const float ax = tdx * wMul, ay = tdy * hMul;
+	const float mn = ax < ay ? ax : ay;
+	unsigned pixels = (unsigned)(long long)(mn * 0.6f);   // uint(float) of the x86-64 build: cvttss2si to 64 bits, low word
+	int mip = pixels ? 32 - __builtin_clz(pixels) : 0;           // while(pixels) { mip++; pixels >>= 1; }
+	mip = mip < mips - 1 ? mip : mips - 1;
+	const unsigned char *data = A.texels + T->base + T->lvl[mip & 15];
+	const int wm = w >> mip, pitch = 3 * (wm > 1 ? wm : 1);
+	int x1 = (int)px, y1 = (int)py;
+	int x2 = x1 + 1, y2 = y1 + 1;
+	const float dx = px - (float)x1, dy = py - (float)y1;
+	y1 = h - y1; y2 = h - y2;
+	x1 >>= mip; y1 >>= mip; x2 >>= mip; y2 >>= mip;
+	const int xm = (w - 1) >> mip, ym = (h - 1) >> mip;
+	x1 &= xm; y1 &= ym; x2 &= xm; y2 &= ym;
+	x1 = x1 + x1 + x1; x2 = x2 + x2 + x2;
+	y1 *= pitch; y2 *= pitch;
+	const int o[4] = {x1 + y1, x2 + y1, x1 + y2, x2 + y2};
+	float ch[4][3];
+#pragma unroll
+	for(int k = 0; k < 4; k++) {
+		// a tap = ONE 4-byte load at byte alignment (offsets are multiples of 3), three bytes of it used, as the reference's DATA(a, b); the device
+		// copy of every texture is padded by 4 bytes for the last texel's.  Chosen by the resource report over three byte loads: the same VGPRs,
+		// SGPRs and occupancy, 32 instructions fewer per kernel (profiles/materials.txt)
+		unsigned v;
+		__builtin_memcpy(&v, data + o[k], 4);
+		ch[k][0] = (float)(int)(v & 255u); ch[k][1] = (float)(int)((v >> 8) & 255u); ch[k][2] = (float)(int)((v >> 16) & 255u);
+	}
+#pragma unroll
+	for(int c = 0; c < 3; c++) {   // Lerp(a, b, x) = a + (b - a) * x (veclib/vecbase.h:80)
+		const float top = ch[0][c] + (ch[1][c] - ch[0][c]) * dx;
+		const float bot = ch[2][c] + (ch[3][c] - ch[2][c]) * dx;
+		out[c] = (top + (bot - top) * dy) * (1.0f / 255.0f);
+	}
+}
+
+// broadcast of the block's first lane (lanes 4b .. 4b + 3 -> lane 4b): quad_perm [0, 0, 0, 0]
+__device__ __forceinline__ int blockFirst(int v) { return __builtin_amdgcn_mov_dpp(v, 0x00, 0xf, 0xf, true); }
+// a predicate over all four lanes of the block
+__device__ __forceinline__ bool blockAll(bool p, int lane) {
+	const unsigned long long b = __builtin_amdgcn_ballot_w64(p);
+	return ((b >> (lane & ~3)) & 15ull) == 15ull;
+}
+
+// (a + b * x) + c * y and a + (b * x + c * y): the two associations of src/scene_trace.cpp:204 / :218-220,:245-249,:272-279
+__device__ __forceinline__ float lerpL(float a, float b, float c, float x, float y) { return (a + b * x) + c * y; }
+__device__ __forceinline__ float lerpR(float a, float b, float c, float x, float y) { return a + (b * x + c * y); }
+
+__global__ __launch_bounds__(64) void k_mat_sample(MatArgs A) {
+	const int lane = threadIdx.x & 63;
+	const int li = (int)blockIdx.x;
+	if(li >= A.s.nPackets) return;
+	const PacketPos P = packetOf(A.s, li);
+	const size_t quad = P.pidx * 64 + lane;
+	const float inf = __builtin_inff();
+	float d[3][4];
+	matRays(A.s, P, lane, d);
+	float bx[4], by[4];
+	bool hit[4];
+	int obj[4];
+	{
+		const float4 tv = *(const float4 *)(A.s.hitT + quad * 4), uv = *(const float4 *)(A.hitU + quad * 4), vv = *(const float4 *)(A.hitV + quad * 4);
+		const int4 iv = *(const int4 *)(A.s.hitId + quad * 4);
+		const float t[4] = {tv.x, tv.y, tv.z, tv.w};
+		const int id[4] = {iv.x, iv.y, iv.z, iv.w};
+		bx[0] = uv.x; bx[1] = uv.y; bx[2] = uv.z; bx[3] = uv.w;
+		by[0] = vv.x; by[1] = vv.y; by[2] = vv.z; by[3] = vv.w;
+#pragma unroll
+		for(int l = 0; l < 4; l++) {
+			hit[l] = t[l] < inf;
+			int i = id[l] < 0 ? 0 : id[l];
+			i = i < A.nTris ? i : A.nTris - 1;
+			obj[l] = hit[l] ? i : 0;       // object = Condition(mask, tObject, 0), :161
+		}
+	}
+	// mask4 == 0x0f0f0f0f, and the 16 objects equal to the block's first (:178-182)
+	const bool full = blockAll(hit[0] && hit[1] && hit[2] && hit[3], lane);
+	const int obj0b = blockFirst(obj[0]);
+	const bool single = blockAll(obj[0] == obj0b && obj[1] == obj0b && obj[2] == obj0b && obj[3] == obj0b, lane) && full;
+
+	float nrm[3][4], tc[2][4], tdx = 0.0f, tdy = 0.0f;
+	int mid[4];
+#pragma unroll
+	for(int l = 0; l < 4; l++) { nrm[0][l] = nrm[1][l] = nrm[2][l] = 0.0f; tc[0][l] = tc[1][l] = 0.0f; mid[l] = -1; }
+	if(single) {
+		// (a): one triangle for the block
+		const ShTri T = loadShTri(A, obj0b);
+		const int m = matIdOf(A, T.matId);
+		const bool flat = T.matId < 0;
+		const bool texd = m >= 0 && A.mats[m].kind == MAT_TEX;     // Material::fTexCoords
+#pragma unroll
+		for(int l = 0; l < 4; l++) {
+			mid[l] = m;
+			if(texd) {
+#pragma unroll
+				for(int c = 0; c < 2; c++) tc[c][l] = lerpL(T.uv[0][c], T.uv[1][c], T.uv[2][c], bx[l], by[l]);
+#pragma unroll
+				for(int c = 0; c < 3; c++) nrm[c][l] = lerpL(T.nrm[0][c], T.nrm[1][c], T.nrm[2][c], bx[l], by[l]);
+			} else {
+#pragma unroll
+				for(int c = 0; c < 3; c++) nrm[c][l] = flat ? T.nrm[0][c] : lerpR(T.nrm[0][c], T.nrm[1][c], T.nrm[2][c], bx[l], by[l]);
+			}
+		}
+		if(texd) {   // texDiff = Maximize(texCoord) - Minimize(texCoord) of the quad (:219; finite values: the fold's order is immaterial)
+			tdx = vmax(vmax(tc[0][0], tc[0][1]), vmax(tc[0][2], tc[0][3])) - vmin(vmin(tc[0][0], tc[0][1]), vmin(tc[0][2], tc[0][3]));
+			tdy = vmax(vmax(tc[1][0], tc[1][1]), vmax(tc[1][2], tc[1][3])) - vmin(vmin(tc[1][0], tc[1][1]), vmin(tc[1][2], tc[1][3]));
+		}
+	} else {
+		// (b): per quad; lane 0's triangle for all four lanes if lane 0 hit, then lanes 1..3 whose triangle differs from obj[0] (0 when lane 0 missed)
+		if(hit[0]) {
+			const ShTri T = loadShTri(A, obj[0]);
+			const int m = matIdOf(A, T.matId);
+#pragma unroll
+			for(int l = 0; l < 4; l++) {
+				mid[l] = hit[l] ? m : -1;
+#pragma unroll
+				for(int c = 0; c < 2; c++) tc[c][l] = lerpL(T.uv[0][c], T.uv[1][c], T.uv[2][c], bx[l], by[l]);
+#pragma unroll
+				for(int c = 0; c < 3; c++) nrm[c][l] = lerpL(T.nrm[0][c], T.nrm[1][c], T.nrm[2][c], bx[l], by[l]);
+			}
+		}
+#pragma unroll
+		for(int l = 1; l < 4; l++)
+			if(hit[l] && obj[l] != obj[0]) {
+				const ShTri T = loadShTri(A, obj[l]);
+				mid[l] = matIdOf(A, T.matId);
+#pragma unroll
+				for(int c = 0; c < 2; c++) tc[c][l] = lerpL(T.uv[0][c], T.uv[1][c], T.uv[2][c], bx[l], by[l]);
+#pragma unroll
+				for(int c = 0; c < 3; c++) nrm[c][l] = lerpL(T.nrm[0][c], T.nrm[1][c], T.nrm[2][c], bx[l], by[l]);
+			}
+	}
+	// One material for 16 hit rays: Shade unmasked (:224, :301-308); otherwise (c) every selected lane by its own material on the masked path
+	// (:310-355).  The per-material masks of (c) are disjoint -- a lane has one matId -- and a masked Shade writes only its own lanes, so the order
+	// in which the reference walks its material list cannot show: shading each lane once by its own material is the same.
+	const int mid0b = blockFirst(mid[0]);
+	const bool unmasked = blockAll(mid[0] == mid0b && mid[1] == mid0b && mid[2] == mid0b && mid[3] == mid0b, lane) && full;
+
+	float diff[3][4], spec[3][4];
+#pragma unroll
+	for(int l = 0; l < 4; l++) {
+		// the lane's material: loaded values of an unrolled loop (compile-time indices), never a runtime-indexed array
+		int kind = MAT_SIMPLE, ndotr = 1, tex = 0;
+		float col[3] = {1.0f, 1.0f, 1.0f}, sp[3] = {0.0f, 0.0f, 0.0f};   // defaultMat = SimpleMaterial<true>(1, 1, 1), src/scene.cpp:6
+		if(mid[l] >= 0) {
+			const uint4 *r = (const uint4 *)(A.mats + mid[l]);
+			const uint4 a = r[0], b = r[1], c = r[2];
+			kind = (int)a.x; ndotr = (int)a.y;
+			col[0] = asf(a.z); col[1] = asf(a.w); col[2] = asf(b.x);
+			sp[0] = asf(b.y); sp[1] = asf(b.z); sp[2] = asf(b.w);
+			tex = (int)c.x;
+		}
+		const float dn = d[0][l] * nrm[0][l] + d[1][l] * nrm[1][l] + d[2][l] * nrm[2][l];
+		const float adn = __builtin_fabsf(dn);
+		float t1[3] = {0.0f, 0.0f, 0.0f};
+		// the kinds present among the wave's lanes: a branch per kind that needs code of its own, skipped when no lane has it
+		if(__builtin_amdgcn_ballot_w64(kind == MAT_TEX && hit[l]) != 0) {
+			if(kind == MAT_TEX && hit[l]) matSampleTex(A, tex, tc[0][l], tc[1][l], tdx, tdy, t1);
+		}
+#pragma unroll
+		for(int c = 0; c < 3; c++) {
+			float df, sf;
+			if(kind == MAT_TEX) { df = ndotr ? t1[c] * dn : t1[c]; sf = df; }
+			else if(kind == MAT_UBER) { df = col[c] * adn; sf = unmasked ? df : sp[c]; }
+			else { df = ndotr ? col[c] * adn : col[c]; sf = df; }
+			diff[c][l] = hit[l] ? df : 0.0f;
+			spec[c][l] = hit[l] ? sf : 0.0f;
+			nrm[c][l] = hit[l] ? nrm[c][l] : 0.0f;
+		}
+	}
+	float4 *o = (float4 *)(A.samples + P.pidx * (9 * 256)) + lane;
+#pragma unroll
+	for(int c = 0; c < 3; c++) {
+		o[(0 + c) * 64] = make_float4(nrm[c][0], nrm[c][1], nrm[c][2], nrm[c][3]);
+		o[(3 + c) * 64] = make_float4(diff[c][0], diff[c][1], diff[c][2], diff[c][3]);
+		o[(6 + c) * 64] = make_float4(spec[c][0], spec[c][1], spec[c][2], spec[c][3]);
+	}
+}
+
+// position and hit mask as in simple shading (src/scene_trace.cpp:157-165), the normal from the sample buffer
+__device__ __forceinline__ void matLoadSamples(const MatArgs &A, const PacketPos &P, int lane, Samples &S) {
+	const size_t quad = P.pidx * 64 + lane;
+	const float inf = __builtin_inff();
+	float d[3][4];
+	matRays(A.s, P, lane, d);
+	const float4 tv = *(const float4 *)(A.s.hitT + quad * 4);
+	const float t[4] = {tv.x, tv.y, tv.z, tv.w};
+	const float4 *sm = (const float4 *)(A.samples + P.pidx * (9 * 256)) + lane;
+	const float4 n0 = sm[0], n1 = sm[64], n2 = sm[128];
+	const float nn[3][4] = {{n0.x, n0.y, n0.z, n0.w}, {n1.x, n1.y, n1.z, n1.w}, {n2.x, n2.y, n2.z, n2.w}};
+#pragma unroll
+	for(int l = 0; l < 4; l++) {
+		S.hit[l] = t[l] < inf;
+		S.sdn[l] = 0.0f;
+#pragma unroll
+		for(int c = 0; c < 3; c++) { S.pos[c][l] = d[c][l] * t[l] + A.s.g.org[c]; S.nrm[c][l] = nn[c][l]; }
+	}
+}
+
+// ---- one (packet, light): the shadow packet (src/scene_trace.cpp:538-558) and BVH::TraverseShadow, by the walks of lightPacket ----
+// TWINS: the set-up and the walk selection below are those of lightPacket (snail_dev.inc; its main pass and its deferred M_EXACT pass folded into
+// one kernel, look-ups checked), and k_inst_light (instances_shade.inc) has the same set-up around the instanced walk.  A change to the shadow
+// packet, to the classify / walkSharedAsm / walk dispatch or to the stats booking belongs in all three.
+template <bool DEEP>
+__global__ __launch_bounds__(64) void k_mat_light(MatArgs A) {
+	__shared__ float lds[LDS_FLOATS_PER_WAVE];
+	const int lane = threadIdx.x & 63;
+	const int li = (int)blockIdx.x, n = (int)blockIdx.y;
+	if(li >= A.s.nPackets || n >= A.s.nLights) return;
+	const PacketPos P = packetOf(A.s, li);
+	const float lp[3] = {A.s.lights[n][0], A.s.lights[n][1], A.s.lights[n][2]};
+	const float radius = A.s.lights[n][6], radSq = radius * radius;
+	Quad Q;
+	{
+		Samples S;
+		matLoadSamples(A, P, lane, S);
+		float tMin[3], tMax[3];
+		hitBounds(S, tMin, tMax);
+		if(lightCulled(tMin, tMax, lp, radSq)) return;   // (wave-uniform; k_mat_final skips the light by the same test)
+#pragma unroll
+		for(int l = 0; l < 4; l++) {
+			float sd[3], distance, dotv;
+			shadowLane(S, l, lp, sd, distance, dotv, Q.dist[l]);
+#pragma unroll
+			for(int c = 0; c < 3; c++) { Q.d[c][l] = sd[c]; Q.id[c][l] = S.hit[l] ? InvDiv(sd[c] + 0.00000001f) : 0.0f; }
+		}
+	}
+	unsigned rays = 0;   // stats.TracingRays(CountMaskBits(ForWhich(mask))), :557
+#pragma unroll
+	for(int l = 0; l < 4; l++) rays += (unsigned)__builtin_popcountll(__builtin_amdgcn_ballot_w64(Q.dist[l] > 0.0f));
+	float lorg[3][4];
+#pragma unroll
+	for(int c = 0; c < 3; c++)
+#pragma unroll
+		for(int l = 0; l < 4; l++) lorg[c][l] = lp[c];
+	Counters st = {0, 0, 0, 0, 0};
+	int stid[4];
+	float bu[4], bv[4];
+	// the walk lightPacket picks for this packet (the same counters); a packet that needs M_EXACT (a non-finite value: practically never) is
+	// walked here instead of in a second launch
+	const bool fin = finite4(Q.id) && finite4(Q.d);
+	int oct;
+	const int mode = classify(A.s.fastOK != 0 && originSaneDev(lp), fin, true, Q.id, Q.dist, oct);
+	if(mode == M_EXACT) walk<true, false, true, M_EXACT, false, DEEP, false>(A.s.nodes, A.s.tris, 64, lane, lorg, Q, 15u, stid, bu, bv, lds, st);
+	else if(DEEP) {
+		if(mode == M_COH) walk<true, false, true, M_COH, false, DEEP, false>(A.s.nodes, A.s.tris, 64, lane, lorg, Q, 15u, stid, bu, bv, lds, st, oct);
+		else walk<true, false, true, M_FAST, false, DEEP, false>(A.s.nodes, A.s.tris, 64, lane, lorg, Q, 15u, stid, bu, bv, lds, st);
+	} else if(A.s.pack) {
+		const uint4 *pn = A.s.relLight[n];   // this light's origin-relative records
+		if(mode == M_COH) walkSharedAsm<true, true, true, false, false, false>(pn, A.s.tris, 64, lane, lorg, Q, 15u, stid, bu, bv, lds, st, oct);
+		else walkSharedAsm<true, false, true, false, false, false>(pn, A.s.tris, 64, lane, lorg, Q, 15u, stid, bu, bv, lds, st, 0);
+	} else if(mode == M_COH) walkSharedAsm<true, true, false, false, false, false>(A.s.nodes, A.s.tris, 64, lane, lorg, Q, 15u, stid, bu, bv, lds, st, oct);
+	else walkSharedAsm<true, false, false, false, false, false>(A.s.nodes, A.s.tris, 64, lane, lorg, Q, 15u, stid, bu, bv, lds, st, 0);
+	flushStats(A.s.stats, st, rays, lane);
+	*(float4 *)(A.s.sDist + ((size_t)n * (size_t)A.s.nPackets + P.pidx) * 256 + (size_t)lane * 4) = make_float4(Q.dist[0], Q.dist[1], Q.dist[2], Q.dist[3]);
+}
+
+// ---- one packet: the lights' contributions from the surviving distances, the colour and its store (shadeAndStore with two sample colours) ----
+// TWINS: the per-light tail, the colour sum, ConvColor and both stores (packet-major words; the frame's three aligned dwords or the byte-wise
+// tail, with the alignment rule) are shadeAndStore's (snail_dev.inc, non-fused, checked form), which k_final and k_inst_final (instances_shade.inc)
+// call; this copy differs only in taking diffuse and specular from the sample buffer.  A change to the attenuation or to the store rule belongs
+// in both.
+__global__ __launch_bounds__(64) void k_mat_final(MatArgs A) {
+	const int lane = threadIdx.x & 63;
+	const int li = (int)blockIdx.x;
+	if(li >= A.s.nPackets) return;
+	const PacketPos P = packetOf(A.s, li);
+	const size_t quad = P.pidx * 64 + lane;
+	Samples S;
+	matLoadSamples(A, P, lane, S);
+	float lDiff[3][4], lSpec[3][4];
+#pragma unroll
+	for(int c = 0; c < 3; c++)
+#pragma unroll
+		for(int l = 0; l < 4; l++) { lDiff[c][l] = A.s.ambient[c]; lSpec[c][l] = 0.0f; }
+	if(A.s.nLights) {
+		float tMin[3], tMax[3];
+		hitBounds(S, tMin, tMax);
+		const size_t packets = (size_t)A.s.nPackets;
+		for(int n = 0; n < A.s.nLights; n++) {
+			const float lp[3] = {A.s.lights[n][0], A.s.lights[n][1], A.s.lights[n][2]};
+			const float lc[3] = {A.s.lights[n][3], A.s.lights[n][4], A.s.lights[n][5]};
+			const float radius = A.s.lights[n][6], iRadius = 1.0f / radius, radSq = radius * radius;
+			if(lightCulled(tMin, tMax, lp, radSq)) continue;
+			const float4 sv = *(const float4 *)(A.s.sDist + ((size_t)n * packets + P.pidx) * 256 + (size_t)lane * 4);
+			const float sdist[4] = {sv.x, sv.y, sv.z, sv.w};
+#pragma unroll
+			for(int l = 0; l < 4; l++) {
+				float sd[3], distance, dotv, unused;
+				shadowLane(S, l, lp, sd, distance, dotv, unused);
+				if(sdist[l] > 0.0f) {
+					float atten = distance * iRadius;
+					atten = Max<M_EXACT>(0.0f, ((1.0f - atten) * 0.2f + FastInv(16.0f * atten * atten)) - 0.0625f);
+					const float diffMul = dotv * atten;
+					float specMul = dotv;
+					specMul *= specMul; specMul *= specMul; specMul *= specMul; specMul *= specMul;
+					specMul *= atten;
+#pragma unroll
+					for(int c = 0; c < 3; c++) { lDiff[c][l] += lc[c] * diffMul; lSpec[c][l] += lc[c] * specMul; }
+				}
+			}
+		}
+	}
+	// outColor = diffuse * lDiffuse + specular * lSpecular, or diffuse without lights (src/scene_trace.cpp:504-512)
+	const float4 *sm = (const float4 *)(A.samples + P.pidx * (9 * 256)) + lane;
+	float col[3][4];
+#pragma unroll
+	for(int c = 0; c < 3; c++) {
+		const float4 dv = sm[(3 + c) * 64], sv = sm[(6 + c) * 64];
+		const float df[4] = {dv.x, dv.y, dv.z, dv.w}, sf[4] = {sv.x, sv.y, sv.z, sv.w};
+#pragma unroll
+		for(int l = 0; l < 4; l++) col[c][l] = A.s.nLights ? df[l] * lDiff[c][l] + sf[l] * lSpec[c][l] : df[l];
+	}
+	unsigned bytes[12];
+#pragma unroll
+	for(int l = 0; l < 4; l++) { bytes[l * 3 + 0] = (unsigned)convChannelW(col[2][l]); bytes[l * 3 + 1] = (unsigned)convChannelW(col[1][l]); bytes[l * 3 + 2] = (unsigned)convChannelW(col[0][l]); }
+	if(A.s.bgrPackets) {
+		unsigned *o = (unsigned *)(A.s.bgrPackets + (quad * 4) * 3);
+#pragma unroll
+		for(int k = 0; k < 3; k++) o[k] = bytes[4 * k] | (bytes[4 * k + 1] << 8) | (bytes[4 * k + 2] << 16) | (bytes[4 * k + 3] << 24);
+		return;
+	}
+	const int yy = P.py + (lane >> 2), xx = P.px + (lane & 3) * 4;
+	if(yy < A.s.resy) {
+		unsigned char *dd = A.s.frame + (size_t)yy * A.s.pitch + (size_t)xx * 3;
+		if(xx + 3 < A.s.resx && (A.s.pitch & 3) == 0 && ((unsigned long long)A.s.frame & 3) == 0) {
+			unsigned *dw = (unsigned *)dd;
+#pragma unroll
+			for(int k = 0; k < 3; k++) dw[k] = bytes[4 * k] | (bytes[4 * k + 1] << 8) | (bytes[4 * k + 2] << 16) | (bytes[4 * k + 3] << 24);
+		} else {
+#pragma unroll
+			for(int l = 0; l < 4; l++)
+				if(xx + l < A.s.resx) { dd[l * 3 + 0] = (unsigned char)bytes[l * 3 + 0]; dd[l * 3 + 1] = (unsigned char)bytes[l * 3 + 1]; dd[l * 3 + 2] = (unsigned char)bytes[l * 3 + 2]; }
+		}
+	}
+}
+
+} // namespace SNAIL_DEV_NS

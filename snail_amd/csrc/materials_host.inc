@@ -1,0 +1,425 @@
+// materials_host.inc -- the C-ABI of include/snail_materials.h: ShTriangle records and mip chains on the host, the material set of a plain
+// scene, and the staged launches of materials.inc (primary hits -> k_mat_sample -> k_mat_light per (packet, light) -> k_mat_final).
+#include "../../include/snail_materials.h"
+
+struct SnailMaterials {
+	SnailScene *scene = nullptr;
+	int device = 0;
+	int nTris = 0, nMap = 0, nMats = 0, nTex = 0;
+	char *dBase = nullptr;   // ONE allocation: records, map, materials, texture descriptors, texels
+	const uint4 *dShTris = nullptr;
+	const int *dMap = nullptr;
+	const dev::MatRec *dMats = nullptr;
+	const dev::TexRec *dTex = nullptr;
+	const unsigned char *dTexels = nullptr;
+	// intermediates of the lit frames, one set per launch in flight (round-robin, each guarded by an event; booked under the scene's lock)
+	struct Bufs {
+		float *hitT = nullptr, *hitU = nullptr, *hitV = nullptr, *samples = nullptr, *sDist = nullptr;
+		int *hitId = nullptr;
+		static size_t bytes(size_t np, int nLights) { return np * 256 * 4 * (size_t)(4 + 9 + (nLights > 0 ? nLights : 0)); }
+		void carve(char *base, size_t np) {
+			const size_t plane = np * 256 * 4;
+			hitT = (float *)base; hitU = (float *)(base + plane); hitV = (float *)(base + 2 * plane); hitId = (int *)(base + 3 * plane);
+			samples = (float *)(base + 4 * plane); sDist = (float *)(base + 13 * plane);
+		}
+	};
+	struct Set {
+		char *base = nullptr;
+		size_t packets = 0;
+		int lights = 0;
+		hipEvent_t done = nullptr;
+		bool used = false;
+	};
+	enum { kSets = 8 };
+	Set set[kSets];
+	unsigned setCount = 0;
+	struct FrameList { int pw, ph; int32_t *d; };
+	std::vector<FrameList> frameLists;   // a whole frame's packet list, cached by packet-grid size
+};
+
+namespace {
+
+bool matPow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
+int matTexLevels(int w, int h) {
+	int m = w > h ? w : h, l = 0;
+	while((1 << l) < m) l++;
+	return l + 1;   // min(32, Log2(max(w, h)) + 1), src/mipmap_texture.cpp:106
+}
+size_t matLevelBytes(int w, int h, int m) {
+	const size_t lw = (size_t)std::max(w >> m, 1), lh = (size_t)std::max(h >> m, 1);
+	return 3 * lw * lh;
+}
+bool matTexShapeOK(int w, int h) { return matPow2(w) && matPow2(h) && w <= 8192 && h <= 8192; }
+
+int checkMaterials(const SnailMaterials *m, const char *fn) {
+	if(!m || !m->scene || !m->dBase) { snail_set_error("%s: invalid material set handle", fn); return 1; }
+	return checkScene(m->scene, fn);
+}
+int checkMatFrameArgs(const char *fn, const float cam[13], int resx, int resy, const float *lights7, int nLights, const float ambient[3], int flags) {
+	if(flags) { snail_set_error("%s: flags must be 0 (got 0x%x): no bounce, transparency or antialiasing under full shading yet", fn, flags); return 1; }
+	if(!cam || resx <= 0 || resy <= 0 || nLights < 0 || nLights > SNAIL_MAX_LIGHTS || (nLights && !lights7) || !ambient) {
+		snail_set_error("%s: bad arguments (camera, resolution, at most %d lights, ambient)", fn, SNAIL_MAX_LIGHTS);
+		return 1;
+	}
+	return 0;
+}
+
+void matFillArgs(const SnailMaterials *m, dev::MatArgs &A, const float cam[13], int resx, int resy, const int32_t *dXY, int np) {
+	const SnailScene *s = m->scene;
+	memset(&A, 0, sizeof(A));
+	A.s.hostTab = s->arith == SNAIL_ARITH_HOST_SSE ? s->dTab : nullptr;
+	A.s.nodes = s->dNodes; A.s.tris = s->dTris; A.s.pf = (const uint4 *)s->dPF;
+	A.s.g = makeGen(cam, resx, resy);
+	A.s.resx = resx; A.s.resy = resy; A.s.pw = (resx + 15) / 16; A.s.ph = (resy + 15) / 16;
+	A.s.fastOK = s->fastOK && originSane(cam);
+	A.s.pack = stackPack(s);
+	A.s.packetXY = (const int2 *)dXY; A.s.nPackets = np; A.s.nBlocks = np;
+	A.shtris = m->dShTris; A.nTris = m->nTris;
+	A.matMap = m->dMap; A.nMap = m->nMap;
+	A.mats = m->dMats; A.nMats = m->nMats;
+	A.tex = m->dTex; A.texels = m->dTexels;
+}
+
+// the stages of one lit frame over the packet list dXY into `frame` (or packet-major `bgrPackets`), intermediates in W; the scene's mu held
+int matShade(SnailMaterials *m, const char *fn, const float cam[13], int resx, int resy, const int32_t *dXY, int np, const float *lights7, int nLights,
+			 const float ambient[3], uint8_t *frame, int pitch, uint8_t *bgrPackets, const SnailMaterials::Bufs &W, uint64_t *dStats, hipStream_t st) {
+	SnailScene *s = m->scene;
+	SceneUse use(s, st);
+	if(use.rc) return use.rc;
+	if(int rc = launchPrimary(s, cam, resx, resy, 0, 0, 0, 0, dXY, np, W.hitT, W.hitU, W.hitV, W.hitId, dStats, st)) return rc;
+	dev::MatArgs A;
+	matFillArgs(m, A, cam, resx, resy, dXY, np);
+	A.s.nLights = nLights;
+	for(int n = 0; n < nLights; n++) for(int k = 0; k < 7; k++) A.s.lights[n][k] = lights7[n * 7 + k];
+	for(int c = 0; c < 3; c++) { A.s.ambient[c] = ambient[c]; A.s.color[c] = 1.0f; }
+	A.s.hitT = W.hitT; A.s.hitId = W.hitId; A.hitU = W.hitU; A.hitV = W.hitV;
+	A.samples = W.samples; A.s.sDist = W.sDist;
+	A.s.frame = frame; A.s.pitch = pitch; A.s.bgrPackets = bgrPackets;
+	A.s.stats = (dev::u64 *)dStats;
+	const bool sse = s->arith == SNAIL_ARITH_HOST_SSE;
+	const dim3 grid(np), wave(64);
+	SNAIL_LAUNCH(sse, MatArgs, grid, wave, 0, st, A, k_mat_sample);
+	HIP_TRY(hipGetLastError());
+	if(nLights) {
+		int relWhich[SNAIL_MAX_LIGHTS];
+		for(int n = 0; n < SNAIL_MAX_LIGHTS; n++) { relWhich[n] = -1; A.s.relLight[n] = nullptr; }
+		// every origin-relative copy taken here is booked as used on st on EVERY way out (first error kept): a copy whose fill was enqueued must not
+		// be recycled under it, whether or not the walk that wanted it was launched
+		int lrc = 0;
+		if(A.s.pack && !useDeep(s))
+			for(int n = 0; n < nLights && !lrc; n++) lrc = relFor(s, A.s.lights[n], st, &A.s.relLight[n], &relWhich[n]);
+		if(!lrc) {
+			const dim3 lgrid(np, nLights);
+			if(useDeep(s)) SNAIL_LAUNCH(sse, MatArgs, lgrid, wave, 0, st, A, k_mat_light<true>);
+			else SNAIL_LAUNCH(sse, MatArgs, lgrid, wave, 0, st, A, k_mat_light<false>);
+			const hipError_t e = hipGetLastError();
+			if(e != hipSuccess) { snail_set_error("%s: k_mat_light: %s", fn, hipGetErrorString(e)); lrc = 100 + (int)e; }
+		}
+		for(int n = 0; n < nLights; n++)
+			if(relWhich[n] >= 0) { const int urc = relUsed(s, relWhich[n], st); if(!lrc) lrc = urc; }
+		if(lrc) return lrc;
+	}
+	SNAIL_LAUNCH(sse, MatArgs, grid, wave, 0, st, A, k_mat_final);
+	HIP_TRY(hipGetLastError());
+	return 0;
+}
+
+// the packet list of a whole frame, cached in the set by packet-grid size (the scene's mu held)
+int matFrameList(SnailMaterials *m, int resx, int resy, const int32_t **dXY, int *np) {
+	const int pw = (resx + 15) / 16, ph = (resy + 15) / 16;
+	*np = pw * ph;
+	for(auto &f : m->frameLists)
+		if(f.pw == pw && f.ph == ph) { *dXY = f.d; return 0; }
+	if(m->frameLists.size() >= 16) {
+		HIP_TRY(hipDeviceSynchronize());
+		for(auto &f : m->frameLists) (void)hipFree(f.d);
+		m->frameLists.clear();
+	}
+	std::vector<int32_t> xy((size_t)pw * ph * 2);
+	for(int y = 0; y < ph; y++)
+		for(int x = 0; x < pw; x++) { xy[((size_t)y * pw + x) * 2] = x * 16; xy[((size_t)y * pw + x) * 2 + 1] = y * 16; }
+	SnailMaterials::FrameList f = {pw, ph, nullptr};
+	HIP_TRY(hipMalloc((void **)&f.d, xy.size() * 4));
+	if(hipMemcpy(f.d, xy.data(), xy.size() * 4, hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(f.d); snail_set_error("frame packet list: upload failed"); return 1; }
+	m->frameLists.push_back(f);
+	*dXY = f.d;
+	return 0;
+}
+
+// snail_render_materials_dev / _packets_dev (the scene's mu held): the next set of intermediates, grown if need be, its previous user waited for on st
+int matShadeDev(SnailMaterials *m, const char *fn, const float cam[13], int resx, int resy, const int32_t *dXY, int np, const float *lights7, int nLights,
+				const float ambient[3], uint8_t *frame, int pitch, uint8_t *bgrPackets, uint64_t *dStats, hipStream_t st) {
+	if(!dXY) { if(int rc = matFrameList(m, resx, resy, &dXY, &np)) return rc; }
+	SnailMaterials::Set &W = m->set[m->setCount++ % SnailMaterials::kSets];
+	if(!W.base || W.packets < (size_t)np || W.lights < nLights) {   // grown: its previous user may still be running
+		HIP_TRY(hipDeviceSynchronize());
+		if(W.base) (void)hipFree(W.base);
+		const size_t packets = std::max(W.packets, (size_t)np);
+		const int lights = std::max(W.lights, nLights);
+		W.base = nullptr; W.packets = 0; W.lights = 0; W.used = false;
+		HIP_TRY(hipMalloc((void **)&W.base, SnailMaterials::Bufs::bytes(packets, lights)));
+		W.packets = packets; W.lights = lights;
+	}
+	if(!W.done) HIP_TRY(hipEventCreateWithFlags(&W.done, hipEventDisableTiming));
+	if(W.used) HIP_TRY(hipStreamWaitEvent(st, W.done, 0));
+	SnailMaterials::Bufs B;
+	B.carve(W.base, (size_t)np);
+	const int rc = matShade(m, fn, cam, resx, resy, dXY, np, lights7, nLights, ambient, frame, pitch, bgrPackets, B, dStats, st);
+	// also when a stage failed after earlier ones were enqueued: they may still be running on these buffers, and the set's next user (on any
+	// stream) must come after them.  Should the record itself fail, the set is marked grown-from-scratch: its next user synchronises the device.
+	if(hipEventRecord(W.done, st) == hipSuccess) W.used = true;
+	else {
+		W.packets = 0; W.used = false;
+		if(!rc) { snail_set_error("%s: hipEventRecord failed", fn); return 1; }
+	}
+	return rc;
+}
+
+} // namespace
+
+extern "C" {
+
+int snail_shtris_pack(const float *uv6, const float *nrm9, const int32_t *matIdx, const uint8_t *flat, int n, const int32_t *perm, void *out64) {
+	if(n < 0 || (n && (!uv6 || !nrm9 || !matIdx || !out64))) { snail_set_error("snail_shtris_pack: null array"); return 1; }
+	for(int i = 0; i < n; i++) {
+		const int src = perm ? perm[i] : i;
+		if(src < 0 || src >= n) { snail_set_error("snail_shtris_pack: perm[%d] = %d is outside 0..%d", i, src, n - 1); return 1; }
+		const float *uv = uv6 + (size_t)src * 6, *nr = nrm9 + (size_t)src * 9;
+		for(int k = 0; k < 6; k++)
+			if(!(std::fabs(uv[k]) < 1048576.0f)) { snail_set_error("snail_shtris_pack: triangle %d: texture coordinate not finite or not below 2^20", src); return 1; }
+		for(int k = 0; k < 9; k++)
+			if(!std::isfinite(nr[k])) { snail_set_error("snail_shtris_pack: triangle %d: normal not finite", src); return 1; }
+		if(matIdx[src] < 0) { snail_set_error("snail_shtris_pack: triangle %d: negative material index", src); return 1; }
+		float o[15];
+		// the ShTriangle constructor (src/triangle.h:188-208): elements 1 and 2 minus element 0, in fp32
+		o[0] = uv[0]; o[1] = uv[1];
+		o[2] = uv[2] - uv[0]; o[3] = uv[3] - uv[1];
+		o[4] = uv[4] - uv[0]; o[5] = uv[5] - uv[1];
+		for(int c = 0; c < 3; c++) { o[6 + c] = nr[c]; o[9 + c] = nr[3 + c] - nr[c]; o[12 + c] = nr[6 + c] - nr[c]; }
+		char *rec = (char *)out64 + (size_t)i * 64;
+		memcpy(rec, o, 60);
+		const uint32_t id = (uint32_t)matIdx[src] | ((flat && flat[src]) ? 0x80000000u : 0u);
+		memcpy(rec + 60, &id, 4);
+	}
+	return 0;
+}
+
+int64_t snail_texture_size(int w, int h, int *nLevels) {
+	if(nLevels) *nLevels = 0;
+	if(!matTexShapeOK(w, h)) return 0;
+	const int levels = matTexLevels(w, h);
+	size_t total = 0;
+	for(int m = 0; m < levels; m++) total += matLevelBytes(w, h, m);
+	if(nLevels) *nLevels = levels;
+	return (int64_t)total;
+}
+
+int snail_texture_build(const uint8_t *level0, int w, int h, uint8_t *out, int64_t cap, int *nLevels) {
+	if(!matTexShapeOK(w, h)) { snail_set_error("snail_texture_build: %d x %d: width and height must be powers of two of at most 8192", w, h); return 1; }
+	int levels = 0;
+	const int64_t total = snail_texture_size(w, h, &levels);
+	if(!level0 || !out || cap < total) { snail_set_error("snail_texture_build: null buffer, or fewer than the %lld bytes of a %d x %d texture", (long long)total, w, h); return 1; }
+	memcpy(out, level0, (size_t)w * h * 3);
+	// What MipmapTexture::GenMip computes for rgb8 (src/mipmap_texture.cpp:256-285), level by level inside the one buffer, by byte index:
+	//   one row on both levels (:259-265)   pixel x, channel c = (lo[6x + c] + lo[6x + 4 + c]) / 2 -- the partner byte is 4 on, not 3 (the rgba8
+	//                                        stride), so channels mix across the pair and the last pair's blue reads lo[6x + 6]: the first byte of
+	//                                        the level being written (already stored: channels go in order), which follows in this buffer
+	//   one column on both levels (:266-272) the byte and the one a row below, / 2
+	//   otherwise (:273-283)                 the 2 x 2 block's four bytes of the channel, / 4
+	// Sums in unsigned, integer division.  (lo and hi alias one buffer on purpose: no restrict, stores in the order x, then channel.)
+	size_t at = 0;   // first byte of the level read
+	for(int m = 1; m < levels; m++) {
+		const size_t loW = (size_t)std::max(w >> (m - 1), 1), loH = (size_t)std::max(h >> (m - 1), 1);
+		const size_t hiW = (size_t)std::max(w >> m, 1), hiH = (size_t)std::max(h >> m, 1);
+		const size_t loRow = 3 * loW, hiRow = 3 * hiW;
+		const uint8_t *lo = out + at;
+		uint8_t *hi = out + at + loRow * loH;
+		if(loH == hiH) {
+			for(size_t x = 0; x < hiW; x++)
+				for(size_t c = 0; c < 3; c++) hi[3 * x + c] = (uint8_t)(((unsigned)lo[6 * x + c] + (unsigned)lo[6 * x + 4 + c]) / 2u);
+		} else if(loW == hiW) {
+			for(size_t y = 0; y < hiH; y++)
+				for(size_t c = 0; c < 3; c++) hi[y * hiRow + c] = (uint8_t)(((unsigned)lo[2 * y * loRow + c] + (unsigned)lo[(2 * y + 1) * loRow + c]) / 2u);
+		} else {
+			for(size_t y = 0; y < hiH; y++)
+				for(size_t x = 0; x < hiW; x++) {
+					const uint8_t *q = lo + 2 * y * loRow + 6 * x;   // the block's upper left pixel
+					for(size_t c = 0; c < 3; c++)
+						hi[y * hiRow + 3 * x + c] = (uint8_t)(((unsigned)q[c] + (unsigned)q[3 + c] + (unsigned)q[loRow + c] + (unsigned)q[loRow + 3 + c]) / 4u);
+				}
+		}
+		at += loRow * loH;
+	}
+	if(nLevels) *nLevels = levels;
+	return 0;
+}
+
+SnailMaterials *snail_materials_create(SnailScene *scene, const void *shtris64, int nTris, const int32_t *matMap, int nMap, const SnailMaterial *mats, int nMats,
+									   const SnailTexture *textures, int nTex) {
+	const char *fn = "snail_materials_create";
+	if(nTris <= 0 || nMap <= 0 || nMats < 0 || nTex < 0 || !shtris64 || !matMap || (nMats && !mats) || (nTex && !textures)) {
+		snail_set_error("%s: bad counts or null arrays (at least one triangle and one map entry)", fn);
+		return nullptr;
+	}
+	for(int k = 0; k < nTex; k++) {
+		if(!matTexShapeOK(textures[k].width, textures[k].height)) {
+			snail_set_error("%s: texture %d is %d x %d: width and height must be powers of two of at most 8192", fn, k, textures[k].width, textures[k].height);
+			return nullptr;
+		}
+		if(!textures[k].levels) { snail_set_error("%s: texture %d has no texels", fn, k); return nullptr; }
+	}
+	for(int k = 0; k < nMats; k++) {
+		const SnailMaterial &M = mats[k];
+		if(M.kind == SNAIL_MAT_TRANSPARENT) { snail_set_error("%s: material %d is of the transparent kind: transparency under full shading stays with the host renderer", fn, k); return nullptr; }
+		if(M.kind != SNAIL_MAT_SIMPLE && M.kind != SNAIL_MAT_TEX && M.kind != SNAIL_MAT_UBER) { snail_set_error("%s: material %d: unknown kind %d", fn, k, M.kind); return nullptr; }
+		if(M.kind == SNAIL_MAT_UBER && !(M.dissolve <= 0.0f || M.dissolve >= 1.0f)) {
+			snail_set_error("%s: material %d: UBER with dissolve %g could select a transparent lane (accepted: dissolve <= 0 or >= 1)", fn, k, (double)M.dissolve);
+			return nullptr;
+		}
+		if(M.kind == SNAIL_MAT_TEX && (M.texture < 0 || M.texture >= nTex)) { snail_set_error("%s: material %d: texture index %d outside 0..%d", fn, k, M.texture, nTex - 1); return nullptr; }
+	}
+	for(int k = 0; k < nMap; k++)
+		if(matMap[k] < -1 || matMap[k] >= nMats) { snail_set_error("%s: map entry %d = %d is outside -1..%d", fn, k, matMap[k], nMats - 1); return nullptr; }
+	for(int i = 0; i < nTris; i++) {
+		uint32_t id;
+		memcpy(&id, (const char *)shtris64 + (size_t)i * 64 + 60, 4);
+		if((int)(id & 0x7fffffffu) >= nMap) { snail_set_error("%s: record %d: material index %u outside the map of %d entries", fn, i, id & 0x7fffffffu, nMap); return nullptr; }
+	}
+	if(checkScene(scene, fn)) return nullptr;
+	if(nTris != scene->nTris) { snail_set_error("%s: %d records for a scene of %d triangles", fn, nTris, scene->nTris); return nullptr; }
+
+	// the device copy
+	std::vector<dev::MatRec> recs((size_t)std::max(nMats, 1));
+	memset(recs.data(), 0, recs.size() * sizeof(dev::MatRec));
+	for(int k = 0; k < nMats; k++) {
+		dev::MatRec &R = recs[k];
+		R.kind = mats[k].kind; R.ndotr = mats[k].nDotR ? 1 : 0; R.tex = mats[k].kind == SNAIL_MAT_TEX ? mats[k].texture : 0;
+		for(int c = 0; c < 3; c++) { R.col[c] = mats[k].diffuse[c]; R.spec[c] = mats[k].specular[c]; }
+		if(mats[k].kind == SNAIL_MAT_UBER) std::swap(R.col[0], R.col[2]);   // UberMaterial::UberMaterial: Swap(diffuse.x, diffuse.z)
+	}
+	std::vector<dev::TexRec> trecs((size_t)std::max(nTex, 1));
+	memset(trecs.data(), 0, trecs.size() * sizeof(dev::TexRec));
+	size_t texelBytes = 0;
+	for(int k = 0; k < nTex; k++) {
+		dev::TexRec &T = trecs[k];
+		T.base = texelBytes; T.w = textures[k].width; T.h = textures[k].height; T.mips = matTexLevels(T.w, T.h);
+		size_t off = 0;
+		for(int l = 0; l < T.mips; l++) { T.lvl[l] = (unsigned)off; off += matLevelBytes(T.w, T.h, l); }
+		texelBytes += (off + 4 + 15) & ~(size_t)15;   // 4 bytes of padding: a tap may be read as 4 bytes
+	}
+	typedef HostCallScope H;
+	const size_t oTris = 0, oMap = oTris + H::pad((size_t)nTris * 64), oMats = oMap + H::pad((size_t)nMap * 4), oTex = oMats + H::pad(recs.size() * sizeof(dev::MatRec)),
+				 oTexels = oTex + H::pad(trecs.size() * sizeof(dev::TexRec)), total = oTexels + H::pad(texelBytes + 16);
+	DeviceGuard guard(scene->device);
+	char *base = nullptr;
+	hipError_t e = hipMalloc((void **)&base, total);
+	if(e == hipSuccess) e = hipMemset(base, 0, total);
+	if(e == hipSuccess) e = hipMemcpy(base + oTris, shtris64, (size_t)nTris * 64, hipMemcpyHostToDevice);
+	if(e == hipSuccess) e = hipMemcpy(base + oMap, matMap, (size_t)nMap * 4, hipMemcpyHostToDevice);
+	if(e == hipSuccess) e = hipMemcpy(base + oMats, recs.data(), recs.size() * sizeof(dev::MatRec), hipMemcpyHostToDevice);
+	if(e == hipSuccess) e = hipMemcpy(base + oTex, trecs.data(), trecs.size() * sizeof(dev::TexRec), hipMemcpyHostToDevice);
+	for(int k = 0; k < nTex && e == hipSuccess; k++)
+		e = hipMemcpy(base + oTexels + trecs[k].base, textures[k].levels, (size_t)snail_texture_size(trecs[k].w, trecs[k].h, nullptr), hipMemcpyHostToDevice);
+	if(e != hipSuccess) {
+		snail_set_error("%s: device copy failed: %s", fn, hipGetErrorString(e));
+		if(base) (void)hipFree(base);
+		return nullptr;
+	}
+	SnailMaterials *m = new SnailMaterials();
+	m->scene = scene; m->device = scene->device;
+	m->nTris = nTris; m->nMap = nMap; m->nMats = nMats; m->nTex = nTex;
+	m->dBase = base;
+	m->dShTris = (const uint4 *)(base + oTris); m->dMap = (const int *)(base + oMap); m->dMats = (const dev::MatRec *)(base + oMats);
+	m->dTex = (const dev::TexRec *)(base + oTex); m->dTexels = (const unsigned char *)(base + oTexels);
+	return m;
+}
+
+void snail_materials_destroy(SnailMaterials *m) {
+	if(!m) return;
+	DeviceGuard guard(m->device);
+	(void)hipDeviceSynchronize();
+	for(auto &W : m->set) {
+		if(W.base) (void)hipFree(W.base);
+		if(W.done) (void)hipEventDestroy(W.done);
+	}
+	for(auto &f : m->frameLists) (void)hipFree(f.d);
+	if(m->dBase) (void)hipFree(m->dBase);
+	delete m;
+}
+
+int snail_materials_shade_packets_dev(SnailMaterials *m, const float cam[13], int resx, int resy, const int32_t *dPacketXY, int nPackets, const float *dT,
+									  const float *dU, const float *dV, const int32_t *dTriId, float *dSamples, void *stream) {
+	const char *fn = "snail_materials_shade_packets_dev";
+	if(int rc = checkMaterials(m, fn)) return rc;
+	if(nPackets <= 0) return 0;
+	if(!cam || resx <= 0 || resy <= 0 || !dPacketXY || !dT || !dU || !dV || !dTriId || !dSamples || ((unsigned long long)dSamples & 15)) {
+		snail_set_error("%s: bad camera or resolution, a null buffer, or samples not 16-byte aligned", fn);
+		return 1;
+	}
+	DeviceGuard guard(m->device);
+	SNAIL_LOCK(m->scene);
+	dev::MatArgs A;
+	matFillArgs(m, A, cam, resx, resy, dPacketXY, nPackets);
+	A.s.hitT = dT; A.s.hitId = dTriId; A.hitU = dU; A.hitV = dV;
+	A.samples = dSamples;
+	const bool sse = m->scene->arith == SNAIL_ARITH_HOST_SSE;
+	SNAIL_LAUNCH(sse, MatArgs, dim3(nPackets), dim3(64), 0, (hipStream_t)stream, A, k_mat_sample);
+	HIP_TRY(hipGetLastError());
+	return 0;
+}
+
+int snail_render_materials_dev(SnailMaterials *m, const float cam[13], int resx, int resy, const float *lights7, int nLights, const float ambient[3], int flags,
+							   uint8_t *frame, int pitch, uint64_t *dStats, void *stream) {
+	const char *fn = "snail_render_materials_dev";
+	if(int rc = checkMatFrameArgs(fn, cam, resx, resy, lights7, nLights, ambient, flags)) return rc;
+	if(int rc = checkMaterials(m, fn)) return rc;
+	if(!frame || pitch < resx * 3) { snail_set_error("%s: null frame or a pitch below 3 * resx", fn); return 1; }
+	DeviceGuard guard(m->device);
+	SNAIL_LOCK(m->scene);
+	return matShadeDev(m, fn, cam, resx, resy, nullptr, 0, lights7, nLights, ambient, frame, pitch, nullptr, dStats, (hipStream_t)stream);
+}
+
+int snail_render_materials_packets_dev(SnailMaterials *m, const float cam[13], int resx, int resy, const int32_t *dPacketXY, int nPackets, const float *lights7,
+									   int nLights, const float ambient[3], int flags, uint8_t *bgrPackets, uint64_t *dStats, void *stream) {
+	const char *fn = "snail_render_materials_packets_dev";
+	if(int rc = checkMatFrameArgs(fn, cam, resx, resy, lights7, nLights, ambient, flags)) return rc;
+	if(int rc = checkMaterials(m, fn)) return rc;
+	if(!dPacketXY && nPackets > 0) { snail_set_error("%s: null packet list", fn); return 1; }
+	if(nPackets <= 0) return 0;
+	if(!bgrPackets || ((unsigned long long)bgrPackets & 3)) { snail_set_error("%s: null or unaligned output", fn); return 1; }
+	DeviceGuard guard(m->device);
+	SNAIL_LOCK(m->scene);
+	return matShadeDev(m, fn, cam, resx, resy, dPacketXY, nPackets, lights7, nLights, ambient, nullptr, 0, bgrPackets, dStats, (hipStream_t)stream);
+}
+
+int snail_render_materials_image(SnailMaterials *m, const float cam[13], int resx, int resy, const float *lights7, int nLights, const float ambient[3], int flags,
+								 uint8_t *image, int pitch, uint64_t stats[4]) {
+	const char *fn = "snail_render_materials_image";
+	if(int rc = checkMatFrameArgs(fn, cam, resx, resy, lights7, nLights, ambient, flags)) return rc;
+	if(int rc = checkMaterials(m, fn)) return rc;
+	if(!image || pitch < resx * 3) { snail_set_error("%s: null image or a pitch below 3 * resx", fn); return 1; }
+	DeviceGuard guard(m->device);
+	HostCallScope hc(m->scene, fn);
+	if(hc.rc) return hc.rc;
+	if(int rc = hc.zeroStats()) return rc;
+	const int pw = (resx + 15) / 16, ph = (resy + 15) / 16, np = pw * ph;
+	std::vector<int32_t> xy((size_t)np * 2);
+	for(int y = 0; y < ph; y++)
+		for(int x = 0; x < pw; x++) { xy[((size_t)y * pw + x) * 2] = x * 16; xy[((size_t)y * pw + x) * 2 + 1] = y * 16; }
+	typedef HostCallScope H;
+	const size_t imgBytes = (size_t)pitch * resy, bufBytes = SnailMaterials::Bufs::bytes((size_t)np, nLights);
+	if(int rc = hc.reserve(H::pad(xy.size() * 4) + H::pad(bufBytes) + H::pad(imgBytes + 4))) return rc;
+	void *dXY = nullptr;
+	if(int rc = hc.put(&dXY, xy.data(), xy.size() * 4)) return rc;
+	SnailMaterials::Bufs W;
+	W.carve((char *)hc.carve(bufBytes), (size_t)np);
+	uint8_t *dImg = (uint8_t *)hc.carve(imgBytes + 4);
+	{
+		SNAIL_LOCK(m->scene);
+		if(int rc = matShade(m, fn, cam, resx, resy, (const int32_t *)dXY, np, lights7, nLights, ambient, dImg, pitch, nullptr, W, hc.stats(), hc.stream())) return rc;
+	}
+	HIP_TRY(hipMemcpy2DAsync(image, (size_t)pitch, dImg, (size_t)pitch, (size_t)resx * 3, (size_t)resy, hipMemcpyDeviceToHost, hc.stream()));
+	return hc.finish(stats);
+}
+
+} // extern "C"

@@ -78,6 +78,7 @@ void snail_set_error(const char *fmt, ...) {
 #include "snail_dev.inc"
 #include "instances.inc"
 #include "instances_shade.inc"
+#include "materials.inc"
 #undef SNAIL_DEV_NS
 #undef SNAIL_ARITH_SSE
 #define SNAIL_DEV_NS dev_sse
@@ -85,6 +86,7 @@ void snail_set_error(const char *fmt, ...) {
 #include "snail_dev.inc"
 #include "instances.inc"
 #include "instances_shade.inc"
+#include "materials.inc"
 #undef SNAIL_DEV_NS
 #undef SNAIL_ARITH_SSE
 #include "heatmap.inc"           // the heat-map store stage: plain fp32, once for both arithmetics (its C-ABI: heatmap_host.inc)
@@ -1732,3 +1734,4 @@ int snail_account_primary(SnailScene *s, const float cam[13], int resx, int resy
 #include "instances_host.inc"
 #include "instances_tiles_host.inc"
 #include "heatmap_host.inc"
+#include "materials_host.inc"

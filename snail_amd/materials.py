@@ -1,0 +1,207 @@
+"""Full shading of plain scenes: the host-side mirror of the reference's shading data -- ShTriangle records, shading::Material objects
+and MipmapTexture / PointSampler -- over the C-ABI of include/snail_materials.h.
+
+  Texture(level0)                                   <-> MipmapTexture(image, rgb8) + GenMips, sampled by sampling::PointSampler
+  Material.simple / .textured / .uber               <-> SimpleMaterial<NDotR>, TexMaterial<NDotR>, UberMaterial(MaterialDesc)
+  pack_shtris(uv, nrm, mat_index, flat, perm)       <-> the ShTriangle constructor + the builder's permutation of shTris
+  MaterialSet(scene, uv, nrm, mat_index, flat, material_map, materials, textures)   <-> BVH::shTris / BVH::materials + Scene::materials
+  .shade_packets / .render / .render_packets / .render_image_host   <-> Scene::RayTrace with gVals[6] && HasShadingData(), primary packets
+
+Out of this module (the host renderer keeps them): the bounce and transparency under full shading, 4x AA, tile lists, OBJ / MTL ingest."""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from .scene import Scene, _stream_ptr, _torch
+
+KIND_SIMPLE, KIND_TEX, KIND_UBER, KIND_TRANSPARENT = 0, 1, 2, 3
+MATERIAL_DTYPE = np.dtype([("kind", "<i4"), ("ndotr", "<i4"), ("diffuse", "<f4", 3), ("specular", "<f4", 3), ("dissolve", "<f4"), ("texture", "<i4")])
+assert MATERIAL_DTYPE.itemsize == 40
+SAMPLE_COMPONENTS = 9        # normal, diffuse, specular
+
+
+def texture_size(w: int, h: int):
+    """(bytes of the mip chain, levels); SnailError for a shape that is refused"""
+    n = C.c_int(0)
+    b = _lib.lib().snail_texture_size(int(w), int(h), C.addressof(n))
+    if b <= 0:
+        raise _lib.SnailError("texture %d x %d: width and height must be powers of two of at most 8192" % (w, h))
+    return int(b), n.value
+
+
+class Texture:
+    """An rgb8 texture with its mip chain (snail_texture_build): level0 = uint8 [h, w, 3] in the byte order the sampler reads (byte 0 -> red)."""
+
+    def __init__(self, level0):
+        a = np.ascontiguousarray(level0, dtype=np.uint8)
+        if a.ndim != 3 or a.shape[2] != 3:
+            raise ValueError("level0 must be uint8 [h, w, 3]")
+        self.height, self.width = int(a.shape[0]), int(a.shape[1])
+        size, _ = texture_size(self.width, self.height)
+        self.levels = np.zeros(size, dtype=np.uint8)
+        n = C.c_int(0)
+        _lib.check(_lib.lib().snail_texture_build(_lib.ptr(a), self.width, self.height, _lib.ptr(self.levels), size, C.addressof(n)), "snail_texture_build")
+        self.n_levels = n.value
+
+
+class Material:
+    """One record of MATERIAL_DTYPE."""
+
+    def __init__(self, kind, ndotr=True, diffuse=(1.0, 1.0, 1.0), specular=(0.0, 0.0, 0.0), dissolve=0.0, texture=0):
+        self.rec = np.zeros((), dtype=MATERIAL_DTYPE)
+        self.rec["kind"], self.rec["ndotr"], self.rec["diffuse"], self.rec["specular"] = int(kind), 1 if ndotr else 0, diffuse, specular
+        self.rec["dissolve"], self.rec["texture"] = dissolve, int(texture)
+
+    @classmethod
+    def simple(cls, color, ndotr: bool = True):
+        return cls(KIND_SIMPLE, ndotr, diffuse=color)
+
+    @classmethod
+    def textured(cls, texture_index: int, ndotr: bool = True):
+        return cls(KIND_TEX, ndotr, texture=texture_index)
+
+    @classmethod
+    def uber(cls, diffuse, specular, dissolve: float = 0.0):
+        """MaterialDesc's diffuse / specular / dissolveFactor (the constructor's swap of diffuse.x and .z happens in the library)"""
+        return cls(KIND_UBER, True, diffuse=diffuse, specular=specular, dissolve=dissolve)
+
+    @classmethod
+    def transparent(cls):
+        """The TransparentMaterial kind: always refused by MaterialSet (kept so that a host can show the refusal)."""
+        return cls(KIND_TRANSPARENT)
+
+
+def pack_shtris(uv, nrm, mat_index, flat=None, perm=None) -> np.ndarray:
+    """snail_shtris_pack: uv [n, 3, 2], nrm [n, 3, 3], mat_index [n], flat [n] of the INPUT triangles -> uint8 [n, 64] records in triId order
+    (perm = BVH slot -> input triangle, e.g. HostBVH.perm)."""
+    uv = np.ascontiguousarray(uv, dtype=np.float32).reshape(-1, 6)
+    nr = np.ascontiguousarray(nrm, dtype=np.float32).reshape(-1, 9)
+    mi = np.ascontiguousarray(mat_index, dtype=np.int32).reshape(-1)
+    n = len(uv)
+    fl = np.zeros(n, dtype=np.uint8) if flat is None else np.ascontiguousarray(np.asarray(flat).astype(bool), dtype=np.uint8).reshape(-1)
+    pm = None if perm is None else np.ascontiguousarray(perm, dtype=np.int32).reshape(-1)
+    if len(nr) != n or len(mi) != n or len(fl) != n or (pm is not None and len(pm) != n):
+        raise ValueError("uv, nrm, mat_index, flat and perm must hold one entry per triangle")
+    out = np.zeros((n, 64), dtype=np.uint8)
+    _lib.check(_lib.lib().snail_shtris_pack(_lib.ptr(uv), _lib.ptr(nr), _lib.ptr(mi), _lib.ptr(fl), n, _lib.ptr(pm), _lib.ptr(out)), "snail_shtris_pack")
+    return out
+
+
+def _material_records(materials) -> np.ndarray:
+    recs = np.zeros(len(materials), dtype=MATERIAL_DTYPE)
+    for k, m in enumerate(materials):
+        recs[k] = m.rec
+    return recs
+
+
+def create_set(scene_handle, shtris, material_map, materials, textures):
+    """snail_materials_create over raw arguments -> handle (c_void_p); SnailError with the library's text when the set is refused"""
+    sh = np.ascontiguousarray(shtris, dtype=np.uint8).reshape(-1, 64)
+    mp = np.ascontiguousarray(material_map, dtype=np.int32).reshape(-1)
+    recs = _material_records(materials)
+
+    class _Tex(C.Structure):
+        _fields_ = [("levels", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32)]
+    tex = (_Tex * max(len(textures), 1))()
+    for k, t in enumerate(textures):
+        tex[k].levels, tex[k].width, tex[k].height = t.levels.ctypes.data, t.width, t.height
+    h = _lib.lib().snail_materials_create(scene_handle, _lib.ptr(sh), len(sh), _lib.ptr(mp), len(mp), _lib.ptr(recs) if len(recs) else None, len(recs),
+                                          C.cast(tex, C.c_void_p) if len(textures) else None, len(textures))
+    if not h:
+        raise _lib.SnailError("snail_materials_create: %s" % _lib.lib().snail_last_error().decode())
+    return C.c_void_p(h)
+
+
+class MaterialSet:
+    """The shading data of a plain scene on its GPU.  uv / nrm / mat_index / flat describe the INPUT triangles (the order the scene was built
+    from; scene.bvh.perm permutes them into triId order); material_map[i] = -1 (the default material) or an index into `materials`.
+    The scene is kept alive by this object.
+
+    The records are permuted ONCE, by the tree the scene holds now, so the scene must have been built from host triangles (Scene(HostBVH),
+    Scene.from_fast, Scene.from_lbvh).  A scene whose tree is built or rebuilt on the device (Scene.from_fast_dev / rebuild_fast_dev) is
+    refused: a rebuild renumbers the triangles, and a set made before it would shade every hit with another triangle's data."""
+
+    def __init__(self, scene: Scene, uv, nrm, mat_index, flat=None, material_map=(-1,), materials=(), textures=()):
+        self.scene = scene
+        self._h = None
+        if getattr(scene, "_fast_dev", False):
+            raise _lib.SnailError("MaterialSet: the scene's tree is built on the device (from_fast_dev) and may be rebuilt there, which renumbers "
+                                  "the triangles; build the scene from host triangles (Scene(HostBVH.build(..)), Scene.from_fast, Scene.from_lbvh)")
+        perm = getattr(scene.bvh, "perm", None)
+        if perm is None:
+            raise _lib.SnailError("MaterialSet: the scene carries no permutation (BVH slot -> input triangle), so its shading data cannot be put into triId order")
+        self.shtris = pack_shtris(uv, nrm, mat_index, flat, perm)
+        self._h = create_set(scene._h, self.shtris, material_map, list(materials), list(textures))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            _lib.lib().snail_materials_destroy(self._h)
+            self._h = None
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @staticmethod
+    def _lights(lights7):
+        return np.ascontiguousarray(lights7 if lights7 is not None else np.zeros((0, 7)), dtype=np.float32).reshape(-1, 7)
+
+    def shade_packets(self, cam, resx: int, resy: int, packet_xy, hits, out=None, stream=None):
+        """The samples of a packet list from its hit records (t, u, v, tri_id: packet-major [n, 256] device tensors, as Scene.trace_packets
+        returns them) -> float32 [n, 9, 64, 4]: normal xyz, diffuse rgb, specular rgb per (quad, lane).  snail_materials_shade_packets_dev."""
+        torch = _torch()
+        n = int(packet_xy.shape[0])
+        if out is None:
+            out = torch.empty((n, SAMPLE_COMPONENTS, 64, 4), dtype=torch.float32, device=self.scene._dev())
+        cam13 = np.ascontiguousarray(cam.as_array13(), dtype=np.float32)
+        rc = _lib.lib().snail_materials_shade_packets_dev(self._h, _lib.ptr(cam13), resx, resy, _lib.ptr(packet_xy), n, _lib.ptr(hits[0]), _lib.ptr(hits[1]),
+                                                          _lib.ptr(hits[2]), _lib.ptr(hits[3]), _lib.ptr(out), _stream_ptr(stream))
+        _lib.check(rc, "snail_materials_shade_packets_dev")
+        return out
+
+    def render(self, cam, resx: int, resy: int, lights7=None, ambient=(0.1, 0.1, 0.1), out=None, stats=None, stream=None, flags: int = 0):
+        """The lit frame, [resy, resx, 3] uint8 (B,G,R) (or `out`: a uint8 device tensor [resy, pitch] / [resy, w, 3] whose rows may be wider)."""
+        torch = _torch()
+        if out is None:
+            out = torch.zeros((resy, resx, 3), dtype=torch.uint8, device=self.scene._dev())
+        pitch = int(out.stride(0))
+        lights = self._lights(lights7)
+        cam13 = np.ascontiguousarray(cam.as_array13(), dtype=np.float32)
+        amb = np.ascontiguousarray(ambient, dtype=np.float32)
+        rc = _lib.lib().snail_render_materials_dev(self._h, _lib.ptr(cam13), resx, resy, _lib.ptr(lights) if len(lights) else None, len(lights), _lib.ptr(amb),
+                                                   int(flags), _lib.ptr(out), pitch, _lib.ptr(stats), _stream_ptr(stream))
+        _lib.check(rc, "snail_render_materials_dev")
+        return out
+
+    def render_packets(self, cam, resx: int, resy: int, packet_xy, lights7=None, ambient=(0.1, 0.1, 0.1), out=None, stats=None, stream=None, flags: int = 0):
+        """render for an explicit packet list: packet-major [n, 256, 3] uint8 (B,G,R)."""
+        torch = _torch()
+        n = int(packet_xy.shape[0])
+        if out is None:
+            out = torch.empty((n, 256, 3), dtype=torch.uint8, device=self.scene._dev())
+        lights = self._lights(lights7)
+        cam13 = np.ascontiguousarray(cam.as_array13(), dtype=np.float32)
+        amb = np.ascontiguousarray(ambient, dtype=np.float32)
+        rc = _lib.lib().snail_render_materials_packets_dev(self._h, _lib.ptr(cam13), resx, resy, _lib.ptr(packet_xy), n, _lib.ptr(lights) if len(lights) else None,
+                                                           len(lights), _lib.ptr(amb), int(flags), _lib.ptr(out), _lib.ptr(stats), _stream_ptr(stream))
+        _lib.check(rc, "snail_render_materials_packets_dev")
+        return out
+
+    def render_image_host(self, cam, resx: int, resy: int, lights7=None, ambient=(0.1, 0.1, 0.1), flags: int = 0, pitch: int | None = None, fill: int = 0):
+        """snail_render_materials_image: the frame in host memory, uint8 [resy, pitch] (pitch = 3 * resx unless given; bytes past a row's
+        pixels keep `fill`), and the call's TreeStats."""
+        pitch = resx * 3 if pitch is None else int(pitch)
+        img = np.full((resy, pitch), fill, dtype=np.uint8)
+        stats = np.zeros(4, dtype=np.uint64)
+        lights = self._lights(lights7)
+        cam13 = np.ascontiguousarray(cam.as_array13(), dtype=np.float32)
+        amb = np.ascontiguousarray(ambient, dtype=np.float32)
+        rc = _lib.lib().snail_render_materials_image(self._h, _lib.ptr(cam13), resx, resy, _lib.ptr(lights) if len(lights) else None, len(lights), _lib.ptr(amb),
+                                                     int(flags), _lib.ptr(img), pitch, _lib.ptr(stats))
+        _lib.check(rc, "snail_render_materials_image")
+        return img, stats

@@ -1,0 +1,148 @@
+"""What full shading costs: ms per 1920x1080 frame of the atrium stand-in with one light, IEEE arithmetic, of
+  whitted        snail_render_whitted_dev (simple shading; with --parent-lib PATH: of THAT build of libsnailhip.so, e.g. the parent commit's,
+                 loaded beside the product library; without it: of the product build, and labelled so),
+  default_flat   MaterialSet.render with every material the default and every triangle flat with its plane normal (the same picture),
+  textured       MaterialSet.render with the tests' textured set (tests/materials_cases.py: materials by input index mod 5, uv in [-3, 3],
+                 bent vertex normals),
+and the sample stage alone (snail_materials_shade_packets_dev over the frame's packets, textured set).  Every figure: device events around a
+window of --frames frames enqueued back to back (400: a fifth of a second per window for the frames), the variants alternating, --reps
+rounds, medians (and the spread).  For the sample stage that figure is the launch-to-launch interval of back-to-back launches, an upper bound
+on its kernel time; the kernel time itself comes from a kernel trace of a run of its own:
+    rocprofv3 --kernel-trace --stats -d DIR -- python tools/materials_time.py --trace 50
+(--trace N: N textured frames and N launches of the sample stage after the warm-up, nothing timed, nothing written).  The frames of
+whitted and default_flat are compared byte for byte before anything is timed.  No threshold: a measurement.  Writes the report to --out
+(default: stdout only).  The shading data comes from the tests' case helpers (tests/materials_cases.py: vertex_data, plane_normals,
+materials_mod5, TEXTURES), which are handed the product's HostBVH where they document an OracleScene -- they read only .tris["plane"] and
+.perm, which both carry; importing them imports tests/oracle_lib.py but never loads or builds the oracle library.
+
+    python tools/materials_time.py [--res 1920x1080] [--frames 400] [--reps 7] [--parent-lib PATH] [--out profiles/materials.txt] [--trace N]"""
+import argparse
+import ctypes as C
+import os
+import statistics
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from snail_amd import FPSCamera, HostBVH, _lib, scenes  # noqa: E402
+from snail_amd import materials as P  # noqa: E402
+from snail_amd.scene import Scene, _stream_ptr  # noqa: E402
+
+
+class ParentScene:
+    """snail_scene_create + snail_render_whitted_dev of another build of the library, through raw ctypes (the C-ABI of snail_hip.h)"""
+
+    def __init__(self, path, hb):
+        L = C.CDLL(path)
+        for name in ("snail_scene_create", "snail_render_whitted_dev", "snail_scene_destroy", "snail_last_error"):
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = _lib.SIGNATURES[name]
+        self.L = L
+        h = L.snail_scene_create(_lib.ptr(hb.nodes), hb.n_nodes, _lib.ptr(hb.tris), hb.n_tris, hb.depth, 0)
+        if not h:
+            raise RuntimeError("parent snail_scene_create: %s" % L.snail_last_error().decode())
+        self.h = C.c_void_p(h)
+
+    def render_whitted(self, cam13, resx, resy, lights, amb, col, out):
+        rc = self.L.snail_render_whitted_dev(self.h, _lib.ptr(cam13), resx, resy, _lib.ptr(lights), len(lights), _lib.ptr(amb), _lib.ptr(col), 0, _lib.ptr(out),
+                                             resx * 3, None, _stream_ptr(None))
+        if rc:
+            raise RuntimeError("parent snail_render_whitted_dev: %s" % self.L.snail_last_error().decode())
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--res", default="1920x1080")
+    ap.add_argument("--frames", type=int, default=400)
+    ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--detail", type=float, default=scenes.ATRIUM_DETAIL)
+    ap.add_argument("--parent-lib", default=None)
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--trace", type=int, default=0)
+    a = ap.parse_args()
+    resx, resy = (int(v) for v in a.res.split("x"))
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit("materials_time.py measures on the GPU; there is none here")
+    from tests import materials_cases as K
+
+    tv = scenes.atrium(detail=a.detail)
+    hb = HostBVH.build(tv)
+    sc = Scene(hb, 0)
+    pos, ang, pitch = scenes.atrium_camera()
+    cam = FPSCamera(pos, ang, pitch).camera()
+    cam13 = np.ascontiguousarray(cam.as_array13(), dtype=np.float32)
+    lo, hi = hb.bbox()
+    lights = np.array([[*(lo + (hi - lo) * np.array([0.5, 0.7, 0.5], dtype=np.float32)), 1.0, 0.9, 0.8, 2.0 * float((hi - lo).max())]], dtype=np.float32)
+    amb = np.full(3, 0.1, dtype=np.float32); white = np.ones(3, dtype=np.float32)
+
+    n = len(tv)
+    flat_set = P.MaterialSet(sc, np.zeros((n, 3, 2), np.float32), K.plane_normals(hb), np.zeros(n, np.int32), np.ones(n, bool))
+    uv, nrm, flat = K.vertex_data(hb, tv, 22)
+    descs, mmap = K.materials_mod5()
+    mats = [P.Material.simple(d[1], d[2]) if d[0] == "simple" else P.Material.textured(d[1], d[2]) if d[0] == "tex" else P.Material.uber(d[1], d[2], d[3]) for d in descs]
+    tex_set = P.MaterialSet(sc, uv, nrm, np.arange(n, dtype=np.int32) % 5, flat, mmap, mats, [P.Texture(t) for t in K.TEXTURES()])
+    parent = ParentScene(a.parent_lib, hb) if a.parent_lib else None
+
+    out = [torch.zeros((resy, resx, 3), dtype=torch.uint8, device="cuda:0") for _ in range(3)]
+    variants = {
+        "whitted": (lambda: parent.render_whitted(cam13, resx, resy, lights, amb, white, out[0])) if parent else (lambda: sc.render_whitted(cam, resx, resy, lights, out=out[0])),
+        "default_flat": lambda: flat_set.render(cam, resx, resy, lights, out=out[1]),
+        "textured": lambda: tex_set.render(cam, resx, resy, lights, out=out[2]),
+    }
+    for fn in variants.values():        # warm-up: code objects, the handles' scratch, the origin-relative node copies
+        fn(); fn()
+    torch.cuda.synchronize()
+    same = bool(torch.equal(out[0], out[1]))
+    # the sample stage alone
+    pw, ph = (resx + 15) // 16, (resy + 15) // 16
+    xy = torch.tensor([(x * 16, y * 16) for y in range(ph) for x in range(pw)], dtype=torch.int32, device="cuda:0")
+    hits = sc.trace_packets(cam, resx, resy, xy)
+    smp = tex_set.shade_packets(cam, resx, resy, xy, hits)
+    variants["sample_stage"] = lambda: tex_set.shade_packets(cam, resx, resy, xy, hits, out=smp)
+    torch.cuda.synchronize()
+    if a.trace:         # a run under a kernel trace: the launches, nothing else
+        for _ in range(a.trace):
+            variants["textured"]()
+        for _ in range(a.trace):
+            variants["sample_stage"]()
+        torch.cuda.synchronize()
+        print("trace run: %d textured frames, %d sample-stage launches" % (a.trace, a.trace))
+        return
+
+    times = {k: [] for k in variants}
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    for _ in range(a.reps):
+        for k, fn in variants.items():      # alternating: one window of each per round
+            e0.record()
+            for _ in range(a.frames):
+                fn()
+            e1.record()
+            e1.synchronize()
+            times[k].append(e0.elapsed_time(e1) / a.frames)
+    rays = pw * ph * 256
+    lines = ["full shading, %s, %dx%d (%d packets), one light, IEEE; %d rounds of %d frames per variant, alternating; ms per frame: median (min .. max)" %
+             ("atrium detail %.2f: %d triangles" % (a.detail, n), resx, resy, pw * ph, a.reps, a.frames),
+             "device: %s" % torch.cuda.get_device_name(0),
+             "whitted = snail_render_whitted_dev of %s" % ("the build given as --parent-lib" if parent else "THIS build (no --parent-lib given)"),
+             "default_flat frame equals the whitted frame byte for byte: %s" % same]
+    med = {}
+    for k, v in times.items():
+        med[k] = statistics.median(v)
+        lines.append("  %-13s %8.3f  (%.3f .. %.3f)" % (k, med[k], min(v), max(v)))
+    lines.append("default_flat - whitted: %+.3f ms; textured - whitted: %+.3f ms; sample stage, launch to launch: %.3f ms (an upper bound on its kernel time; %.1f GB/s over its 36 B/ray written + 16 B/ray of hit records read)"
+                 % (med["default_flat"] - med["whitted"], med["textured"] - med["whitted"], med["sample_stage"], rays * 52 / med["sample_stage"] / 1e6))
+    text = "\n".join(lines)
+    print(text)
+    if a.out:
+        with open(a.out, "w") as fh:
+            fh.write(text + "\n")
+    if not same:
+        raise SystemExit("default_flat and whitted frames differ")
+
+
+if __name__ == "__main__":
+    main()
