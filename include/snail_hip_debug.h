@@ -46,6 +46,10 @@ int snail_debug_anyorder(SnailScene *, const float cam[13], int resx, int resy, 
  * of this build}.  tools/occupancy.py. */
 int snail_debug_occupancy(int out[4]);
 
+/* The scene's origin-relative node array of `org` (taken from its cache, or filled as a launch from that origin would fill it): *count = the
+ * records that carry the "this node's box contains the origin" bit, which lets a primary packet's visit skip the box test. */
+int snail_debug_rel_flag_count(SnailScene *, const float org[3], int *count);
+
 #ifdef __cplusplus
 }
 #endif

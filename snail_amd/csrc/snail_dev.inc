@@ -1156,6 +1156,12 @@ __device__ __forceinline__ void walk(const uint4 *__restrict__ nodes, const uint
 //   and no shift on the far child's request; of a leaf record = 0x80000000 | byte offset of its first triangle record, count: the
 //   "near child" request of a leaf -- issued BEFORE its box test, as for any node -- fetches that triangle's line, which the leaf code
 //   would otherwise wait for from cold (a leaf's triangle loads are the longest stall of a packet's walk).
+//   An ORIGIN-RELATIVE copy of these records (k_rel_nodes*) additionally sets bit 31 of an inner record's word 7 when the node's box contains
+//   the origin (relOriginInside): every ray from that origin passes such a box, whatever its direction and for every distance >= 0, so a
+//   primary packet's visit of it needs no slab test (SNAIL_OIN_*, below).  The child order only looks at bits 0..2 of the word (sign16 is
+//   three bits wide in the shared-origin walks), so every other reader of a relative array ignores the bit.  Bit 31 and not a lower one: a
+//   leaf's word 7 is its triangle count, any value below 2^31 in a caller's tree, and the loop tests the bit before it knows the node's kind.
+#define SNAIL_REL_INSIDE_BIT 31
 #define SNAIL_MOV_REC(D0, D1, D2, D3, S0, S1, S2, S3)                                                                                       \
 	" s_mov_b64 " D0 ", " S0 "\n s_mov_b64 " D1 ", " S1 "\n s_mov_b64 " D2 ", " S2 "\n s_mov_b64 " D3 ", " S3 "\n"
 #define SNAIL_A_FROM_T SNAIL_MOV_REC("s[84:85]", "s[86:87]", "s[88:89]", "s[90:91]", "s[68:69]", "s[70:71]", "s[72:73]", "s[74:75]")
@@ -1197,11 +1203,46 @@ __device__ __forceinline__ void walk(const uint4 *__restrict__ nodes, const uint
 // the lane range of a stack word as an EXEC mask, kept for the top entry in %[alive] so that a pop only moves it
 #define SNAIL_PF2_ALIVE " s_sub_u32 %[cur], %[last], %[first]\n s_bfm_b64 %[alive], %[cur], %[first]\n s_bitset1_b64 %[alive], %[last]\n"
 #define SNAIL_PF2_FIRSTLAST " s_ff1_i32_b64 %[first], exec\n s_flbit_i32_b64 %[last], exec\n s_xor_b32 %[last], %[last], 63\n"
+// ---- visits of nodes that CONTAIN the packets' origin (primary packets over origin-relative records: the users whose TAIL is SNAIL_TAIL_POS) ----
+// Such a record carries SNAIL_REL_INSIDE_BIT.  Its relative near words are <= 0 and its far words >= 0, the reciprocal directions are finite
+// (the fast paths' precondition), so every near product is <= 0 and every far product >= 0 (or a zero of either sign; no 0 x inf), and with
+// distances >= 0 SNAIL_TAIL_POS yields min(tf, dist) - max(tn, 0) >= 0 or -0, which v_cmpx_le_f32 0, s accepts: EVERY lane of EXEC survives.
+// The node is inner by construction.  So the visit is its scalar work alone -- the top entry's record request, the near / far child and the
+// near child's request, and in the pending copies the push -- in an out-of-line copy per visit copy, which each of them enters by two scalar
+// instructions right after its record has arrived and which leaves for the other set's pending copy with EXEC untouched.  Nothing is counted
+// differently: pops are counted at the pop.  A walk whose lanes may be masked (dist = -inf fails every box: SNAIL_TAIL_ANY) has no such
+// path and compiles to what it did before; it also never sees the bit (bits 0..2 of the word are all it reads).
+// Invariants as below: the copies request into T and into the other set exactly where the visit would have, after the same waits.
+static_assert(SNAIL_REL_INSIDE_BIT == 31, "SNAIL_OIN_TEST_SNAIL_TAIL_POS names the bit in its text");
+#define SNAIL_OIN_TEST_SNAIL_TAIL_POS(AUX, LBL) " s_bitcmp1_b32 " AUX ", 31\n s_cbranch_scc1 " LBL "_%=\n"
+#define SNAIL_OIN_TEST_SNAIL_TAIL_ANY(AUX, LBL) ""
+#define SNAIL_OIN_TEST_of(TAIL) SNAIL_OIN_TEST_##TAIL
+#define SNAIL_OIN_PENDING(X, Y, OTHERSET, SUB, AUX, FARX, FARY, CNTVISIT, LEAFREQ)                                                          \
+				 "L_oin" X "p_%=:\n" CNTVISIT /* T <- the pusher's far child has been requested */                                         \
+				 SNAIL_PF2_NEARFAR(SUB, AUX, FARX, OTHERSET, LEAFREQ)                                                                        \
+				 SNAIL_PF2_FIRSTLAST /* of the pusher = of this node: EXEC stays */                                                          \
+				 " s_lshl_b32 %[off], %[last], 6\n s_or_b32 %[off], %[off], %[first]\n s_lshl_b32 %[off], %[off], 20\n"                    \
+				 SNAIL_PF2_ALIVE                                                                                                            \
+				 " s_lshr_b32 %[topw], " FARY ", 5\n s_or_b32 %[topw], %[topw], %[off]\n"                                                    \
+				 " v_writelane_b32 %[stkN], %[topw], m0\n s_add_u32 m0, m0, 1\n"                                                            \
+				 " s_branch L_visit" Y "p_%=\n"
+#define SNAIL_OIN_COPIES_SNAIL_TAIL_POS(CNTVISIT, LEAFREQ)                                                                                  \
+				 "L_oinAq_%=:\n" CNTVISIT /* after a pop: topw = the new top entry's word */                                                \
+				 " s_and_b32 %[cur], %[topw], 0xfffff\n s_lshl_b32 %[off], %[cur], 5\n"                                                    \
+				 " s_load_dwordx8 s[68:75], %[base], %[off]\n"                                                                             \
+				 SNAIL_PF2_NEARFAR("s90", "s91", "%[fl]", "s[76:83]", LEAFREQ)                                                               \
+				 " s_bfe_u32 %[first], %[topw], 0x60014\n s_lshr_b32 %[last], %[topw], 26\n" SNAIL_PF2_ALIVE                               \
+				 " s_branch L_visitBp_%=\n"                                                                                                \
+				 SNAIL_OIN_PENDING("B", "A", "s[84:91]", "s82", "s83", "%[width]", "%[fl]", CNTVISIT, LEAFREQ)                               \
+				 SNAIL_OIN_PENDING("A", "B", "s[76:83]", "s90", "s91", "%[fl]", "%[width]", CNTVISIT, LEAFREQ)
+#define SNAIL_OIN_COPIES_SNAIL_TAIL_ANY(CNTVISIT, LEAFREQ) ""
+#define SNAIL_OIN_COPIES_of(TAIL) SNAIL_OIN_COPIES_##TAIL
 // a visit entered from a descent: the push of (FARY, survivors' first / last) happens here, between the slab products
 #define SNAIL_PF2_PENDING(X, OTHERSET, SUB, AUX, FARX, FARY, PRE, SLAB, TAIL, CNTVISIT, LEAFREQ, NX, FX, NY, FY, NZ, FZ)                                                   \
 				 "L_visit" X "p_%=:\n"                                                                                                      \
 				 " s_waitcnt lgkmcnt(0)\n" /* this record has arrived; T's last request too */                                                \
 				 " s_load_dwordx8 s[68:75], %[base], " FARY "\n" /* the pusher's far child is the new top entry */                             \
+				 SNAIL_OIN_TEST_of(TAIL)(AUX, "L_oin" X "p")                                                                                  \
 				 CNTVISIT PRE(NX, FX, NY, FY, NZ, FZ)                                                                                        \
 				 SLAB("0", NX, FX, NY, FY, NZ, FZ) TAIL("0", "s0")                                                                           \
 				 SNAIL_PF2_NEARFAR(SUB, AUX, FARX, OTHERSET, LEAFREQ)                                                                        \
@@ -1234,6 +1275,7 @@ __device__ __forceinline__ void walk(const uint4 *__restrict__ nodes, const uint
 				 /* the popped node's visit (record set A); the NEW top entry's word and record are fetched inside it */                  \
 				 " s_sub_u32 %[off], m0, 1\n s_max_i32 %[off], %[off], 0\n" /* (an empty stack re-reads entry 0: harmless, never used) */  \
 				 " v_readlane_b32 %[topw], %[stkN], %[off]\n"                                                                              \
+				 SNAIL_OIN_TEST_of(TAIL)("s91", "L_oinAq")                                                                                  \
 				 CNTVISIT PRE(NXA, FXA, NYA, FYA, NZA, FZA)                                                                                 \
 				 SLAB("0", NXA, FXA, NYA, FYA, NZA, FZA) TAIL("0", "s0")                                                          \
 				 " s_and_b32 %[cur], %[topw], 0xfffff\n s_lshl_b32 %[off], %[cur], 5\n"                                                    \
@@ -1250,6 +1292,7 @@ __device__ __forceinline__ void walk(const uint4 *__restrict__ nodes, const uint
 				 SNAIL_PF2_PENDING("A", "s[76:83]", "s90", "s91", "%[fl]", "%[width]", PRE, SLAB, TAIL, CNTVISIT, LEAFREQ, NXA, FXA, NYA, FYA, NZA, FZA)                   \
 				 " s_branch L_visitBp_%=\n"                                                                                                \
 				 SNAIL_PF2_LEAF("A", "s90", "s91") SNAIL_PF2_LEAF("B", "s82", "s83")                                                       \
+				 SNAIL_OIN_COPIES_of(TAIL)(CNTVISIT, LEAFREQ)                                                                               \
 				 "L_fail_%=:\n"                                                                                                            \
 				 " s_cmp_eq_u32 m0, 0\n s_cbranch_scc0 L_pop_%=\n"                                                                      \
 				 "L_done_%=:\n s_mov_b32 %[leafSub], 0\n s_mov_b32 %[leafAux], 0\n s_waitcnt lgkmcnt(0)\n"                                  \
@@ -3023,7 +3066,22 @@ __global__ __launch_bounds__(256) void k_pf_encode(const uint4 *__restrict__ nod
 }
 
 // slot i of the prefetching loop's copy -> slot i of a camera-relative array: bmin - o, bmax - o (the subtraction SNAIL_PRE_SHARED makes at
-// every visit, made once per node and origin), link words unchanged
+// every visit, made once per node and origin), link words unchanged but for the "contains the origin" bit of an inner record's word 7
+// (SNAIL_REL_INSIDE_BIT, see the record layout above SNAIL_MOV_REC): a property of (node, origin), so it lives here and not in the loop's own copy.
+// The box contains the origin exactly when its three relative near words are <= 0 and its three far words >= 0, as stored (-0 counts as 0, a NaN fails).
+__host__ __device__ inline bool relOriginInside(const unsigned (&w)[6]) {
+	bool in = true;
+	for(int k = 0; k < 3; k++) {
+		const float n = __builtin_bit_cast(float, w[k]), f = __builtin_bit_cast(float, w[3 + k]);
+		in = in && n <= 0.0f && f >= 0.0f;
+	}
+	return in;
+}
+// word 7 of the relative record: inner records only (a leaf's visit must reach the leaf code, and its word 7 is a triangle count); an empty slot (slot 0,
+// the slots past a rebuilt tree: word 7 = 0, no axis bit) is no node
+__host__ __device__ inline unsigned relAux(const unsigned (&rel)[6], unsigned sub, unsigned aux) {
+	return !(sub & 0x80000000u) && (aux & 7u) && relOriginInside(rel) ? aux | (1u << SNAIL_REL_INSIDE_BIT) : aux;
+}
 __global__ __launch_bounds__(256) void k_rel_nodes(const uint4 *__restrict__ pf, int nSlots, float ox, float oy, float oz, uint4 *__restrict__ rel) {
 	const int i = (int)(blockIdx.x * 256 + threadIdx.x);
 	if(i >= nSlots) return;
@@ -3033,7 +3091,7 @@ __global__ __launch_bounds__(256) void k_rel_nodes(const uint4 *__restrict__ pf,
 	unsigned out[6];
 	for(int k = 0; k < 6; k++) out[k] = __float_as_uint(__uint_as_float(in[k]) - o[k % 3]);
 	rel[(size_t)i * 2] = make_uint4(out[0], out[1], out[2], out[3]);
-	rel[(size_t)i * 2 + 1] = make_uint4(out[4], out[5], b.z, b.w);
+	rel[(size_t)i * 2 + 1] = make_uint4(out[4], out[5], b.z, relAux(out, b.z, b.w));
 }
 
 // the same for up to SNAIL_MAX_BATCH origins at once (the frames of one multi-frame launch of a moving camera): every record is read once
@@ -3051,9 +3109,18 @@ __global__ __launch_bounds__(256) void k_rel_nodes_multi(const uint4 *__restrict
 		unsigned out[6];
 		for(int k = 0; k < 6; k++) out[k] = __float_as_uint(__uint_as_float(in[k]) - A.org[f][k % 3]);
 		A.dst[f][(size_t)i * 2] = make_uint4(out[0], out[1], out[2], out[3]);
-		A.dst[f][(size_t)i * 2 + 1] = make_uint4(out[4], out[5], b.z, b.w);
+		A.dst[f][(size_t)i * 2 + 1] = make_uint4(out[4], out[5], b.z, relAux(out, b.z, b.w));
 	}
 }
+#ifdef SNAIL_DEBUG_API
+// diagnostic (snail_debug_rel_flag_count): the slots of an origin-relative array that carry the "contains the origin" bit
+__global__ __launch_bounds__(256) void k_rel_flag_count(const uint4 *__restrict__ rel, int nSlots, unsigned long long *__restrict__ out) {
+	const int i = (int)(blockIdx.x * 256 + threadIdx.x);
+	const bool flagged = i < nSlots && !(rel[(size_t)i * 2 + 1].z & 0x80000000u) && ((rel[(size_t)i * 2 + 1].w >> SNAIL_REL_INSIDE_BIT) & 1u);
+	const u64 m = __builtin_amdgcn_ballot_w64(flagged);
+	if((threadIdx.x & 63) == 0 && m) atomicAdd(out, (unsigned long long)__builtin_popcountll(m));
+}
+#endif
 
 // ---- single-ray accounting walk (SURVEY.md section 8d): V_n, V_t per ray ----------------------------
 struct AccountArgs {

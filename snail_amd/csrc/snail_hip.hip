@@ -1684,6 +1684,34 @@ int snail_debug_occupancy(int out[4]) {
 	return 0;
 }
 
+// The origin-relative node array of `org` (found in the scene's cache or filled, as a launch would) and the number of its slots that carry the
+// "contains the origin" bit (dev::relAux)
+int snail_debug_rel_flag_count(SnailScene *s, const float org[3], int *count) {
+	if(int rc = checkScene(s, "snail_debug_rel_flag_count")) return rc;
+	if(!org || !count) { snail_set_error("snail_debug_rel_flag_count: null argument"); return 1; }
+	if(!stackPack(s)) { snail_set_error("snail_debug_rel_flag_count: this scene keeps no origin-relative node records"); return 1; }
+	DeviceGuard guard(s->device);
+	HostCallScope hc(s, "snail_debug_rel_flag_count");
+	if(hc.rc) return hc.rc;
+	if(int rc = hc.zeroStats()) return rc;
+	{
+		SNAIL_LOCK(s);
+		SceneUse use(s, hc.stream());
+		if(use.rc) return use.rc;
+		const uint4 *rel = nullptr;
+		int which = -1;
+		if(int rc = relFor(s, org, hc.stream(), &rel, &which)) return rc;
+		const int nSlots = s->nNodes + 1;
+		hipLaunchKernelGGL(dev::k_rel_flag_count, dim3((unsigned)((nSlots + 255) / 256)), dim3(256), 0, hc.stream(), rel, nSlots, (unsigned long long *)hc.stats());
+		HIP_TRY(hipGetLastError());
+		if(int rc = relUsed(s, which, hc.stream())) return rc;
+	}
+	uint64_t st[4] = {0, 0, 0, 0};
+	if(int rc = hc.finish(st)) return rc;
+	*count = (int)st[0];
+	return 0;
+}
+
 #endif // SNAIL_DEBUG_API
 
 int snail_account_packets(SnailScene *s, const float cam[13], int resx, int resy, uint32_t *out8) {
