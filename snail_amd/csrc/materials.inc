@@ -9,6 +9,17 @@
 //   k_mat_final            the tail of TraceLight per light, outColor = diffuse * lDiffuse + specular * lSpecular, ConvColor, store  :567-601, :484-512
 // hitBounds / lightCulled / shadowLane and the shadow walks are the plain pipeline's device functions, called on these samples; what differs is
 // that N.L takes the interpolated normal and that diffuse and specular are two buffers.  Table look-ups in their fully checked form.
+// With the one mirrored bounce of gVals[7] (include/snail_materials_bounce.h; src/scene_trace.cpp:454-466, :603-618), between k_mat_sample and
+// k_mat_light:
+//   k_mat_mirror           primary samples -> mirrored packets (Reflect about the INTERPOLATED normal) + lane masks, in the layout and masked-lane
+//                          convention of k_final<SRC_PRIMARY, DST_MIRROR>; books the nested call's TracingRays           Scene::TraceReflection
+//   k_rays<false, true>    TraversePrimary<0, 1> of the mirrored packets, with barycentrics (launchRays, unchanged)
+//   k_mat_sample_rays      the sample stage on generic packets: RayGroup<0, hasMask>, hasMask = not all 256 lanes selected (:615-617)
+//   k_mat_light_rays<DEEP> / k_mat_colour_rays   the nested lights and outColor as FLOATS [packet][256][3] (no ConvColor)
+// and k_mat_final_blend instead of k_mat_final: diffuse += (colour - diffuse) * 0.3 on the hit lanes, before the lights (:462-465).
+// The light and colour stages are ONE body each, templated by their source (SRC_PRIMARY: rays from the camera, a hit = t < inf; SRC_MIRROR:
+// rays, masks and hits from the mirrored-packet buffers, a hit = t < inf AND the lane's mask bit: a masked lane carries -inf, not inf); the
+// primary kernels keep their names.
 namespace SNAIL_DEV_NS {
 
 enum { MAT_SIMPLE = 0, MAT_TEX = 1, MAT_UBER = 2 };
@@ -35,6 +46,11 @@ struct MatArgs {
 	const TexRec *tex;
 	const unsigned char *texels;
 	float *samples;            // [packet][9][64][4]
+	// SRC_MIRROR (generic packets: s.rDir / s.rOrg / s.rMask (null = all lanes selected) / s.rDist / s.rObj are rays and hits, indexed by list position)
+	const float *rU, *rV;      // barycentric.x / .y of those hits: quad q's four lanes at rU + q * rUVStride (8: launchRays' bary buffer, 4: planes)
+	int rUVStride;
+	float *nSamples;           // the samples of the generic packets, [packet][9][64][4]
+	float *nSDist;             // their shadow distances, [light][packet][256]
 };
 
 // RayGenerator::Generate for the lane's quad, exactly as in loadSamples (checked look-ups)
@@ -135,6 +151,16 @@ __device__ __forceinline__ bool blockAll(bool p, int lane) {
 __device__ __forceinline__ float lerpL(float a, float b, float c, float x, float y) { return (a + b * x) + c * y; }
 __device__ __forceinline__ float lerpR(float a, float b, float c, float x, float y) { return a + (b * x + c * y); }
 
+// the packet of a stage's block: the list entry (SRC_PRIMARY), or the list position alone (SRC_MIRROR: generic packets have no place in a frame)
+template <int SRC>
+__device__ __forceinline__ PacketPos matPacket(const MatArgs &A, int li) {
+	if(SRC != SRC_MIRROR) return packetOf(A.s, li);
+	PacketPos P;
+	P.px = P.py = 0; P.pidx = (size_t)li; P.valid = true;
+	return P;
+}
+
+// (TWINS: k_mat_sample_rays below is this kernel for generic packets; a change to the branches, the kinds or the output belongs in both.)
 __global__ __launch_bounds__(64) void k_mat_sample(MatArgs A) {
 	const int lane = threadIdx.x & 63;
 	const int li = (int)blockIdx.x;
@@ -266,43 +292,197 @@ __global__ __launch_bounds__(64) void k_mat_sample(MatArgs A) {
 	}
 }
 
-// position and hit mask as in simple shading (src/scene_trace.cpp:157-165), the normal from the sample buffer
-__device__ __forceinline__ void matLoadSamples(const MatArgs &A, const PacketPos &P, int lane, Samples &S) {
+// The sample stage on GENERIC packets, RayGroup<0, hasMask> (the nested call of the bounce): k_mat_sample with the directions read from the
+// packet, a hit = t < inf AND the lane's mask bit, and branch (a) shaded with the packet's own hasMask.  A second kernel, not a template
+// argument of k_mat_sample: by the resource report the shared body cost the primary kernel two VGPRs (profiles/materials_resources.txt).
+// TWINS: everything else -- blocks, the triId-0 quirk, texDiff, the mip choice, the kinds, the output -- is k_mat_sample's; a change there
+// belongs in both.
+__global__ __launch_bounds__(64) void k_mat_sample_rays(MatArgs A) {
+	const int lane = threadIdx.x & 63;
+	const int li = (int)blockIdx.x;
+	if(li >= A.s.nPackets) return;
+	const PacketPos P = matPacket<SRC_MIRROR>(A, li);
 	const size_t quad = P.pidx * 64 + lane;
 	const float inf = __builtin_inff();
 	float d[3][4];
-	matRays(A.s, P, lane, d);
-	const float4 tv = *(const float4 *)(A.s.hitT + quad * 4);
+	unsigned mask4 = 15u;
+	loadQuad3(A.s.rDir, quad, d);
+	if(A.s.rMask) mask4 = A.s.rMask[quad] & 15u;
+	// hasMask is the PACKET's: RayGroup<0, 0> when all 256 lanes are selected, RayGroup<0, 1> otherwise (src/scene_trace.cpp:615-617)
+	const bool pktMasked = __builtin_amdgcn_ballot_w64(mask4 != 15u) != 0;
+	float bx[4], by[4];
+	bool hit[4];
+	int obj[4];
+	{
+		const size_t uvq = quad * (size_t)A.rUVStride;
+		const float4 tv = *(const float4 *)(A.s.rDist + quad * 4), uv = *(const float4 *)(A.rU + uvq), vv = *(const float4 *)(A.rV + uvq);
+		const int4 iv = *(const int4 *)(A.s.rObj + quad * 4);
+		const float t[4] = {tv.x, tv.y, tv.z, tv.w};
+		const int id[4] = {iv.x, iv.y, iv.z, iv.w};
+		bx[0] = uv.x; bx[1] = uv.y; bx[2] = uv.z; bx[3] = uv.w;
+		by[0] = vv.x; by[1] = vv.y; by[2] = vv.z; by[3] = vv.w;
+#pragma unroll
+		for(int l = 0; l < 4; l++) {
+			hit[l] = t[l] < inf && ((mask4 >> l) & 1u) != 0;   // mask = tDistance < maxDist && selector, :157
+			int i = id[l] < 0 ? 0 : id[l];
+			i = i < A.nTris ? i : A.nTris - 1;
+			obj[l] = hit[l] ? i : 0;       // object = Condition(mask, tObject, 0), :161
+		}
+	}
+	// mask4 == 0x0f0f0f0f, and the 16 objects equal to the block's first (:178-182)
+	const bool full = blockAll(hit[0] && hit[1] && hit[2] && hit[3], lane);
+	const int obj0b = blockFirst(obj[0]);
+	const bool single = blockAll(obj[0] == obj0b && obj[1] == obj0b && obj[2] == obj0b && obj[3] == obj0b, lane) && full;
+
+	float nrm[3][4], tc[2][4], tdx = 0.0f, tdy = 0.0f;
+	int mid[4];
+#pragma unroll
+	for(int l = 0; l < 4; l++) { nrm[0][l] = nrm[1][l] = nrm[2][l] = 0.0f; tc[0][l] = tc[1][l] = 0.0f; mid[l] = -1; }
+	if(single) {
+		// (a): one triangle for the block
+		const ShTri T = loadShTri(A, obj0b);
+		const int m = matIdOf(A, T.matId);
+		const bool flat = T.matId < 0;
+		const bool texd = m >= 0 && A.mats[m].kind == MAT_TEX;     // Material::fTexCoords
+#pragma unroll
+		for(int l = 0; l < 4; l++) {
+			mid[l] = m;
+			if(texd) {
+#pragma unroll
+				for(int c = 0; c < 2; c++) tc[c][l] = lerpL(T.uv[0][c], T.uv[1][c], T.uv[2][c], bx[l], by[l]);
+#pragma unroll
+				for(int c = 0; c < 3; c++) nrm[c][l] = lerpL(T.nrm[0][c], T.nrm[1][c], T.nrm[2][c], bx[l], by[l]);
+			} else {
+#pragma unroll
+				for(int c = 0; c < 3; c++) nrm[c][l] = flat ? T.nrm[0][c] : lerpR(T.nrm[0][c], T.nrm[1][c], T.nrm[2][c], bx[l], by[l]);
+			}
+		}
+		if(texd) {   // texDiff = Maximize(texCoord) - Minimize(texCoord) of the quad (:219; finite values: the fold's order is immaterial)
+			tdx = vmax(vmax(tc[0][0], tc[0][1]), vmax(tc[0][2], tc[0][3])) - vmin(vmin(tc[0][0], tc[0][1]), vmin(tc[0][2], tc[0][3]));
+			tdy = vmax(vmax(tc[1][0], tc[1][1]), vmax(tc[1][2], tc[1][3])) - vmin(vmin(tc[1][0], tc[1][1]), vmin(tc[1][2], tc[1][3]));
+		}
+	} else {
+		// (b): per quad; lane 0's triangle for all four lanes if lane 0 hit, then lanes 1..3 whose triangle differs from obj[0] (0 when lane 0 missed)
+		if(hit[0]) {
+			const ShTri T = loadShTri(A, obj[0]);
+			const int m = matIdOf(A, T.matId);
+#pragma unroll
+			for(int l = 0; l < 4; l++) {
+				mid[l] = hit[l] ? m : -1;
+#pragma unroll
+				for(int c = 0; c < 2; c++) tc[c][l] = lerpL(T.uv[0][c], T.uv[1][c], T.uv[2][c], bx[l], by[l]);
+#pragma unroll
+				for(int c = 0; c < 3; c++) nrm[c][l] = lerpL(T.nrm[0][c], T.nrm[1][c], T.nrm[2][c], bx[l], by[l]);
+			}
+		}
+#pragma unroll
+		for(int l = 1; l < 4; l++)
+			if(hit[l] && obj[l] != obj[0]) {
+				const ShTri T = loadShTri(A, obj[l]);
+				mid[l] = matIdOf(A, T.matId);
+#pragma unroll
+				for(int c = 0; c < 2; c++) tc[c][l] = lerpL(T.uv[0][c], T.uv[1][c], T.uv[2][c], bx[l], by[l]);
+#pragma unroll
+				for(int c = 0; c < 3; c++) nrm[c][l] = lerpL(T.nrm[0][c], T.nrm[1][c], T.nrm[2][c], bx[l], by[l]);
+			}
+	}
+	// One material for 16 hit rays: Shade unmasked (:224, :301-308); otherwise (c) every selected lane by its own material on the masked path
+	// (:310-355).  The per-material masks of (c) are disjoint -- a lane has one matId -- and a masked Shade writes only its own lanes, so the order
+	// in which the reference walks its material list cannot show: shading each lane once by its own material is the same.
+	// Branch (a) calls Shade with the packet's own hasMask (:224), (b)'s single-material call is RayGroup<.., 0> whatever the packet is (:308).
+	const int mid0b = blockFirst(mid[0]);
+	const bool unmasked = blockAll(mid[0] == mid0b && mid[1] == mid0b && mid[2] == mid0b && mid[3] == mid0b, lane) && full && !(single && pktMasked);
+
+	float diff[3][4], spec[3][4];
+#pragma unroll
+	for(int l = 0; l < 4; l++) {
+		// the lane's material: loaded values of an unrolled loop (compile-time indices), never a runtime-indexed array
+		int kind = MAT_SIMPLE, ndotr = 1, tex = 0;
+		float col[3] = {1.0f, 1.0f, 1.0f}, sp[3] = {0.0f, 0.0f, 0.0f};   // defaultMat = SimpleMaterial<true>(1, 1, 1), src/scene.cpp:6
+		if(mid[l] >= 0) {
+			const uint4 *r = (const uint4 *)(A.mats + mid[l]);
+			const uint4 a = r[0], b = r[1], c = r[2];
+			kind = (int)a.x; ndotr = (int)a.y;
+			col[0] = asf(a.z); col[1] = asf(a.w); col[2] = asf(b.x);
+			sp[0] = asf(b.y); sp[1] = asf(b.z); sp[2] = asf(b.w);
+			tex = (int)c.x;
+		}
+		const float dn = d[0][l] * nrm[0][l] + d[1][l] * nrm[1][l] + d[2][l] * nrm[2][l];
+		const float adn = __builtin_fabsf(dn);
+		float t1[3] = {0.0f, 0.0f, 0.0f};
+		// the kinds present among the wave's lanes: a branch per kind that needs code of its own, skipped when no lane has it
+		if(__builtin_amdgcn_ballot_w64(kind == MAT_TEX && hit[l]) != 0) {
+			if(kind == MAT_TEX && hit[l]) matSampleTex(A, tex, tc[0][l], tc[1][l], tdx, tdy, t1);
+		}
+#pragma unroll
+		for(int c = 0; c < 3; c++) {
+			float df, sf;
+			if(kind == MAT_TEX) { df = ndotr ? t1[c] * dn : t1[c]; sf = df; }
+			else if(kind == MAT_UBER) { df = col[c] * adn; sf = unmasked ? df : sp[c]; }
+			else { df = ndotr ? col[c] * adn : col[c]; sf = df; }
+			diff[c][l] = hit[l] ? df : 0.0f;
+			spec[c][l] = hit[l] ? sf : 0.0f;
+			nrm[c][l] = hit[l] ? nrm[c][l] : 0.0f;
+		}
+	}
+	float4 *o = (float4 *)(A.nSamples + P.pidx * (9 * 256)) + lane;
+#pragma unroll
+	for(int c = 0; c < 3; c++) {
+		o[(0 + c) * 64] = make_float4(nrm[c][0], nrm[c][1], nrm[c][2], nrm[c][3]);
+		o[(3 + c) * 64] = make_float4(diff[c][0], diff[c][1], diff[c][2], diff[c][3]);
+		o[(6 + c) * 64] = make_float4(spec[c][0], spec[c][1], spec[c][2], spec[c][3]);
+	}
+}
+
+// position and hit mask as in simple shading (src/scene_trace.cpp:157-165), the normal from the sample buffer.  SRC_MIRROR: the mirrored
+// packet's own rays, position = reflDir * t + reflOrig, hit = t < inf and the lane's mask bit, the normal from the nested sample buffer.
+template <int SRC>
+__device__ __forceinline__ void matLoadSamples(const MatArgs &A, const PacketPos &P, int lane, Samples &S) {
+	const size_t quad = P.pidx * 64 + lane;
+	const float inf = __builtin_inff();
+	float d[3][4], org[3][4];
+	unsigned mask4 = 15u;
+	if(SRC == SRC_MIRROR) {
+		loadQuad3(A.s.rDir, quad, d);
+		loadQuad3(A.s.rOrg, quad, org);
+		if(A.s.rMask) mask4 = A.s.rMask[quad] & 15u;
+	} else {
+		matRays(A.s, P, lane, d);
+#pragma unroll
+		for(int c = 0; c < 3; c++)
+#pragma unroll
+			for(int l = 0; l < 4; l++) org[c][l] = A.s.g.org[c];
+	}
+	const float4 tv = *(const float4 *)((SRC == SRC_MIRROR ? A.s.rDist : A.s.hitT) + quad * 4);
 	const float t[4] = {tv.x, tv.y, tv.z, tv.w};
-	const float4 *sm = (const float4 *)(A.samples + P.pidx * (9 * 256)) + lane;
+	const float4 *sm = (const float4 *)((SRC == SRC_MIRROR ? A.nSamples : A.samples) + P.pidx * (9 * 256)) + lane;
 	const float4 n0 = sm[0], n1 = sm[64], n2 = sm[128];
 	const float nn[3][4] = {{n0.x, n0.y, n0.z, n0.w}, {n1.x, n1.y, n1.z, n1.w}, {n2.x, n2.y, n2.z, n2.w}};
 #pragma unroll
 	for(int l = 0; l < 4; l++) {
-		S.hit[l] = t[l] < inf;
+		S.hit[l] = t[l] < inf && (SRC != SRC_MIRROR || ((mask4 >> l) & 1u) != 0);
 		S.sdn[l] = 0.0f;
 #pragma unroll
-		for(int c = 0; c < 3; c++) { S.pos[c][l] = d[c][l] * t[l] + A.s.g.org[c]; S.nrm[c][l] = nn[c][l]; }
+		for(int c = 0; c < 3; c++) { S.pos[c][l] = d[c][l] * t[l] + org[c][l]; S.nrm[c][l] = nn[c][l]; }
 	}
 }
-
 // ---- one (packet, light): the shadow packet (src/scene_trace.cpp:538-558) and BVH::TraverseShadow, by the walks of lightPacket ----
 // TWINS: the set-up and the walk selection below are those of lightPacket (snail_dev.inc; its main pass and its deferred M_EXACT pass folded into
 // one kernel, look-ups checked), and k_inst_light (instances_shade.inc) has the same set-up around the instanced walk.  A change to the shadow
 // packet, to the classify / walkSharedAsm / walk dispatch or to the stats booking belongs in all three.
-template <bool DEEP>
-__global__ __launch_bounds__(64) void k_mat_light(MatArgs A) {
-	__shared__ float lds[LDS_FLOATS_PER_WAVE];
+// SRC_MIRROR: the nested call's lights on the mirrored packets' samples -- the same shadow packet (the light's shared origin) and walks.
+template <bool DEEP, int SRC>
+__device__ __forceinline__ void matLight(const MatArgs &A, float *lds) {
 	const int lane = threadIdx.x & 63;
 	const int li = (int)blockIdx.x, n = (int)blockIdx.y;
 	if(li >= A.s.nPackets || n >= A.s.nLights) return;
-	const PacketPos P = packetOf(A.s, li);
+	const PacketPos P = matPacket<SRC>(A, li);
 	const float lp[3] = {A.s.lights[n][0], A.s.lights[n][1], A.s.lights[n][2]};
 	const float radius = A.s.lights[n][6], radSq = radius * radius;
 	Quad Q;
 	{
 		Samples S;
-		matLoadSamples(A, P, lane, S);
+		matLoadSamples<SRC>(A, P, lane, S);
 		float tMin[3], tMax[3];
 		hitBounds(S, tMin, tMax);
 		if(lightCulled(tMin, tMax, lp, radSq)) return;   // (wave-uniform; k_mat_final skips the light by the same test)
@@ -341,7 +521,17 @@ __global__ __launch_bounds__(64) void k_mat_light(MatArgs A) {
 	} else if(mode == M_COH) walkSharedAsm<true, true, false, false, false, false>(A.s.nodes, A.s.tris, 64, lane, lorg, Q, 15u, stid, bu, bv, lds, st, oct);
 	else walkSharedAsm<true, false, false, false, false, false>(A.s.nodes, A.s.tris, 64, lane, lorg, Q, 15u, stid, bu, bv, lds, st, 0);
 	flushStats(A.s.stats, st, rays, lane);
-	*(float4 *)(A.s.sDist + ((size_t)n * (size_t)A.s.nPackets + P.pidx) * 256 + (size_t)lane * 4) = make_float4(Q.dist[0], Q.dist[1], Q.dist[2], Q.dist[3]);
+	*(float4 *)((SRC == SRC_MIRROR ? A.nSDist : A.s.sDist) + ((size_t)n * (size_t)A.s.nPackets + P.pidx) * 256 + (size_t)lane * 4) = make_float4(Q.dist[0], Q.dist[1], Q.dist[2], Q.dist[3]);
+}
+template <bool DEEP>
+__global__ __launch_bounds__(64) void k_mat_light(MatArgs A) {
+	__shared__ float lds[LDS_FLOATS_PER_WAVE];
+	matLight<DEEP, SRC_PRIMARY>(A, lds);
+}
+template <bool DEEP>
+__global__ __launch_bounds__(64) void k_mat_light_rays(MatArgs A) {
+	__shared__ float lds[LDS_FLOATS_PER_WAVE];
+	matLight<DEEP, SRC_MIRROR>(A, lds);
 }
 
 // ---- one packet: the lights' contributions from the surviving distances, the colour and its store (shadeAndStore with two sample colours) ----
@@ -349,14 +539,18 @@ __global__ __launch_bounds__(64) void k_mat_light(MatArgs A) {
 // tail, with the alignment rule) are shadeAndStore's (snail_dev.inc, non-fused, checked form), which k_final and k_inst_final (instances_shade.inc)
 // call; this copy differs only in taking diffuse and specular from the sample buffer.  A change to the attenuation or to the store rule belongs
 // in both.
-__global__ __launch_bounds__(64) void k_mat_final(MatArgs A) {
+// SRC_MIRROR: the nested call's outColor, stored as FLOATS r, g, b per ray in A.s.rCol [packet][256][3] (the analogue of k_final<SRC_MIRROR,
+// DST_COLOR>).  BLEND (primary): diffuse = diffuse + (reflColor - diffuse) * 0.3 on the selector's lanes (= the hit lanes) before the lights,
+// specular untouched (src/scene_trace.cpp:462-465).
+template <int SRC, bool BLEND>
+__device__ __forceinline__ void matFinal(const MatArgs &A) {
 	const int lane = threadIdx.x & 63;
 	const int li = (int)blockIdx.x;
 	if(li >= A.s.nPackets) return;
-	const PacketPos P = packetOf(A.s, li);
+	const PacketPos P = matPacket<SRC>(A, li);
 	const size_t quad = P.pidx * 64 + lane;
 	Samples S;
-	matLoadSamples(A, P, lane, S);
+	matLoadSamples<SRC>(A, P, lane, S);
 	float lDiff[3][4], lSpec[3][4];
 #pragma unroll
 	for(int c = 0; c < 3; c++)
@@ -371,7 +565,7 @@ __global__ __launch_bounds__(64) void k_mat_final(MatArgs A) {
 			const float lc[3] = {A.s.lights[n][3], A.s.lights[n][4], A.s.lights[n][5]};
 			const float radius = A.s.lights[n][6], iRadius = 1.0f / radius, radSq = radius * radius;
 			if(lightCulled(tMin, tMax, lp, radSq)) continue;
-			const float4 sv = *(const float4 *)(A.s.sDist + ((size_t)n * packets + P.pidx) * 256 + (size_t)lane * 4);
+			const float4 sv = *(const float4 *)((SRC == SRC_MIRROR ? A.nSDist : A.s.sDist) + ((size_t)n * packets + P.pidx) * 256 + (size_t)lane * 4);
 			const float sdist[4] = {sv.x, sv.y, sv.z, sv.w};
 #pragma unroll
 			for(int l = 0; l < 4; l++) {
@@ -391,14 +585,30 @@ __global__ __launch_bounds__(64) void k_mat_final(MatArgs A) {
 		}
 	}
 	// outColor = diffuse * lDiffuse + specular * lSpecular, or diffuse without lights (src/scene_trace.cpp:504-512)
-	const float4 *sm = (const float4 *)(A.samples + P.pidx * (9 * 256)) + lane;
+	const float4 *sm = (const float4 *)((SRC == SRC_MIRROR ? A.nSamples : A.samples) + P.pidx * (9 * 256)) + lane;
 	float col[3][4];
 #pragma unroll
 	for(int c = 0; c < 3; c++) {
 		const float4 dv = sm[(3 + c) * 64], sv = sm[(6 + c) * 64];
-		const float df[4] = {dv.x, dv.y, dv.z, dv.w}, sf[4] = {sv.x, sv.y, sv.z, sv.w};
+		float df[4] = {dv.x, dv.y, dv.z, dv.w};
+		const float sf[4] = {sv.x, sv.y, sv.z, sv.w};
+		if(BLEND) {
+#pragma unroll
+			for(int l = 0; l < 4; l++) {
+				const float refl = A.s.rCol[(quad * 4 + l) * 3 + c];
+				if(S.hit[l]) df[l] = df[l] + (refl - df[l]) * 0.3f;
+			}
+		}
 #pragma unroll
 		for(int l = 0; l < 4; l++) col[c][l] = A.s.nLights ? df[l] * lDiff[c][l] + sf[l] * lSpec[c][l] : df[l];
+	}
+	if(SRC == SRC_MIRROR) {
+#pragma unroll
+		for(int l = 0; l < 4; l++) {
+			float *rc = A.s.rCol + (quad * 4 + l) * 3;
+			rc[0] = col[0][l]; rc[1] = col[1][l]; rc[2] = col[2][l];
+		}
+		return;
 	}
 	unsigned bytes[12];
 #pragma unroll
@@ -422,6 +632,70 @@ __global__ __launch_bounds__(64) void k_mat_final(MatArgs A) {
 				if(xx + l < A.s.resx) { dd[l * 3 + 0] = (unsigned char)bytes[l * 3 + 0]; dd[l * 3 + 1] = (unsigned char)bytes[l * 3 + 1]; dd[l * 3 + 2] = (unsigned char)bytes[l * 3 + 2]; }
 		}
 	}
+}
+__global__ __launch_bounds__(64) void k_mat_final(MatArgs A) { matFinal<SRC_PRIMARY, false>(A); }
+__global__ __launch_bounds__(64) void k_mat_final_blend(MatArgs A) { matFinal<SRC_PRIMARY, true>(A); }
+__global__ __launch_bounds__(64) void k_mat_colour_rays(MatArgs A) { matFinal<SRC_MIRROR, false>(A); }
+
+// ---- one packet: primary samples -> mirrored packets.  Scene::TraceReflection (src/scene_trace.cpp:603-618) on the samples of full shading:
+// reflDir = Reflect(dir, samples.normal) (src/rtbase_math.h:54-58) with the INTERPOLATED normal of the sample buffer (zeros on a lane that missed),
+// reflOrig = position + reflDir * 0.001, idir = SafeInv(reflDir); selector = hit lanes.
+// TWINS: the output -- layout, zeros for masked lanes, distance inf / -inf (:112-115), object 0, one mask byte per quad, the nested call's
+// TracingRays(CountMaskBits(mask)) (:116-117) and, in the table arithmetic, SafeInv one component at a time -- is that of k_final<SRC_PRIMARY,
+// DST_MIRROR> (snail_dev.inc); only the normal's source differs.
+__global__ __launch_bounds__(64) void k_mat_mirror(MatArgs A) {
+	const int lane = threadIdx.x & 63;
+	const int li = (int)blockIdx.x;
+	if(li >= A.s.nPackets) return;
+	const PacketPos P = packetOf(A.s, li);
+	const size_t quad = P.pidx * 64 + lane;
+	const float inf = __builtin_inff();
+	Samples S;
+	float d[3][4];
+	matRays(A.s, P, lane, d);
+	matLoadSamples<SRC_PRIMARY>(A, P, lane, S);
+	float rd[3][4], ro[3][4], rdist[4];
+	unsigned sel = 0;
+#pragma unroll
+	for(int l = 0; l < 4; l++) {
+		const float dt = S.nrm[0][l] * d[0][l] + S.nrm[1][l] * d[1][l] + S.nrm[2][l] * d[2][l];
+		const float dt2 = dt + dt;
+#pragma unroll
+		for(int c = 0; c < 3; c++) {
+			const float r = d[c][l] - S.nrm[c][l] * dt2;
+			rd[c][l] = S.hit[l] ? r : 0.0f;
+			ro[c][l] = S.hit[l] ? S.pos[c][l] + r * 0.001f : 0.0f;
+		}
+		rdist[l] = S.hit[l] ? inf : -inf;
+		sel |= S.hit[l] ? (1u << l) : 0u;
+	}
+	float4 *po = (float4 *)(A.s.rOrg + quad * 12), *pd = (float4 *)(A.s.rDir + quad * 12), *pi = (float4 *)(A.s.rIDir + quad * 12);
+#pragma unroll
+	for(int c = 0; c < 3; c++) {
+		po[c] = make_float4(ro[c][0], ro[c][1], ro[c][2], ro[c][3]);
+		pd[c] = make_float4(rd[c][0], rd[c][1], rd[c][2], rd[c][3]);
+	}
+#pragma unroll
+	for(int c = 0; c < 3; c++) {   // SafeInv (src/rtbase.h:117-120); table arithmetic: a component's four look-ups in one batch
+		float x4[4], r4[4];
+#pragma unroll
+		for(int l = 0; l < 4; l++) x4[l] = rd[c][l] + 0.00000001f;
+#if SNAIL_ARITH_SSE
+		InvN<4>(x4, r4);
+#else
+#pragma unroll
+		for(int l = 0; l < 4; l++) r4[l] = Inv(x4[l]);
+#endif
+		pi[c] = make_float4(r4[0], r4[1], r4[2], r4[3]);
+	}
+	A.s.rMask[quad] = (unsigned char)sel;
+	*(float4 *)(A.s.rDist + quad * 4) = make_float4(rdist[0], rdist[1], rdist[2], rdist[3]);
+	*(int4 *)(A.s.rObj + quad * 4) = make_int4(0, 0, 0, 0);
+	unsigned cnt = 0;
+#pragma unroll
+	for(int l = 0; l < 4; l++) cnt += (unsigned)__builtin_popcountll(__builtin_amdgcn_ballot_w64(S.hit[l]));
+	const Counters none = {0, 0, 0, 0, 0};
+	flushStats(A.s.stats, none, cnt, lane);
 }
 
 } // namespace SNAIL_DEV_NS

@@ -1,6 +1,9 @@
 // materials_host.inc -- the C-ABI of include/snail_materials.h: ShTriangle records and mip chains on the host, the material set of a plain
-// scene, and the staged launches of materials.inc (primary hits -> k_mat_sample -> k_mat_light per (packet, light) -> k_mat_final).
+// scene, and the staged launches of materials.inc (primary hits -> k_mat_sample -> k_mat_light per (packet, light) -> k_mat_final); and the
+// C-ABI of include/snail_materials_bounce.h: the same frames with the one mirrored bounce of gVals[7] (-> k_mat_mirror -> launchRays with
+// barycentrics -> k_mat_sample_rays -> k_mat_light_rays -> k_mat_colour_rays between the sample stage and the primary lights, k_mat_final_blend last).
 #include "../../include/snail_materials.h"
+#include "../../include/snail_materials_bounce.h"
 
 struct SnailMaterials {
 	SnailScene *scene = nullptr;
@@ -23,10 +26,27 @@ struct SnailMaterials {
 			samples = (float *)(base + 4 * plane); sDist = (float *)(base + 13 * plane);
 		}
 	};
+	// ... and those of the bounce: the mirrored packets (rays, mask, distance, object, bary), the nested samples, colour and shadow distances
+	struct BounceBufs {
+		float *rOrg = nullptr, *rDir = nullptr, *rIDir = nullptr, *rDist = nullptr, *bary = nullptr, *nSamples = nullptr, *rCol = nullptr, *nSDist = nullptr;
+		int *rObj = nullptr;
+		unsigned char *rMask = nullptr;
+		static size_t bytes(size_t np, int nLights) { return np * 256 * 4 * (size_t)(25 + (nLights > 0 ? nLights : 0)) + ((np * 64 + 255) & ~(size_t)255); }
+		void carve(char *base, size_t np, int nLights) {
+			const size_t plane = np * 256 * 4;
+			rOrg = (float *)base; rDir = (float *)(base + 3 * plane); rIDir = (float *)(base + 6 * plane); rDist = (float *)(base + 9 * plane);
+			rObj = (int *)(base + 10 * plane); bary = (float *)(base + 11 * plane); nSamples = (float *)(base + 13 * plane); rCol = (float *)(base + 22 * plane);
+			nSDist = (float *)(base + 25 * plane);
+			rMask = (unsigned char *)(base + (size_t)(25 + (nLights > 0 ? nLights : 0)) * plane);
+		}
+	};
 	struct Set {
 		char *base = nullptr;
 		size_t packets = 0;
 		int lights = 0;
+		char *bounce = nullptr;   // allocated only once a bounce has been asked for; grown under the same rule
+		size_t bouncePackets = 0;
+		int bounceLights = 0;
 		hipEvent_t done = nullptr;
 		bool used = false;
 	};
@@ -80,9 +100,12 @@ void matFillArgs(const SnailMaterials *m, dev::MatArgs &A, const float cam[13], 
 	A.tex = m->dTex; A.texels = m->dTexels;
 }
 
-// the stages of one lit frame over the packet list dXY into `frame` (or packet-major `bgrPackets`), intermediates in W; the scene's mu held
+// the stages of one lit frame over the packet list dXY into `frame` (or packet-major `bgrPackets`), intermediates in W; the scene's mu held.
+// R (or null): the intermediates of the one mirrored bounce -- primary -> sample -> mirror -> launchRays -> nested sample -> nested lights ->
+// nested colour -> primary lights -> blend and store.
 int matShade(SnailMaterials *m, const char *fn, const float cam[13], int resx, int resy, const int32_t *dXY, int np, const float *lights7, int nLights,
-			 const float ambient[3], uint8_t *frame, int pitch, uint8_t *bgrPackets, const SnailMaterials::Bufs &W, uint64_t *dStats, hipStream_t st) {
+			 const float ambient[3], uint8_t *frame, int pitch, uint8_t *bgrPackets, const SnailMaterials::Bufs &W, const SnailMaterials::BounceBufs *R,
+			 uint64_t *dStats, hipStream_t st) {
 	SnailScene *s = m->scene;
 	SceneUse use(s, st);
 	if(use.rc) return use.rc;
@@ -96,20 +119,46 @@ int matShade(SnailMaterials *m, const char *fn, const float cam[13], int resx, i
 	A.samples = W.samples; A.s.sDist = W.sDist;
 	A.s.frame = frame; A.s.pitch = pitch; A.s.bgrPackets = bgrPackets;
 	A.s.stats = (dev::u64 *)dStats;
+	if(R) {
+		A.s.rOrg = R->rOrg; A.s.rDir = R->rDir; A.s.rIDir = R->rIDir; A.s.rMask = R->rMask; A.s.rDist = R->rDist; A.s.rObj = R->rObj; A.s.rCol = R->rCol;
+		A.rU = R->bary; A.rV = R->bary + 4; A.rUVStride = 8;
+		A.nSamples = R->nSamples; A.nSDist = R->nSDist;
+		A.s.blend = 1;
+	}
 	const bool sse = s->arith == SNAIL_ARITH_HOST_SSE;
 	const dim3 grid(np), wave(64);
 	SNAIL_LAUNCH(sse, MatArgs, grid, wave, 0, st, A, k_mat_sample);
 	HIP_TRY(hipGetLastError());
+	if(R) {
+		SNAIL_LAUNCH(sse, MatArgs, grid, wave, 0, st, A, k_mat_mirror);
+		HIP_TRY(hipGetLastError());
+		// the walk reads the barycentrics it was given and writes them back for lanes without a hit: zeros, not what the buffer last held
+		HIP_TRY(hipMemsetAsync(R->bary, 0, (size_t)np * 256 * 8, st));
+		if(int rc = launchRays(s, false, np, 64, 0, R->rOrg, R->rDir, R->rIDir, R->rMask, R->rDist, R->rObj, R->bary, dStats, st)) return rc;
+		SNAIL_LAUNCH(sse, MatArgs, grid, wave, 0, st, A, k_mat_sample_rays);
+		HIP_TRY(hipGetLastError());
+	}
+	int lrc = 0;
 	if(nLights) {
 		int relWhich[SNAIL_MAX_LIGHTS];
 		for(int n = 0; n < SNAIL_MAX_LIGHTS; n++) { relWhich[n] = -1; A.s.relLight[n] = nullptr; }
 		// every origin-relative copy taken here is booked as used on st on EVERY way out (first error kept): a copy whose fill was enqueued must not
-		// be recycled under it, whether or not the walk that wanted it was launched
-		int lrc = 0;
+		// be recycled under it, whether or not the walk that wanted it was launched.  The nested lights walk from the same origins: the same copies.
 		if(A.s.pack && !useDeep(s))
 			for(int n = 0; n < nLights && !lrc; n++) lrc = relFor(s, A.s.lights[n], st, &A.s.relLight[n], &relWhich[n]);
+		const dim3 lgrid(np, nLights);
+		if(!lrc && R) {
+			if(useDeep(s)) SNAIL_LAUNCH(sse, MatArgs, lgrid, wave, 0, st, A, k_mat_light_rays<true>);
+			else SNAIL_LAUNCH(sse, MatArgs, lgrid, wave, 0, st, A, k_mat_light_rays<false>);
+			const hipError_t e = hipGetLastError();
+			if(e != hipSuccess) { snail_set_error("%s: k_mat_light_rays: %s", fn, hipGetErrorString(e)); lrc = 100 + (int)e; }
+		}
+		if(!lrc && R) {
+			SNAIL_LAUNCH(sse, MatArgs, grid, wave, 0, st, A, k_mat_colour_rays);
+			const hipError_t e = hipGetLastError();
+			if(e != hipSuccess) { snail_set_error("%s: k_mat_colour_rays: %s", fn, hipGetErrorString(e)); lrc = 100 + (int)e; }
+		}
 		if(!lrc) {
-			const dim3 lgrid(np, nLights);
 			if(useDeep(s)) SNAIL_LAUNCH(sse, MatArgs, lgrid, wave, 0, st, A, k_mat_light<true>);
 			else SNAIL_LAUNCH(sse, MatArgs, lgrid, wave, 0, st, A, k_mat_light<false>);
 			const hipError_t e = hipGetLastError();
@@ -118,8 +167,12 @@ int matShade(SnailMaterials *m, const char *fn, const float cam[13], int resx, i
 		for(int n = 0; n < nLights; n++)
 			if(relWhich[n] >= 0) { const int urc = relUsed(s, relWhich[n], st); if(!lrc) lrc = urc; }
 		if(lrc) return lrc;
+	} else if(R) {
+		SNAIL_LAUNCH(sse, MatArgs, grid, wave, 0, st, A, k_mat_colour_rays);
+		HIP_TRY(hipGetLastError());
 	}
-	SNAIL_LAUNCH(sse, MatArgs, grid, wave, 0, st, A, k_mat_final);
+	if(R) SNAIL_LAUNCH(sse, MatArgs, grid, wave, 0, st, A, k_mat_final_blend);
+	else SNAIL_LAUNCH(sse, MatArgs, grid, wave, 0, st, A, k_mat_final);
 	HIP_TRY(hipGetLastError());
 	return 0;
 }
@@ -148,7 +201,7 @@ int matFrameList(SnailMaterials *m, int resx, int resy, const int32_t **dXY, int
 
 // snail_render_materials_dev / _packets_dev (the scene's mu held): the next set of intermediates, grown if need be, its previous user waited for on st
 int matShadeDev(SnailMaterials *m, const char *fn, const float cam[13], int resx, int resy, const int32_t *dXY, int np, const float *lights7, int nLights,
-				const float ambient[3], uint8_t *frame, int pitch, uint8_t *bgrPackets, uint64_t *dStats, hipStream_t st) {
+				const float ambient[3], uint8_t *frame, int pitch, uint8_t *bgrPackets, uint64_t *dStats, hipStream_t st, bool refl = false) {
 	if(!dXY) { if(int rc = matFrameList(m, resx, resy, &dXY, &np)) return rc; }
 	SnailMaterials::Set &W = m->set[m->setCount++ % SnailMaterials::kSets];
 	if(!W.base || W.packets < (size_t)np || W.lights < nLights) {   // grown: its previous user may still be running
@@ -160,16 +213,27 @@ int matShadeDev(SnailMaterials *m, const char *fn, const float cam[13], int resx
 		HIP_TRY(hipMalloc((void **)&W.base, SnailMaterials::Bufs::bytes(packets, lights)));
 		W.packets = packets; W.lights = lights;
 	}
+	if(refl && (!W.bounce || W.bouncePackets < (size_t)np || W.bounceLights < nLights)) {   // the bounce's part: only when asked for, grown the same way
+		HIP_TRY(hipDeviceSynchronize());
+		if(W.bounce) (void)hipFree(W.bounce);
+		const size_t packets = std::max(W.bouncePackets, (size_t)np);
+		const int lights = std::max(W.bounceLights, nLights);
+		W.bounce = nullptr; W.bouncePackets = 0; W.bounceLights = 0; W.used = false;
+		HIP_TRY(hipMalloc((void **)&W.bounce, SnailMaterials::BounceBufs::bytes(packets, lights)));
+		W.bouncePackets = packets; W.bounceLights = lights;
+	}
 	if(!W.done) HIP_TRY(hipEventCreateWithFlags(&W.done, hipEventDisableTiming));
 	if(W.used) HIP_TRY(hipStreamWaitEvent(st, W.done, 0));
 	SnailMaterials::Bufs B;
 	B.carve(W.base, (size_t)np);
-	const int rc = matShade(m, fn, cam, resx, resy, dXY, np, lights7, nLights, ambient, frame, pitch, bgrPackets, B, dStats, st);
+	SnailMaterials::BounceBufs RB;
+	if(refl) RB.carve(W.bounce, (size_t)np, nLights);
+	const int rc = matShade(m, fn, cam, resx, resy, dXY, np, lights7, nLights, ambient, frame, pitch, bgrPackets, B, refl ? &RB : nullptr, dStats, st);
 	// also when a stage failed after earlier ones were enqueued: they may still be running on these buffers, and the set's next user (on any
 	// stream) must come after them.  Should the record itself fail, the set is marked grown-from-scratch: its next user synchronises the device.
 	if(hipEventRecord(W.done, st) == hipSuccess) W.used = true;
 	else {
-		W.packets = 0; W.used = false;
+		W.packets = 0; W.bouncePackets = 0; W.used = false;
 		if(!rc) { snail_set_error("%s: hipEventRecord failed", fn); return 1; }
 	}
 	return rc;
@@ -340,6 +404,7 @@ void snail_materials_destroy(SnailMaterials *m) {
 	(void)hipDeviceSynchronize();
 	for(auto &W : m->set) {
 		if(W.base) (void)hipFree(W.base);
+		if(W.bounce) (void)hipFree(W.bounce);
 		if(W.done) (void)hipEventDestroy(W.done);
 	}
 	for(auto &f : m->frameLists) (void)hipFree(f.d);
@@ -368,34 +433,31 @@ int snail_materials_shade_packets_dev(SnailMaterials *m, const float cam[13], in
 	return 0;
 }
 
-int snail_render_materials_dev(SnailMaterials *m, const float cam[13], int resx, int resy, const float *lights7, int nLights, const float ambient[3], int flags,
-							   uint8_t *frame, int pitch, uint64_t *dStats, void *stream) {
-	const char *fn = "snail_render_materials_dev";
-	if(int rc = checkMatFrameArgs(fn, cam, resx, resy, lights7, nLights, ambient, flags)) return rc;
+} // extern "C"
+
+// the three frame functions after their flags have been judged (refl: the one mirrored bounce)
+static int matFrameDev(const char *fn, SnailMaterials *m, const float cam[13], int resx, int resy, const float *lights7, int nLights, const float ambient[3], bool refl,
+					   uint8_t *frame, int pitch, uint64_t *dStats, void *stream) {
 	if(int rc = checkMaterials(m, fn)) return rc;
 	if(!frame || pitch < resx * 3) { snail_set_error("%s: null frame or a pitch below 3 * resx", fn); return 1; }
 	DeviceGuard guard(m->device);
 	SNAIL_LOCK(m->scene);
-	return matShadeDev(m, fn, cam, resx, resy, nullptr, 0, lights7, nLights, ambient, frame, pitch, nullptr, dStats, (hipStream_t)stream);
+	return matShadeDev(m, fn, cam, resx, resy, nullptr, 0, lights7, nLights, ambient, frame, pitch, nullptr, dStats, (hipStream_t)stream, refl);
 }
 
-int snail_render_materials_packets_dev(SnailMaterials *m, const float cam[13], int resx, int resy, const int32_t *dPacketXY, int nPackets, const float *lights7,
-									   int nLights, const float ambient[3], int flags, uint8_t *bgrPackets, uint64_t *dStats, void *stream) {
-	const char *fn = "snail_render_materials_packets_dev";
-	if(int rc = checkMatFrameArgs(fn, cam, resx, resy, lights7, nLights, ambient, flags)) return rc;
+static int matFramePacketsDev(const char *fn, SnailMaterials *m, const float cam[13], int resx, int resy, const int32_t *dPacketXY, int nPackets, const float *lights7,
+							  int nLights, const float ambient[3], bool refl, uint8_t *bgrPackets, uint64_t *dStats, void *stream) {
 	if(int rc = checkMaterials(m, fn)) return rc;
 	if(!dPacketXY && nPackets > 0) { snail_set_error("%s: null packet list", fn); return 1; }
 	if(nPackets <= 0) return 0;
 	if(!bgrPackets || ((unsigned long long)bgrPackets & 3)) { snail_set_error("%s: null or unaligned output", fn); return 1; }
 	DeviceGuard guard(m->device);
 	SNAIL_LOCK(m->scene);
-	return matShadeDev(m, fn, cam, resx, resy, dPacketXY, nPackets, lights7, nLights, ambient, nullptr, 0, bgrPackets, dStats, (hipStream_t)stream);
+	return matShadeDev(m, fn, cam, resx, resy, dPacketXY, nPackets, lights7, nLights, ambient, nullptr, 0, bgrPackets, dStats, (hipStream_t)stream, refl);
 }
 
-int snail_render_materials_image(SnailMaterials *m, const float cam[13], int resx, int resy, const float *lights7, int nLights, const float ambient[3], int flags,
-								 uint8_t *image, int pitch, uint64_t stats[4]) {
-	const char *fn = "snail_render_materials_image";
-	if(int rc = checkMatFrameArgs(fn, cam, resx, resy, lights7, nLights, ambient, flags)) return rc;
+static int matFrameImage(const char *fn, SnailMaterials *m, const float cam[13], int resx, int resy, const float *lights7, int nLights, const float ambient[3], bool refl,
+						 uint8_t *image, int pitch, uint64_t stats[4]) {
 	if(int rc = checkMaterials(m, fn)) return rc;
 	if(!image || pitch < resx * 3) { snail_set_error("%s: null image or a pitch below 3 * resx", fn); return 1; }
 	DeviceGuard guard(m->device);
@@ -407,19 +469,124 @@ int snail_render_materials_image(SnailMaterials *m, const float cam[13], int res
 	for(int y = 0; y < ph; y++)
 		for(int x = 0; x < pw; x++) { xy[((size_t)y * pw + x) * 2] = x * 16; xy[((size_t)y * pw + x) * 2 + 1] = y * 16; }
 	typedef HostCallScope H;
-	const size_t imgBytes = (size_t)pitch * resy, bufBytes = SnailMaterials::Bufs::bytes((size_t)np, nLights);
-	if(int rc = hc.reserve(H::pad(xy.size() * 4) + H::pad(bufBytes) + H::pad(imgBytes + 4))) return rc;
+	const size_t imgBytes = (size_t)pitch * resy, bufBytes = SnailMaterials::Bufs::bytes((size_t)np, nLights),
+				 bounceBytes = refl ? SnailMaterials::BounceBufs::bytes((size_t)np, nLights) : 0;
+	if(int rc = hc.reserve(H::pad(xy.size() * 4) + H::pad(bufBytes) + (refl ? H::pad(bounceBytes) : 0) + H::pad(imgBytes + 4))) return rc;
 	void *dXY = nullptr;
 	if(int rc = hc.put(&dXY, xy.data(), xy.size() * 4)) return rc;
 	SnailMaterials::Bufs W;
 	W.carve((char *)hc.carve(bufBytes), (size_t)np);
+	SnailMaterials::BounceBufs RB;
+	if(refl) RB.carve((char *)hc.carve(bounceBytes), (size_t)np, nLights);
 	uint8_t *dImg = (uint8_t *)hc.carve(imgBytes + 4);
 	{
 		SNAIL_LOCK(m->scene);
-		if(int rc = matShade(m, fn, cam, resx, resy, (const int32_t *)dXY, np, lights7, nLights, ambient, dImg, pitch, nullptr, W, hc.stats(), hc.stream())) return rc;
+		if(int rc = matShade(m, fn, cam, resx, resy, (const int32_t *)dXY, np, lights7, nLights, ambient, dImg, pitch, nullptr, W, refl ? &RB : nullptr, hc.stats(), hc.stream())) return rc;
 	}
 	HIP_TRY(hipMemcpy2DAsync(image, (size_t)pitch, dImg, (size_t)pitch, (size_t)resx * 3, (size_t)resy, hipMemcpyDeviceToHost, hc.stream()));
 	return hc.finish(stats);
+}
+
+// include/snail_materials_bounce.h: flags = 0 or SNAIL_RENDER_REFLECTIONS, judged before anything else
+static int checkBounceFrameArgs(const char *fn, const float cam[13], int resx, int resy, const float *lights7, int nLights, const float ambient[3], int flags) {
+	if(flags & ~SNAIL_RENDER_REFLECTIONS) {
+		snail_set_error("%s: flags must be 0 or SNAIL_RENDER_REFLECTIONS (got 0x%x): no depth shading, transparency or antialiasing under full shading", fn, flags);
+		return 1;
+	}
+	return checkMatFrameArgs(fn, cam, resx, resy, lights7, nLights, ambient, 0);
+}
+
+extern "C" {
+
+int snail_render_materials_dev(SnailMaterials *m, const float cam[13], int resx, int resy, const float *lights7, int nLights, const float ambient[3], int flags,
+							   uint8_t *frame, int pitch, uint64_t *dStats, void *stream) {
+	const char *fn = "snail_render_materials_dev";
+	if(int rc = checkMatFrameArgs(fn, cam, resx, resy, lights7, nLights, ambient, flags)) return rc;
+	return matFrameDev(fn, m, cam, resx, resy, lights7, nLights, ambient, false, frame, pitch, dStats, stream);
+}
+
+int snail_render_materials_packets_dev(SnailMaterials *m, const float cam[13], int resx, int resy, const int32_t *dPacketXY, int nPackets, const float *lights7,
+									   int nLights, const float ambient[3], int flags, uint8_t *bgrPackets, uint64_t *dStats, void *stream) {
+	const char *fn = "snail_render_materials_packets_dev";
+	if(int rc = checkMatFrameArgs(fn, cam, resx, resy, lights7, nLights, ambient, flags)) return rc;
+	return matFramePacketsDev(fn, m, cam, resx, resy, dPacketXY, nPackets, lights7, nLights, ambient, false, bgrPackets, dStats, stream);
+}
+
+int snail_render_materials_image(SnailMaterials *m, const float cam[13], int resx, int resy, const float *lights7, int nLights, const float ambient[3], int flags,
+								 uint8_t *image, int pitch, uint64_t stats[4]) {
+	const char *fn = "snail_render_materials_image";
+	if(int rc = checkMatFrameArgs(fn, cam, resx, resy, lights7, nLights, ambient, flags)) return rc;
+	return matFrameImage(fn, m, cam, resx, resy, lights7, nLights, ambient, false, image, pitch, stats);
+}
+
+// ---- include/snail_materials_bounce.h ----
+int snail_materials_bounce_dev(SnailMaterials *m, const float cam[13], int resx, int resy, const float *lights7, int nLights, const float ambient[3], int flags,
+							   uint8_t *frame, int pitch, uint64_t *dStats, void *stream) {
+	const char *fn = "snail_materials_bounce_dev";
+	if(int rc = checkBounceFrameArgs(fn, cam, resx, resy, lights7, nLights, ambient, flags)) return rc;
+	return matFrameDev(fn, m, cam, resx, resy, lights7, nLights, ambient, (flags & SNAIL_RENDER_REFLECTIONS) != 0, frame, pitch, dStats, stream);
+}
+
+int snail_materials_bounce_packets_dev(SnailMaterials *m, const float cam[13], int resx, int resy, const int32_t *dPacketXY, int nPackets, const float *lights7,
+									   int nLights, const float ambient[3], int flags, uint8_t *bgrPackets, uint64_t *dStats, void *stream) {
+	const char *fn = "snail_materials_bounce_packets_dev";
+	if(int rc = checkBounceFrameArgs(fn, cam, resx, resy, lights7, nLights, ambient, flags)) return rc;
+	return matFramePacketsDev(fn, m, cam, resx, resy, dPacketXY, nPackets, lights7, nLights, ambient, (flags & SNAIL_RENDER_REFLECTIONS) != 0, bgrPackets, dStats, stream);
+}
+
+int snail_materials_bounce_image(SnailMaterials *m, const float cam[13], int resx, int resy, const float *lights7, int nLights, const float ambient[3], int flags,
+								 uint8_t *image, int pitch, uint64_t stats[4]) {
+	const char *fn = "snail_materials_bounce_image";
+	if(int rc = checkBounceFrameArgs(fn, cam, resx, resy, lights7, nLights, ambient, flags)) return rc;
+	return matFrameImage(fn, m, cam, resx, resy, lights7, nLights, ambient, (flags & SNAIL_RENDER_REFLECTIONS) != 0, image, pitch, stats);
+}
+
+int snail_materials_mirror_packets_dev(SnailMaterials *m, const float cam[13], int resx, int resy, const int32_t *dPacketXY, int nPackets, const float *dT,
+									   const float *dSamples, float *dOrigin, float *dDir, float *dIDir, uint8_t *dMask, float *dDistance, int32_t *dObject,
+									   uint64_t *dStats, void *stream) {
+	const char *fn = "snail_materials_mirror_packets_dev";
+	if(int rc = checkMaterials(m, fn)) return rc;
+	if(nPackets <= 0) return 0;
+	if(!cam || resx <= 0 || resy <= 0 || !dPacketXY || !dT || !dSamples || !dOrigin || !dDir || !dIDir || !dMask || !dDistance || !dObject ||
+	   (((unsigned long long)dSamples | (unsigned long long)dOrigin | (unsigned long long)dDir | (unsigned long long)dIDir | (unsigned long long)dDistance | (unsigned long long)dObject) & 15)) {
+		snail_set_error("%s: bad camera or resolution, a null buffer, or a buffer not 16-byte aligned", fn);
+		return 1;
+	}
+	DeviceGuard guard(m->device);
+	SNAIL_LOCK(m->scene);
+	dev::MatArgs A;
+	matFillArgs(m, A, cam, resx, resy, dPacketXY, nPackets);
+	A.s.hitT = dT; A.samples = const_cast<float *>(dSamples);
+	A.s.rOrg = dOrigin; A.s.rDir = dDir; A.s.rIDir = dIDir; A.s.rMask = dMask; A.s.rDist = dDistance; A.s.rObj = dObject;
+	A.s.stats = (dev::u64 *)dStats;
+	const bool sse = m->scene->arith == SNAIL_ARITH_HOST_SSE;
+	SNAIL_LAUNCH(sse, MatArgs, dim3(nPackets), dim3(64), 0, (hipStream_t)stream, A, k_mat_mirror);
+	HIP_TRY(hipGetLastError());
+	return 0;
+}
+
+int snail_materials_shade_rays_dev(SnailMaterials *m, int nPackets, const float *dDir, const uint8_t *dMask, const float *dT, const float *dU, const float *dV,
+								   const int32_t *dTriId, float *dSamples, void *stream) {
+	const char *fn = "snail_materials_shade_rays_dev";
+	if(int rc = checkMaterials(m, fn)) return rc;
+	if(nPackets <= 0) return 0;
+	if(!dDir || !dT || !dU || !dV || !dTriId || !dSamples ||
+	   (((unsigned long long)dDir | (unsigned long long)dT | (unsigned long long)dU | (unsigned long long)dV | (unsigned long long)dTriId | (unsigned long long)dSamples) & 15)) {
+		snail_set_error("%s: a null buffer, or a buffer not 16-byte aligned", fn);
+		return 1;
+	}
+	DeviceGuard guard(m->device);
+	SNAIL_LOCK(m->scene);
+	dev::MatArgs A;
+	const float noCam[13] = {0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0, 1, 1};   // (generic packets carry their rays: no stage of this call generates any)
+	matFillArgs(m, A, noCam, 16, 16, nullptr, nPackets);
+	A.s.rDir = const_cast<float *>(dDir); A.s.rMask = const_cast<uint8_t *>(dMask); A.s.rDist = const_cast<float *>(dT); A.s.rObj = const_cast<int32_t *>(dTriId);
+	A.rU = dU; A.rV = dV; A.rUVStride = 4;
+	A.nSamples = dSamples;
+	const bool sse = m->scene->arith == SNAIL_ARITH_HOST_SSE;
+	SNAIL_LAUNCH(sse, MatArgs, dim3(nPackets), dim3(64), 0, (hipStream_t)stream, A, k_mat_sample_rays);
+	HIP_TRY(hipGetLastError());
+	return 0;
 }
 
 } // extern "C"

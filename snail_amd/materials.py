@@ -7,7 +7,10 @@ and MipmapTexture / PointSampler -- over the C-ABI of include/snail_materials.h.
   MaterialSet(scene, uv, nrm, mat_index, flat, material_map, materials, textures)   <-> BVH::shTris / BVH::materials + Scene::materials
   .shade_packets / .render / .render_packets / .render_image_host   <-> Scene::RayTrace with gVals[6] && HasShadingData(), primary packets
 
-Out of this module (the host renderer keeps them): the bounce and transparency under full shading, 4x AA, tile lists, OBJ / MTL ingest."""
+  .mirror_packets / .shade_rays, reflections=True   <-> the one mirrored bounce of gVals[7] (Scene::TraceReflection and its nested
+                                                        RayTrace<0, hasMask>), include/snail_materials_bounce.h
+
+Out of this module (the host renderer keeps them): transparency under full shading, 4x AA, tile lists, OBJ / MTL ingest."""
 from __future__ import annotations
 
 import ctypes as C
@@ -21,6 +24,7 @@ KIND_SIMPLE, KIND_TEX, KIND_UBER, KIND_TRANSPARENT = 0, 1, 2, 3
 MATERIAL_DTYPE = np.dtype([("kind", "<i4"), ("ndotr", "<i4"), ("diffuse", "<f4", 3), ("specular", "<f4", 3), ("dissolve", "<f4"), ("texture", "<i4")])
 assert MATERIAL_DTYPE.itemsize == 40
 SAMPLE_COMPONENTS = 9        # normal, diffuse, specular
+RENDER_REFLECTIONS = 1       # SNAIL_RENDER_REFLECTIONS (include/snail_hip.h)
 
 
 def texture_size(w: int, h: int):
@@ -164,8 +168,38 @@ class MaterialSet:
         _lib.check(rc, "snail_materials_shade_packets_dev")
         return out
 
-    def render(self, cam, resx: int, resy: int, lights7=None, ambient=(0.1, 0.1, 0.1), out=None, stats=None, stream=None, flags: int = 0):
-        """The lit frame, [resy, resx, 3] uint8 (B,G,R) (or `out`: a uint8 device tensor [resy, pitch] / [resy, w, 3] whose rows may be wider)."""
+    def mirror_packets(self, cam, resx: int, resy: int, packet_xy, t, samples, stats=None, stream=None):
+        """Scene::TraceReflection on the primary samples of a packet list (t: the hits' distances [n, 256]; samples: shade_packets' buffer) ->
+        (origin, dir, idir [n, 64, 3, 4] float32, mask [n, 64] uint8, distance [n, 256] float32, object [n, 256] int32): the mirrored packets
+        in the layouts snail_trace_rays_dev takes.  snail_materials_mirror_packets_dev."""
+        torch = _torch()
+        n = int(packet_xy.shape[0])
+        dev = self.scene._dev()
+        org, d, idir = (torch.empty((n, 64, 3, 4), dtype=torch.float32, device=dev) for _ in range(3))
+        mask = torch.empty((n, 64), dtype=torch.uint8, device=dev)
+        dist = torch.empty((n, 256), dtype=torch.float32, device=dev)
+        obj = torch.empty((n, 256), dtype=torch.int32, device=dev)
+        cam13 = np.ascontiguousarray(cam.as_array13(), dtype=np.float32)
+        rc = _lib.lib().snail_materials_mirror_packets_dev(self._h, _lib.ptr(cam13), resx, resy, _lib.ptr(packet_xy), n, _lib.ptr(t), _lib.ptr(samples), _lib.ptr(org),
+                                                           _lib.ptr(d), _lib.ptr(idir), _lib.ptr(mask), _lib.ptr(dist), _lib.ptr(obj), _lib.ptr(stats), _stream_ptr(stream))
+        _lib.check(rc, "snail_materials_mirror_packets_dev")
+        return org, d, idir, mask, dist, obj
+
+    def shade_rays(self, dirs, mask, t, u, v, tri_id, out=None, stream=None):
+        """The samples of generic packets (RayGroup<0, hasMask>): dirs [n, 64, 3, 4], mask [n, 64] uint8 or None (every lane selected), hit
+        records t / u / v / tri_id [n, 256] (device tensors) -> float32 [n, 9, 64, 4].  snail_materials_shade_rays_dev."""
+        torch = _torch()
+        n = int(dirs.shape[0])
+        if out is None:
+            out = torch.empty((n, SAMPLE_COMPONENTS, 64, 4), dtype=torch.float32, device=self.scene._dev())
+        rc = _lib.lib().snail_materials_shade_rays_dev(self._h, n, _lib.ptr(dirs), _lib.ptr(mask), _lib.ptr(t), _lib.ptr(u), _lib.ptr(v), _lib.ptr(tri_id), _lib.ptr(out),
+                                                       _stream_ptr(stream))
+        _lib.check(rc, "snail_materials_shade_rays_dev")
+        return out
+
+    def render(self, cam, resx: int, resy: int, lights7=None, ambient=(0.1, 0.1, 0.1), out=None, stats=None, stream=None, flags: int = 0, reflections: bool = False):
+        """The lit frame, [resy, resx, 3] uint8 (B,G,R) (or `out`: a uint8 device tensor [resy, pitch] / [resy, w, 3] whose rows may be wider).
+        reflections=True: with the one mirrored bounce of gVals[7] (snail_materials_bounce_dev; `flags` are then that function's)."""
         torch = _torch()
         if out is None:
             out = torch.zeros((resy, resx, 3), dtype=torch.uint8, device=self.scene._dev())
@@ -173,13 +207,19 @@ class MaterialSet:
         lights = self._lights(lights7)
         cam13 = np.ascontiguousarray(cam.as_array13(), dtype=np.float32)
         amb = np.ascontiguousarray(ambient, dtype=np.float32)
+        if reflections:
+            rc = _lib.lib().snail_materials_bounce_dev(self._h, _lib.ptr(cam13), resx, resy, _lib.ptr(lights) if len(lights) else None, len(lights), _lib.ptr(amb),
+                                                       int(flags) | RENDER_REFLECTIONS, _lib.ptr(out), pitch, _lib.ptr(stats), _stream_ptr(stream))
+            _lib.check(rc, "snail_materials_bounce_dev")
+            return out
         rc = _lib.lib().snail_render_materials_dev(self._h, _lib.ptr(cam13), resx, resy, _lib.ptr(lights) if len(lights) else None, len(lights), _lib.ptr(amb),
                                                    int(flags), _lib.ptr(out), pitch, _lib.ptr(stats), _stream_ptr(stream))
         _lib.check(rc, "snail_render_materials_dev")
         return out
 
-    def render_packets(self, cam, resx: int, resy: int, packet_xy, lights7=None, ambient=(0.1, 0.1, 0.1), out=None, stats=None, stream=None, flags: int = 0):
-        """render for an explicit packet list: packet-major [n, 256, 3] uint8 (B,G,R)."""
+    def render_packets(self, cam, resx: int, resy: int, packet_xy, lights7=None, ambient=(0.1, 0.1, 0.1), out=None, stats=None, stream=None, flags: int = 0,
+                       reflections: bool = False):
+        """render for an explicit packet list: packet-major [n, 256, 3] uint8 (B,G,R).  reflections=True: snail_materials_bounce_packets_dev."""
         torch = _torch()
         n = int(packet_xy.shape[0])
         if out is None:
@@ -187,20 +227,31 @@ class MaterialSet:
         lights = self._lights(lights7)
         cam13 = np.ascontiguousarray(cam.as_array13(), dtype=np.float32)
         amb = np.ascontiguousarray(ambient, dtype=np.float32)
+        if reflections:
+            rc = _lib.lib().snail_materials_bounce_packets_dev(self._h, _lib.ptr(cam13), resx, resy, _lib.ptr(packet_xy), n, _lib.ptr(lights) if len(lights) else None,
+                                                               len(lights), _lib.ptr(amb), int(flags) | RENDER_REFLECTIONS, _lib.ptr(out), _lib.ptr(stats), _stream_ptr(stream))
+            _lib.check(rc, "snail_materials_bounce_packets_dev")
+            return out
         rc = _lib.lib().snail_render_materials_packets_dev(self._h, _lib.ptr(cam13), resx, resy, _lib.ptr(packet_xy), n, _lib.ptr(lights) if len(lights) else None,
                                                            len(lights), _lib.ptr(amb), int(flags), _lib.ptr(out), _lib.ptr(stats), _stream_ptr(stream))
         _lib.check(rc, "snail_render_materials_packets_dev")
         return out
 
-    def render_image_host(self, cam, resx: int, resy: int, lights7=None, ambient=(0.1, 0.1, 0.1), flags: int = 0, pitch: int | None = None, fill: int = 0):
+    def render_image_host(self, cam, resx: int, resy: int, lights7=None, ambient=(0.1, 0.1, 0.1), flags: int = 0, pitch: int | None = None, fill: int = 0,
+                          reflections: bool = False):
         """snail_render_materials_image: the frame in host memory, uint8 [resy, pitch] (pitch = 3 * resx unless given; bytes past a row's
-        pixels keep `fill`), and the call's TreeStats."""
+        pixels keep `fill`), and the call's TreeStats.  reflections=True: snail_materials_bounce_image."""
         pitch = resx * 3 if pitch is None else int(pitch)
         img = np.full((resy, pitch), fill, dtype=np.uint8)
         stats = np.zeros(4, dtype=np.uint64)
         lights = self._lights(lights7)
         cam13 = np.ascontiguousarray(cam.as_array13(), dtype=np.float32)
         amb = np.ascontiguousarray(ambient, dtype=np.float32)
+        if reflections:
+            rc = _lib.lib().snail_materials_bounce_image(self._h, _lib.ptr(cam13), resx, resy, _lib.ptr(lights) if len(lights) else None, len(lights), _lib.ptr(amb),
+                                                         int(flags) | RENDER_REFLECTIONS, _lib.ptr(img), pitch, _lib.ptr(stats))
+            _lib.check(rc, "snail_materials_bounce_image")
+            return img, stats
         rc = _lib.lib().snail_render_materials_image(self._h, _lib.ptr(cam13), resx, resy, _lib.ptr(lights) if len(lights) else None, len(lights), _lib.ptr(amb),
                                                      int(flags), _lib.ptr(img), pitch, _lib.ptr(stats))
         _lib.check(rc, "snail_render_materials_image")

@@ -15,7 +15,14 @@ whitted and default_flat are compared byte for byte before anything is timed.  N
 materials_mod5, TEXTURES), which are handed the product's HostBVH where they document an OracleScene -- they read only .tris["plane"] and
 .perm, which both carry; importing them imports tests/oracle_lib.py but never loads or builds the oracle library.
 
-    python tools/materials_time.py [--res 1920x1080] [--frames 400] [--reps 7] [--parent-lib PATH] [--out profiles/materials.txt] [--trace N]"""
+--reflections: the same measurement of the one mirrored bounce of gVals[7] (include/snail_materials_bounce.h) instead -- whitted_refl
+(snail_render_whitted_dev with SNAIL_WHITTED_REFLECTIONS, the simple-shading bounce, always of THIS build), default_flat_refl and
+textured_refl (MaterialSet.render(reflections=True)), and the three stages that have entry points of their own, launch to launch over the
+frame's packets with the textured set: mirror (snail_materials_mirror_packets_dev), mirror+walk (that and snail_trace_rays_dev with masks and
+barycentrics) and sample_rays (snail_materials_shade_rays_dev).  The frames of whitted_refl and default_flat_refl are compared byte for
+byte first.  The kernels' own times, the nested light and colour stages included, come from a kernel trace of --reflections --trace N.
+
+    python tools/materials_time.py [--res 1920x1080] [--frames 400] [--reps 7] [--parent-lib PATH] [--out profiles/materials.txt] [--trace N] [--reflections]"""
 import argparse
 import ctypes as C
 import os
@@ -62,6 +69,7 @@ def main():
     ap.add_argument("--parent-lib", default=None)
     ap.add_argument("--out", default=None)
     ap.add_argument("--trace", type=int, default=0)
+    ap.add_argument("--reflections", action="store_true")
     a = ap.parse_args()
     resx, resy = (int(v) for v in a.res.split("x"))
     import torch
@@ -85,6 +93,8 @@ def main():
     descs, mmap = K.materials_mod5()
     mats = [P.Material.simple(d[1], d[2]) if d[0] == "simple" else P.Material.textured(d[1], d[2]) if d[0] == "tex" else P.Material.uber(d[1], d[2], d[3]) for d in descs]
     tex_set = P.MaterialSet(sc, uv, nrm, np.arange(n, dtype=np.int32) % 5, flat, mmap, mats, [P.Texture(t) for t in K.TEXTURES()])
+    if a.reflections:
+        return bounce(a, sc, cam, resx, resy, lights, flat_set, tex_set, n)
     parent = ParentScene(a.parent_lib, hb) if a.parent_lib else None
 
     out = [torch.zeros((resy, resx, 3), dtype=torch.uint8, device="cuda:0") for _ in range(3)]
@@ -142,6 +152,85 @@ def main():
             fh.write(text + "\n")
     if not same:
         raise SystemExit("default_flat and whitted frames differ")
+
+
+def bounce(a, sc, cam, resx, resy, lights, flat_set, tex_set, n):
+    """--reflections: the bounce under simple and under full shading, and its stages"""
+    import torch
+    out = [torch.zeros((resy, resx, 3), dtype=torch.uint8, device="cuda:0") for _ in range(3)]
+    variants = {
+        "whitted_refl": lambda: sc.render_whitted(cam, resx, resy, lights, out=out[0], reflections=True),
+        "default_flat_refl": lambda: flat_set.render(cam, resx, resy, lights, out=out[1], reflections=True),
+        "textured_refl": lambda: tex_set.render(cam, resx, resy, lights, out=out[2], reflections=True),
+    }
+    for fn in variants.values():
+        fn(); fn()
+    torch.cuda.synchronize()
+    same = bool(torch.equal(out[0], out[1]))
+    if a.trace:
+        for _ in range(a.trace):
+            variants["textured_refl"]()
+        torch.cuda.synchronize()
+        print("trace run: %d textured frames with the bounce" % a.trace)
+        return
+    # the stages with entry points of their own, on the textured set's own intermediates
+    pw, ph = (resx + 15) // 16, (resy + 15) // 16
+    xy = torch.tensor([(x * 16, y * 16) for y in range(ph) for x in range(pw)], dtype=torch.int32, device="cuda:0")
+    hits = sc.trace_packets(cam, resx, resy, xy)
+    smp = tex_set.shade_packets(cam, resx, resy, xy, hits)
+    org, d, idir, mask, dist, obj = tex_set.mirror_packets(cam, resx, resy, xy, hits[0], smp)
+    np_ = pw * ph
+    bary = torch.zeros((np_, 64, 8), dtype=torch.float32, device="cuda:0")
+    L = _lib.lib()
+    cam13 = np.ascontiguousarray(cam.as_array13(), dtype=np.float32)
+
+    def mirror():
+        _lib.check(L.snail_materials_mirror_packets_dev(tex_set._h, _lib.ptr(cam13), resx, resy, _lib.ptr(xy), np_, _lib.ptr(hits[0]), _lib.ptr(smp), _lib.ptr(org), _lib.ptr(d),
+                                                        _lib.ptr(idir), _lib.ptr(mask), _lib.ptr(dist), _lib.ptr(obj), None, _stream_ptr(None)), "snail_materials_mirror_packets_dev")
+
+    def walk():      # (after the first launch the distances are the hits': every later walk finds nothing nearer -- so the mirror stage runs before each)
+        _lib.check(L.snail_trace_rays_dev(sc._h, np_, 64, 0, _lib.ptr(org), _lib.ptr(d), _lib.ptr(idir), _lib.ptr(mask), _lib.ptr(dist), _lib.ptr(obj), _lib.ptr(bary), None,
+                                             _stream_ptr(None)), "snail_trace_rays_dev")
+
+    def mirror_and_walk():
+        mirror(); walk()
+    mirror_and_walk()
+    t, tid = dist.reshape(np_, 256).clone(), obj.reshape(np_, 256).clone()
+    u, v = bary[:, :, 0:4].reshape(np_, 256).contiguous(), bary[:, :, 4:8].reshape(np_, 256).contiguous()
+    nsmp = tex_set.shade_rays(d, mask, t, u, v, tid)
+    variants["mirror"] = mirror
+    variants["mirror+walk"] = mirror_and_walk
+    variants["sample_rays"] = lambda: tex_set.shade_rays(d, mask, t, u, v, tid, out=nsmp)
+    torch.cuda.synchronize()
+    times = {k: [] for k in variants}
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    for _ in range(a.reps):
+        for k, fn in variants.items():
+            e0.record()
+            for _ in range(a.frames):
+                fn()
+            e1.record()
+            e1.synchronize()
+            times[k].append(e0.elapsed_time(e1) / a.frames)
+    lines = ["the mirrored bounce (gVals[7]), %s, %dx%d (%d packets), one light, IEEE; %d rounds of %d frames per variant, alternating; ms per frame: median (min .. max)" %
+             ("atrium detail %.2f: %d triangles" % (a.detail, n), resx, resy, pw * ph, a.reps, a.frames),
+             "device: %s" % torch.cuda.get_device_name(0),
+             "whitted_refl = snail_render_whitted_dev with SNAIL_WHITTED_REFLECTIONS of THIS build, in the same run",
+             "default_flat_refl frame equals the whitted_refl frame byte for byte: %s" % same,
+             "mirrored lanes selected: %d of %d; of them hit: %d" % (int((dist > float("-inf")).sum()), np_ * 256, int(torch.isfinite(t).sum()))]
+    med = {}
+    for k, v in times.items():
+        med[k] = statistics.median(v)
+        lines.append("  %-18s %8.3f  (%.3f .. %.3f)" % (k, med[k], min(v), max(v)))
+    lines.append("default_flat_refl / whitted_refl: %.3f; textured_refl / whitted_refl: %.3f; mirrored walk alone (mirror+walk - mirror): %.3f ms; the stage figures are launch to launch (upper bounds on kernel times)"
+                 % (med["default_flat_refl"] / med["whitted_refl"], med["textured_refl"] / med["whitted_refl"], med["mirror+walk"] - med["mirror"]))
+    text = "\n".join(lines)
+    print(text)
+    if a.out:
+        with open(a.out, "w") as fh:
+            fh.write(text + "\n")
+    if not same:
+        raise SystemExit("default_flat_refl and whitted_refl frames differ")
 
 
 if __name__ == "__main__":
