@@ -58,6 +58,7 @@
 #include "snail_bvh_fast.h"
 #include "snail_instances.h"
 #include "snail_heatmap.h"
+#include "snail_materials_tiles.h"
 
 #ifndef SNAIL_CHECK
 #define SNAIL_CHECK(expr)                                                                              \
@@ -220,6 +221,10 @@ public:
 
 	SnailScene *Handle() const { return scene; }
 	const FrameHits &Frame() const { return frame; }
+	// The shading data of this tree on its device (include/snail_materials.h: snail_materials_create over Handle()), for the full-shaded
+	// Render(...) calls (SNAIL_ADAPTER_DEVICE_MATERIALS, below).  Not owned: the host destroys the set, before this object.  NULL by default.
+	void AttachMaterials(SnailMaterials *m) { materials = m; }
+	SnailMaterials *Materials() const { return materials; }
 
 private:
 	void Release() {
@@ -229,6 +234,7 @@ private:
 	const RefBVH *ref = nullptr;
 	int arith = SNAIL_ARITH_IEEE;         // what SetArith selected last (re-applied by Upload)
 	SnailScene *scene = nullptr;          // = handles[0]
+	SnailMaterials *materials = nullptr;  // AttachMaterials
 	std::vector<SnailScene *> handles;    // one per device
 	mutable FrameHits frame;
 	mutable bool haveFrame = false;
@@ -490,7 +496,7 @@ private:
 // What of Scene<AccStruct> / the global switches the device pipeline honours: scene.lights (pos, color, radius: src/light.h:5-16),
 // scene.ambientLight, the default material's colour (Scene::Scene sets (1,1,1), src/scene.cpp:6-10; SimpleMaterial::color is private,
 // hence a parameter), gVals[1] (depth shading), gVals[7] (one mirrored bounce) and gVals[9] (4x antialiasing, src/render.cpp:60-62, :71-110).  Textured materials / full shading data (gVals[6])
-// stay with the host path (HipBVH under the reference's own Render).
+// stay with the host path (HipBVH under the reference's own Render) unless the host opts in to the device's full shading (below).
 // The reference's renderer reads more global switches than that (src/rtbase.cpp:16, toggled by F-keys, broadcast to the render nodes
 // every frame: src/server.cpp:372-376).  Those the device pipeline does NOT implement -- a call with one of them set must not come back
 // as a plain frame with status 0: the Render(...) overloads below hand such a call to the reference's own renderer over the
@@ -509,6 +515,29 @@ enum { kDeviceHeatmap = 1 };
 #else
 enum { kDeviceHeatmap = 0 };
 #endif
+// gVals[6] on the device (include/snail_materials_tiles.h): define SNAIL_ADAPTER_DEVICE_MATERIALS before the include, attach a material set to the
+// tree (HipBVH::AttachMaterials) and the Render(...) overloads send a call with gVals[6] && HasShadingData() to snail_materials_render_tiles /
+// snail_materials_render_frame -- the tile list with gVals[1], [7], [9] and [8] (tint by `rank`), the image with gVals[1], [7], [9] -- when a
+// set is attached, the tree is on one device, an image is not asked to be tinted (gVals[8]) and gVals[5] is off or overridden by gVals[1].  An
+// attached set is sufficient for equivalence: a set that could select a transparent lane cannot exist, because snail_materials_create refuses
+// it, so the frame the device makes is the frame the reference's full-shading branch makes.  Every other gVals[6] call keeps the reference's
+// renderer: no set, several devices, an image with gVals[8], and gVals[5] without gVals[1] -- the last even with the device heat-map opted in,
+// whose counters are those of simple shading (under full shading the shadow lanes follow the interpolated normals, so the counts differ).
+// Opt-in, so that hosts and mocks built without it keep today's routing.
+#ifdef SNAIL_ADAPTER_DEVICE_MATERIALS
+enum { kDeviceMaterials = 1 };
+#else
+enum { kDeviceMaterials = 0 };
+#endif
+inline const char *UnsupportedSwitch(const int *gv, bool hasShadingData, bool tileList, bool deviceHeatmap, bool deviceMaterials) {
+	if(gv[6] && hasShadingData) {
+		if(deviceMaterials && (!gv[5] || gv[1]) && (tileList || !gv[8])) return nullptr;
+		return "gVals[6] (full shading: materials / textures, src/scene_trace.cpp:145)";
+	}
+	if(gv[5] && !deviceHeatmap) return "gVals[5] (TreeStats visualisation, src/scene_trace.cpp:513-517)";
+	if(gv[8] && tileList) return "gVals[8] (per-rank tint of the tiles, src/render.cpp:118-132)";
+	return nullptr;
+}
 inline const char *UnsupportedSwitch(const int *gv, bool hasShadingData, bool tileList, bool deviceHeatmap = false) {
 	if(gv[6] && hasShadingData) return "gVals[6] (full shading: materials / textures, src/scene_trace.cpp:145)";
 	if(gv[5] && !deviceHeatmap) return "gVals[5] (TreeStats visualisation, src/scene_trace.cpp:513-517)";
@@ -521,7 +550,7 @@ struct RenderMode {
 	bool reflections = false;   // gVals[7]
 	bool antialias = false;     // gVals[9]
 	float color[3] = {1.0f, 1.0f, 1.0f};
-	bool rankTint = false;      // gVals[8]: read by RenderInstancedTiles alone (the tile list of an instanced scene), which is given the rank
+	bool rankTint = false;      // gVals[8]: read by RenderInstancedTiles and RenderMaterialTiles alone (tile lists), which are given the rank
 	bool statsHeat = false;     // gVals[5]: the TreeStats heat-map (include/snail_heatmap.h); without effect under depthShading, as in the reference
 };
 
@@ -637,6 +666,36 @@ inline StatsT RenderInstancedImage(const SceneT &scene, const CameraT &camera, I
 	return detail::toStats<StatsT>(st);
 }
 
+#ifdef SNAIL_ADAPTER_DEVICE_MATERIALS
+// The two calls with full shading (gVals[6] on a tree with an attached material set), entirely on the device: snail_materials_render_tiles /
+// snail_materials_render_frame (include/snail_materials_tiles.h).  mode.rankTint = gVals[8]: the tiles tinted by detail::RankTint(rank); the
+// image form has no tint.  The default material's colour is the set's (mode.color is not read).
+template <class StatsT, class SceneT, class CameraT>
+inline StatsT RenderMaterialTiles(const SceneT &scene, const CameraT &camera, unsigned resx, unsigned resy, unsigned char *data, const std::vector<int> &coords,
+								  const std::vector<int> &offsets, const RenderMode &mode = RenderMode(), unsigned rank = 0) {
+	float c[13];
+	detail::cam13(camera, c);
+	const std::vector<float> l = detail::lights7(scene);
+	std::vector<int64_t> off(offsets.begin(), offsets.end());
+	const float amb[3] = {scene.ambientLight.x, scene.ambientLight.y, scene.ambientLight.z};
+	uint64_t st[4] = {0, 0, 0, 0};
+	SNAIL_CHECK(snail_materials_render_tiles(scene.geometry.Materials(), c, (int)resx, (int)resy, coords.data(), off.data(), (int)(coords.size() / 4), l.data(),
+											 (int)(l.size() / 7), amb, detail::renderFlags(mode), mode.rankTint ? detail::RankTint(rank) : nullptr, data, st));
+	return detail::toStats<StatsT>(st);
+}
+template <class StatsT, class SceneT, class CameraT, class ImageT>
+inline StatsT RenderMaterialImage(const SceneT &scene, const CameraT &camera, ImageT &image, const RenderMode &mode = RenderMode()) {
+	float c[13];
+	detail::cam13(camera, c);
+	const std::vector<float> l = detail::lights7(scene);
+	const float amb[3] = {scene.ambientLight.x, scene.ambientLight.y, scene.ambientLight.z};
+	uint64_t st[4] = {0, 0, 0, 0};
+	SNAIL_CHECK(snail_materials_render_frame(scene.geometry.Materials(), c, (int)image.Width(), (int)image.Height(), l.data(), (int)(l.size() / 7), amb,
+											 detail::renderFlags(mode), (unsigned char *)image.DataPointer(), (int)image.Pitch(), st));
+	return detail::toStats<StatsT>(st);
+}
+#endif
+
 } // namespace snail
 
 // ---- overloads with the reference's own signatures (src/render.h:16-23) ---------------------------------------------------------
@@ -665,20 +724,29 @@ inline StatsT RenderInstancedImage(const SceneT &scene, const CameraT &camera, I
 template <class RefBVH>
 inline TreeStats Render(const Scene<snail::HipBVH<RefBVH>> &scene, const Camera &camera, uint resx, uint resy, unsigned char *data, const vector<int> &coords,
 						const vector<int> &offsets, const Options options, uint rank, uint threads) {
-	if(const char *why = snail::UnsupportedSwitch(gVals, scene.geometry.HasShadingData(), true, snail::kDeviceHeatmap && scene.geometry.DeviceCount() <= 1))
+	const bool deviceMaterials = snail::kDeviceMaterials && scene.geometry.Materials() != nullptr && scene.geometry.DeviceCount() <= 1;
+	if(const char *why = snail::UnsupportedSwitch(gVals, scene.geometry.HasShadingData(), true, snail::kDeviceHeatmap && scene.geometry.DeviceCount() <= 1, deviceMaterials))
 		SNAIL_HOST_RENDER(why, gVals[9] ? 2 : 1, resx, resy, Render<snail::HipBVH<RefBVH>>(scene, camera, resx, resy, data, coords, offsets, options, rank, threads));
-	(void)rank; (void)threads; // (no tint requested; the host thread pool has no device counterpart)
+	(void)rank; (void)threads; // (a tint only under full shading; the host thread pool has no device counterpart)
 	snail::RenderMode mode;
 	mode.statsHeat = gVals[5] != 0;
 	mode.depthShading = gVals[1] != 0;
 	mode.reflections = gVals[7] != 0;   // the bounce is gated by gVals[7] alone (src/scene_trace.cpp:454); Options::reflections is stored and never read (src/render.cpp:24,37)
 	(void)options;
 	mode.antialias = gVals[9] != 0;
+#ifdef SNAIL_ADAPTER_DEVICE_MATERIALS
+	if(gVals[6] && scene.geometry.HasShadingData()) {   // (UnsupportedSwitch let it through: a set is attached, one device, gVals[5] off or under gVals[1])
+		mode.statsHeat = false;
+		mode.rankTint = gVals[8] != 0;
+		return snail::RenderMaterialTiles<TreeStats>(scene, camera, resx, resy, data, coords, offsets, mode, rank);
+	}
+#endif
 	return snail::RenderTiles<TreeStats>(scene, camera, resx, resy, data, coords, offsets, mode);
 }
 template <class RefBVH>
 inline TreeStats Render(const Scene<snail::HipBVH<RefBVH>> &scene, const Camera &camera, MipmapTexture &image, const Options options, uint threads) {
-	if(const char *why = snail::UnsupportedSwitch(gVals, scene.geometry.HasShadingData(), false, snail::kDeviceHeatmap != 0))
+	const bool deviceMaterials = snail::kDeviceMaterials && scene.geometry.Materials() != nullptr && scene.geometry.DeviceCount() <= 1;
+	if(const char *why = snail::UnsupportedSwitch(gVals, scene.geometry.HasShadingData(), false, snail::kDeviceHeatmap != 0, deviceMaterials))
 		SNAIL_HOST_RENDER(why, gVals[9] ? 2 : 1, image.Width(), image.Height(), Render<snail::HipBVH<RefBVH>>(scene, camera, image, options, threads));
 	(void)threads;
 	snail::RenderMode mode;
@@ -687,6 +755,12 @@ inline TreeStats Render(const Scene<snail::HipBVH<RefBVH>> &scene, const Camera 
 	mode.reflections = gVals[7] != 0;   // the bounce is gated by gVals[7] alone (src/scene_trace.cpp:454); Options::reflections is stored and never read (src/render.cpp:24,37)
 	(void)options;
 	mode.antialias = gVals[9] != 0;
+#ifdef SNAIL_ADAPTER_DEVICE_MATERIALS
+	if(gVals[6] && scene.geometry.HasShadingData()) {   // (UnsupportedSwitch let it through: a set is attached, one device, no gVals[8], gVals[5] off or under gVals[1])
+		mode.statsHeat = false;
+		return snail::RenderMaterialImage<TreeStats>(scene, camera, image, mode);
+	}
+#endif
 	return snail::RenderImage<TreeStats>(scene, camera, image, mode);
 }
 // Scene<snail::HipDBVH<...>>: the image is made on the device (snail_instances_render_image: gVals[1] depth shading, or the lit frame of

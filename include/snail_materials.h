@@ -4,9 +4,9 @@
  * mip-mapped rgb8 textures, then the lights of the simple-shading pipeline of snail_hip.h on those samples.  A header of its own: snail_hip.h
  * and its symbol list stay as they are.  Plain C.
  *
- * NOT here (the host renderer keeps them): the mirrored bounce and the transparency continuation under full shading (both nest a full-shaded
- * RayTrace<0,1>), 4x antialiasing, tile lists, multi-device frames, the heat-map, the ordered launches, OBJ vt / vn / usemtl and MTL ingest,
- * the DXT and SAT samplers and rgba8 textures.
+ * NOT here: the mirrored bounce is snail_materials_bounce.h's; 4x antialiasing, depth shading, the tint and tile lists are
+ * snail_materials_tiles.h's.  The host renderer keeps the transparency continuation under full shading, multi-device frames, the heat-map, the
+ * ordered launches, OBJ vt / vn / usemtl and MTL ingest, the DXT and SAT samplers and rgba8 textures.
  */
 #ifndef SNAIL_MATERIALS_H
 #define SNAIL_MATERIALS_H

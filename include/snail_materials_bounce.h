@@ -8,9 +8,9 @@
  * The nested call never bounces again (cache.reflections < 1), and no material a set accepts can select a transparent lane, so it takes
  * neither continuation.
  *
- * NOT here (the host renderer keeps them): the transparency continuation, 4x antialiasing, tile lists, multi-device frames, the heat-map
- * and the ordered launches (dispatch-order feedback) under the bounce, and the adapter's routing: a call with gVals[6] still goes to the
- * host renderer.
+ * NOT here: 4x antialiasing, depth shading, the tint and tile lists with the bounce are snail_materials_tiles.h's, and with them the adapter's
+ * routing of a call with gVals[6] (SNAIL_ADAPTER_DEVICE_MATERIALS, snail_adapter.hpp).  The host renderer keeps the transparency
+ * continuation, multi-device frames, the heat-map and the ordered launches (dispatch-order feedback) under the bounce.
  */
 #ifndef SNAIL_MATERIALS_BOUNCE_H
 #define SNAIL_MATERIALS_BOUNCE_H

@@ -17,6 +17,8 @@
 //   k_mat_sample_rays      the sample stage on generic packets: RayGroup<0, hasMask>, hasMask = not all 256 lanes selected (:615-617)
 //   k_mat_light_rays<DEEP> / k_mat_colour_rays   the nested lights and outColor as FLOATS [packet][256][3] (no ConvColor)
 // and k_mat_final_blend instead of k_mat_final: diffuse += (colour - diffuse) * 0.3 on the hit lanes, before the lights (:462-465).
+// For the tile renderer (include/snail_materials_tiles.h) the primary colour stage has a float exit: k_mat_colour / k_mat_colour_blend leave outColor
+// as floats [packet][256][3] in ShadeArgs::colPackets, and k_inst_store (instances_shade.inc) goes on from there.
 // The light and colour stages are ONE body each, templated by their source (SRC_PRIMARY: rays from the camera, a hit = t < inf; SRC_MIRROR:
 // rays, masks and hits from the mirrored-packet buffers, a hit = t < inf AND the lane's mask bit: a masked lane carries -inf, not inf); the
 // primary kernels keep their names.
@@ -542,7 +544,9 @@ __global__ __launch_bounds__(64) void k_mat_light_rays(MatArgs A) {
 // SRC_MIRROR: the nested call's outColor, stored as FLOATS r, g, b per ray in A.s.rCol [packet][256][3] (the analogue of k_final<SRC_MIRROR,
 // DST_COLOR>).  BLEND (primary): diffuse = diffuse + (reflColor - diffuse) * 0.3 on the selector's lanes (= the hit lanes) before the lights,
 // specular untouched (src/scene_trace.cpp:462-465).
-template <int SRC, bool BLEND>
+// FLOATS (primary): outColor stays FLOATS r, g, b per ray in A.s.colPackets [packet][256][3] -- the layout k_inst_store (instances_shade.inc) reads --
+// for the tile renderer's reduction, tint and stores (include/snail_materials_tiles.h); the store rule below is not repeated for them.
+template <int SRC, bool BLEND, bool FLOATS = false>
 __device__ __forceinline__ void matFinal(const MatArgs &A) {
 	const int lane = threadIdx.x & 63;
 	const int li = (int)blockIdx.x;
@@ -610,6 +614,13 @@ __device__ __forceinline__ void matFinal(const MatArgs &A) {
 		}
 		return;
 	}
+	if(FLOATS) {
+		float4 *o = (float4 *)(A.s.colPackets + quad * 12);
+		o[0] = make_float4(col[0][0], col[1][0], col[2][0], col[0][1]);
+		o[1] = make_float4(col[1][1], col[2][1], col[0][2], col[1][2]);
+		o[2] = make_float4(col[2][2], col[0][3], col[1][3], col[2][3]);
+		return;
+	}
 	unsigned bytes[12];
 #pragma unroll
 	for(int l = 0; l < 4; l++) { bytes[l * 3 + 0] = (unsigned)convChannelW(col[2][l]); bytes[l * 3 + 1] = (unsigned)convChannelW(col[1][l]); bytes[l * 3 + 2] = (unsigned)convChannelW(col[0][l]); }
@@ -636,6 +647,8 @@ __device__ __forceinline__ void matFinal(const MatArgs &A) {
 __global__ __launch_bounds__(64) void k_mat_final(MatArgs A) { matFinal<SRC_PRIMARY, false>(A); }
 __global__ __launch_bounds__(64) void k_mat_final_blend(MatArgs A) { matFinal<SRC_PRIMARY, true>(A); }
 __global__ __launch_bounds__(64) void k_mat_colour_rays(MatArgs A) { matFinal<SRC_MIRROR, false>(A); }
+__global__ __launch_bounds__(64) void k_mat_colour(MatArgs A) { matFinal<SRC_PRIMARY, false, true>(A); }
+__global__ __launch_bounds__(64) void k_mat_colour_blend(MatArgs A) { matFinal<SRC_PRIMARY, true, true>(A); }
 
 // ---- one packet: primary samples -> mirrored packets.  Scene::TraceReflection (src/scene_trace.cpp:603-618) on the samples of full shading:
 // reflDir = Reflect(dir, samples.normal) (src/rtbase_math.h:54-58) with the INTERPOLATED normal of the sample buffer (zeros on a lane that missed),

@@ -4,6 +4,7 @@
 // barycentrics -> k_mat_sample_rays -> k_mat_light_rays -> k_mat_colour_rays between the sample stage and the primary lights, k_mat_final_blend last).
 #include "../../include/snail_materials.h"
 #include "../../include/snail_materials_bounce.h"
+#include "../../include/snail_materials_tiles.h"
 
 struct SnailMaterials {
 	SnailScene *scene = nullptr;
@@ -47,14 +48,27 @@ struct SnailMaterials {
 		char *bounce = nullptr;   // allocated only once a bounce has been asked for; grown under the same rule
 		size_t bouncePackets = 0;
 		int bounceLights = 0;
+		char *tiles = nullptr;    // the tile renderer's part (Set::TileBufs), only once it was asked for; grown under the same rule
+		size_t tilesPackets = 0;
 		hipEvent_t done = nullptr;
 		bool used = false;
+	};
+	// ... and those of the tile renderer (materials_tiles_host.inc): the packets' float colours and, under 4x antialiasing, the sub-packet list
+	struct TileBufs {
+		float *col = nullptr;
+		int32_t *xy2 = nullptr;
+		static size_t bytes(size_t np) { return np * 256 * 12 + np * 8; }
+		void carve(char *base, size_t np) { col = (float *)base; xy2 = (int32_t *)(base + np * 256 * 12); }
 	};
 	enum { kSets = 8 };
 	Set set[kSets];
 	unsigned setCount = 0;
 	struct FrameList { int pw, ph; int32_t *d; };
 	std::vector<FrameList> frameLists;   // a whole frame's packet list, cached by packet-grid size
+	// snail_materials_render_tiles: ONE cached tile job per set (the structure of instances_tiles_host.inc); its calls take turns under renderMu,
+	// which is taken before the scene's mu
+	std::mutex renderMu;
+	InstTileJob *tileJob = nullptr;
 };
 
 namespace {
@@ -105,7 +119,7 @@ void matFillArgs(const SnailMaterials *m, dev::MatArgs &A, const float cam[13], 
 // nested colour -> primary lights -> blend and store.
 int matShade(SnailMaterials *m, const char *fn, const float cam[13], int resx, int resy, const int32_t *dXY, int np, const float *lights7, int nLights,
 			 const float ambient[3], uint8_t *frame, int pitch, uint8_t *bgrPackets, const SnailMaterials::Bufs &W, const SnailMaterials::BounceBufs *R,
-			 uint64_t *dStats, hipStream_t st) {
+			 uint64_t *dStats, hipStream_t st, float *colPackets = nullptr) {
 	SnailScene *s = m->scene;
 	SceneUse use(s, st);
 	if(use.rc) return use.rc;
@@ -118,6 +132,7 @@ int matShade(SnailMaterials *m, const char *fn, const float cam[13], int resx, i
 	A.s.hitT = W.hitT; A.s.hitId = W.hitId; A.hitU = W.hitU; A.hitV = W.hitV;
 	A.samples = W.samples; A.s.sDist = W.sDist;
 	A.s.frame = frame; A.s.pitch = pitch; A.s.bgrPackets = bgrPackets;
+	A.s.colPackets = colPackets;   // the float colours k_inst_store goes on from, instead of bytes (k_mat_colour / k_mat_colour_blend)
 	A.s.stats = (dev::u64 *)dStats;
 	if(R) {
 		A.s.rOrg = R->rOrg; A.s.rDir = R->rDir; A.s.rIDir = R->rIDir; A.s.rMask = R->rMask; A.s.rDist = R->rDist; A.s.rObj = R->rObj; A.s.rCol = R->rCol;
@@ -171,7 +186,10 @@ int matShade(SnailMaterials *m, const char *fn, const float cam[13], int resx, i
 		SNAIL_LAUNCH(sse, MatArgs, grid, wave, 0, st, A, k_mat_colour_rays);
 		HIP_TRY(hipGetLastError());
 	}
-	if(R) SNAIL_LAUNCH(sse, MatArgs, grid, wave, 0, st, A, k_mat_final_blend);
+	if(colPackets) {
+		if(R) SNAIL_LAUNCH(sse, MatArgs, grid, wave, 0, st, A, k_mat_colour_blend);
+		else SNAIL_LAUNCH(sse, MatArgs, grid, wave, 0, st, A, k_mat_colour);
+	} else if(R) SNAIL_LAUNCH(sse, MatArgs, grid, wave, 0, st, A, k_mat_final_blend);
 	else SNAIL_LAUNCH(sse, MatArgs, grid, wave, 0, st, A, k_mat_final);
 	HIP_TRY(hipGetLastError());
 	return 0;
@@ -200,9 +218,8 @@ int matFrameList(SnailMaterials *m, int resx, int resy, const int32_t **dXY, int
 }
 
 // snail_render_materials_dev / _packets_dev (the scene's mu held): the next set of intermediates, grown if need be, its previous user waited for on st
-int matShadeDev(SnailMaterials *m, const char *fn, const float cam[13], int resx, int resy, const int32_t *dXY, int np, const float *lights7, int nLights,
-				const float ambient[3], uint8_t *frame, int pitch, uint8_t *bgrPackets, uint64_t *dStats, hipStream_t st, bool refl = false) {
-	if(!dXY) { if(int rc = matFrameList(m, resx, resy, &dXY, &np)) return rc; }
+// the next set of intermediates for np packets (the scene's mu held); tiles: with the tile renderer's part
+int matNextSet(SnailMaterials *m, int np, int nLights, bool refl, bool tiles, hipStream_t st, SnailMaterials::Set **out) {
 	SnailMaterials::Set &W = m->set[m->setCount++ % SnailMaterials::kSets];
 	if(!W.base || W.packets < (size_t)np || W.lights < nLights) {   // grown: its previous user may still be running
 		HIP_TRY(hipDeviceSynchronize());
@@ -222,21 +239,43 @@ int matShadeDev(SnailMaterials *m, const char *fn, const float cam[13], int resx
 		HIP_TRY(hipMalloc((void **)&W.bounce, SnailMaterials::BounceBufs::bytes(packets, lights)));
 		W.bouncePackets = packets; W.bounceLights = lights;
 	}
+	if(tiles && (!W.tiles || W.tilesPackets < (size_t)np)) {
+		HIP_TRY(hipDeviceSynchronize());
+		if(W.tiles) (void)hipFree(W.tiles);
+		const size_t packets = std::max(W.tilesPackets, (size_t)np);
+		W.tiles = nullptr; W.tilesPackets = 0; W.used = false;
+		HIP_TRY(hipMalloc((void **)&W.tiles, SnailMaterials::TileBufs::bytes(packets)));
+		W.tilesPackets = packets;
+	}
 	if(!W.done) HIP_TRY(hipEventCreateWithFlags(&W.done, hipEventDisableTiming));
 	if(W.used) HIP_TRY(hipStreamWaitEvent(st, W.done, 0));
+	*out = &W;
+	return 0;
+}
+// after the set's user has enqueued its stages (rc: how that went)
+int matSetDone(SnailMaterials::Set &W, const char *fn, int rc, hipStream_t st) {
+	// also when a stage failed after earlier ones were enqueued: they may still be running on these buffers, and the set's next user (on any
+	// stream) must come after them.  Should the record itself fail, the set is marked grown-from-scratch: its next user synchronises the device.
+	if(hipEventRecord(W.done, st) == hipSuccess) W.used = true;
+	else {
+		W.packets = 0; W.bouncePackets = 0; W.tilesPackets = 0; W.used = false;
+		if(!rc) { snail_set_error("%s: hipEventRecord failed", fn); return 1; }
+	}
+	return rc;
+}
+
+int matShadeDev(SnailMaterials *m, const char *fn, const float cam[13], int resx, int resy, const int32_t *dXY, int np, const float *lights7, int nLights,
+				const float ambient[3], uint8_t *frame, int pitch, uint8_t *bgrPackets, uint64_t *dStats, hipStream_t st, bool refl = false) {
+	if(!dXY) { if(int rc = matFrameList(m, resx, resy, &dXY, &np)) return rc; }
+	SnailMaterials::Set *Wp = nullptr;
+	if(int rc = matNextSet(m, np, nLights, refl, false, st, &Wp)) return rc;
+	SnailMaterials::Set &W = *Wp;
 	SnailMaterials::Bufs B;
 	B.carve(W.base, (size_t)np);
 	SnailMaterials::BounceBufs RB;
 	if(refl) RB.carve(W.bounce, (size_t)np, nLights);
 	const int rc = matShade(m, fn, cam, resx, resy, dXY, np, lights7, nLights, ambient, frame, pitch, bgrPackets, B, refl ? &RB : nullptr, dStats, st);
-	// also when a stage failed after earlier ones were enqueued: they may still be running on these buffers, and the set's next user (on any
-	// stream) must come after them.  Should the record itself fail, the set is marked grown-from-scratch: its next user synchronises the device.
-	if(hipEventRecord(W.done, st) == hipSuccess) W.used = true;
-	else {
-		W.packets = 0; W.bouncePackets = 0; W.used = false;
-		if(!rc) { snail_set_error("%s: hipEventRecord failed", fn); return 1; }
-	}
-	return rc;
+	return matSetDone(W, fn, rc, st);
 }
 
 } // namespace
@@ -405,8 +444,10 @@ void snail_materials_destroy(SnailMaterials *m) {
 	for(auto &W : m->set) {
 		if(W.base) (void)hipFree(W.base);
 		if(W.bounce) (void)hipFree(W.bounce);
+		if(W.tiles) (void)hipFree(W.tiles);
 		if(W.done) (void)hipEventDestroy(W.done);
 	}
+	freeInstTileJob(m->tileJob);
 	for(auto &f : m->frameLists) (void)hipFree(f.d);
 	if(m->dBase) (void)hipFree(m->dBase);
 	delete m;

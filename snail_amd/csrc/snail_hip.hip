@@ -1763,3 +1763,4 @@ int snail_account_primary(SnailScene *s, const float cam[13], int resx, int resy
 #include "instances_tiles_host.inc"
 #include "heatmap_host.inc"
 #include "materials_host.inc"
+#include "materials_tiles_host.inc"

@@ -10,7 +10,11 @@ and MipmapTexture / PointSampler -- over the C-ABI of include/snail_materials.h.
   .mirror_packets / .shade_rays, reflections=True   <-> the one mirrored bounce of gVals[7] (Scene::TraceReflection and its nested
                                                         RayTrace<0, hasMask>), include/snail_materials_bounce.h
 
-Out of this module (the host renderer keeps them): transparency under full shading, 4x AA, tile lists, OBJ / MTL ingest."""
+  .frame_packets / .render_tiles_host / .render_frame_host   <-> RenderTask::Work around those frames: tile lists with the planar store,
+                                                        4x AA (gVals[9]), depth shading (gVals[1]) and the tint (gVals[8]),
+                                                        include/snail_materials_tiles.h
+
+Out of this module (the host renderer keeps them): transparency under full shading, OBJ / MTL ingest."""
 from __future__ import annotations
 
 import ctypes as C
@@ -25,6 +29,8 @@ MATERIAL_DTYPE = np.dtype([("kind", "<i4"), ("ndotr", "<i4"), ("diffuse", "<f4",
 assert MATERIAL_DTYPE.itemsize == 40
 SAMPLE_COMPONENTS = 9        # normal, diffuse, specular
 RENDER_REFLECTIONS = 1       # SNAIL_RENDER_REFLECTIONS (include/snail_hip.h)
+RENDER_DEPTH = 2             # SNAIL_RENDER_DEPTH
+RENDER_AA4 = 4               # SNAIL_RENDER_AA4
 
 
 def texture_size(w: int, h: int):
@@ -255,4 +261,56 @@ class MaterialSet:
         rc = _lib.lib().snail_render_materials_image(self._h, _lib.ptr(cam13), resx, resy, _lib.ptr(lights) if len(lights) else None, len(lights), _lib.ptr(amb),
                                                      int(flags), _lib.ptr(img), pitch, _lib.ptr(stats))
         _lib.check(rc, "snail_render_materials_image")
+        return img, stats
+
+    # ---- include/snail_materials_tiles.h: any of RENDER_REFLECTIONS / RENDER_DEPTH / RENDER_AA4, the tint, tile lists -------------------
+    def _tile_args(self, cam, lights7, ambient, tint):
+        lights = self._lights(lights7)
+        cam13 = np.ascontiguousarray(cam.as_array13(), dtype=np.float32)
+        amb = np.ascontiguousarray(ambient, dtype=np.float32)
+        tnt = None if tint is None else np.ascontiguousarray(tint, dtype=np.float32).reshape(3)
+        return lights, (_lib.ptr(lights) if len(lights) else None), cam13, amb, tnt
+
+    def frame_packets(self, cam, resx: int, resy: int, packet_xy, lights7=None, flags: int = 0, tint=None, ambient=(0.1, 0.1, 0.1), out=None, stats=None,
+                      stream=None):
+        """snail_materials_frame_packets_dev: the packets of an explicit list (int32 [n, 2] device tensor) with any of RENDER_REFLECTIONS /
+        RENDER_DEPTH / RENDER_AA4 and an optional tint (three factors, gVals[8]): packet-major [n, 256, 3] uint8 (B,G,R)."""
+        torch = _torch()
+        n = int(packet_xy.shape[0])
+        if out is None:
+            out = torch.empty((n, 256, 3), dtype=torch.uint8, device=self.scene._dev())
+        lights, lp, cam13, amb, tnt = self._tile_args(cam, lights7, ambient, tint)
+        rc = _lib.lib().snail_materials_frame_packets_dev(self._h, _lib.ptr(cam13), resx, resy, _lib.ptr(packet_xy), n, lp, len(lights), _lib.ptr(amb), int(flags),
+                                                          _lib.ptr(tnt), _lib.ptr(out), _lib.ptr(stats), _stream_ptr(stream))
+        _lib.check(rc, "snail_materials_frame_packets_dev")
+        return out
+
+    def render_tiles_host(self, cam, resx: int, resy: int, tiles, offsets=None, lights7=None, flags: int = 0, tint=None, ambient=(0.1, 0.1, 0.1), data=None):
+        """snail_materials_render_tiles: the tile-list renderer of src/render.h:16-19 with full shading.  tiles = [n, 4] (x, y, w, h); returns
+        (data, offsets, stats) with tile k's planes R, G-R, B-R at data[offsets[k]:offsets[k] + 3 w h], back to back unless the caller
+        brings `offsets` (and, if it likes, a `data` buffer of its own).  tint = three factors (gVals[8]) or None."""
+        t = np.ascontiguousarray(tiles, dtype=np.int32).reshape(-1, 4)
+        size = 3 * t[:, 2].astype(np.int64) * t[:, 3]
+        if offsets is None:
+            offsets = np.concatenate([[0], np.cumsum(size)[:-1]]).astype(np.int64)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        if data is None:
+            data = np.zeros(int((offsets + size).max()) if len(t) else 0, dtype=np.uint8)
+        lights, lp, cam13, amb, tnt = self._tile_args(cam, lights7, ambient, tint)
+        stats = np.zeros(4, dtype=np.uint64)
+        rc = _lib.lib().snail_materials_render_tiles(self._h, _lib.ptr(cam13), resx, resy, _lib.ptr(t), _lib.ptr(offsets), len(t), lp, len(lights), _lib.ptr(amb),
+                                                     int(flags), _lib.ptr(tnt), _lib.ptr(data), _lib.ptr(stats))
+        _lib.check(rc, "snail_materials_render_tiles")
+        return data, offsets, stats
+
+    def render_frame_host(self, cam, resx: int, resy: int, lights7=None, flags: int = 0, ambient=(0.1, 0.1, 0.1), pitch: int | None = None, fill: int = 0):
+        """snail_materials_render_frame: render_image_host with RENDER_DEPTH and RENDER_AA4 accepted -> (uint8 [resy, pitch] (B,G,R rows; pitch =
+        3 * resx unless given, bytes past a row's pixels keep `fill`), stats)."""
+        pitch = resx * 3 if pitch is None else int(pitch)
+        img = np.full((resy, pitch), fill, dtype=np.uint8)
+        stats = np.zeros(4, dtype=np.uint64)
+        lights, lp, cam13, amb, _ = self._tile_args(cam, lights7, ambient, None)
+        rc = _lib.lib().snail_materials_render_frame(self._h, _lib.ptr(cam13), resx, resy, lp, len(lights), _lib.ptr(amb), int(flags), _lib.ptr(img), pitch,
+                                                     _lib.ptr(stats))
+        _lib.check(rc, "snail_materials_render_frame")
         return img, stats

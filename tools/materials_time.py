@@ -22,7 +22,15 @@ frame's packets with the textured set: mirror (snail_materials_mirror_packets_de
 barycentrics) and sample_rays (snail_materials_shade_rays_dev).  The frames of whitted_refl and default_flat_refl are compared byte for
 byte first.  The kernels' own times, the nested light and colour stages included, come from a kernel trace of --reflections --trace N.
 
-    python tools/materials_time.py [--res 1920x1080] [--frames 400] [--reps 7] [--parent-lib PATH] [--out profiles/materials.txt] [--trace N] [--reflections]"""
+--tiles [--aa]: snail_materials_render_tiles (include/snail_materials_tiles.h) over the reference's 16x64 tile map of the frame (divide_image),
+textured set, without and with the bounce (and, with --aa, under SNAIL_RENDER_AA4 as well), beside the per-frame time of
+snail_materials_bounce_dev at the same resolution in the same run.  The tile call is a host call -- it returns after its one device-to-host copy
+-- so it is timed on the host's clock, one call after the other; the frame call is timed by device events around a window enqueued back to
+back, and once more call by call with a wait after each, which is the like-for-like figure.  No threshold: a measurement.  --out APPENDS in
+this mode, with --commit as the label of what was measured.
+
+    python tools/materials_time.py [--res 1920x1080] [--frames 400] [--reps 7] [--parent-lib PATH] [--out profiles/materials.txt] [--trace N] [--reflections]
+                                   [--tiles [--aa] [--commit LABEL]]"""
 import argparse
 import ctypes as C
 import os
@@ -70,6 +78,9 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--trace", type=int, default=0)
     ap.add_argument("--reflections", action="store_true")
+    ap.add_argument("--tiles", action="store_true")
+    ap.add_argument("--aa", action="store_true")
+    ap.add_argument("--commit", default="unlabelled")
     a = ap.parse_args()
     resx, resy = (int(v) for v in a.res.split("x"))
     import torch
@@ -93,6 +104,8 @@ def main():
     descs, mmap = K.materials_mod5()
     mats = [P.Material.simple(d[1], d[2]) if d[0] == "simple" else P.Material.textured(d[1], d[2]) if d[0] == "tex" else P.Material.uber(d[1], d[2], d[3]) for d in descs]
     tex_set = P.MaterialSet(sc, uv, nrm, np.arange(n, dtype=np.int32) % 5, flat, mmap, mats, [P.Texture(t) for t in K.TEXTURES()])
+    if a.tiles:
+        return tiles(a, sc, cam, resx, resy, lights, tex_set, n)
     if a.reflections:
         return bounce(a, sc, cam, resx, resy, lights, flat_set, tex_set, n)
     parent = ParentScene(a.parent_lib, hb) if a.parent_lib else None
@@ -231,6 +244,70 @@ def bounce(a, sc, cam, resx, resy, lights, flat_set, tex_set, n):
             fh.write(text + "\n")
     if not same:
         raise SystemExit("default_flat_refl and whitted_refl frames differ")
+
+
+def tiles(a, sc, cam, resx, resy, lights, tex_set, n):
+    """--tiles: the tile list of a full-shaded frame beside the frame call"""
+    import time
+
+    import torch
+    from snail_amd.render import divide_image
+    tl = divide_image(resx, resy)
+    out = torch.zeros((resy, resx, 3), dtype=torch.uint8, device="cuda:0")
+    size = int((3 * tl[:, 2].astype(np.int64) * tl[:, 3]).sum())
+    data = np.zeros(size, dtype=np.uint8)
+    flag_sets = [("", 0), ("_refl", P.RENDER_REFLECTIONS)] + ([("_aa", P.RENDER_AA4), ("_aa_refl", P.RENDER_AA4 | P.RENDER_REFLECTIONS)] if a.aa else [])
+    frame = {"frame" + k: (lambda f=f: tex_set.render(cam, resx, resy, lights, out=out, reflections=bool(f))) for k, f in flag_sets[:2]}
+    tile = {"tiles" + k: (lambda f=f: tex_set.render_tiles_host(cam, resx, resy, tl, lights7=lights, flags=f, data=data)) for k, f in flag_sets}
+    for fn in list(frame.values()) + list(tile.values()):      # warm-up: code objects, the set's groups at their largest, the cached tile job
+        fn(); fn()
+    torch.cuda.synchronize()
+    # the planes of the tile call are the frame call's pixels (R, G-R, B-R per tile, src/render.cpp:146-168)
+    frame["frame_refl"]()
+    torch.cuda.synchronize()
+    tile["tiles_refl"]()
+    f = out.cpu().numpy()
+    want = []
+    for x, y, w, h in tl.tolist():
+        t = f[y:y + h, x:x + w]
+        want += [t[..., 2].reshape(-1), (t[..., 1] - t[..., 2]).reshape(-1), (t[..., 0] - t[..., 2]).reshape(-1)]
+    same = bool(np.array_equal(np.concatenate(want), data))
+    ev = {k: [] for k in frame}
+    wall = {k: [] for k in list(frame) + list(tile)}
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    for _ in range(a.reps):
+        for k, fn in frame.items():       # a window enqueued back to back, device events
+            e0.record()
+            for _ in range(a.frames):
+                fn()
+            e1.record()
+            e1.synchronize()
+            ev[k].append(e0.elapsed_time(e1) / a.frames)
+        for k, fn in list(frame.items()) + list(tile.items()):       # call by call on the host's clock, a wait after each frame call
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(a.frames):
+                fn()
+                if k in frame:
+                    torch.cuda.synchronize()
+            wall[k].append((time.perf_counter() - t0) * 1e3 / a.frames)
+    pw, ph = (resx + 15) // 16, (resy + 15) // 16
+    lines = ["", "full-shaded tile list [%s], %s, %dx%d, %d tiles of 16x64 (%d packets; the frame: %d), one light, IEEE, textured set; %d rounds of %d calls per variant, alternating; ms per call: median (min .. max)" %
+             (a.commit, "atrium detail %.2f: %d triangles" % (a.detail, n), resx, resy, len(tl), int(sum(((w + 15) // 16) * ((h + 15) // 16) for _, _, w, h in tl.tolist())), pw * ph, a.reps, a.frames),
+             "device: %s" % torch.cuda.get_device_name(0),
+             "frame* = snail_render_materials_dev / snail_materials_bounce_dev; tiles* = snail_materials_render_tiles (planar store + ONE device-to-host copy of %d bytes inside the call)" % size,
+             "tiles_refl planes equal the planar encoding of the frame_refl frame: %s" % same]
+    for k, v in ev.items():
+        lines.append("  %-16s %8.3f  (%.3f .. %.3f)   back to back, device events" % (k, statistics.median(v), min(v), max(v)))
+    for k, v in wall.items():
+        lines.append("  %-16s %8.3f  (%.3f .. %.3f)   call by call, host clock" % (k, statistics.median(v), min(v), max(v)))
+    text = "\n".join(lines)
+    print(text)
+    if a.out:
+        with open(a.out, "a") as fh:
+            fh.write(text + "\n")
+    if not same:
+        raise SystemExit("the tile list and the frame differ")
 
 
 if __name__ == "__main__":
