@@ -50,6 +50,11 @@ int snail_debug_occupancy(int out[4]);
  * records that carry the "this node's box contains the origin" bit, which lets a primary packet's visit skip the box test. */
 int snail_debug_rel_flag_count(SnailScene *, const float org[3], int *count);
 
+/* The same array: out[c] = the records (inner and leaf) whose relative near word c (bmin - org) is > 0, out[3 + c] = those whose relative far
+ * word c (bmax - org) is < 0, c = x, y, z.  One such bit on an axis lets a sign-coherent primary packet's visit drop the clamp of its entry
+ * distance. */
+int snail_debug_rel_axis_flag_count(SnailScene *, const float org[3], int out[6]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -173,6 +173,7 @@ DEBUG_SIGNATURES = {
     "snail_debug_occupancy": (_I, [_VP]),
     "snail_debug_anyorder": (_I, [_VP, _F13, _I, _I, _I, _I, _VP]),
     "snail_debug_rel_flag_count": (_I, [_VP, _VP, _VP]),
+    "snail_debug_rel_axis_flag_count": (_I, [_VP, _VP, _VP]),
 }
 DEBUG_LIB_PATH = os.path.join(HERE, "libsnailhip_debug.so")
 _dbg = None

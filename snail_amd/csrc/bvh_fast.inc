@@ -228,7 +228,7 @@ SnailScene *snail_scene_create_fast_dev(const float *d_verts9, int nTris, int de
 	const int cap = 2 * nTris - 1;
 	s->device = device; s->nNodes = cap; s->nTris = nTris;
 	const size_t trisOff = pfTrisOffset(cap), pfBytes = trisOff + (size_t)nTris * 64;
-	const bool fits = (size_t)cap + 1 < ((size_t)1 << 20) && pfBytes < ((size_t)1 << 31);
+	const bool fits = pfFits((size_t)cap + 1, (size_t)nTris);
 	s->trisOff = (int)(fits ? trisOff : 0);
 	s->pfOKButNesting = fits ? 1 : 0;   // (children are numbered in pairs from 1 on)
 	hipError_t e;

@@ -1070,6 +1070,8 @@ __device__ __forceinline__ void walk(const uint4 *__restrict__ nodes, const uint
 // min(min(tf,dist) - tn, tf)
 #define SNAIL_TAIL_POS(L, S) "v_max_f32 %[t0], 0, %[t0]\n v_min_f32 %[t3], %[t3], %[d" L "]\n v_sub_f32 %[" S "], %[t3], %[t0]\n"
 #define SNAIL_TAIL_ANY(L, S) "v_min_f32 %[t4], %[t3], %[d" L "]\n v_sub_f32 %[t4], %[t4], %[t0]\n v_min_f32 %[" S "], %[t4], %[t3]\n"
+// POSF: SNAIL_TAIL_POS at a node whose record proves tn >= 0 for every ray of the packet (SNAIL_POSENTRY_*, below): min(tf,dist) - tn
+#define SNAIL_TAIL_POSF(L, S) "v_min_f32 %[t3], %[t3], %[d" L "]\n v_sub_f32 %[" S "], %[t3], %[t0]\n"
 // the traversal stack inside this loop: two words per entry (node; first | last << 8) in two VGPRs.  (The prefetching loop below keeps ONE
 // word, node | first << 20 | last << 26, for trees of at most 2^20 node slots: one lane read per pop and one lane write per push instead
 // of two -- these are the most expensive instructions of the loop, ~4 cycles each against 1.6 for a multiply.)
@@ -1161,6 +1163,8 @@ __device__ __forceinline__ void walk(const uint4 *__restrict__ nodes, const uint
 //   primary packet's visit of it needs no slab test (SNAIL_OIN_*, below).  The child order only looks at bits 0..2 of the word (sign16 is
 //   three bits wide in the shared-origin walks), so every other reader of a relative array ignores the bit.  Bit 31 and not a lower one: a
 //   leaf's word 7 is its triangle count, any value below 2^31 in a caller's tree, and the loop tests the bit before it knows the node's kind.
+//   Bits 25..30 of word 7 of an origin-relative record, inner or leaf, say which of its six relative words lie strictly ahead of the origin
+//   (SNAIL_POSENTRY_*, below); a leaf's count lies below them (the pack path takes trees of fewer than 2^25 triangles only) and SNAIL_PF2_LEAF masks it.
 #define SNAIL_REL_INSIDE_BIT 31
 #define SNAIL_MOV_REC(D0, D1, D2, D3, S0, S1, S2, S3)                                                                                       \
 	" s_mov_b64 " D0 ", " S0 "\n s_mov_b64 " D1 ", " S1 "\n s_mov_b64 " D2 ", " S2 "\n s_mov_b64 " D3 ", " S3 "\n"
@@ -1203,7 +1207,8 @@ __device__ __forceinline__ void walk(const uint4 *__restrict__ nodes, const uint
 // the lane range of a stack word as an EXEC mask, kept for the top entry in %[alive] so that a pop only moves it
 #define SNAIL_PF2_ALIVE " s_sub_u32 %[cur], %[last], %[first]\n s_bfm_b64 %[alive], %[cur], %[first]\n s_bitset1_b64 %[alive], %[last]\n"
 #define SNAIL_PF2_FIRSTLAST " s_ff1_i32_b64 %[first], exec\n s_flbit_i32_b64 %[last], exec\n s_xor_b32 %[last], %[last], 63\n"
-// ---- visits of nodes that CONTAIN the packets' origin (primary packets over origin-relative records: the users whose TAIL is SNAIL_TAIL_POS) ----
+// ---- visits of nodes that CONTAIN the packets' origin (primary packets over origin-relative records: the users whose TAIL is SNAIL_TAIL_POS,
+// which test the bit in line, and SNAIL_TAIL_POSF, which test it in their out-of-line slow copies: SNAIL_POSENTRY_*) ----
 // Such a record carries SNAIL_REL_INSIDE_BIT.  Its relative near words are <= 0 and its far words >= 0, the reciprocal directions are finite
 // (the fast paths' precondition), so every near product is <= 0 and every far product >= 0 (or a zero of either sign; no 0 x inf), and with
 // distances >= 0 SNAIL_TAIL_POS yields min(tf, dist) - max(tn, 0) >= 0 or -0, which v_cmpx_le_f32 0, s accepts: EVERY lane of EXEC survives.
@@ -1214,8 +1219,9 @@ __device__ __forceinline__ void walk(const uint4 *__restrict__ nodes, const uint
 // path and compiles to what it did before; it also never sees the bit (bits 0..2 of the word are all it reads).
 // Invariants as below: the copies request into T and into the other set exactly where the visit would have, after the same waits.
 static_assert(SNAIL_REL_INSIDE_BIT == 31, "SNAIL_OIN_TEST_SNAIL_TAIL_POS names the bit in its text");
-#define SNAIL_OIN_TEST_SNAIL_TAIL_POS(AUX, LBL) " s_bitcmp1_b32 " AUX ", 31\n s_cbranch_scc1 " LBL "_%=\n"
-#define SNAIL_OIN_TEST_SNAIL_TAIL_ANY(AUX, LBL) ""
+#define SNAIL_OIN_TEST_SNAIL_TAIL_POS(AUX, CP, OMASK) " s_bitcmp1_b32 " AUX ", 31\n s_cbranch_scc1 L_oin" CP "_%=\n"
+#define SNAIL_OIN_TEST_SNAIL_TAIL_ANY(AUX, CP, OMASK) ""
+#define SNAIL_OIN_TEST_SNAIL_TAIL_POSF(AUX, CP, OMASK) " s_and_b32 vcc_lo, " AUX ", " OMASK "\n s_cbranch_scc0 L_slow" CP "_%=\n"
 #define SNAIL_OIN_TEST_of(TAIL) SNAIL_OIN_TEST_##TAIL
 #define SNAIL_OIN_PENDING(X, Y, OTHERSET, SUB, AUX, FARX, FARY, CNTVISIT, LEAFREQ)                                                          \
 				 "L_oin" X "p_%=:\n" CNTVISIT /* T <- the pusher's far child has been requested */                                         \
@@ -1236,13 +1242,17 @@ static_assert(SNAIL_REL_INSIDE_BIT == 31, "SNAIL_OIN_TEST_SNAIL_TAIL_POS names t
 				 SNAIL_OIN_PENDING("B", "A", "s[84:91]", "s82", "s83", "%[width]", "%[fl]", CNTVISIT, LEAFREQ)                               \
 				 SNAIL_OIN_PENDING("A", "B", "s[76:83]", "s90", "s91", "%[fl]", "%[width]", CNTVISIT, LEAFREQ)
 #define SNAIL_OIN_COPIES_SNAIL_TAIL_ANY(CNTVISIT, LEAFREQ) ""
+#define SNAIL_OIN_COPIES_SNAIL_TAIL_POSF SNAIL_OIN_COPIES_SNAIL_TAIL_POS /* (entered from the SNAIL_POSENTRY_* slow copies) */
 #define SNAIL_OIN_COPIES_of(TAIL) SNAIL_OIN_COPIES_##TAIL
 // a visit entered from a descent: the push of (FARY, survivors' first / last) happens here, between the slab products
-#define SNAIL_PF2_PENDING(X, OTHERSET, SUB, AUX, FARX, FARY, PRE, SLAB, TAIL, CNTVISIT, LEAFREQ, NX, FX, NY, FY, NZ, FZ)                                                   \
+#define SNAIL_PF2_PENDING(X, OTHERSET, SUB, AUX, FARX, FARY, PRE, SLAB, TAIL, CNTVISIT, LEAFREQ, OMASK, NX, FX, NY, FY, NZ, FZ)                                            \
 				 "L_visit" X "p_%=:\n"                                                                                                      \
 				 " s_waitcnt lgkmcnt(0)\n" /* this record has arrived; T's last request too */                                                \
 				 " s_load_dwordx8 s[68:75], %[base], " FARY "\n" /* the pusher's far child is the new top entry */                             \
-				 SNAIL_OIN_TEST_of(TAIL)(AUX, "L_oin" X "p")                                                                                  \
+				 SNAIL_OIN_TEST_of(TAIL)(AUX, X "p", OMASK)                                                                                   \
+				 SNAIL_PF2_PENDBODY(X, OTHERSET, SUB, AUX, FARX, FARY, PRE, SLAB, TAIL, CNTVISIT, LEAFREQ, NX, FX, NY, FY, NZ, FZ)
+// (the pending visit from its slab test on: the text that follows the entry test, and the whole of a SNAIL_POSENTRY_* slow copy)
+#define SNAIL_PF2_PENDBODY(X, OTHERSET, SUB, AUX, FARX, FARY, PRE, SLAB, TAIL, CNTVISIT, LEAFREQ, NX, FX, NY, FY, NZ, FZ)                                                  \
 				 CNTVISIT PRE(NX, FX, NY, FY, NZ, FZ)                                                                                        \
 				 SLAB("0", NX, FX, NY, FY, NZ, FZ) TAIL("0", "s0")                                                                           \
 				 SNAIL_PF2_NEARFAR(SUB, AUX, FARX, OTHERSET, LEAFREQ)                                                                        \
@@ -1255,11 +1265,55 @@ static_assert(SNAIL_REL_INSIDE_BIT == 31, "SNAIL_OIN_TEST_SNAIL_TAIL_POS names t
 				 " v_writelane_b32 %[stkN], %[topw], m0\n s_add_u32 m0, m0, 1\n" SNAIL_PF2_ISLEAF(SUB)                                       \
 				 SLAB("3", NX, FX, NY, FY, NZ, FZ) TAIL("3", "s3")                                                                           \
 				 SNAIL_PF2_TAIL(X, SUB)
+// the popped node's visit (record set A) from its slab test on; the NEW top entry's word and record are fetched inside it
+#define SNAIL_PF2_POPBODY(PRE, SLAB, TAIL, CNTVISIT, LEAFREQ, NXA, FXA, NYA, FYA, NZA, FZA)                                                  \
+				 CNTVISIT PRE(NXA, FXA, NYA, FYA, NZA, FZA)                                                                                 \
+				 SLAB("0", NXA, FXA, NYA, FYA, NZA, FZA) TAIL("0", "s0")                                                          \
+				 " s_and_b32 %[cur], %[topw], 0xfffff\n s_lshl_b32 %[off], %[cur], 5\n"                                                    \
+				 " s_load_dwordx8 s[68:75], %[base], %[off]\n"                                                                             \
+				 SLAB("1", NXA, FXA, NYA, FYA, NZA, FZA) TAIL("1", "s1")                                                          \
+				 SNAIL_PF2_NEARFAR("s90", "s91", "%[fl]", "s[76:83]", LEAFREQ)                                                                       \
+				 SLAB("2", NXA, FXA, NYA, FYA, NZA, FZA) TAIL("2", "s2")                                                          \
+				 " s_bfe_u32 %[first], %[topw], 0x60014\n s_lshr_b32 %[last], %[topw], 26\n" SNAIL_PF2_ALIVE SNAIL_PF2_ISLEAF("s90")        \
+				 SLAB("3", NXA, FXA, NYA, FYA, NZA, FZA) TAIL("3", "s3")                                                          \
+				 SNAIL_PF2_TAIL("A", "s90")
+// ---- visits whose record proves tn >= 0 (the eight octant statements of primary packets over origin-relative records: TAIL = SNAIL_TAIL_POSF) ----
+// Word 7 of an origin-relative record carries six more bits (dev::relAux): SNAIL_REL_NEARPOS_BIT + c when relative near word c (bmin - o) is > 0,
+// SNAIL_REL_FARNEG_BIT + c when relative far word c (bmax - o) is < 0.  In a sign octant the near plane of axis c is bmin when the directions are
+// positive there and bmax when they are negative, so ONE of the two bits of an axis says that this axis' near product is a product of two
+// factors of one sign, both non-zero and the direction's finite: >= +0.  tn = max3 of the near products is then >= +0 too, max(tn, 0) = tn
+// (but for the sign of a zero, which only moves s = t3 - t0 between +0 and -0: v_cmpx_le_f32 0, s accepts both), and the visit drops the four
+// v_max_f32 of SNAIL_TAIL_POS: 43 vector instructions instead of 47.  Each visit copy tests the octant's three bits at once
+// (s_and_b32 with the octant statement's immediate, OMASK; vcc_lo is free until the visit's v_cmpx) in place of the in-line SNAIL_OIN_TEST, and the
+// rare record without such an axis -- the nodes that contain the origin among them: every near word <= 0, every far word >= 0 -- leaves for an
+// out-of-line copy that makes that test and otherwise runs the full visit, clamp kept, word for word the in-line text of a SNAIL_TAIL_POS walk:
+// the same requests after the same waits, and it leaves for the same labels (the in-line text falls into the next pending copy, this one jumps).
+#define SNAIL_REL_NEARPOS_BIT 25
+#define SNAIL_REL_FARNEG_BIT 28
+#define SNAIL_REL_COUNT_MASK 0x01ffffffu /* a leaf's triangle count below the flag bits (the pack path's trees: counts < 2^25, snail_hip.hip: pfFits) */
+static_assert(SNAIL_REL_NEARPOS_BIT == 25 && SNAIL_REL_FARNEG_BIT == 28 && SNAIL_REL_COUNT_MASK == (1u << SNAIL_REL_NEARPOS_BIT) - 1u,
+			  "SNAIL_DESCEND_PF2_OCT's masks and SNAIL_PF2_LEAF name the bits in their text");
+#define SNAIL_POSENTRY_PENDING(X, Y, OTHERSET, SUB, AUX, FARX, FARY, PRE, SLAB, CNTVISIT, LEAFREQ, NX, FX, NY, FY, NZ, FZ)                    \
+				 "L_slow" X "p_%=:\n" /* T <- the pusher's far child has been requested */                                                  \
+				 SNAIL_OIN_TEST_SNAIL_TAIL_POS(AUX, X "p", "")                                                                               \
+				 SNAIL_PF2_PENDBODY(X, OTHERSET, SUB, AUX, FARX, FARY, PRE, SLAB, SNAIL_TAIL_POS, CNTVISIT, LEAFREQ, NX, FX, NY, FY, NZ, FZ)  \
+				 " s_branch L_visit" Y "p_%=\n"
+#define SNAIL_POSENTRY_COPIES_SNAIL_TAIL_POSF(PRE, SLAB, CNTVISIT, LEAFREQ, NXA, FXA, NYA, FYA, NZA, FZA, NXB, FXB, NYB, FYB, NZB, FZB)        \
+				 "L_slowAq_%=:\n" /* after a pop: topw = the new top entry's word */                                                        \
+				 SNAIL_OIN_TEST_SNAIL_TAIL_POS("s91", "Aq", "")                                                                              \
+				 SNAIL_PF2_POPBODY(PRE, SLAB, SNAIL_TAIL_POS, CNTVISIT, LEAFREQ, NXA, FXA, NYA, FYA, NZA, FZA)                               \
+				 " s_branch L_visitBp_%=\n"                                                                                                \
+				 SNAIL_POSENTRY_PENDING("B", "A", "s[84:91]", "s82", "s83", "%[width]", "%[fl]", PRE, SLAB, CNTVISIT, LEAFREQ, NXB, FXB, NYB, FYB, NZB, FZB) \
+				 SNAIL_POSENTRY_PENDING("A", "B", "s[76:83]", "s90", "s91", "%[fl]", "%[width]", PRE, SLAB, CNTVISIT, LEAFREQ, NXA, FXA, NYA, FYA, NZA, FZA)
+#define SNAIL_POSENTRY_COPIES_SNAIL_TAIL_POS(PRE, SLAB, CNTVISIT, LEAFREQ, NXA, FXA, NYA, FYA, NZA, FZA, NXB, FXB, NYB, FYB, NZB, FZB) ""
+#define SNAIL_POSENTRY_COPIES_SNAIL_TAIL_ANY(PRE, SLAB, CNTVISIT, LEAFREQ, NXA, FXA, NYA, FYA, NZA, FZA, NXB, FXB, NYB, FYB, NZB, FZB) ""
+#define SNAIL_POSENTRY_COPIES_of(TAIL) SNAIL_POSENTRY_COPIES_##TAIL
+// (the count of a leaf of an origin-relative array lies below the flag bits of its word 7; in the loop's plain copy the mask changes nothing)
 #define SNAIL_PF2_LEAF(X, SUB, AUX)                                                                                                         \
 				 "L_leaf" X "_%=:\n" SNAIL_PF2_FIRSTLAST                                                                                    \
 				 " s_bfe_u32 %[leafSub], " SUB ", 0x190006\n s_sub_u32 %[leafSub], %[leafSub], 0x80000\n s_bitset1_b32 %[leafSub], 31\n"   \
-				 " s_mov_b32 %[leafAux], " AUX "\n s_waitcnt lgkmcnt(0)\n s_branch L_end_%=\n"
-#define SNAIL_DESCEND_PF2X(EXTRACLOB, PREVARS, PRE, ORGOPS, SLAB, TAIL, CNTPOP, CNTVISIT, LEAFREQ, NXA, FXA, NYA, FYA, NZA, FZA, NXB, FXB, NYB, FYB, NZB, FZB)                                                  \
+				 " s_and_b32 %[leafAux], " AUX ", 0x01ffffff\n s_waitcnt lgkmcnt(0)\n s_branch L_end_%=\n"
+#define SNAIL_DESCEND_PF2X(EXTRACLOB, OMASK, PREVARS, PRE, ORGOPS, SLAB, TAIL, CNTPOP, CNTVISIT, LEAFREQ, NXA, FXA, NYA, FYA, NZA, FZA, NXB, FXB, NYB, FYB, NZB, FZB)                                                  \
 	asm volatile(SNAIL_DRAIN_SMEM " s_mov_b32 m0, %[sp]\n"                                                                                \
 				 "L_entry_%=:\n"                                                                                                           \
 				 " s_cmp_eq_u32 m0, 0\n s_cbranch_scc1 L_done_%=\n"                                                                     \
@@ -1275,24 +1329,16 @@ static_assert(SNAIL_REL_INSIDE_BIT == 31, "SNAIL_OIN_TEST_SNAIL_TAIL_POS names t
 				 /* the popped node's visit (record set A); the NEW top entry's word and record are fetched inside it */                  \
 				 " s_sub_u32 %[off], m0, 1\n s_max_i32 %[off], %[off], 0\n" /* (an empty stack re-reads entry 0: harmless, never used) */  \
 				 " v_readlane_b32 %[topw], %[stkN], %[off]\n"                                                                              \
-				 SNAIL_OIN_TEST_of(TAIL)("s91", "L_oinAq")                                                                                  \
-				 CNTVISIT PRE(NXA, FXA, NYA, FYA, NZA, FZA)                                                                                 \
-				 SLAB("0", NXA, FXA, NYA, FYA, NZA, FZA) TAIL("0", "s0")                                                          \
-				 " s_and_b32 %[cur], %[topw], 0xfffff\n s_lshl_b32 %[off], %[cur], 5\n"                                                    \
-				 " s_load_dwordx8 s[68:75], %[base], %[off]\n"                                                                             \
-				 SLAB("1", NXA, FXA, NYA, FYA, NZA, FZA) TAIL("1", "s1")                                                          \
-				 SNAIL_PF2_NEARFAR("s90", "s91", "%[fl]", "s[76:83]", LEAFREQ)                                                                       \
-				 SLAB("2", NXA, FXA, NYA, FYA, NZA, FZA) TAIL("2", "s2")                                                          \
-				 " s_bfe_u32 %[first], %[topw], 0x60014\n s_lshr_b32 %[last], %[topw], 26\n" SNAIL_PF2_ALIVE SNAIL_PF2_ISLEAF("s90")        \
-				 SLAB("3", NXA, FXA, NYA, FYA, NZA, FZA) TAIL("3", "s3")                                                          \
-				 SNAIL_PF2_TAIL("A", "s90")                                                                                                 \
+				 SNAIL_OIN_TEST_of(TAIL)("s91", "Aq", OMASK)                                                                                 \
+				 SNAIL_PF2_POPBODY(PRE, SLAB, TAIL, CNTVISIT, LEAFREQ, NXA, FXA, NYA, FYA, NZA, FZA)                                         \
 				 /* falls through: A descends into B, its push pending */                                                                   \
-				 SNAIL_PF2_PENDING("B", "s[84:91]", "s82", "s83", "%[width]", "%[fl]", PRE, SLAB, TAIL, CNTVISIT, LEAFREQ, NXB, FXB, NYB, FYB, NZB, FZB)                   \
+				 SNAIL_PF2_PENDING("B", "s[84:91]", "s82", "s83", "%[width]", "%[fl]", PRE, SLAB, TAIL, CNTVISIT, LEAFREQ, OMASK, NXB, FXB, NYB, FYB, NZB, FZB)            \
 				 /* falls through: B descends into A, its push pending */                                                                   \
-				 SNAIL_PF2_PENDING("A", "s[76:83]", "s90", "s91", "%[fl]", "%[width]", PRE, SLAB, TAIL, CNTVISIT, LEAFREQ, NXA, FXA, NYA, FYA, NZA, FZA)                   \
+				 SNAIL_PF2_PENDING("A", "s[76:83]", "s90", "s91", "%[fl]", "%[width]", PRE, SLAB, TAIL, CNTVISIT, LEAFREQ, OMASK, NXA, FXA, NYA, FYA, NZA, FZA)            \
 				 " s_branch L_visitBp_%=\n"                                                                                                \
 				 SNAIL_PF2_LEAF("A", "s90", "s91") SNAIL_PF2_LEAF("B", "s82", "s83")                                                       \
 				 SNAIL_OIN_COPIES_of(TAIL)(CNTVISIT, LEAFREQ)                                                                               \
+				 SNAIL_POSENTRY_COPIES_of(TAIL)(PRE, SLAB, CNTVISIT, LEAFREQ, NXA, FXA, NYA, FYA, NZA, FZA, NXB, FXB, NYB, FYB, NZB, FZB)    \
 				 "L_fail_%=:\n"                                                                                                            \
 				 " s_cmp_eq_u32 m0, 0\n s_cbranch_scc0 L_pop_%=\n"                                                                      \
 				 "L_done_%=:\n s_mov_b32 %[leafSub], 0\n s_mov_b32 %[leafAux], 0\n s_waitcnt lgkmcnt(0)\n"                                  \
@@ -1321,8 +1367,8 @@ static_assert(SNAIL_REL_INSIDE_BIT == 31, "SNAIL_OIN_TEST_SNAIL_TAIL_POS names t
 #define SNAIL_PRE_NONE_X(NX, FX, NY, FY, NZ, FZ) "" /* = SNAIL_PRE_NONE, in walks that compile without the six unused operands */
 #define SNAIL_PREVARS_SNAIL_PRE_NONE_X SNAIL_PREVARS_EMPTY
 #define SNAIL_PREVARS_of(PRE) SNAIL_PREVARS_##PRE
-#define SNAIL_DESCEND_PF2(PRE, ORGOPS, SLAB, TAIL, CNTPOP, CNTVISIT, LEAFREQ, NXA, FXA, NYA, FYA, NZA, FZA, NXB, FXB, NYB, FYB, NZB, FZB)                 \
-	SNAIL_DESCEND_PF2X(, SNAIL_PREVARS_of(PRE), PRE, ORGOPS, SLAB, TAIL, CNTPOP, CNTVISIT, LEAFREQ, NXA, FXA, NYA, FYA, NZA, FZA, NXB, FXB, NYB, FYB, NZB, FZB)
+#define SNAIL_DESCEND_PF2M(OMASK, PRE, ORGOPS, SLAB, TAIL, CNTPOP, CNTVISIT, LEAFREQ, NXA, FXA, NYA, FYA, NZA, FZA, NXB, FXB, NYB, FYB, NZB, FZB)                 \
+	SNAIL_DESCEND_PF2X(, OMASK, SNAIL_PREVARS_of(PRE), PRE, ORGOPS, SLAB, TAIL, CNTPOP, CNTVISIT, LEAFREQ, NXA, FXA, NYA, FYA, NZA, FZA, NXB, FXB, NYB, FYB, NZB, FZB)
 // coherent packets WITHOUT one statement per sign octant: the near / far plane of each axis is picked on the scalar side, per visit, into
 // s62..s67 (nine scalar instructions that issue beside the visit's vector ones) -- for walks whose leaf code leaves the compiler no room
 // for eight copies of this loop (per-ray origins)
@@ -1333,18 +1379,20 @@ static_assert(SNAIL_REL_INSIDE_BIT == 31, "SNAIL_OIN_TEST_SNAIL_TAIL_POS names t
 #define SNAIL_SLABO_SEL(L, NX, FX, NY, FY, NZ, FZ) SNAIL_SLABO_COH(L, "s62", "s65", "s63", "s66", "s64", "s67")
 #define SNAIL_SEL_CLOB , "s62", "s63", "s64", "s65", "s66", "s67"
 #define SNAIL_DESCEND_PF2_SEL(ORGOPS, SLAB, TAIL, CNTPOP, CNTVISIT, LEAFREQ)                                                                \
-	SNAIL_DESCEND_PF2X(SNAIL_SEL_CLOB, SNAIL_PREVARS_NONE, SNAIL_PRE_SEL, ORGOPS, SLAB, TAIL, CNTPOP, CNTVISIT, LEAFREQ, "s84", "s87", "s85", "s88", "s86", "s89", "s76", "s79", "s77", "s80", "s78", "s81")
-#define SNAIL_DESCEND_PF2_PLAIN(PRE, ORGOPS, SLAB, TAIL, CNTPOP, CNTVISIT, LEAFREQ) SNAIL_DESCEND_PF2(PRE, ORGOPS, SLAB, TAIL, CNTPOP, CNTVISIT, LEAFREQ, "s84", "s87", "s85", "s88", "s86", "s89", "s76", "s79", "s77", "s80", "s78", "s81")
+	SNAIL_DESCEND_PF2X(SNAIL_SEL_CLOB, "0", SNAIL_PREVARS_NONE, SNAIL_PRE_SEL, ORGOPS, SLAB, TAIL, CNTPOP, CNTVISIT, LEAFREQ, "s84", "s87", "s85", "s88", "s86", "s89", "s76", "s79", "s77", "s80", "s78", "s81")
+#define SNAIL_DESCEND_PF2_PLAIN(PRE, ORGOPS, SLAB, TAIL, CNTPOP, CNTVISIT, LEAFREQ) SNAIL_DESCEND_PF2M("0", PRE, ORGOPS, SLAB, TAIL, CNTPOP, CNTVISIT, LEAFREQ, "s84", "s87", "s85", "s88", "s86", "s89", "s76", "s79", "s77", "s80", "s78", "s81")
+// (the first argument of a case: the octant's three bits of SNAIL_POSENTRY_* -- per axis SNAIL_REL_FARNEG_BIT + c where the octant's sign bit c is
+// set, the near plane being bmax there, else SNAIL_REL_NEARPOS_BIT + c; read by the statements whose TAIL is SNAIL_TAIL_POSF only)
 #define SNAIL_DESCEND_PF2_OCT(PRE, ORGOPS, SLAB, TAIL, CNTPOP, CNTVISIT, LEAFREQ, OCT)                                                                                                    \
 	switch(OCT) {                                                                                                                          \
-	case 0: SNAIL_DESCEND_PF2(PRE, ORGOPS, SLAB, TAIL, CNTPOP, CNTVISIT, LEAFREQ, "s84", "s87", "s85", "s88", "s86", "s89", "s76", "s79", "s77", "s80", "s78", "s81"); break;            \
-	case 1: SNAIL_DESCEND_PF2(PRE, ORGOPS, SLAB, TAIL, CNTPOP, CNTVISIT, LEAFREQ, "s87", "s84", "s85", "s88", "s86", "s89", "s79", "s76", "s77", "s80", "s78", "s81"); break;            \
-	case 2: SNAIL_DESCEND_PF2(PRE, ORGOPS, SLAB, TAIL, CNTPOP, CNTVISIT, LEAFREQ, "s84", "s87", "s88", "s85", "s86", "s89", "s76", "s79", "s80", "s77", "s78", "s81"); break;            \
-	case 3: SNAIL_DESCEND_PF2(PRE, ORGOPS, SLAB, TAIL, CNTPOP, CNTVISIT, LEAFREQ, "s87", "s84", "s88", "s85", "s86", "s89", "s79", "s76", "s80", "s77", "s78", "s81"); break;            \
-	case 4: SNAIL_DESCEND_PF2(PRE, ORGOPS, SLAB, TAIL, CNTPOP, CNTVISIT, LEAFREQ, "s84", "s87", "s85", "s88", "s89", "s86", "s76", "s79", "s77", "s80", "s81", "s78"); break;            \
-	case 5: SNAIL_DESCEND_PF2(PRE, ORGOPS, SLAB, TAIL, CNTPOP, CNTVISIT, LEAFREQ, "s87", "s84", "s85", "s88", "s89", "s86", "s79", "s76", "s77", "s80", "s81", "s78"); break;            \
-	case 6: SNAIL_DESCEND_PF2(PRE, ORGOPS, SLAB, TAIL, CNTPOP, CNTVISIT, LEAFREQ, "s84", "s87", "s88", "s85", "s89", "s86", "s76", "s79", "s80", "s77", "s81", "s78"); break;            \
-	default: SNAIL_DESCEND_PF2(PRE, ORGOPS, SLAB, TAIL, CNTPOP, CNTVISIT, LEAFREQ, "s87", "s84", "s88", "s85", "s89", "s86", "s79", "s76", "s80", "s77", "s81", "s78"); break;           \
+	case 0: SNAIL_DESCEND_PF2M("0x0e000000", PRE, ORGOPS, SLAB, TAIL, CNTPOP, CNTVISIT, LEAFREQ, "s84", "s87", "s85", "s88", "s86", "s89", "s76", "s79", "s77", "s80", "s78", "s81"); break;            \
+	case 1: SNAIL_DESCEND_PF2M("0x1c000000", PRE, ORGOPS, SLAB, TAIL, CNTPOP, CNTVISIT, LEAFREQ, "s87", "s84", "s85", "s88", "s86", "s89", "s79", "s76", "s77", "s80", "s78", "s81"); break;            \
+	case 2: SNAIL_DESCEND_PF2M("0x2a000000", PRE, ORGOPS, SLAB, TAIL, CNTPOP, CNTVISIT, LEAFREQ, "s84", "s87", "s88", "s85", "s86", "s89", "s76", "s79", "s80", "s77", "s78", "s81"); break;            \
+	case 3: SNAIL_DESCEND_PF2M("0x38000000", PRE, ORGOPS, SLAB, TAIL, CNTPOP, CNTVISIT, LEAFREQ, "s87", "s84", "s88", "s85", "s86", "s89", "s79", "s76", "s80", "s77", "s78", "s81"); break;            \
+	case 4: SNAIL_DESCEND_PF2M("0x46000000", PRE, ORGOPS, SLAB, TAIL, CNTPOP, CNTVISIT, LEAFREQ, "s84", "s87", "s85", "s88", "s89", "s86", "s76", "s79", "s77", "s80", "s81", "s78"); break;            \
+	case 5: SNAIL_DESCEND_PF2M("0x54000000", PRE, ORGOPS, SLAB, TAIL, CNTPOP, CNTVISIT, LEAFREQ, "s87", "s84", "s85", "s88", "s89", "s86", "s79", "s76", "s77", "s80", "s81", "s78"); break;            \
+	case 6: SNAIL_DESCEND_PF2M("0x62000000", PRE, ORGOPS, SLAB, TAIL, CNTPOP, CNTVISIT, LEAFREQ, "s84", "s87", "s88", "s85", "s89", "s86", "s76", "s79", "s80", "s77", "s81", "s78"); break;            \
+	default: SNAIL_DESCEND_PF2M("0x70000000", PRE, ORGOPS, SLAB, TAIL, CNTPOP, CNTVISIT, LEAFREQ, "s87", "s84", "s88", "s85", "s89", "s86", "s79", "s76", "s80", "s77", "s81", "s78"); break;           \
 	}
 
 // near/far plane registers by sign octant (bit k set = idir negative on axis k: near plane = bmax[k]); s[84:86] = bmin, s[87:89] = bmax
@@ -1405,7 +1453,7 @@ __device__ __forceinline__ void walkSharedAsm(const uint4 *__restrict__ nodes /*
 			if(COH) {
 				if(SHADOW && REL) { SNAIL_DESCEND_PF2_OCT(SNAIL_PRE_NONE_X, SNAIL_ORG_SHARED, SNAIL_SLAB_COH_R, SNAIL_TAIL_ANY, "", SNAIL_COUNT, SNAIL_PF_LEAFREQ_SLOT0, oct) }
 				else if(SHADOW) { SNAIL_DESCEND_PF2_OCT(SNAIL_PRE_SHARED, SNAIL_ORG_SHARED, SNAIL_SLAB_COH, SNAIL_TAIL_ANY, "", SNAIL_COUNT, SNAIL_PF_LEAFREQ_TRI, oct) }
-				else if(POSDIST) { SNAIL_DESCEND_PF2_OCT(SNAIL_PRE_NONE_X, SNAIL_ORG_SHARED, SNAIL_SLAB_COH_R, SNAIL_TAIL_POS, SNAIL_COUNT, "", SNAIL_PF_LEAFREQ_SLOT0, oct) }
+				else if(POSDIST) { SNAIL_DESCEND_PF2_OCT(SNAIL_PRE_NONE_X, SNAIL_ORG_SHARED, SNAIL_SLAB_COH_R, SNAIL_TAIL_POSF, SNAIL_COUNT, "", SNAIL_PF_LEAFREQ_SLOT0, oct) }
 				else { SNAIL_DESCEND_PF2_OCT(SNAIL_PRE_SHARED, SNAIL_ORG_SHARED, SNAIL_SLAB_COH, SNAIL_TAIL_ANY, SNAIL_COUNT, "", SNAIL_PF_LEAFREQ_TRI, oct) }
 			} else {
 				if(SHADOW && REL) { SNAIL_DESCEND_PF2_PLAIN(SNAIL_PRE_NONE_X, SNAIL_ORG_SHARED, SNAIL_SLAB_FAST_R, SNAIL_TAIL_ANY, "", SNAIL_COUNT, SNAIL_PF_LEAFREQ_SLOT0); }
@@ -3079,8 +3127,18 @@ __host__ __device__ inline bool relOriginInside(const unsigned (&w)[6]) {
 }
 // word 7 of the relative record: inner records only (a leaf's visit must reach the leaf code, and its word 7 is a triangle count); an empty slot (slot 0,
 // the slots past a rebuilt tree: word 7 = 0, no axis bit) is no node
+// Inner AND leaf records carry the six "this plane lies ahead of the origin" bits of SNAIL_POSENTRY_* (a leaf's count lies below them,
+// SNAIL_REL_COUNT_MASK): SNAIL_REL_NEARPOS_BIT + c when near word c is > 0, SNAIL_REL_FARNEG_BIT + c when far word c is < 0, both strict: a zero of
+// either sign and a NaN set nothing, and so a record that contains the origin has none of them.
 __host__ __device__ inline unsigned relAux(const unsigned (&rel)[6], unsigned sub, unsigned aux) {
-	return !(sub & 0x80000000u) && (aux & 7u) && relOriginInside(rel) ? aux | (1u << SNAIL_REL_INSIDE_BIT) : aux;
+	const bool leaf = (sub & 0x80000000u) != 0;
+	if(!leaf && !(aux & 7u)) return aux;
+	unsigned bits = 0;
+	for(int c = 0; c < 3; c++) {
+		if(__builtin_bit_cast(float, rel[c]) > 0.0f) bits |= 1u << (SNAIL_REL_NEARPOS_BIT + c);
+		if(__builtin_bit_cast(float, rel[3 + c]) < 0.0f) bits |= 1u << (SNAIL_REL_FARNEG_BIT + c);
+	}
+	return !leaf && relOriginInside(rel) ? aux | (1u << SNAIL_REL_INSIDE_BIT) : aux | bits;
 }
 __global__ __launch_bounds__(256) void k_rel_nodes(const uint4 *__restrict__ pf, int nSlots, float ox, float oy, float oz, uint4 *__restrict__ rel) {
 	const int i = (int)(blockIdx.x * 256 + threadIdx.x);
@@ -3119,6 +3177,16 @@ __global__ __launch_bounds__(256) void k_rel_flag_count(const uint4 *__restrict_
 	const bool flagged = i < nSlots && !(rel[(size_t)i * 2 + 1].z & 0x80000000u) && ((rel[(size_t)i * 2 + 1].w >> SNAIL_REL_INSIDE_BIT) & 1u);
 	const u64 m = __builtin_amdgcn_ballot_w64(flagged);
 	if((threadIdx.x & 63) == 0 && m) atomicAdd(out, (unsigned long long)__builtin_popcountll(m));
+}
+// diagnostic (snail_debug_rel_axis_flag_count): the records that carry each of the six bits of SNAIL_POSENTRY_*, near x, y, z, far x, y, z;
+// two 32-bit counts per word of out[3] (an array has fewer than 2^20 slots)
+__global__ __launch_bounds__(256) void k_rel_axis_flag_count(const uint4 *__restrict__ rel, int nSlots, unsigned long long *__restrict__ out) {
+	const int i = (int)(blockIdx.x * 256 + threadIdx.x);
+	const unsigned w = i < nSlots ? rel[(size_t)i * 2 + 1].w : 0u;
+	for(int k = 0; k < 3; k++) {
+		const u64 lo = __builtin_amdgcn_ballot_w64((w >> (SNAIL_REL_NEARPOS_BIT + 2 * k)) & 1u), hi = __builtin_amdgcn_ballot_w64((w >> (SNAIL_REL_NEARPOS_BIT + 2 * k + 1)) & 1u);
+		if((threadIdx.x & 63) == 0 && (lo | hi)) atomicAdd(out + k, (unsigned long long)__builtin_popcountll(lo) | (unsigned long long)__builtin_popcountll(hi) << 32);
+	}
 }
 #endif
 

@@ -796,6 +796,14 @@ int snail_device_count(void) {
 // byte offset of the triangle records in SnailScene::dPF: a CONSTANT (2^25 = room for 2^20 record slots), so that the prefetching loop
 // turns a leaf record's triangle offset back into an index with immediates (SNAIL_PF2_LEAF)
 static size_t pfTrisOffset(int) { return (size_t)1 << 25; }
+// A tree may take the pack path (the loop's copy and its origin-relative arrays) when its record slots fit a stack word (2^20), a leaf's
+// byte offset fits 31 bits, and every leaf's triangle count lies below the flag bits that an origin-relative record keeps in the same word
+// (dev::relAux, SNAIL_REL_COUNT_MASK): a count never exceeds nTris, and the offset bound alone already keeps nTris below 2^25 - 2^19 -- stated
+// here on its own so that it does not hang on the value of pfTrisOffset.
+static bool pfFits(size_t nSlots, size_t nTris) {
+	const size_t pfBytes = pfTrisOffset(0) + nTris * 64;
+	return nSlots < ((size_t)1 << 20) && pfBytes < ((size_t)1 << 31) && nTris <= (size_t)SNAIL_REL_COUNT_MASK;
+}
 
 SnailScene *snail_scene_create(const void *nodes32, int nNodes, const void *tris64, int nTris, int depth, int device) {
 	if(!nodes32 || !tris64 || nNodes <= 0 || nTris <= 0) { snail_set_error("snail_scene_create: empty scene"); return nullptr; }
@@ -863,7 +871,7 @@ SnailScene *snail_scene_create(const void *nodes32, int nNodes, const void *tris
 	// ONE allocation: [slot 0][the node records re-encoded for the record-prefetching loop][triangle records]; the caller's node
 	// records, verbatim, in a second one (every other walk reads those)
 	const size_t trisOff = pfTrisOffset(nNodes), pfBytes = trisOff + (size_t)nTris * 64;
-	const bool fits = (size_t)nNodes + 1 < ((size_t)1 << 20) && pfBytes < ((size_t)1 << 31);
+	const bool fits = pfFits((size_t)nNodes + 1, (size_t)nTris);   // (leaf counts are <= nTris: validated above)
 	s->pfOKButNesting = pairsOdd && fits;
 	s->pfOK = s->pfOKButNesting && nestedOK;
 	s->trisOff = (int)(fits ? trisOff : 0);
@@ -908,7 +916,7 @@ SnailScene *snail_scene_create_lbvh(const float *tri_verts, int nTris, int devic
 	// the LBVH is nested by construction (bottom-up refit: a parent's box is the exact union of its children's) and its children live in
 	// slots 1 + 2i, 2 + 2i: the record-prefetching loop's copy is encoded on the device, the triangle records move behind it
 	const size_t trisOff = pfTrisOffset(s->nNodes), pfBytes = trisOff + (size_t)nTris * 64;
-	const bool fits = (size_t)s->nNodes + 1 < ((size_t)1 << 20) && pfBytes < ((size_t)1 << 31);
+	const bool fits = pfFits((size_t)s->nNodes + 1, (size_t)nTris);
 	s->trisOff = (int)(fits ? trisOff : 0);
 	s->nestedOK = 1; s->pfOKButNesting = s->pfOK = fits ? 1 : 0;
 	hipError_t e;
@@ -1709,6 +1717,33 @@ int snail_debug_rel_flag_count(SnailScene *s, const float org[3], int *count) {
 	uint64_t st[4] = {0, 0, 0, 0};
 	if(int rc = hc.finish(st)) return rc;
 	*count = (int)st[0];
+	return 0;
+}
+
+// The same array's records that carry each of the six "plane ahead of the origin" bits (dev::relAux): out[c] near word c > 0, out[3 + c] far word c < 0
+int snail_debug_rel_axis_flag_count(SnailScene *s, const float org[3], int out[6]) {
+	if(int rc = checkScene(s, "snail_debug_rel_axis_flag_count")) return rc;
+	if(!org || !out) { snail_set_error("snail_debug_rel_axis_flag_count: null argument"); return 1; }
+	if(!stackPack(s)) { snail_set_error("snail_debug_rel_axis_flag_count: this scene keeps no origin-relative node records"); return 1; }
+	DeviceGuard guard(s->device);
+	HostCallScope hc(s, "snail_debug_rel_axis_flag_count");
+	if(hc.rc) return hc.rc;
+	if(int rc = hc.zeroStats()) return rc;
+	{
+		SNAIL_LOCK(s);
+		SceneUse use(s, hc.stream());
+		if(use.rc) return use.rc;
+		const uint4 *rel = nullptr;
+		int which = -1;
+		if(int rc = relFor(s, org, hc.stream(), &rel, &which)) return rc;
+		const int nSlots = s->nNodes + 1;
+		hipLaunchKernelGGL(dev::k_rel_axis_flag_count, dim3((unsigned)((nSlots + 255) / 256)), dim3(256), 0, hc.stream(), rel, nSlots, (unsigned long long *)hc.stats());
+		HIP_TRY(hipGetLastError());
+		if(int rc = relUsed(s, which, hc.stream())) return rc;
+	}
+	uint64_t st[4] = {0, 0, 0, 0};
+	if(int rc = hc.finish(st)) return rc;
+	for(int k = 0; k < 3; k++) { out[2 * k] = (int)(st[k] & 0xffffffffu); out[2 * k + 1] = (int)(st[k] >> 32); }
 	return 0;
 }
 
