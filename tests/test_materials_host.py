@@ -10,10 +10,11 @@ from tests import materials_ref as M
 from tests import oracle_lib as O
 
 
-@pytest.mark.parametrize("w,h", [(64, 64), (32, 8), (8, 2), (1, 1), (2, 1), (1, 4), (16, 1)])
+@pytest.mark.parametrize("w,h", [(64, 64), (32, 8), (8, 2), (1, 1), (2, 1), (1, 4), (16, 1),
+                                 (2, 2), (1, 8), (8, 1), (8, 32), (8192, 2), (2, 8192), (4, 2048), (256, 256)])
 def test_texture_build_equals_the_restatement(w, h):
     """(8, 2): its level 4 x 1 -> 2 x 1 -> 1 x 1 goes through the height-1 row case, whose src[4 + i] reads across pixels and, for the last
-    pair, one byte into the level being written"""
+    pair, one byte into the level being written.  The second row: the shapes of tests/materials_synth.py that the first lacks"""
     level0 = np.random.RandomState(w * 100 + h).randint(0, 256, size=(h, w, 3)).astype(np.uint8)
     t = P.Texture(level0)
     want = M.gen_mips(level0)
