@@ -59,6 +59,7 @@
 #include "snail_instances.h"
 #include "snail_heatmap.h"
 #include "snail_materials_tiles.h"
+#include "snail_materials_transparency.h"
 
 #ifndef SNAIL_CHECK
 #define SNAIL_CHECK(expr)                                                                              \
@@ -518,10 +519,12 @@ enum { kDeviceHeatmap = 0 };
 // gVals[6] on the device (include/snail_materials_tiles.h): define SNAIL_ADAPTER_DEVICE_MATERIALS before the include, attach a material set to the
 // tree (HipBVH::AttachMaterials) and the Render(...) overloads send a call with gVals[6] && HasShadingData() to snail_materials_render_tiles /
 // snail_materials_render_frame -- the tile list with gVals[1], [7], [9] and [8] (tint by `rank`), the image with gVals[1], [7], [9] -- when a
-// set is attached, the tree is on one device, an image is not asked to be tinted (gVals[8]) and gVals[5] is off or overridden by gVals[1].  An
-// attached set is sufficient for equivalence: a set that could select a transparent lane cannot exist, because snail_materials_create refuses
-// it, so the frame the device makes is the frame the reference's full-shading branch makes.  Every other gVals[6] call keeps the reference's
-// renderer: no set, several devices, an image with gVals[8], and gVals[5] without gVals[1] -- the last even with the device heat-map opted in,
+// set is attached that cannot select a transparent lane (snail_materials_can_select_transparent == 0), the tree is on one device, an image is
+// not asked to be tinted (gVals[8]) and gVals[5] is off or overridden by gVals[1].  A set of snail_materials_create never can;
+// snail_materials_create_transparent (include/snail_materials_transparency.h) makes sets that can, whose frames need the transparency
+// continuation, which the tile functions this routing goes through do not run: they refuse such a set, and the routing leaves it with the reference's renderer.
+// For a set that passes, the frame the device makes is the frame the reference's full-shading branch makes.  Every other gVals[6] call keeps the
+// reference's renderer: no set, a set that can select a transparent lane, several devices, an image with gVals[8], and gVals[5] without gVals[1] -- the last even with the device heat-map opted in,
 // whose counters are those of simple shading (under full shading the shadow lanes follow the interpolated normals, so the counts differ).
 // Opt-in, so that hosts and mocks built without it keep today's routing.
 #ifdef SNAIL_ADAPTER_DEVICE_MATERIALS
@@ -724,7 +727,8 @@ inline StatsT RenderMaterialImage(const SceneT &scene, const CameraT &camera, Im
 template <class RefBVH>
 inline TreeStats Render(const Scene<snail::HipBVH<RefBVH>> &scene, const Camera &camera, uint resx, uint resy, unsigned char *data, const vector<int> &coords,
 						const vector<int> &offsets, const Options options, uint rank, uint threads) {
-	const bool deviceMaterials = snail::kDeviceMaterials && scene.geometry.Materials() != nullptr && scene.geometry.DeviceCount() <= 1;
+	const bool deviceMaterials = snail::kDeviceMaterials && scene.geometry.Materials() != nullptr && scene.geometry.DeviceCount() <= 1 &&
+								 snail_materials_can_select_transparent(scene.geometry.Materials()) == 0;
 	if(const char *why = snail::UnsupportedSwitch(gVals, scene.geometry.HasShadingData(), true, snail::kDeviceHeatmap && scene.geometry.DeviceCount() <= 1, deviceMaterials))
 		SNAIL_HOST_RENDER(why, gVals[9] ? 2 : 1, resx, resy, Render<snail::HipBVH<RefBVH>>(scene, camera, resx, resy, data, coords, offsets, options, rank, threads));
 	(void)rank; (void)threads; // (a tint only under full shading; the host thread pool has no device counterpart)
@@ -745,7 +749,8 @@ inline TreeStats Render(const Scene<snail::HipBVH<RefBVH>> &scene, const Camera 
 }
 template <class RefBVH>
 inline TreeStats Render(const Scene<snail::HipBVH<RefBVH>> &scene, const Camera &camera, MipmapTexture &image, const Options options, uint threads) {
-	const bool deviceMaterials = snail::kDeviceMaterials && scene.geometry.Materials() != nullptr && scene.geometry.DeviceCount() <= 1;
+	const bool deviceMaterials = snail::kDeviceMaterials && scene.geometry.Materials() != nullptr && scene.geometry.DeviceCount() <= 1 &&
+								 snail_materials_can_select_transparent(scene.geometry.Materials()) == 0;
 	if(const char *why = snail::UnsupportedSwitch(gVals, scene.geometry.HasShadingData(), false, snail::kDeviceHeatmap != 0, deviceMaterials))
 		SNAIL_HOST_RENDER(why, gVals[9] ? 2 : 1, image.Width(), image.Height(), Render<snail::HipBVH<RefBVH>>(scene, camera, image, options, threads));
 	(void)threads;

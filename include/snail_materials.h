@@ -5,8 +5,10 @@
  * and its symbol list stay as they are.  Plain C.
  *
  * NOT here: the mirrored bounce is snail_materials_bounce.h's; 4x antialiasing, depth shading, the tint and tile lists are
- * snail_materials_tiles.h's.  The host renderer keeps the transparency continuation under full shading, multi-device frames, the heat-map, the
- * ordered launches, OBJ vt / vn / usemtl and MTL ingest, the DXT and SAT samplers and rgba8 textures.
+ * snail_materials_tiles.h's; the material kinds that can select a transparent lane, their sample stages and the continuation's packets are
+ * snail_materials_transparency.h's and the frames of the continuation too (a set that holds such a kind is refused by every function here that takes a set).  The host renderer keeps
+ * multi-device frames, the heat-map, the ordered launches, OBJ vt / vn / usemtl and
+ * MTL ingest, the DXT and SAT samplers and rgba8 textures.
  */
 #ifndef SNAIL_MATERIALS_H
 #define SNAIL_MATERIALS_H
@@ -43,7 +45,7 @@ enum { SNAIL_MAT_SIMPLE = 0, SNAIL_MAT_TEX = 1, SNAIL_MAT_UBER = 2, SNAIL_MAT_TR
  *   SNAIL_MAT_UBER    UberMaterial: `diffuse` / `specular` / `dissolve` are the MaterialDesc's; the constructor's Swap(diffuse.x, diffuse.z) is
  *                     applied by snail_materials_create.  diffuse * Abs(d.n); specular = the sample's diffuse on the unmasked path, `specular`
  *                     on the masked one
- *   SNAIL_MAT_TRANSPARENT  refused (below) */
+ *   SNAIL_MAT_TRANSPARENT  refused here (below); accepted by snail_materials_create_transparent (snail_materials_transparency.h) */
 typedef struct SnailMaterial {
 	int32_t kind, nDotR;
 	float diffuse[3], specular[3];

@@ -5,12 +5,13 @@
  * A header of its own: snail_materials.h (whose frame functions keep refusing every nonzero flag), snail_hip.h and their symbol lists stay
  * as they are.  Plain C.
  *
- * The nested call never bounces again (cache.reflections < 1), and no material a set accepts can select a transparent lane, so it takes
- * neither continuation.
+ * The nested call never bounces again (cache.reflections < 1), and no set these functions accept can select a transparent lane (a set of
+ * snail_materials_create_transparent that can is refused, snail_materials_transparency.h), so it takes neither continuation.
  *
  * NOT here: 4x antialiasing, depth shading, the tint and tile lists with the bounce are snail_materials_tiles.h's, and with them the adapter's
- * routing of a call with gVals[6] (SNAIL_ADAPTER_DEVICE_MATERIALS, snail_adapter.hpp).  The host renderer keeps the transparency
- * continuation, multi-device frames, the heat-map and the ordered launches (dispatch-order feedback) under the bounce.
+ * routing of a call with gVals[6] (SNAIL_ADAPTER_DEVICE_MATERIALS, snail_adapter.hpp); the transparent kinds and the frames of the
+ * transparency continuation are snail_materials_transparency.h's.  The host renderer keeps the transparency continuation together with
+ * the bounce, multi-device frames, the heat-map and the ordered launches (dispatch-order feedback) under the bounce.
  */
 #ifndef SNAIL_MATERIALS_BOUNCE_H
 #define SNAIL_MATERIALS_BOUNCE_H

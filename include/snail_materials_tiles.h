@@ -31,7 +31,9 @@
  *   flags in {0, SNAIL_RENDER_REFLECTIONS} without tint      the bytes and counters of snail_materials_bounce_packets_dev
  *   SNAIL_RENDER_DEPTH, with or without SNAIL_RENDER_AA4     the bytes and counters of snail_render_tiles on the set's scene with the same flags
  *
- * NOT here (the host renderer keeps them): the transparency continuation; full-shaded tiles dealt over several devices; the heat-map
+ * NOT here (the host renderer keeps them): tiles, 4x antialiasing and the tint with the transparency continuation (the transparent kinds and
+ * the continuation's plain frames are snail_materials_transparency.h's; a set that can select a transparent lane is refused by the functions here);
+ * full-shaded tiles dealt over several devices; the heat-map
  * (gVals[5]) under full shading; the ordered launches (dispatch-order feedback); materials on instanced scenes.
  */
 #ifndef SNAIL_MATERIALS_TILES_H

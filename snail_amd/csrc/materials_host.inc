@@ -10,6 +10,7 @@ struct SnailMaterials {
 	SnailScene *scene = nullptr;
 	int device = 0;
 	int nTris = 0, nMap = 0, nMats = 0, nTex = 0;
+	bool canSelectTransparent = false;   // holds SNAIL_MAT_TRANSPARENT or UBER with 0 < dissolve < 1 (snail_materials_create_transparent alone makes such a set)
 	char *dBase = nullptr;   // ONE allocation: records, map, materials, texture descriptors, texels
 	const uint4 *dShTris = nullptr;
 	const int *dMap = nullptr;
@@ -50,6 +51,8 @@ struct SnailMaterials {
 		int bounceLights = 0;
 		char *tiles = nullptr;    // the tile renderer's part (Set::TileBufs), only once it was asked for; grown under the same rule
 		size_t tilesPackets = 0;
+		char *transp = nullptr;   // the per-level intermediates of the transparency frames (materials_transparency_host.inc), only once asked for; sized by
+		size_t transpBytes = 0;   // packets, lights and the depth asked for, grown under the same rule
 		hipEvent_t done = nullptr;
 		bool used = false;
 	};
@@ -85,9 +88,18 @@ size_t matLevelBytes(int w, int h, int m) {
 }
 bool matTexShapeOK(int w, int h) { return matPow2(w) && matPow2(h) && w <= 8192 && h <= 8192; }
 
-int checkMaterials(const SnailMaterials *m, const char *fn) {
+// any set: the entry points of include/snail_materials_transparency.h
+int checkMaterialsAny(const SnailMaterials *m, const char *fn) {
 	if(!m || !m->scene || !m->dBase) { snail_set_error("%s: invalid material set handle", fn); return 1; }
 	return checkScene(m->scene, fn);
+}
+// the entry points of snail_materials.h, _bounce.h and _tiles.h: their kernels know neither the transparent kind nor the selector
+int checkMaterials(const SnailMaterials *m, const char *fn) {
+	if(m && m->canSelectTransparent) {
+		snail_set_error("%s: the set holds a material that can select a transparent lane, which this function's kernels do not know (include/snail_materials_transparency.h)", fn);
+		return 1;
+	}
+	return checkMaterialsAny(m, fn);
 }
 int checkMatFrameArgs(const char *fn, const float cam[13], int resx, int resy, const float *lights7, int nLights, const float ambient[3], int flags) {
 	if(flags) { snail_set_error("%s: flags must be 0 (got 0x%x): no bounce, transparency or antialiasing under full shading yet", fn, flags); return 1; }
@@ -258,7 +270,7 @@ int matSetDone(SnailMaterials::Set &W, const char *fn, int rc, hipStream_t st) {
 	// stream) must come after them.  Should the record itself fail, the set is marked grown-from-scratch: its next user synchronises the device.
 	if(hipEventRecord(W.done, st) == hipSuccess) W.used = true;
 	else {
-		W.packets = 0; W.bouncePackets = 0; W.tilesPackets = 0; W.used = false;
+		W.packets = 0; W.bouncePackets = 0; W.tilesPackets = 0; W.transpBytes = 0; W.used = false;
 		if(!rc) { snail_set_error("%s: hipEventRecord failed", fn); return 1; }
 	}
 	return rc;
@@ -357,9 +369,12 @@ int snail_texture_build(const uint8_t *level0, int w, int h, uint8_t *out, int64
 	return 0;
 }
 
-SnailMaterials *snail_materials_create(SnailScene *scene, const void *shtris64, int nTris, const int32_t *matMap, int nMap, const SnailMaterial *mats, int nMats,
-									   const SnailTexture *textures, int nTex) {
-	const char *fn = "snail_materials_create";
+} // extern "C"
+
+// the two creators: snail_materials_create (transp = false: its refusals) and snail_materials_create_transparent (include/snail_materials_transparency.h)
+static SnailMaterials *matCreate(const char *fn, bool transp, SnailScene *scene, const void *shtris64, int nTris, const int32_t *matMap, int nMap, const SnailMaterial *mats,
+								 int nMats, const int32_t *opacityTexture, const SnailTexture *textures, int nTex) {
+	bool canSelect = false;
 	if(nTris <= 0 || nMap <= 0 || nMats < 0 || nTex < 0 || !shtris64 || !matMap || (nMats && !mats) || (nTex && !textures)) {
 		snail_set_error("%s: bad counts or null arrays (at least one triangle and one map entry)", fn);
 		return nullptr;
@@ -373,12 +388,20 @@ SnailMaterials *snail_materials_create(SnailScene *scene, const void *shtris64, 
 	}
 	for(int k = 0; k < nMats; k++) {
 		const SnailMaterial &M = mats[k];
-		if(M.kind == SNAIL_MAT_TRANSPARENT) { snail_set_error("%s: material %d is of the transparent kind: transparency under full shading stays with the host renderer", fn, k); return nullptr; }
-		if(M.kind != SNAIL_MAT_SIMPLE && M.kind != SNAIL_MAT_TEX && M.kind != SNAIL_MAT_UBER) { snail_set_error("%s: material %d: unknown kind %d", fn, k, M.kind); return nullptr; }
-		if(M.kind == SNAIL_MAT_UBER && !(M.dissolve <= 0.0f || M.dissolve >= 1.0f)) {
+		if(M.kind == SNAIL_MAT_TRANSPARENT && !transp) { snail_set_error("%s: material %d is of the transparent kind: transparency under full shading stays with the host renderer", fn, k); return nullptr; }
+		if(M.kind != SNAIL_MAT_SIMPLE && M.kind != SNAIL_MAT_TEX && M.kind != SNAIL_MAT_UBER && M.kind != SNAIL_MAT_TRANSPARENT) { snail_set_error("%s: material %d: unknown kind %d", fn, k, M.kind); return nullptr; }
+		if(M.kind == SNAIL_MAT_UBER && !transp && !(M.dissolve <= 0.0f || M.dissolve >= 1.0f)) {
 			snail_set_error("%s: material %d: UBER with dissolve %g could select a transparent lane (accepted: dissolve <= 0 or >= 1)", fn, k, (double)M.dissolve);
 			return nullptr;
 		}
+		if(M.kind == SNAIL_MAT_UBER && std::isnan(M.dissolve)) { snail_set_error("%s: material %d: UBER with a NaN dissolve", fn, k); return nullptr; }   // (transp: the other creator has refused it above)
+		if(M.kind == SNAIL_MAT_TRANSPARENT) {
+			if(M.texture < 0 || M.texture >= nTex) { snail_set_error("%s: material %d: texture index %d outside 0..%d", fn, k, M.texture, nTex - 1); return nullptr; }
+			if(!opacityTexture) { snail_set_error("%s: material %d is of the transparent kind and the opacity texture array is null", fn, k); return nullptr; }
+			if(opacityTexture[k] < 0 || opacityTexture[k] >= nTex) { snail_set_error("%s: material %d: opacity texture index %d outside 0..%d", fn, k, opacityTexture[k], nTex - 1); return nullptr; }
+			canSelect = true;
+		}
+		if(M.kind == SNAIL_MAT_UBER && M.dissolve > 0.0f && M.dissolve < 1.0f) canSelect = true;
 		if(M.kind == SNAIL_MAT_TEX && (M.texture < 0 || M.texture >= nTex)) { snail_set_error("%s: material %d: texture index %d outside 0..%d", fn, k, M.texture, nTex - 1); return nullptr; }
 	}
 	for(int k = 0; k < nMap; k++)
@@ -396,7 +419,10 @@ SnailMaterials *snail_materials_create(SnailScene *scene, const void *shtris64, 
 	memset(recs.data(), 0, recs.size() * sizeof(dev::MatRec));
 	for(int k = 0; k < nMats; k++) {
 		dev::MatRec &R = recs[k];
-		R.kind = mats[k].kind; R.ndotr = mats[k].nDotR ? 1 : 0; R.tex = mats[k].kind == SNAIL_MAT_TEX ? mats[k].texture : 0;
+		R.kind = mats[k].kind; R.ndotr = mats[k].nDotR ? 1 : 0; R.tex = (mats[k].kind == SNAIL_MAT_TEX || mats[k].kind == SNAIL_MAT_TRANSPARENT) ? mats[k].texture : 0;
+		// the padding, read by the kernels of materials_transparency.inc alone: the opacity map, and the dissolve factor's bits
+		R.pad[0] = mats[k].kind == SNAIL_MAT_TRANSPARENT ? opacityTexture[k] : 0;
+		memcpy(&R.pad[1], &mats[k].dissolve, 4);
 		for(int c = 0; c < 3; c++) { R.col[c] = mats[k].diffuse[c]; R.spec[c] = mats[k].specular[c]; }
 		if(mats[k].kind == SNAIL_MAT_UBER) std::swap(R.col[0], R.col[2]);   // UberMaterial::UberMaterial: Swap(diffuse.x, diffuse.z)
 	}
@@ -432,9 +458,17 @@ SnailMaterials *snail_materials_create(SnailScene *scene, const void *shtris64, 
 	m->scene = scene; m->device = scene->device;
 	m->nTris = nTris; m->nMap = nMap; m->nMats = nMats; m->nTex = nTex;
 	m->dBase = base;
+	m->canSelectTransparent = canSelect;
 	m->dShTris = (const uint4 *)(base + oTris); m->dMap = (const int *)(base + oMap); m->dMats = (const dev::MatRec *)(base + oMats);
 	m->dTex = (const dev::TexRec *)(base + oTex); m->dTexels = (const unsigned char *)(base + oTexels);
 	return m;
+}
+
+extern "C" {
+
+SnailMaterials *snail_materials_create(SnailScene *scene, const void *shtris64, int nTris, const int32_t *matMap, int nMap, const SnailMaterial *mats, int nMats,
+									   const SnailTexture *textures, int nTex) {
+	return matCreate("snail_materials_create", false, scene, shtris64, nTris, matMap, nMap, mats, nMats, nullptr, textures, nTex);
 }
 
 void snail_materials_destroy(SnailMaterials *m) {
@@ -445,6 +479,7 @@ void snail_materials_destroy(SnailMaterials *m) {
 		if(W.base) (void)hipFree(W.base);
 		if(W.bounce) (void)hipFree(W.bounce);
 		if(W.tiles) (void)hipFree(W.tiles);
+		if(W.transp) (void)hipFree(W.transp);
 		if(W.done) (void)hipEventDestroy(W.done);
 	}
 	freeInstTileJob(m->tileJob);

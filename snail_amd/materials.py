@@ -14,7 +14,13 @@ and MipmapTexture / PointSampler -- over the C-ABI of include/snail_materials.h.
                                                         4x AA (gVals[9]), depth shading (gVals[1]) and the tint (gVals[8]),
                                                         include/snail_materials_tiles.h
 
-Out of this module (the host renderer keeps them): transparency under full shading, OBJ / MTL ingest."""
+  Material.transparent, MaterialSet(..., transparent=True), .can_select_transparent, .shade_packets_transp / .shade_rays_transp /
+  .continue_packets, .render_transparent / .render_transparent_packets / .render_transparent_image_host
+                                                    <-> TransparentMaterial<NDotR> / UberMaterial's dissFactor, Sample::opacity, the transSel
+                                                        selector, Scene::TraceTransparency and its nested RayTrace calls, level by level,
+                                                        include/snail_materials_transparency.h
+
+Out of this module (the host renderer keeps them): transparency together with the bounce or the tile renderer, OBJ / MTL ingest."""
 from __future__ import annotations
 
 import ctypes as C
@@ -60,7 +66,8 @@ class Texture:
 class Material:
     """One record of MATERIAL_DTYPE."""
 
-    def __init__(self, kind, ndotr=True, diffuse=(1.0, 1.0, 1.0), specular=(0.0, 0.0, 0.0), dissolve=0.0, texture=0):
+    def __init__(self, kind, ndotr=True, diffuse=(1.0, 1.0, 1.0), specular=(0.0, 0.0, 0.0), dissolve=0.0, texture=0, opacity_texture=0):
+        self.opacity_texture = int(opacity_texture)      # read for KIND_TRANSPARENT only (snail_materials_create_transparent's opacityTexture)
         self.rec = np.zeros((), dtype=MATERIAL_DTYPE)
         self.rec["kind"], self.rec["ndotr"], self.rec["diffuse"], self.rec["specular"] = int(kind), 1 if ndotr else 0, diffuse, specular
         self.rec["dissolve"], self.rec["texture"] = dissolve, int(texture)
@@ -79,9 +86,10 @@ class Material:
         return cls(KIND_UBER, True, diffuse=diffuse, specular=specular, dissolve=dissolve)
 
     @classmethod
-    def transparent(cls):
-        """The TransparentMaterial kind: always refused by MaterialSet (kept so that a host can show the refusal)."""
-        return cls(KIND_TRANSPARENT)
+    def transparent(cls, texture: int = 0, opacity_texture: int = 0, ndotr: bool = True):
+        """TransparentMaterial<NDotR>: `texture` is the colour map, `opacity_texture` the opacity map (its first channel is the opacity).
+        Accepted by MaterialSet(..., transparent=True) alone; the plain creator refuses the kind."""
+        return cls(KIND_TRANSPARENT, ndotr, texture=texture, opacity_texture=opacity_texture)
 
 
 def pack_shtris(uv, nrm, mat_index, flat=None, perm=None) -> np.ndarray:
@@ -107,8 +115,9 @@ def _material_records(materials) -> np.ndarray:
     return recs
 
 
-def create_set(scene_handle, shtris, material_map, materials, textures):
-    """snail_materials_create over raw arguments -> handle (c_void_p); SnailError with the library's text when the set is refused"""
+def create_set(scene_handle, shtris, material_map, materials, textures, transparent: bool = False):
+    """snail_materials_create (transparent=True: snail_materials_create_transparent) over raw arguments -> handle (c_void_p); SnailError with
+    the library's text when the set is refused"""
     sh = np.ascontiguousarray(shtris, dtype=np.uint8).reshape(-1, 64)
     mp = np.ascontiguousarray(material_map, dtype=np.int32).reshape(-1)
     recs = _material_records(materials)
@@ -118,10 +127,15 @@ def create_set(scene_handle, shtris, material_map, materials, textures):
     tex = (_Tex * max(len(textures), 1))()
     for k, t in enumerate(textures):
         tex[k].levels, tex[k].width, tex[k].height = t.levels.ctypes.data, t.width, t.height
-    h = _lib.lib().snail_materials_create(scene_handle, _lib.ptr(sh), len(sh), _lib.ptr(mp), len(mp), _lib.ptr(recs) if len(recs) else None, len(recs),
-                                          C.cast(tex, C.c_void_p) if len(textures) else None, len(textures))
+    if transparent:
+        op = np.ascontiguousarray([getattr(m, "opacity_texture", 0) for m in materials], dtype=np.int32)
+        h = _lib.lib().snail_materials_create_transparent(scene_handle, _lib.ptr(sh), len(sh), _lib.ptr(mp), len(mp), _lib.ptr(recs) if len(recs) else None, len(recs),
+                                                          _lib.ptr(op) if len(op) else None, C.cast(tex, C.c_void_p) if len(textures) else None, len(textures))
+    else:
+        h = _lib.lib().snail_materials_create(scene_handle, _lib.ptr(sh), len(sh), _lib.ptr(mp), len(mp), _lib.ptr(recs) if len(recs) else None, len(recs),
+                                              C.cast(tex, C.c_void_p) if len(textures) else None, len(textures))
     if not h:
-        raise _lib.SnailError("snail_materials_create: %s" % _lib.lib().snail_last_error().decode())
+        raise _lib.SnailError("%s: %s" % ("snail_materials_create_transparent" if transparent else "snail_materials_create", _lib.lib().snail_last_error().decode()))
     return C.c_void_p(h)
 
 
@@ -134,7 +148,7 @@ class MaterialSet:
     Scene.from_fast, Scene.from_lbvh).  A scene whose tree is built or rebuilt on the device (Scene.from_fast_dev / rebuild_fast_dev) is
     refused: a rebuild renumbers the triangles, and a set made before it would shade every hit with another triangle's data."""
 
-    def __init__(self, scene: Scene, uv, nrm, mat_index, flat=None, material_map=(-1,), materials=(), textures=()):
+    def __init__(self, scene: Scene, uv, nrm, mat_index, flat=None, material_map=(-1,), materials=(), textures=(), transparent: bool = False):
         self.scene = scene
         self._h = None
         if getattr(scene, "_fast_dev", False):
@@ -144,7 +158,7 @@ class MaterialSet:
         if perm is None:
             raise _lib.SnailError("MaterialSet: the scene carries no permutation (BVH slot -> input triangle), so its shading data cannot be put into triId order")
         self.shtris = pack_shtris(uv, nrm, mat_index, flat, perm)
-        self._h = create_set(scene._h, self.shtris, material_map, list(materials), list(textures))
+        self._h = create_set(scene._h, self.shtris, material_map, list(materials), list(textures), transparent)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -202,6 +216,119 @@ class MaterialSet:
                                                        _stream_ptr(stream))
         _lib.check(rc, "snail_materials_shade_rays_dev")
         return out
+
+    # ---- include/snail_materials_transparency.h ----------------------------------------------------------------------------------------
+    @property
+    def can_select_transparent(self) -> bool:
+        """whether the set holds a material that can select a transparent lane (Material.transparent, or Material.uber with 0 < dissolve < 1):
+        such a set is refused by every method above and below this block"""
+        r = _lib.lib().snail_materials_can_select_transparent(self._h)
+        if r < 0:
+            raise _lib.SnailError("snail_materials_can_select_transparent: %s" % _lib.lib().snail_last_error().decode())
+        return bool(r)
+
+    def shade_packets_transp(self, cam, resx: int, resy: int, packet_xy, hits, stream=None):
+        """shade_packets for any set, with Sample::opacity and the transparency selector -> (samples float32 [n, 9, 64, 4], opacity float32
+        [n, 256], sel uint8 [n, 64]: low 4 bits = transSel after the opacity < 1 filter).  snail_materials_shade_packets_transp_dev."""
+        torch = _torch()
+        n = int(packet_xy.shape[0])
+        dev = self.scene._dev()
+        out = torch.empty((n, SAMPLE_COMPONENTS, 64, 4), dtype=torch.float32, device=dev)
+        opacity = torch.empty((n, 256), dtype=torch.float32, device=dev)
+        sel = torch.empty((n, 64), dtype=torch.uint8, device=dev)
+        cam13 = np.ascontiguousarray(cam.as_array13(), dtype=np.float32)
+        rc = _lib.lib().snail_materials_shade_packets_transp_dev(self._h, _lib.ptr(cam13), resx, resy, _lib.ptr(packet_xy), n, _lib.ptr(hits[0]), _lib.ptr(hits[1]),
+                                                                 _lib.ptr(hits[2]), _lib.ptr(hits[3]), _lib.ptr(out), _lib.ptr(opacity), _lib.ptr(sel), _stream_ptr(stream))
+        _lib.check(rc, "snail_materials_shade_packets_transp_dev")
+        return out, opacity, sel
+
+    def shade_rays_transp(self, dirs, mask, t, u, v, tri_id, stream=None):
+        """shade_rays for any set -> (samples, opacity, sel) as shade_packets_transp.  snail_materials_shade_rays_transp_dev."""
+        torch = _torch()
+        n = int(dirs.shape[0])
+        dev = self.scene._dev()
+        out = torch.empty((n, SAMPLE_COMPONENTS, 64, 4), dtype=torch.float32, device=dev)
+        opacity = torch.empty((n, 256), dtype=torch.float32, device=dev)
+        sel = torch.empty((n, 64), dtype=torch.uint8, device=dev)
+        rc = _lib.lib().snail_materials_shade_rays_transp_dev(self._h, n, _lib.ptr(dirs), _lib.ptr(mask), _lib.ptr(t), _lib.ptr(u), _lib.ptr(v), _lib.ptr(tri_id),
+                                                              _lib.ptr(out), _lib.ptr(opacity), _lib.ptr(sel), _stream_ptr(stream))
+        _lib.check(rc, "snail_materials_shade_rays_transp_dev")
+        return out, opacity, sel
+
+    def continue_packets(self, t, sel, cam=None, resx: int = 0, resy: int = 0, packet_xy=None, rays=None, stats=None, stream=None):
+        """Scene::TraceTransparency's packets of one level from its hits t [n, 256] and selector sel [n, 64] (device tensors).  The level's rays:
+        cam / resx / resy / packet_xy (the primary level) or rays = (origin, dir, idir) [n, 64, 3, 4] (generic packets) ->
+        (origin, dir, idir [n, 64, 3, 4] float32, mask [n, 64] uint8, distance [n, 256] float32, object [n, 256] int32, order [n] int32: the
+        packet's index, or -1 when none of its lanes is selected).  snail_materials_continue_packets_dev."""
+        torch = _torch()
+        n = int(t.shape[0])
+        dev = self.scene._dev()
+        org, d, idir = (torch.empty((n, 64, 3, 4), dtype=torch.float32, device=dev) for _ in range(3))
+        mask = torch.empty((n, 64), dtype=torch.uint8, device=dev)
+        dist = torch.empty((n, 256), dtype=torch.float32, device=dev)
+        obj = torch.empty((n, 256), dtype=torch.int32, device=dev)
+        order = torch.empty((n,), dtype=torch.int32, device=dev)
+        cam13 = None if cam is None else np.ascontiguousarray(cam.as_array13(), dtype=np.float32)
+        ro, rd, ri = rays if rays is not None else (None, None, None)
+        rc = _lib.lib().snail_materials_continue_packets_dev(self._h, _lib.ptr(cam13), int(resx), int(resy), _lib.ptr(packet_xy), n, _lib.ptr(ro), _lib.ptr(rd), _lib.ptr(ri),
+                                                             _lib.ptr(t), _lib.ptr(sel), _lib.ptr(org), _lib.ptr(d), _lib.ptr(idir), _lib.ptr(mask), _lib.ptr(dist),
+                                                             _lib.ptr(obj), _lib.ptr(order), _lib.ptr(stats), _stream_ptr(stream))
+        _lib.check(rc, "snail_materials_continue_packets_dev")
+        return org, d, idir, mask, dist, obj, order
+
+    def _truncated(self, truncated):
+        return truncated if truncated is not None else _torch().zeros(1, dtype=_torch().int64, device=self.scene._dev())
+
+    def render_transparent(self, cam, resx: int, resy: int, lights7=None, ambient=(0.1, 0.1, 0.1), out=None, stats=None, stream=None, flags: int = 0,
+                           max_depth: int = 8, truncated=None):
+        """The lit frame with the transparency continuation, at most max_depth levels deep -> (frame [resy, resx, 3] uint8 (B,G,R) or `out`,
+        truncated: an int64 device tensor of one word, += the lanes level max_depth would still select; 0 = the frame is the reference's).
+        snail_materials_transparent_dev."""
+        torch = _torch()
+        if out is None:
+            out = torch.zeros((resy, resx, 3), dtype=torch.uint8, device=self.scene._dev())
+        truncated = self._truncated(truncated)
+        lights = self._lights(lights7)
+        cam13 = np.ascontiguousarray(cam.as_array13(), dtype=np.float32)
+        amb = np.ascontiguousarray(ambient, dtype=np.float32)
+        rc = _lib.lib().snail_materials_transparent_dev(self._h, _lib.ptr(cam13), resx, resy, _lib.ptr(lights) if len(lights) else None, len(lights), _lib.ptr(amb),
+                                                        int(flags), _lib.ptr(out), int(out.stride(0)), int(max_depth), _lib.ptr(truncated), _lib.ptr(stats), _stream_ptr(stream))
+        _lib.check(rc, "snail_materials_transparent_dev")
+        return out, truncated
+
+    def render_transparent_packets(self, cam, resx: int, resy: int, packet_xy, lights7=None, ambient=(0.1, 0.1, 0.1), out=None, stats=None, stream=None,
+                                   flags: int = 0, max_depth: int = 8, truncated=None):
+        """render_transparent for an explicit packet list -> (packet-major [n, 256, 3] uint8 (B,G,R), truncated).
+        snail_materials_transparent_packets_dev."""
+        torch = _torch()
+        n = int(packet_xy.shape[0])
+        if out is None:
+            out = torch.empty((n, 256, 3), dtype=torch.uint8, device=self.scene._dev())
+        truncated = self._truncated(truncated)
+        lights = self._lights(lights7)
+        cam13 = np.ascontiguousarray(cam.as_array13(), dtype=np.float32)
+        amb = np.ascontiguousarray(ambient, dtype=np.float32)
+        rc = _lib.lib().snail_materials_transparent_packets_dev(self._h, _lib.ptr(cam13), resx, resy, _lib.ptr(packet_xy), n, _lib.ptr(lights) if len(lights) else None,
+                                                                len(lights), _lib.ptr(amb), int(flags), _lib.ptr(out), int(max_depth), _lib.ptr(truncated), _lib.ptr(stats),
+                                                                _stream_ptr(stream))
+        _lib.check(rc, "snail_materials_transparent_packets_dev")
+        return out, truncated
+
+    def render_transparent_image_host(self, cam, resx: int, resy: int, lights7=None, ambient=(0.1, 0.1, 0.1), flags: int = 0, pitch: int | None = None, fill: int = 0,
+                                      max_depth: int = 8, truncated=None):
+        """snail_materials_transparent_image: the frame in host memory -> (uint8 [resy, pitch], stats uint64 [4], truncated: uint64 [1], the
+        caller's array (+=) or a new one)"""
+        pitch = resx * 3 if pitch is None else int(pitch)
+        img = np.full((resy, pitch), fill, dtype=np.uint8)
+        stats = np.zeros(4, dtype=np.uint64)
+        truncated = np.zeros(1, dtype=np.uint64) if truncated is None else truncated
+        lights = self._lights(lights7)
+        cam13 = np.ascontiguousarray(cam.as_array13(), dtype=np.float32)
+        amb = np.ascontiguousarray(ambient, dtype=np.float32)
+        rc = _lib.lib().snail_materials_transparent_image(self._h, _lib.ptr(cam13), resx, resy, _lib.ptr(lights) if len(lights) else None, len(lights), _lib.ptr(amb),
+                                                          int(flags), _lib.ptr(img), pitch, int(max_depth), _lib.ptr(truncated), _lib.ptr(stats))
+        _lib.check(rc, "snail_materials_transparent_image")
+        return img, stats, truncated
 
     def render(self, cam, resx: int, resy: int, lights7=None, ambient=(0.1, 0.1, 0.1), out=None, stats=None, stream=None, flags: int = 0, reflections: bool = False):
         """The lit frame, [resy, resx, 3] uint8 (B,G,R) (or `out`: a uint8 device tensor [resy, pitch] / [resy, w, 3] whose rows may be wider).

@@ -29,8 +29,13 @@ snail_materials_bounce_dev at the same resolution in the same run.  The tile cal
 back, and once more call by call with a wait after each, which is the like-for-like figure.  No threshold: a measurement.  --out APPENDS in
 this mode, with --commit as the label of what was measured.
 
+--transparency N: frames with the transparency continuation (include/snail_materials_transparency.h), at most N levels deep, of the tests'
+`panes` case (tests/materials_transparency_cases.py: five panes and a wall, 12 triangles) at its own 96x64 and at 1920x1080 --
+snail_materials_transparent_dev -- beside snail_render_materials_dev on the same set rebuilt with opaque stand-ins, in the same run, both by
+device events around windows enqueued back to back.  No rate is promised: the rows are the record.  --out APPENDS, --commit labels.
+
     python tools/materials_time.py [--res 1920x1080] [--frames 400] [--reps 7] [--parent-lib PATH] [--out profiles/materials.txt] [--trace N] [--reflections]
-                                   [--tiles [--aa] [--commit LABEL]]"""
+                                   [--tiles [--aa] [--commit LABEL]] [--transparency N]"""
 import argparse
 import ctypes as C
 import os
@@ -81,12 +86,15 @@ def main():
     ap.add_argument("--tiles", action="store_true")
     ap.add_argument("--aa", action="store_true")
     ap.add_argument("--commit", default="unlabelled")
+    ap.add_argument("--transparency", type=int, default=0, metavar="N")
     a = ap.parse_args()
     resx, resy = (int(v) for v in a.res.split("x"))
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("materials_time.py measures on the GPU; there is none here")
     from tests import materials_cases as K
+    if a.transparency:
+        return transparency(a)
 
     tv = scenes.atrium(detail=a.detail)
     hb = HostBVH.build(tv)
@@ -308,6 +316,57 @@ def tiles(a, sc, cam, resx, resy, lights, tex_set, n):
             fh.write(text + "\n")
     if not same:
         raise SystemExit("the tile list and the frame differ")
+
+
+def transparency(a):
+    """--transparency N: the panes case with the continuation beside its opaque stand-in"""
+    import torch
+    from tests import materials_transparency_cases as TK
+    c = TK.panes()
+    sc = Scene(HostBVH.build(c["tv"]), 0)
+
+    def material(d, opaque):
+        if d[0] == "transp":
+            return P.Material.textured(d[1], d[3]) if opaque else P.Material.transparent(d[1], d[2], d[3])
+        if d[0] == "uber":
+            return P.Material.uber(d[1], d[2], 0.0 if opaque and 0.0 < d[3] < 1.0 else d[3])
+        return P.Material.simple(d[1], d[2]) if d[0] == "simple" else P.Material.textured(d[1], d[2])
+    tex = [P.Texture(t) for t in c["textures"]]
+    sets = {op: P.MaterialSet(sc, c["uv"], c["nrm"], c["mat_index"], c["flat"], c["material_map"], [material(d, op) for d in c["descs"]], tex, transparent=True)
+            for op in (False, True)}
+    assert sets[False].can_select_transparent and not sets[True].can_select_transparent
+    lines = ["", "transparency continuation [%s], the tests' panes case (%d triangles), its two lights, IEEE, max_depth %d; %d rounds of %d frames per variant, alternating; ms per frame: median (min .. max)" %
+             (a.commit, len(c["tv"]), a.transparency, a.reps, a.frames), "device: %s" % torch.cuda.get_device_name(0),
+             "transparent = snail_materials_transparent_dev; opaque = snail_render_materials_dev on the same set rebuilt with opaque stand-ins (TEX for TRANSPARENT, UBER 0 for UBER 0.5)"]
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    for resx, resy in ((96, 64), (1920, 1080)):
+        out = torch.zeros((resy, resx, 3), dtype=torch.uint8, device="cuda:0")
+        trunc = torch.zeros(1, dtype=torch.int64, device="cuda:0")
+        variants = {"transparent": lambda: sets[False].render_transparent(c["cam"], resx, resy, c["lights"], out=out, max_depth=a.transparency, truncated=trunc),
+                    "opaque": lambda: sets[True].render(c["cam"], resx, resy, c["lights"], out=out)}
+        for fn in variants.values():
+            fn(); fn()
+        torch.cuda.synchronize()
+        trunc.zero_()
+        variants["transparent"]()
+        torch.cuda.synchronize()
+        cut = int(trunc.item())
+        times = {k: [] for k in variants}
+        for _ in range(a.reps):
+            for k, fn in variants.items():
+                e0.record()
+                for _ in range(a.frames):
+                    fn()
+                e1.record()
+                e1.synchronize()
+                times[k].append(e0.elapsed_time(e1) / a.frames)
+        for k, v in times.items():
+            lines.append("  %4dx%-4d %-12s %8.3f  (%.3f .. %.3f)%s" % (resx, resy, k, statistics.median(v), min(v), max(v), "   truncated lanes per frame: %d" % cut if k == "transparent" else ""))
+    text = "\n".join(lines)
+    print(text)
+    if a.out:
+        with open(a.out, "a") as fh:
+            fh.write(text + "\n")
 
 
 if __name__ == "__main__":
