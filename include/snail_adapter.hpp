@@ -60,6 +60,7 @@
 #include "snail_heatmap.h"
 #include "snail_materials_tiles.h"
 #include "snail_materials_transparency.h"
+#include "snail_materials_tree.h"
 
 #ifndef SNAIL_CHECK
 #define SNAIL_CHECK(expr)                                                                              \
@@ -532,6 +533,18 @@ enum { kDeviceMaterials = 1 };
 #else
 enum { kDeviceMaterials = 0 };
 #endif
+// The transparency continuation on the device as well (include/snail_materials_tree.h): define SNAIL_ADAPTER_DEVICE_TRANSPARENCY together with
+// SNAIL_ADAPTER_DEVICE_MATERIALS (alone it is without effect) and the Render(...) overloads send a set that CAN select a transparent lane to
+// snail_materials_tree_render_tiles / snail_materials_tree_render_frame with maxDepth 8, under the same conditions otherwise: one device, no
+// gVals[8] on an image, gVals[5] off or under gVals[1].  The reference has no depth limit, so a frame whose truncated-lane counter moved is not
+// the reference's: it is rendered AGAIN by the reference's renderer (SNAIL_HOST_RENDER; the TreeStats returned are that run's), or, with
+// SNAIL_ADAPTER_NO_HOST_RENDERER, the call aborts with a message naming the depth.  Opt-in: without the macro the routing is what it was.
+#if defined(SNAIL_ADAPTER_DEVICE_TRANSPARENCY) && defined(SNAIL_ADAPTER_DEVICE_MATERIALS)
+enum { kDeviceTransparency = 1 };
+#else
+enum { kDeviceTransparency = 0 };
+#endif
+enum { kTreeMaxDepth = 8 };   // SNAIL_MAT_TRANSP_MAX_DEPTH
 inline const char *UnsupportedSwitch(const int *gv, bool hasShadingData, bool tileList, bool deviceHeatmap, bool deviceMaterials) {
 	if(gv[6] && hasShadingData) {
 		if(deviceMaterials && (!gv[5] || gv[1]) && (tileList || !gv[8])) return nullptr;
@@ -697,6 +710,33 @@ inline StatsT RenderMaterialImage(const SceneT &scene, const CameraT &camera, Im
 											 detail::renderFlags(mode), (unsigned char *)image.DataPointer(), (int)image.Pitch(), st));
 	return detail::toStats<StatsT>(st);
 }
+// ... for a set that can select a transparent lane (SNAIL_ADAPTER_DEVICE_TRANSPARENCY): snail_materials_tree_render_tiles /
+// snail_materials_tree_render_frame (include/snail_materials_tree.h) with maxDepth kTreeMaxDepth; *truncated += the lanes the cut left out
+template <class StatsT, class SceneT, class CameraT>
+inline StatsT RenderMaterialTreeTiles(const SceneT &scene, const CameraT &camera, unsigned resx, unsigned resy, unsigned char *data, const std::vector<int> &coords,
+									  const std::vector<int> &offsets, const RenderMode &mode, unsigned rank, uint64_t *truncated) {
+	float c[13];
+	detail::cam13(camera, c);
+	const std::vector<float> l = detail::lights7(scene);
+	std::vector<int64_t> off(offsets.begin(), offsets.end());
+	const float amb[3] = {scene.ambientLight.x, scene.ambientLight.y, scene.ambientLight.z};
+	uint64_t st[4] = {0, 0, 0, 0};
+	SNAIL_CHECK(snail_materials_tree_render_tiles(scene.geometry.Materials(), c, (int)resx, (int)resy, coords.data(), off.data(), (int)(coords.size() / 4), l.data(),
+												  (int)(l.size() / 7), amb, detail::renderFlags(mode), mode.rankTint ? detail::RankTint(rank) : nullptr, data, kTreeMaxDepth, truncated,
+												  st));
+	return detail::toStats<StatsT>(st);
+}
+template <class StatsT, class SceneT, class CameraT, class ImageT>
+inline StatsT RenderMaterialTreeImage(const SceneT &scene, const CameraT &camera, ImageT &image, const RenderMode &mode, uint64_t *truncated) {
+	float c[13];
+	detail::cam13(camera, c);
+	const std::vector<float> l = detail::lights7(scene);
+	const float amb[3] = {scene.ambientLight.x, scene.ambientLight.y, scene.ambientLight.z};
+	uint64_t st[4] = {0, 0, 0, 0};
+	SNAIL_CHECK(snail_materials_tree_render_frame(scene.geometry.Materials(), c, (int)image.Width(), (int)image.Height(), l.data(), (int)(l.size() / 7), amb,
+												  detail::renderFlags(mode), (unsigned char *)image.DataPointer(), (int)image.Pitch(), kTreeMaxDepth, truncated, st));
+	return detail::toStats<StatsT>(st);
+}
 #endif
 
 } // namespace snail
@@ -727,8 +767,9 @@ inline StatsT RenderMaterialImage(const SceneT &scene, const CameraT &camera, Im
 template <class RefBVH>
 inline TreeStats Render(const Scene<snail::HipBVH<RefBVH>> &scene, const Camera &camera, uint resx, uint resy, unsigned char *data, const vector<int> &coords,
 						const vector<int> &offsets, const Options options, uint rank, uint threads) {
-	const bool deviceMaterials = snail::kDeviceMaterials && scene.geometry.Materials() != nullptr && scene.geometry.DeviceCount() <= 1 &&
-								 snail_materials_can_select_transparent(scene.geometry.Materials()) == 0;
+	const int canSelect = snail::kDeviceMaterials && scene.geometry.Materials() != nullptr && scene.geometry.DeviceCount() <= 1 ?
+							  snail_materials_can_select_transparent(scene.geometry.Materials()) : -1;
+	const bool deviceMaterials = canSelect == 0 || (snail::kDeviceTransparency && canSelect == 1);
 	if(const char *why = snail::UnsupportedSwitch(gVals, scene.geometry.HasShadingData(), true, snail::kDeviceHeatmap && scene.geometry.DeviceCount() <= 1, deviceMaterials))
 		SNAIL_HOST_RENDER(why, gVals[9] ? 2 : 1, resx, resy, Render<snail::HipBVH<RefBVH>>(scene, camera, resx, resy, data, coords, offsets, options, rank, threads));
 	(void)rank; (void)threads; // (a tint only under full shading; the host thread pool has no device counterpart)
@@ -742,6 +783,13 @@ inline TreeStats Render(const Scene<snail::HipBVH<RefBVH>> &scene, const Camera 
 	if(gVals[6] && scene.geometry.HasShadingData()) {   // (UnsupportedSwitch let it through: a set is attached, one device, gVals[5] off or under gVals[1])
 		mode.statsHeat = false;
 		mode.rankTint = gVals[8] != 0;
+		if(canSelect == 1) {   // (SNAIL_ADAPTER_DEVICE_TRANSPARENCY) a frame the depth cut touched is not the reference's: the reference's renderer does it again
+			uint64_t truncated = 0;
+			const TreeStats ts = snail::RenderMaterialTreeTiles<TreeStats>(scene, camera, resx, resy, data, coords, offsets, mode, rank, &truncated);
+			if(!truncated) return ts;
+			SNAIL_HOST_RENDER("a transparency continuation deeper than maxDepth 8 (include/snail_materials_tree.h)", gVals[9] ? 2 : 1, resx, resy,
+							  Render<snail::HipBVH<RefBVH>>(scene, camera, resx, resy, data, coords, offsets, options, rank, threads));
+		}
 		return snail::RenderMaterialTiles<TreeStats>(scene, camera, resx, resy, data, coords, offsets, mode, rank);
 	}
 #endif
@@ -749,8 +797,9 @@ inline TreeStats Render(const Scene<snail::HipBVH<RefBVH>> &scene, const Camera 
 }
 template <class RefBVH>
 inline TreeStats Render(const Scene<snail::HipBVH<RefBVH>> &scene, const Camera &camera, MipmapTexture &image, const Options options, uint threads) {
-	const bool deviceMaterials = snail::kDeviceMaterials && scene.geometry.Materials() != nullptr && scene.geometry.DeviceCount() <= 1 &&
-								 snail_materials_can_select_transparent(scene.geometry.Materials()) == 0;
+	const int canSelect = snail::kDeviceMaterials && scene.geometry.Materials() != nullptr && scene.geometry.DeviceCount() <= 1 ?
+							  snail_materials_can_select_transparent(scene.geometry.Materials()) : -1;
+	const bool deviceMaterials = canSelect == 0 || (snail::kDeviceTransparency && canSelect == 1);
 	if(const char *why = snail::UnsupportedSwitch(gVals, scene.geometry.HasShadingData(), false, snail::kDeviceHeatmap != 0, deviceMaterials))
 		SNAIL_HOST_RENDER(why, gVals[9] ? 2 : 1, image.Width(), image.Height(), Render<snail::HipBVH<RefBVH>>(scene, camera, image, options, threads));
 	(void)threads;
@@ -763,6 +812,13 @@ inline TreeStats Render(const Scene<snail::HipBVH<RefBVH>> &scene, const Camera 
 #ifdef SNAIL_ADAPTER_DEVICE_MATERIALS
 	if(gVals[6] && scene.geometry.HasShadingData()) {   // (UnsupportedSwitch let it through: a set is attached, one device, no gVals[8], gVals[5] off or under gVals[1])
 		mode.statsHeat = false;
+		if(canSelect == 1) {   // (SNAIL_ADAPTER_DEVICE_TRANSPARENCY) as above
+			uint64_t truncated = 0;
+			const TreeStats ts = snail::RenderMaterialTreeImage<TreeStats>(scene, camera, image, mode, &truncated);
+			if(!truncated) return ts;
+			SNAIL_HOST_RENDER("a transparency continuation deeper than maxDepth 8 (include/snail_materials_tree.h)", gVals[9] ? 2 : 1, image.Width(), image.Height(),
+							  Render<snail::HipBVH<RefBVH>>(scene, camera, image, options, threads));
+		}
 		return snail::RenderMaterialImage<TreeStats>(scene, camera, image, mode);
 	}
 #endif

@@ -546,6 +546,8 @@ __global__ __launch_bounds__(64) void k_mat_light_rays(MatArgs A) {
 // specular untouched (src/scene_trace.cpp:462-465).
 // FLOATS (primary): outColor stays FLOATS r, g, b per ray in A.s.colPackets [packet][256][3] -- the layout k_inst_store (instances_shade.inc) reads --
 // for the tile renderer's reduction, tint and stores (include/snail_materials_tiles.h); the store rule below is not repeated for them.
+// TWINS: the BLEND expression and its rounding are repeated by k_mat_blend_refl / _rays (materials_tree.inc), which blends in place in the sample
+// buffer so that the transparency blend can follow it; a change to the factor or the order of the three operations belongs there too.
 template <int SRC, bool BLEND, bool FLOATS = false>
 __device__ __forceinline__ void matFinal(const MatArgs &A) {
 	const int lane = threadIdx.x & 63;
@@ -656,6 +658,8 @@ __global__ __launch_bounds__(64) void k_mat_colour_blend(MatArgs A) { matFinal<S
 // TWINS: the output -- layout, zeros for masked lanes, distance inf / -inf (:112-115), object 0, one mask byte per quad, the nested call's
 // TracingRays(CountMaskBits(mask)) (:116-117) and, in the table arithmetic, SafeInv one component at a time -- is that of k_final<SRC_PRIMARY,
 // DST_MIRROR> (snail_dev.inc); only the normal's source differs.
+// TWINS: k_mat_mirror_rays (materials_tree.inc) is this body with a level's generic packets (matLoadSamples<SRC_MIRROR>) as its source, under that
+// level's order list; a change to Reflect, the offset, the layout or the booking belongs there too.
 __global__ __launch_bounds__(64) void k_mat_mirror(MatArgs A) {
 	const int lane = threadIdx.x & 63;
 	const int li = (int)blockIdx.x;

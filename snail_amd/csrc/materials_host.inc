@@ -72,6 +72,8 @@ struct SnailMaterials {
 	// which is taken before the scene's mu
 	std::mutex renderMu;
 	InstTileJob *tileJob = nullptr;
+	// snail_materials_set_level_budget (materials_tree_host.inc): the bytes the levels of one group of intermediates may take; 0 = SNAIL_MAT_LEVEL_BUDGET
+	uint64_t levelBudget = 0;
 };
 
 namespace {

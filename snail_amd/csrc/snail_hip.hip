@@ -80,6 +80,7 @@ void snail_set_error(const char *fmt, ...) {
 #include "instances_shade.inc"
 #include "materials.inc"
 #include "materials_transparency.inc"
+#include "materials_tree.inc"
 #undef SNAIL_DEV_NS
 #undef SNAIL_ARITH_SSE
 #define SNAIL_DEV_NS dev_sse
@@ -89,6 +90,7 @@ void snail_set_error(const char *fmt, ...) {
 #include "instances_shade.inc"
 #include "materials.inc"
 #include "materials_transparency.inc"
+#include "materials_tree.inc"
 #undef SNAIL_DEV_NS
 #undef SNAIL_ARITH_SSE
 #include "heatmap.inc"           // the heat-map store stage: plain fp32, once for both arithmetics (its C-ABI: heatmap_host.inc)
@@ -1802,3 +1804,4 @@ int snail_account_primary(SnailScene *s, const float cam[13], int resx, int resy
 #include "materials_host.inc"
 #include "materials_tiles_host.inc"
 #include "materials_transparency_host.inc"
+#include "materials_tree_host.inc"

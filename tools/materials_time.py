@@ -34,8 +34,16 @@ this mode, with --commit as the label of what was measured.
 snail_materials_transparent_dev -- beside snail_render_materials_dev on the same set rebuilt with opaque stand-ins, in the same run, both by
 device events around windows enqueued back to back.  No rate is promised: the rows are the record.  --out APPENDS, --commit labels.
 
+--tree [--reflections] [--aa] [--tiles]: the continuation TOGETHER with the bounce, 4x AA and tile lists (include/snail_materials_tree.h) on the
+tests' `room` case (tests/materials_tree_cases.py: `panes` and a wall behind the camera, 14 triangles) at --res, max_depth 8 --
+snail_materials_tree_render_frame (with --tiles: snail_materials_tree_render_tiles over the 16x64 tile map) with the flags asked for -- beside,
+in the same run and the same build, snail_materials_transparent_image (flags = 0) on the same set and snail_materials_render_tiles with the same
+flags on the set rebuilt with opaque stand-ins.  All three are host calls that return after their device-to-host copy: host clock, call by
+call, after a warm-up, the variants alternating, --reps rounds of --frames calls, median (min .. max).  No threshold: a measurement.  --out APPENDS.
+
     python tools/materials_time.py [--res 1920x1080] [--frames 400] [--reps 7] [--parent-lib PATH] [--out profiles/materials.txt] [--trace N] [--reflections]
-                                   [--tiles [--aa] [--commit LABEL]] [--transparency N]"""
+                                   [--tiles [--aa] [--commit LABEL]] [--transparency N]
+                                   [--tree [--reflections] [--aa] [--tiles]]"""
 import argparse
 import ctypes as C
 import os
@@ -87,6 +95,7 @@ def main():
     ap.add_argument("--aa", action="store_true")
     ap.add_argument("--commit", default="unlabelled")
     ap.add_argument("--transparency", type=int, default=0, metavar="N")
+    ap.add_argument("--tree", action="store_true")
     a = ap.parse_args()
     resx, resy = (int(v) for v in a.res.split("x"))
     import torch
@@ -95,6 +104,8 @@ def main():
     from tests import materials_cases as K
     if a.transparency:
         return transparency(a)
+    if a.tree:
+        return tree(a, resx, resy)
 
     tv = scenes.atrium(detail=a.detail)
     hb = HostBVH.build(tv)
@@ -362,6 +373,64 @@ def transparency(a):
                 times[k].append(e0.elapsed_time(e1) / a.frames)
         for k, v in times.items():
             lines.append("  %4dx%-4d %-12s %8.3f  (%.3f .. %.3f)%s" % (resx, resy, k, statistics.median(v), min(v), max(v), "   truncated lanes per frame: %d" % cut if k == "transparent" else ""))
+    text = "\n".join(lines)
+    print(text)
+    if a.out:
+        with open(a.out, "a") as fh:
+            fh.write(text + "\n")
+
+
+def tree(a, resx, resy):
+    """--tree: the room case through the tree functions beside the continuation alone and the opaque tile renderer"""
+    import time
+
+    import torch
+    from snail_amd.render import divide_image
+    from tests import materials_tree_cases as K
+    c = K.room()
+    sc = Scene(HostBVH.build(c["tv"]), 0)
+
+    def material(d, opaque):
+        if d[0] == "transp":
+            return P.Material.textured(d[1], d[3]) if opaque else P.Material.transparent(d[1], d[2], d[3])
+        if d[0] == "uber":
+            return P.Material.uber(d[1], d[2], 0.0 if opaque and 0.0 < d[3] < 1.0 else d[3])
+        return P.Material.simple(d[1], d[2]) if d[0] == "simple" else P.Material.textured(d[1], d[2])
+    tex = [P.Texture(t) for t in c["textures"]]
+    sets = {op: P.MaterialSet(sc, c["uv"], c["nrm"], c["mat_index"], c["flat"], c["material_map"], [material(d, op) for d in c["descs"]], tex, transparent=True)
+            for op in (False, True)}
+    flags = (P.RENDER_REFLECTIONS if a.reflections else 0) | (P.RENDER_AA4 if a.aa else 0)
+    tl = divide_image(resx, resy)
+    data = np.zeros(int((3 * tl[:, 2].astype(np.int64) * tl[:, 3]).sum()), dtype=np.uint8)
+    trunc = np.zeros(1, dtype=np.uint64)
+    variants = {
+        "tree_tiles" if a.tiles else "tree_frame": (lambda: sets[False].render_tree_tiles_host(c["cam"], resx, resy, tl, lights7=c["lights"], flags=flags, data=data, truncated=trunc))
+        if a.tiles else (lambda: sets[False].render_tree_frame_host(c["cam"], resx, resy, c["lights"], flags=flags, truncated=trunc)),
+        "transparent_image": lambda: sets[False].render_transparent_image_host(c["cam"], resx, resy, c["lights"], max_depth=8),
+        "opaque_tiles": lambda: sets[True].render_tiles_host(c["cam"], resx, resy, tl, lights7=c["lights"], flags=flags, data=data),
+    }
+    for fn in variants.values():        # warm-up: code objects, the sets' groups at their largest, the cached tile jobs
+        fn(); fn()
+    torch.cuda.synchronize()
+    wall = {k: [] for k in variants}
+    for _ in range(a.reps):
+        for k, fn in variants.items():
+            t0 = time.perf_counter()
+            for _ in range(a.frames):
+                fn()
+            wall[k].append((time.perf_counter() - t0) * 1e3 / a.frames)
+    pw, ph = (resx + 15) // 16, (resy + 15) // 16
+    one = P.MaterialSet.level_bytes(len(c["lights"]), flags, 8)
+    per = max(1, min((1 << 30) // one, pw * ph))
+    lines = ["", "the tree [%s]: room case (%d triangles), its two lights, IEEE, %dx%d (%d packets), flags %s%s, max_depth 8; %d rounds of %d calls per variant, alternating, "
+             "after 2 warm-up calls each; host clock, ms per call: median (min .. max)" % (a.commit, len(c["tv"]), resx, resy, pw * ph, "REFLECTIONS " if a.reflections else "",
+                                                                                            "AA4" if a.aa else "", a.reps, a.frames), "device: %s" % torch.cuda.get_device_name(0),
+             "tree_* = snail_materials_tree_render_%s with those flags; transparent_image = snail_materials_transparent_image (flags = 0) on the same set; opaque_tiles = "
+             "snail_materials_render_tiles with those flags on the set rebuilt with opaque stand-ins" % ("tiles" if a.tiles else "frame"),
+             "levels of one output packet: %d bytes; default budget: %d output packets per slice, %d slice(s); truncated lanes per tree call: %d" % (
+                 one, per, -(-(pw * ph) // per), int(trunc[0]) // (a.reps * a.frames + 2))]
+    for k, v in wall.items():
+        lines.append("  %-18s %9.3f  (%.3f .. %.3f)" % (k, statistics.median(v), min(v), max(v)))
     text = "\n".join(lines)
     print(text)
     if a.out:
