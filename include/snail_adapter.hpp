@@ -61,6 +61,7 @@
 #include "snail_materials_tiles.h"
 #include "snail_materials_transparency.h"
 #include "snail_materials_tree.h"
+#include "snail_materials_dynamic.h"
 
 #ifndef SNAIL_CHECK
 #define SNAIL_CHECK(expr)                                                                              \
@@ -135,6 +136,14 @@ public:
 	}
 	bool Rebuild(const float *d_verts9, int nTris, int32_t *d_perm = nullptr, int32_t *d_info = nullptr, void *stream = nullptr) {
 		return scene && snail_scene_rebuild_fast_dev(scene, d_verts9, nTris, d_perm, d_info, stream) == 0;
+	}
+	// Rebuild() for a tree that is shaded with gVals[6]: with a set attached (AttachMaterials; one of snail_materials_create_dev over Handle(),
+	// include/snail_materials_dynamic.h) the set's ShTriangle records follow the tree on the same stream -- the builder permutes shTris
+	// together with tris, src/bvh/tree.cpp:122-125 -- from d_nrm9, or from face normals of d_verts9 when it is null; d_info then takes 6 words.
+	// Without a set it is Rebuild() (d_nrm9 unused, 4 words).
+	bool RebuildShaded(const float *d_verts9, const float *d_nrm9, int nTris, int32_t *d_perm = nullptr, int32_t *d_info = nullptr, void *stream = nullptr) {
+		if(!materials) return Rebuild(d_verts9, nTris, d_perm, d_info, stream);
+		return scene && snail_materials_rebuild_dev(materials, d_verts9, d_nrm9, d_perm, d_info, stream) == 0;   // (the set knows its scene's nTris)
 	}
 	void Upload(const RefBVH &bvh, const std::vector<int> &devices) {
 		if(devices.empty()) { std::fprintf(stderr, "FATAL: HipBVH::Upload: no device\n"); std::abort(); }

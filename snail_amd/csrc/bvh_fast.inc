@@ -126,6 +126,7 @@ struct SnailSceneFast {
 	int depthLimit = SNAIL_MAX_DEPTH;   // what the stack form chosen at creation takes (useDeep): 62, or SNAIL_MAX_DEPTH for a handle created deeper
 	hipEvent_t ready = nullptr;
 	bool hasReady = false;
+	unsigned long long rebuilds = 0;   // builds enqueued on the handle so far (under mu): what a set of snail_materials_create_dev compares its own count with
 	struct Use { hipStream_t stream; hipEvent_t ev; };
 	std::vector<Use> uses;
 };
@@ -193,7 +194,26 @@ int fastEnqueue(SnailScene *s, const float *dVerts, int32_t *dPerm, int32_t *dIn
 	HIP_TRY(hipEventRecord(f->ready, st));
 	f->hasReady = true;
 	f->curOnDevice = true;
+	f->rebuilds++;
 	return 0;
+}
+
+// What comes before anything that rewrites what the handle's launches read (mu held): `st` waits for every launch enqueued since the previous
+// rebuild (they read what the commit writes) and for that rebuild itself (one scratch area)
+int fastWaitUsers(SnailScene *s, hipStream_t st) {
+	SnailSceneFast *f = s->fast;
+	for(auto &u : f->uses) HIP_TRY(hipStreamWaitEvent(st, u.ev, 0));
+	if(f->hasReady) HIP_TRY(hipStreamWaitEvent(st, f->ready, 0));
+	return 0;
+}
+
+// snail_scene_rebuild_fast_dev after its arguments were judged (mu held); snail_materials_rebuild_dev's first half
+int fastRebuildLocked(SnailScene *s, const float *dVerts, int32_t *dPerm, int32_t *dInfo, hipStream_t st) {
+	if(int rc = fastWaitUsers(s, st)) return rc;
+	// the origin-relative copies of the node slots describe the old tree: a later launch fills its own again (relFor waits for an array's
+	// previous fill and its last readers before it overwrites it)
+	for(auto &e : s->rel) e.valid = false;
+	return fastEnqueue(s, dVerts, dPerm, dInfo, s->fastOK, st);
 }
 
 // {nNodes, depth, sane} of the tree the handle holds, waiting for a rebuild in flight if there is one
@@ -269,14 +289,7 @@ int snail_scene_rebuild_fast_dev(SnailScene *s, const float *d_verts9, int nTris
 	hipStream_t st = (hipStream_t)stream;
 	DeviceGuard guard(s->device);
 	SNAIL_LOCK(s);
-	SnailSceneFast *f = s->fast;
-	// after every launch enqueued since the previous rebuild (they read what the commit writes) and after that rebuild itself (one scratch area)
-	for(auto &u : f->uses) HIP_TRY(hipStreamWaitEvent(st, u.ev, 0));
-	if(f->hasReady) HIP_TRY(hipStreamWaitEvent(st, f->ready, 0));
-	// the origin-relative copies of the node slots describe the old tree: a later launch fills its own again (relFor waits for an array's
-	// previous fill and its last readers before it overwrites it)
-	for(auto &e : s->rel) e.valid = false;
-	return fastEnqueue(s, d_verts9, d_perm, d_info, s->fastOK, st);
+	return fastRebuildLocked(s, d_verts9, d_perm, d_info, st);
 }
 
 } // extern "C"

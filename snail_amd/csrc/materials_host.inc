@@ -6,8 +6,11 @@
 #include "../../include/snail_materials_bounce.h"
 #include "../../include/snail_materials_tiles.h"
 
+struct SnailMaterialsDyn;   // materials_dynamic_host.inc: what a set of snail_materials_create_dev carries besides the set
+namespace { int dynCheckFresh(const SnailMaterials *, const char *fn); void dynFree(SnailMaterialsDyn *); }
 struct SnailMaterials {
 	SnailScene *scene = nullptr;
+	SnailMaterialsDyn *dyn = nullptr;   // snail_materials_create_dev: the records are packed on the device and follow the scene's rebuilds
 	int device = 0;
 	int nTris = 0, nMap = 0, nMats = 0, nTex = 0;
 	bool canSelectTransparent = false;   // holds SNAIL_MAT_TRANSPARENT or UBER with 0 < dissolve < 1 (snail_materials_create_transparent alone makes such a set)
@@ -93,7 +96,8 @@ bool matTexShapeOK(int w, int h) { return matPow2(w) && matPow2(h) && w <= 8192 
 // any set: the entry points of include/snail_materials_transparency.h
 int checkMaterialsAny(const SnailMaterials *m, const char *fn) {
 	if(!m || !m->scene || !m->dBase) { snail_set_error("%s: invalid material set handle", fn); return 1; }
-	return checkScene(m->scene, fn);
+	if(int rc = checkScene(m->scene, fn)) return rc;
+	return m->dyn ? dynCheckFresh(m, fn) : 0;   // (include/snail_materials_dynamic.h, "staleness"; the scene's mu is not held here)
 }
 // the entry points of snail_materials.h, _bounce.h and _tiles.h: their kernels know neither the transparent kind nor the selector
 int checkMaterials(const SnailMaterials *m, const char *fn) {
@@ -373,46 +377,55 @@ int snail_texture_build(const uint8_t *level0, int w, int h, uint8_t *out, int64
 
 } // extern "C"
 
-// the two creators: snail_materials_create (transp = false: its refusals) and snail_materials_create_transparent (include/snail_materials_transparency.h)
-static SnailMaterials *matCreate(const char *fn, bool transp, SnailScene *scene, const void *shtris64, int nTris, const int32_t *matMap, int nMap, const SnailMaterial *mats,
-								 int nMats, const int32_t *opacityTexture, const SnailTexture *textures, int nTex) {
+// the creators: snail_materials_create (transp = false: its refusals), snail_materials_create_transparent (include/snail_materials_transparency.h)
+// and snail_materials_create_dev (include/snail_materials_dynamic.h).  matCheckHost: what they judge on the caller's HOST data, before a device
+// is touched (dynamic: the records are made on the device, there is no shtris64); matUpload: the device copy.
+static bool matCheckHost(const char *fn, bool transp, bool dynamic, const void *shtris64, int nTris, const int32_t *matMap, int nMap, const SnailMaterial *mats, int nMats,
+						 const int32_t *opacityTexture, const SnailTexture *textures, int nTex, bool *canSelectOut) {
 	bool canSelect = false;
-	if(nTris <= 0 || nMap <= 0 || nMats < 0 || nTex < 0 || !shtris64 || !matMap || (nMats && !mats) || (nTex && !textures)) {
+	if(nTris <= 0 || nMap <= 0 || nMats < 0 || nTex < 0 || (!dynamic && !shtris64) || !matMap || (nMats && !mats) || (nTex && !textures)) {
 		snail_set_error("%s: bad counts or null arrays (at least one triangle and one map entry)", fn);
-		return nullptr;
+		return false;
 	}
 	for(int k = 0; k < nTex; k++) {
 		if(!matTexShapeOK(textures[k].width, textures[k].height)) {
 			snail_set_error("%s: texture %d is %d x %d: width and height must be powers of two of at most 8192", fn, k, textures[k].width, textures[k].height);
-			return nullptr;
+			return false;
 		}
-		if(!textures[k].levels) { snail_set_error("%s: texture %d has no texels", fn, k); return nullptr; }
+		if(!textures[k].levels) { snail_set_error("%s: texture %d has no texels", fn, k); return false; }
 	}
 	for(int k = 0; k < nMats; k++) {
 		const SnailMaterial &M = mats[k];
-		if(M.kind == SNAIL_MAT_TRANSPARENT && !transp) { snail_set_error("%s: material %d is of the transparent kind: transparency under full shading stays with the host renderer", fn, k); return nullptr; }
-		if(M.kind != SNAIL_MAT_SIMPLE && M.kind != SNAIL_MAT_TEX && M.kind != SNAIL_MAT_UBER && M.kind != SNAIL_MAT_TRANSPARENT) { snail_set_error("%s: material %d: unknown kind %d", fn, k, M.kind); return nullptr; }
+		if(M.kind == SNAIL_MAT_TRANSPARENT && !transp) { snail_set_error("%s: material %d is of the transparent kind: transparency under full shading stays with the host renderer", fn, k); return false; }
+		if(M.kind != SNAIL_MAT_SIMPLE && M.kind != SNAIL_MAT_TEX && M.kind != SNAIL_MAT_UBER && M.kind != SNAIL_MAT_TRANSPARENT) { snail_set_error("%s: material %d: unknown kind %d", fn, k, M.kind); return false; }
 		if(M.kind == SNAIL_MAT_UBER && !transp && !(M.dissolve <= 0.0f || M.dissolve >= 1.0f)) {
 			snail_set_error("%s: material %d: UBER with dissolve %g could select a transparent lane (accepted: dissolve <= 0 or >= 1)", fn, k, (double)M.dissolve);
-			return nullptr;
+			return false;
 		}
-		if(M.kind == SNAIL_MAT_UBER && std::isnan(M.dissolve)) { snail_set_error("%s: material %d: UBER with a NaN dissolve", fn, k); return nullptr; }   // (transp: the other creator has refused it above)
+		if(M.kind == SNAIL_MAT_UBER && std::isnan(M.dissolve)) { snail_set_error("%s: material %d: UBER with a NaN dissolve", fn, k); return false; }   // (transp: the other creator has refused it above)
 		if(M.kind == SNAIL_MAT_TRANSPARENT) {
-			if(M.texture < 0 || M.texture >= nTex) { snail_set_error("%s: material %d: texture index %d outside 0..%d", fn, k, M.texture, nTex - 1); return nullptr; }
-			if(!opacityTexture) { snail_set_error("%s: material %d is of the transparent kind and the opacity texture array is null", fn, k); return nullptr; }
-			if(opacityTexture[k] < 0 || opacityTexture[k] >= nTex) { snail_set_error("%s: material %d: opacity texture index %d outside 0..%d", fn, k, opacityTexture[k], nTex - 1); return nullptr; }
+			if(M.texture < 0 || M.texture >= nTex) { snail_set_error("%s: material %d: texture index %d outside 0..%d", fn, k, M.texture, nTex - 1); return false; }
+			if(!opacityTexture) { snail_set_error("%s: material %d is of the transparent kind and the opacity texture array is null", fn, k); return false; }
+			if(opacityTexture[k] < 0 || opacityTexture[k] >= nTex) { snail_set_error("%s: material %d: opacity texture index %d outside 0..%d", fn, k, opacityTexture[k], nTex - 1); return false; }
 			canSelect = true;
 		}
 		if(M.kind == SNAIL_MAT_UBER && M.dissolve > 0.0f && M.dissolve < 1.0f) canSelect = true;
-		if(M.kind == SNAIL_MAT_TEX && (M.texture < 0 || M.texture >= nTex)) { snail_set_error("%s: material %d: texture index %d outside 0..%d", fn, k, M.texture, nTex - 1); return nullptr; }
+		if(M.kind == SNAIL_MAT_TEX && (M.texture < 0 || M.texture >= nTex)) { snail_set_error("%s: material %d: texture index %d outside 0..%d", fn, k, M.texture, nTex - 1); return false; }
 	}
 	for(int k = 0; k < nMap; k++)
-		if(matMap[k] < -1 || matMap[k] >= nMats) { snail_set_error("%s: map entry %d = %d is outside -1..%d", fn, k, matMap[k], nMats - 1); return nullptr; }
-	for(int i = 0; i < nTris; i++) {
+		if(matMap[k] < -1 || matMap[k] >= nMats) { snail_set_error("%s: map entry %d = %d is outside -1..%d", fn, k, matMap[k], nMats - 1); return false; }
+	for(int i = 0; i < nTris && !dynamic; i++) {
 		uint32_t id;
 		memcpy(&id, (const char *)shtris64 + (size_t)i * 64 + 60, 4);
-		if((int)(id & 0x7fffffffu) >= nMap) { snail_set_error("%s: record %d: material index %u outside the map of %d entries", fn, i, id & 0x7fffffffu, nMap); return nullptr; }
+		if((int)(id & 0x7fffffffu) >= nMap) { snail_set_error("%s: record %d: material index %u outside the map of %d entries", fn, i, id & 0x7fffffffu, nMap); return false; }
 	}
+	*canSelectOut = canSelect;
+	return true;
+}
+
+// shtris64 null: the records' room is left zeroed (snail_materials_create_dev packs them on the device)
+static SnailMaterials *matUpload(const char *fn, bool canSelect, SnailScene *scene, const void *shtris64, int nTris, const int32_t *matMap, int nMap, const SnailMaterial *mats,
+								 int nMats, const int32_t *opacityTexture, const SnailTexture *textures, int nTex) {
 	if(checkScene(scene, fn)) return nullptr;
 	if(nTris != scene->nTris) { snail_set_error("%s: %d records for a scene of %d triangles", fn, nTris, scene->nTris); return nullptr; }
 
@@ -445,7 +458,7 @@ static SnailMaterials *matCreate(const char *fn, bool transp, SnailScene *scene,
 	char *base = nullptr;
 	hipError_t e = hipMalloc((void **)&base, total);
 	if(e == hipSuccess) e = hipMemset(base, 0, total);
-	if(e == hipSuccess) e = hipMemcpy(base + oTris, shtris64, (size_t)nTris * 64, hipMemcpyHostToDevice);
+	if(e == hipSuccess && shtris64) e = hipMemcpy(base + oTris, shtris64, (size_t)nTris * 64, hipMemcpyHostToDevice);
 	if(e == hipSuccess) e = hipMemcpy(base + oMap, matMap, (size_t)nMap * 4, hipMemcpyHostToDevice);
 	if(e == hipSuccess) e = hipMemcpy(base + oMats, recs.data(), recs.size() * sizeof(dev::MatRec), hipMemcpyHostToDevice);
 	if(e == hipSuccess) e = hipMemcpy(base + oTex, trecs.data(), trecs.size() * sizeof(dev::TexRec), hipMemcpyHostToDevice);
@@ -464,6 +477,13 @@ static SnailMaterials *matCreate(const char *fn, bool transp, SnailScene *scene,
 	m->dShTris = (const uint4 *)(base + oTris); m->dMap = (const int *)(base + oMap); m->dMats = (const dev::MatRec *)(base + oMats);
 	m->dTex = (const dev::TexRec *)(base + oTex); m->dTexels = (const unsigned char *)(base + oTexels);
 	return m;
+}
+
+static SnailMaterials *matCreate(const char *fn, bool transp, SnailScene *scene, const void *shtris64, int nTris, const int32_t *matMap, int nMap, const SnailMaterial *mats,
+								 int nMats, const int32_t *opacityTexture, const SnailTexture *textures, int nTex) {
+	bool canSelect = false;
+	if(!matCheckHost(fn, transp, false, shtris64, nTris, matMap, nMap, mats, nMats, opacityTexture, textures, nTex, &canSelect)) return nullptr;
+	return matUpload(fn, canSelect, scene, shtris64, nTris, matMap, nMap, mats, nMats, opacityTexture, textures, nTex);
 }
 
 extern "C" {
@@ -487,6 +507,7 @@ void snail_materials_destroy(SnailMaterials *m) {
 	freeInstTileJob(m->tileJob);
 	for(auto &f : m->frameLists) (void)hipFree(f.d);
 	if(m->dBase) (void)hipFree(m->dBase);
+	dynFree(m->dyn);
 	delete m;
 }
 

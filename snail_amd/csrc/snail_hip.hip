@@ -96,6 +96,7 @@ void snail_set_error(const char *fmt, ...) {
 #include "heatmap.inc"           // the heat-map store stage: plain fp32, once for both arithmetics (its C-ABI: heatmap_host.inc)
 #include "build_common.inc"      // the device builders: plain fp32, once for both arithmetics
 #include "instances_build.inc"   // ... of the top-level tree over instances (bvh_fast.inc, of a plain scene, follows lbvh.inc)
+#include "materials_dynamic.inc"  // the ShTriangle records of a material set packed on the device: plain fp32, once for both arithmetics
 
 // A launch in the scene's arithmetic: dev::K, or dev_sse::K with the same argument record (the two namespaces are the same text, so the
 // records have the same layout; they are distinct types, hence the copy).  K comes last because its template arguments hold commas.
@@ -1805,3 +1806,4 @@ int snail_account_primary(SnailScene *s, const float cam[13], int resx, int resy
 #include "materials_tiles_host.inc"
 #include "materials_transparency_host.inc"
 #include "materials_tree_host.inc"
+#include "materials_dynamic_host.inc"

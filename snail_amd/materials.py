@@ -20,6 +20,11 @@ and MipmapTexture / PointSampler -- over the C-ABI of include/snail_materials.h.
                                                         selector, Scene::TraceTransparency and its nested RayTrace calls, level by level,
                                                         include/snail_materials_transparency.h
 
+  MaterialSet.from_dev(scene, d_uv, d_mat_index, ...), .rebuild_dev / .update_dev
+                                                    <-> the builder permuting shTris together with tris (src/bvh/tree.cpp:122-125, :249-252) for a
+                                                        mesh that deforms: records packed on the device behind every device rebuild,
+                                                        include/snail_materials_dynamic.h
+
   .mirror_rays / .tree_frame_packets / .render_tree_tiles_host / .render_tree_frame_host / .set_level_budget / .level_bytes
                                                     <-> the continuation TOGETHER with the bounce (every RayTrace of the continuation chain
                                                         mirrors its hit lanes; the mirrored call continues but never mirrors), tile lists,
@@ -120,18 +125,24 @@ def _material_records(materials) -> np.ndarray:
     return recs
 
 
+class _Tex(C.Structure):
+    _fields_ = [("levels", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32)]
+
+
+def _texture_array(textures):
+    tex = (_Tex * max(len(textures), 1))()
+    for k, t in enumerate(textures):
+        tex[k].levels, tex[k].width, tex[k].height = t.levels.ctypes.data, t.width, t.height
+    return tex
+
+
 def create_set(scene_handle, shtris, material_map, materials, textures, transparent: bool = False):
     """snail_materials_create (transparent=True: snail_materials_create_transparent) over raw arguments -> handle (c_void_p); SnailError with
     the library's text when the set is refused"""
     sh = np.ascontiguousarray(shtris, dtype=np.uint8).reshape(-1, 64)
     mp = np.ascontiguousarray(material_map, dtype=np.int32).reshape(-1)
     recs = _material_records(materials)
-
-    class _Tex(C.Structure):
-        _fields_ = [("levels", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32)]
-    tex = (_Tex * max(len(textures), 1))()
-    for k, t in enumerate(textures):
-        tex[k].levels, tex[k].width, tex[k].height = t.levels.ctypes.data, t.width, t.height
+    tex = _texture_array(textures)
     if transparent:
         op = np.ascontiguousarray([getattr(m, "opacity_texture", 0) for m in materials], dtype=np.int32)
         h = _lib.lib().snail_materials_create_transparent(scene_handle, _lib.ptr(sh), len(sh), _lib.ptr(mp), len(mp), _lib.ptr(recs) if len(recs) else None, len(recs),
@@ -141,6 +152,21 @@ def create_set(scene_handle, shtris, material_map, materials, textures, transpar
                                               C.cast(tex, C.c_void_p) if len(textures) else None, len(textures))
     if not h:
         raise _lib.SnailError("%s: %s" % ("snail_materials_create_transparent" if transparent else "snail_materials_create", _lib.lib().snail_last_error().decode()))
+    return C.c_void_p(h)
+
+
+def create_set_dev(scene_handle, d_uv, d_mat_index, d_flat, n, d_perm, d_nrm, d_verts, material_map, materials, textures, transparent: bool = False, stream=None):
+    """snail_materials_create_dev over raw arguments (device tensors or None) -> handle (c_void_p); SnailError with the library's text when
+    the set is refused"""
+    mp = np.ascontiguousarray(material_map, dtype=np.int32).reshape(-1)
+    recs = _material_records(materials)
+    tex = _texture_array(textures)
+    op = np.ascontiguousarray([getattr(m, "opacity_texture", 0) for m in materials] or [0], dtype=np.int32) if transparent else None
+    h = _lib.lib().snail_materials_create_dev(scene_handle, _lib.ptr(d_uv), _lib.ptr(d_mat_index), _lib.ptr(d_flat), int(n), _lib.ptr(d_perm), _lib.ptr(d_nrm),
+                                              _lib.ptr(d_verts), _lib.ptr(mp), len(mp), _lib.ptr(recs) if len(recs) else None, len(recs), _lib.ptr(op),
+                                              C.cast(tex, C.c_void_p) if len(textures) else None, len(textures), _stream_ptr(stream))
+    if not h:
+        raise _lib.SnailError("snail_materials_create_dev: %s" % _lib.lib().snail_last_error().decode())
     return C.c_void_p(h)
 
 
@@ -164,6 +190,76 @@ class MaterialSet:
             raise _lib.SnailError("MaterialSet: the scene carries no permutation (BVH slot -> input triangle), so its shading data cannot be put into triId order")
         self.shtris = pack_shtris(uv, nrm, mat_index, flat, perm)
         self._h = create_set(scene._h, self.shtris, material_map, list(materials), list(textures), transparent)
+
+    # ---- include/snail_materials_dynamic.h: the set of a deforming mesh ------------------------------------------------------------------
+    @classmethod
+    def from_dev(cls, scene: Scene, d_uv, d_mat_index, d_flat=None, material_map=(-1,), materials=(), textures=(), transparent: bool = False, d_nrm=None,
+                 d_verts=None, stream=None):
+        """The set of a Scene.from_fast_dev scene, its records packed on the device through scene.d_perm (snail_materials_create_dev) and
+        packed again by rebuild_dev / update_dev.  Device tensors on the scene's device, describing the INPUT triangles: d_uv float32
+        [n, 3, 2], d_mat_index int32 [n], d_flat uint8 [n] or None (none flat); normals d_nrm float32 [n, 3, 3], or None for face normals of
+        d_verts float32 [n, 3, 3].  The tensors are copied: they need not outlive the call."""
+        if not getattr(scene, "_fast_dev", False):
+            raise _lib.SnailError("MaterialSet.from_dev: the scene was not made by Scene.from_fast_dev (MaterialSet(...) serves a tree that is never rebuilt)")
+        torch = _torch()
+        n = scene._fast_n
+        d = scene._dev()
+        cls._check_dev("d_uv", d_uv, torch.float32, n * 6, d)
+        cls._check_dev("d_mat_index", d_mat_index, torch.int32, n, d)
+        cls._check_dev("d_flat", d_flat, torch.uint8, n, d, optional=True)
+        cls._check_dev("d_nrm", d_nrm, torch.float32, n * 9, d, optional=True)
+        cls._check_dev("d_verts", d_verts, torch.float32, n * 9, d, optional=True)
+        self = cls.__new__(cls)
+        self.scene, self._h, self.shtris = scene, None, None
+        self._h = create_set_dev(scene._h, d_uv, d_mat_index, d_flat, n, scene.d_perm, d_nrm, d_verts, material_map, list(materials), list(textures), transparent, stream)
+        self._dynamic = True
+        return self
+
+    @staticmethod
+    def _check_dev(name, t, dtype, numel, d, optional=False):
+        if t is None and optional:
+            return
+        if not (hasattr(t, "data_ptr") and t.is_cuda and t.device == d and t.dtype == dtype and t.is_contiguous() and t.numel() == numel):
+            raise ValueError("%s must be a contiguous %s tensor of %d values on %s" % (name, dtype, numel, d))
+
+    def _dyn_args(self, what, d_nrm, d_verts):
+        if not getattr(self, "_dynamic", False):
+            raise _lib.SnailError("%s: the set was not made by MaterialSet.from_dev" % what)
+        torch = _torch()
+        n, d = self.scene._fast_n, self.scene._dev()
+        self._check_dev("d_nrm", d_nrm, torch.float32, n * 9, d, optional=True)
+        self._check_dev("d_verts", d_verts, torch.float32, n * 9, d, optional=True)
+        return torch, d
+
+    def rebuild_dev(self, d_verts, d_nrm=None, stream=None, info=None):
+        """Rebuild the scene from new vertices, as Scene.rebuild_fast_dev does, and pack the records again through the new permutation on the
+        same stream (snail_materials_rebuild_dev): with d_nrm, or with face normals of d_verts when it is None.  No host wait.  -> info, int32
+        [6] device tensor: the rebuild's {status, nNodes, depth, n}, then {records committed (0 / 1), zeroed triangles}.  A status other
+        than 0 leaves tree AND records as they were.  The tensors must stay alive and unchanged until the work enqueued here has run."""
+        torch, d = self._dyn_args("rebuild_dev", d_nrm, d_verts)
+        sc = self.scene
+        sc._check_verts(d_verts, d)
+        if info is None:
+            info = torch.empty(6, dtype=torch.int32, device=d)
+            if stream is not None:
+                info.record_stream(stream)
+        _lib.check(_lib.lib().snail_materials_rebuild_dev(self._h, _lib.ptr(d_verts), _lib.ptr(d_nrm), _lib.ptr(sc.d_perm), _lib.ptr(info), _stream_ptr(stream)),
+                   "snail_materials_rebuild_dev")
+        sc.d_info = info[:4]
+        sc._stale = True           # .bvh / .perm / .depth are read back when next asked, as after Scene.rebuild_fast_dev
+        return info
+
+    def update_dev(self, d_nrm=None, d_verts=None, stream=None, info=None):
+        """Pack the records again through scene.d_perm, and nothing else (snail_materials_update_dev): after the scene was rebuilt by
+        Scene.rebuild_fast_dev or through another set, or for new normals alone.  -> info, int32 [2] device tensor {1, zeroed triangles}."""
+        torch, d = self._dyn_args("update_dev", d_nrm, d_verts)
+        if info is None:
+            info = torch.empty(2, dtype=torch.int32, device=d)
+            if stream is not None:
+                info.record_stream(stream)
+        _lib.check(_lib.lib().snail_materials_update_dev(self._h, _lib.ptr(self.scene.d_perm), _lib.ptr(d_nrm), _lib.ptr(d_verts), _lib.ptr(info), _stream_ptr(stream)),
+                   "snail_materials_update_dev")
+        return info
 
     def close(self):
         if getattr(self, "_h", None):

@@ -41,9 +41,22 @@ in the same run and the same build, snail_materials_transparent_image (flags = 0
 flags on the set rebuilt with opaque stand-ins.  All three are host calls that return after their device-to-host copy: host clock, call by
 call, after a warm-up, the variants alternating, --reps rounds of --frames calls, median (min .. max).  No threshold: a measurement.  --out APPENDS.
 
+--dynamic [--sheet NUxNV]: a DEFORMING mesh under full shading (include/snail_materials_dynamic.h): the tests' patch scene
+(tests/materials_cases.py: patch_scene, a sheet of NU x NV quads, textured set by input index mod 5) alternating between two poses, one
+rebuild and one frame at --res per step, in the same run and alternating:
+  dynamic      MaterialSet.rebuild_dev + .render on one stream, nothing waited for: device events around a window of --frames steps;
+  host_route   what a caller had to do without that header: Scene.rebuild_fast_dev, a host wait, the perm downloaded, pack_shtris on the host,
+               a new set over the rebuilt handle through the C-ABI (snail_materials_create, every texture uploaded again; the Python class
+               refuses such a scene), .render, the old set destroyed -- timed by the HOST clock, a wait at the end of the window, because
+               it contains host work;
+  build_alone  Scene.rebuild_fast_dev alone (k_fast_* and the builder's kernels), device events;
+  repack_alone MaterialSet.update_dev alone (k_shd_pack), device events, launch to launch.
+The two routes' last frames are compared byte for byte first.  No rate is promised: the rows are the record.  --out APPENDS.
+
     python tools/materials_time.py [--res 1920x1080] [--frames 400] [--reps 7] [--parent-lib PATH] [--out profiles/materials.txt] [--trace N] [--reflections]
                                    [--tiles [--aa] [--commit LABEL]] [--transparency N]
-                                   [--tree [--reflections] [--aa] [--tiles]]"""
+                                   [--tree [--reflections] [--aa] [--tiles]]
+                                   [--dynamic [--sheet 180x140]]"""
 import argparse
 import ctypes as C
 import os
@@ -96,6 +109,8 @@ def main():
     ap.add_argument("--commit", default="unlabelled")
     ap.add_argument("--transparency", type=int, default=0, metavar="N")
     ap.add_argument("--tree", action="store_true")
+    ap.add_argument("--dynamic", action="store_true")
+    ap.add_argument("--sheet", default="180x140")
     a = ap.parse_args()
     resx, resy = (int(v) for v in a.res.split("x"))
     import torch
@@ -106,6 +121,8 @@ def main():
         return transparency(a)
     if a.tree:
         return tree(a, resx, resy)
+    if a.dynamic:
+        return dynamic(a, resx, resy)
 
     tv = scenes.atrium(detail=a.detail)
     hb = HostBVH.build(tv)
@@ -436,6 +453,96 @@ def tree(a, resx, resy):
     if a.out:
         with open(a.out, "a") as fh:
             fh.write(text + "\n")
+
+
+def dynamic(a, resx, resy):
+    """--dynamic: rebuild + frame of a deforming sheet through the dynamic set, beside the route over the host and the build alone"""
+    import time
+
+    import torch
+    from tests import materials_cases as K
+    nu, nv = (int(v) for v in a.sheet.split("x"))
+    tvA = K.patch_scene(nu=nu, nv=nv)
+    x, y = tvA[..., 0].astype(np.float64), tvA[..., 1].astype(np.float64)
+    tvB = tvA.copy()
+    tvB[..., 2] = (tvA[..., 2] + 0.22 * np.sin(1.9 * x + 0.4) * np.cos(1.3 * y - 0.2)).astype(np.float32)
+    n = len(tvA)
+    uv, nrmA, flat = K.vertex_data(HostBVH.build_fast(tvA), tvA, 22)
+    nrmB = (nrmA + (np.random.RandomState(31).rand(*nrmA.shape) - 0.5) * 0.5).astype(np.float32)
+    mi = np.arange(n, dtype=np.int32) % 5
+    descs, mmap = K.materials_mod5()
+    mats = [P.Material.simple(d[1], d[2]) if d[0] == "simple" else P.Material.textured(d[1], d[2]) if d[0] == "tex" else P.Material.uber(d[1], d[2], d[3]) for d in descs]
+    tex = [P.Texture(t) for t in K.TEXTURES()]
+    cam = FPSCamera(np.array([0.0, 0.0, -3.2], dtype=np.float32), 0.0, 0.0).camera()
+    lights = np.array([[-0.6, 1.6, -2.6, 1.0, 0.9, 0.8, 14.0]], dtype=np.float32)
+    to = lambda v: torch.from_numpy(np.ascontiguousarray(v)).to("cuda:0")      # noqa: E731
+    dV, dN, nrm = [to(tvA), to(tvB)], [to(nrmA), to(nrmB)], [nrmA, nrmB]
+    fl = np.ascontiguousarray(flat).astype(np.uint8)
+    out = [torch.zeros((resy, resx, 3), dtype=torch.uint8, device="cuda:0") for _ in range(2)]
+    # one handle per route: each keeps the tree of its own last step
+    sc = [Scene.from_fast_dev(dV[0], 0) for _ in range(4)]
+    ms = P.MaterialSet.from_dev(sc[0], to(uv), to(mi), to(fl), mmap, mats, tex, d_nrm=dN[0])
+    ms_pack = P.MaterialSet.from_dev(sc[3], to(uv), to(mi), to(fl), mmap, mats, tex, d_nrm=dN[0])
+    held = {"set": None}
+
+    def dyn_step(k):
+        ms.rebuild_dev(dV[k], dN[k])
+        ms.render(cam, resx, resy, lights, out=out[0])
+
+    def host_step(k):
+        sc[1].rebuild_fast_dev(dV[k])
+        torch.cuda.synchronize()
+        perm = sc[1].d_perm.cpu().numpy()
+        h = P.create_set(sc[1]._h, P.pack_shtris(uv, nrm[k], mi, flat, perm), mmap, mats, tex)
+        new = P.MaterialSet.__new__(P.MaterialSet)
+        new.scene, new._h, new.shtris = sc[1], h, None
+        new.render(cam, resx, resy, lights, out=out[1])
+        if held["set"] is not None:
+            held["set"].close()
+        held["set"] = new
+
+    for k in (1, 0, 1):      # warm-up; both routes end on pose B
+        dyn_step(k); host_step(k)
+        sc[2].rebuild_fast_dev(dV[k]); ms_pack.update_dev(d_nrm=dN[k])
+    torch.cuda.synchronize()
+    same = bool(torch.equal(out[0], out[1]))
+    colours = len(np.unique(out[0].cpu().numpy().reshape(-1, 3), axis=0))
+    ev = {"dynamic": [], "build_alone": [], "repack_alone": []}
+    wall = {"host_route": []}
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    device_variants = {"dynamic": dyn_step, "build_alone": lambda k: sc[2].rebuild_fast_dev(dV[k]), "repack_alone": lambda k: ms_pack.update_dev(d_nrm=dN[k])}
+    for _ in range(a.reps):
+        for name, fn in device_variants.items():
+            e0.record()
+            for f in range(a.frames):
+                fn(f & 1)
+            e1.record()
+            e1.synchronize()
+            ev[name].append(e0.elapsed_time(e1) / a.frames)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for f in range(a.frames):
+            host_step(f & 1)
+        torch.cuda.synchronize()
+        wall["host_route"].append((time.perf_counter() - t0) * 1e3 / a.frames)
+    pw, ph = (resx + 15) // 16, (resy + 15) // 16
+    lines = ["", "full shading of a deforming mesh [%s]: patch scene %dx%d quads (%d triangles) between two poses, textured set, one light, IEEE, %dx%d (%d packets); "
+             "%d rounds of %d steps per variant, alternating, after 3 warm-up steps each; ms per step (one rebuild + one frame): median (min .. max)" %
+             (a.commit, nu, nv, n, resx, resy, pw * ph, a.reps, a.frames), "device: %s" % torch.cuda.get_device_name(0),
+             "the two routes' frames of pose B are equal byte for byte: %s (%d distinct colours)" % (same, colours)]
+    for k, v in ev.items():
+        lines.append("  %-13s %9.3f  (%.3f .. %.3f)   device events around the window, no host wait inside" % (k, statistics.median(v), min(v), max(v)))
+    for k, v in wall.items():
+        lines.append("  %-13s %9.3f  (%.3f .. %.3f)   HOST clock (it contains host work: a wait, the perm's download, the host pack, a new set with its textures)" %
+                     (k, statistics.median(v), min(v), max(v)))
+    lines.append("  repack_alone moves %d bytes per step (<= 65 read + 64 written per triangle): launch to launch, an upper bound on k_shd_pack's time" % (n * 129))
+    text = "\n".join(lines)
+    print(text)
+    if a.out:
+        with open(a.out, "a") as fh:
+            fh.write(text + "\n")
+    if not same:
+        raise SystemExit("the dynamic set's frame and the host route's differ")
 
 
 if __name__ == "__main__":
