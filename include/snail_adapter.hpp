@@ -61,6 +61,7 @@
 #include "snail_materials_tiles.h"
 #include "snail_materials_transparency.h"
 #include "snail_materials_tree.h"
+#include "snail_materials_heatmap.h"
 #include "snail_materials_dynamic.h"
 
 #ifndef SNAIL_CHECK
@@ -535,7 +536,8 @@ enum { kDeviceHeatmap = 0 };
 // continuation, which the tile functions this routing goes through do not run: they refuse such a set, and the routing leaves it with the reference's renderer.
 // For a set that passes, the frame the device makes is the frame the reference's full-shading branch makes.  Every other gVals[6] call keeps the
 // reference's renderer: no set, a set that can select a transparent lane, several devices, an image with gVals[8], and gVals[5] without gVals[1] -- the last even with the device heat-map opted in,
-// whose counters are those of simple shading (under full shading the shadow lanes follow the interpolated normals, so the counts differ).
+// whose counters are those of simple shading (under full shading the shadow lanes follow the interpolated normals, so the counts differ); the
+// heat-map of full shading has an opt-in of its own, SNAIL_ADAPTER_DEVICE_MATERIALS_HEATMAP (below).
 // Opt-in, so that hosts and mocks built without it keep today's routing.
 #ifdef SNAIL_ADAPTER_DEVICE_MATERIALS
 enum { kDeviceMaterials = 1 };
@@ -553,10 +555,22 @@ enum { kDeviceTransparency = 1 };
 #else
 enum { kDeviceTransparency = 0 };
 #endif
+// gVals[5] under full shading on the device as well (include/snail_materials_heatmap.h): define SNAIL_ADAPTER_DEVICE_MATERIALS_HEATMAP together with
+// SNAIL_ADAPTER_DEVICE_MATERIALS (alone it is without effect) and the Render(...) overloads send a call with gVals[6] && HasShadingData() &&
+// gVals[5] && !gVals[1] to snail_materials_render_heat_tiles / snail_materials_render_heat_frame with gVals[7], [9] and, on tile lists, [8], at
+// maxDepth 8 -- under the conditions of the materials routing above: a set is attached, one device, no gVals[8] on an image, and a set that can
+// select a transparent lane only with SNAIL_ADAPTER_DEVICE_TRANSPARENCY.  A frame whose truncated-lane counter moved is rendered again by the
+// reference's renderer (or aborts under SNAIL_ADAPTER_NO_HOST_RENDERER), as the lit frames are.  Opt-in: without the macro the routing is what it was.
+#if defined(SNAIL_ADAPTER_DEVICE_MATERIALS_HEATMAP) && defined(SNAIL_ADAPTER_DEVICE_MATERIALS)
+enum { kDeviceMaterialsHeatmap = 1 };
+#else
+enum { kDeviceMaterialsHeatmap = 0 };
+#endif
 enum { kTreeMaxDepth = 8 };   // SNAIL_MAT_TRANSP_MAX_DEPTH
-inline const char *UnsupportedSwitch(const int *gv, bool hasShadingData, bool tileList, bool deviceHeatmap, bool deviceMaterials) {
+// (deviceMaterialsHeatmap: the heat-map under full shading is on the device too; defaulted, so that the callers of the five-argument form keep its meaning)
+inline const char *UnsupportedSwitch(const int *gv, bool hasShadingData, bool tileList, bool deviceHeatmap, bool deviceMaterials, bool deviceMaterialsHeatmap = false) {
 	if(gv[6] && hasShadingData) {
-		if(deviceMaterials && (!gv[5] || gv[1]) && (tileList || !gv[8])) return nullptr;
+		if(deviceMaterials && (!gv[5] || gv[1] || deviceMaterialsHeatmap) && (tileList || !gv[8])) return nullptr;
 		return "gVals[6] (full shading: materials / textures, src/scene_trace.cpp:145)";
 	}
 	if(gv[5] && !deviceHeatmap) return "gVals[5] (TreeStats visualisation, src/scene_trace.cpp:513-517)";
@@ -746,6 +760,32 @@ inline StatsT RenderMaterialTreeImage(const SceneT &scene, const CameraT &camera
 												  detail::renderFlags(mode), (unsigned char *)image.DataPointer(), (int)image.Pitch(), kTreeMaxDepth, truncated, st));
 	return detail::toStats<StatsT>(st);
 }
+#ifdef SNAIL_ADAPTER_DEVICE_MATERIALS_HEATMAP
+// ... and with gVals[5] (and without gVals[1]) the heat-map of the same tree of calls, for ANY attached set: snail_materials_render_heat_tiles /
+// snail_materials_render_heat_frame (include/snail_materials_heatmap.h) with maxDepth kTreeMaxDepth; the ambient light reaches no counter
+template <class StatsT, class SceneT, class CameraT>
+inline StatsT RenderMaterialHeatTiles(const SceneT &scene, const CameraT &camera, unsigned resx, unsigned resy, unsigned char *data, const std::vector<int> &coords,
+									  const std::vector<int> &offsets, const RenderMode &mode, unsigned rank, uint64_t *truncated) {
+	float c[13];
+	detail::cam13(camera, c);
+	const std::vector<float> l = detail::lights7(scene);
+	std::vector<int64_t> off(offsets.begin(), offsets.end());
+	uint64_t st[4] = {0, 0, 0, 0};
+	SNAIL_CHECK(snail_materials_render_heat_tiles(scene.geometry.Materials(), c, (int)resx, (int)resy, coords.data(), off.data(), (int)(coords.size() / 4), l.data(),
+												  (int)(l.size() / 7), detail::renderFlags(mode), mode.rankTint ? detail::RankTint(rank) : nullptr, data, kTreeMaxDepth, truncated, st));
+	return detail::toStats<StatsT>(st);
+}
+template <class StatsT, class SceneT, class CameraT, class ImageT>
+inline StatsT RenderMaterialHeatImage(const SceneT &scene, const CameraT &camera, ImageT &image, const RenderMode &mode, uint64_t *truncated) {
+	float c[13];
+	detail::cam13(camera, c);
+	const std::vector<float> l = detail::lights7(scene);
+	uint64_t st[4] = {0, 0, 0, 0};
+	SNAIL_CHECK(snail_materials_render_heat_frame(scene.geometry.Materials(), c, (int)image.Width(), (int)image.Height(), l.data(), (int)(l.size() / 7), detail::renderFlags(mode),
+												  (unsigned char *)image.DataPointer(), (int)image.Pitch(), kTreeMaxDepth, truncated, st));
+	return detail::toStats<StatsT>(st);
+}
+#endif
 #endif
 
 } // namespace snail
@@ -779,7 +819,8 @@ inline TreeStats Render(const Scene<snail::HipBVH<RefBVH>> &scene, const Camera 
 	const int canSelect = snail::kDeviceMaterials && scene.geometry.Materials() != nullptr && scene.geometry.DeviceCount() <= 1 ?
 							  snail_materials_can_select_transparent(scene.geometry.Materials()) : -1;
 	const bool deviceMaterials = canSelect == 0 || (snail::kDeviceTransparency && canSelect == 1);
-	if(const char *why = snail::UnsupportedSwitch(gVals, scene.geometry.HasShadingData(), true, snail::kDeviceHeatmap && scene.geometry.DeviceCount() <= 1, deviceMaterials))
+	if(const char *why = snail::UnsupportedSwitch(gVals, scene.geometry.HasShadingData(), true, snail::kDeviceHeatmap && scene.geometry.DeviceCount() <= 1, deviceMaterials,
+												  snail::kDeviceMaterialsHeatmap != 0))
 		SNAIL_HOST_RENDER(why, gVals[9] ? 2 : 1, resx, resy, Render<snail::HipBVH<RefBVH>>(scene, camera, resx, resy, data, coords, offsets, options, rank, threads));
 	(void)rank; (void)threads; // (a tint only under full shading; the host thread pool has no device counterpart)
 	snail::RenderMode mode;
@@ -792,6 +833,15 @@ inline TreeStats Render(const Scene<snail::HipBVH<RefBVH>> &scene, const Camera 
 	if(gVals[6] && scene.geometry.HasShadingData()) {   // (UnsupportedSwitch let it through: a set is attached, one device, gVals[5] off or under gVals[1])
 		mode.statsHeat = false;
 		mode.rankTint = gVals[8] != 0;
+#ifdef SNAIL_ADAPTER_DEVICE_MATERIALS_HEATMAP
+		if(gVals[5] && !gVals[1]) {   // the heat-map of the full-shaded tree, any set; a frame the depth cut touched is the reference's renderer's, as below
+			uint64_t truncated = 0;
+			const TreeStats ts = snail::RenderMaterialHeatTiles<TreeStats>(scene, camera, resx, resy, data, coords, offsets, mode, rank, &truncated);
+			if(!truncated) return ts;
+			SNAIL_HOST_RENDER("a transparency continuation deeper than maxDepth 8 (include/snail_materials_heatmap.h)", gVals[9] ? 2 : 1, resx, resy,
+							  Render<snail::HipBVH<RefBVH>>(scene, camera, resx, resy, data, coords, offsets, options, rank, threads));
+		}
+#endif
 		if(canSelect == 1) {   // (SNAIL_ADAPTER_DEVICE_TRANSPARENCY) a frame the depth cut touched is not the reference's: the reference's renderer does it again
 			uint64_t truncated = 0;
 			const TreeStats ts = snail::RenderMaterialTreeTiles<TreeStats>(scene, camera, resx, resy, data, coords, offsets, mode, rank, &truncated);
@@ -809,7 +859,7 @@ inline TreeStats Render(const Scene<snail::HipBVH<RefBVH>> &scene, const Camera 
 	const int canSelect = snail::kDeviceMaterials && scene.geometry.Materials() != nullptr && scene.geometry.DeviceCount() <= 1 ?
 							  snail_materials_can_select_transparent(scene.geometry.Materials()) : -1;
 	const bool deviceMaterials = canSelect == 0 || (snail::kDeviceTransparency && canSelect == 1);
-	if(const char *why = snail::UnsupportedSwitch(gVals, scene.geometry.HasShadingData(), false, snail::kDeviceHeatmap != 0, deviceMaterials))
+	if(const char *why = snail::UnsupportedSwitch(gVals, scene.geometry.HasShadingData(), false, snail::kDeviceHeatmap != 0, deviceMaterials, snail::kDeviceMaterialsHeatmap != 0))
 		SNAIL_HOST_RENDER(why, gVals[9] ? 2 : 1, image.Width(), image.Height(), Render<snail::HipBVH<RefBVH>>(scene, camera, image, options, threads));
 	(void)threads;
 	snail::RenderMode mode;
@@ -821,6 +871,15 @@ inline TreeStats Render(const Scene<snail::HipBVH<RefBVH>> &scene, const Camera 
 #ifdef SNAIL_ADAPTER_DEVICE_MATERIALS
 	if(gVals[6] && scene.geometry.HasShadingData()) {   // (UnsupportedSwitch let it through: a set is attached, one device, no gVals[8], gVals[5] off or under gVals[1])
 		mode.statsHeat = false;
+#ifdef SNAIL_ADAPTER_DEVICE_MATERIALS_HEATMAP
+		if(gVals[5] && !gVals[1]) {   // as above
+			uint64_t truncated = 0;
+			const TreeStats ts = snail::RenderMaterialHeatImage<TreeStats>(scene, camera, image, mode, &truncated);
+			if(!truncated) return ts;
+			SNAIL_HOST_RENDER("a transparency continuation deeper than maxDepth 8 (include/snail_materials_heatmap.h)", gVals[9] ? 2 : 1, image.Width(), image.Height(),
+							  Render<snail::HipBVH<RefBVH>>(scene, camera, image, options, threads));
+		}
+#endif
 		if(canSelect == 1) {   // (SNAIL_ADAPTER_DEVICE_TRANSPARENCY) as above
 			uint64_t truncated = 0;
 			const TreeStats ts = snail::RenderMaterialTreeImage<TreeStats>(scene, camera, image, mode, &truncated);

@@ -7,7 +7,7 @@
  * NOT here: the mirrored bounce is snail_materials_bounce.h's; 4x antialiasing, depth shading, the tint and tile lists are
  * snail_materials_tiles.h's; the material kinds that can select a transparent lane, their sample stages and the continuation's packets are
  * snail_materials_transparency.h's and the frames of the continuation too (a set that holds such a kind is refused by every function here that takes a set).  The host renderer keeps
- * multi-device frames, the heat-map, the ordered launches, OBJ vt / vn / usemtl and
+ * multi-device frames, the ordered launches (the heat-map, gVals[5], of full shading is snail_materials_heatmap.h's), OBJ vt / vn / usemtl and
  * MTL ingest, the DXT and SAT samplers and rgba8 textures.
  */
 #ifndef SNAIL_MATERIALS_H

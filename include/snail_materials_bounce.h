@@ -11,7 +11,8 @@
  * NOT here: 4x antialiasing, depth shading, the tint and tile lists with the bounce are snail_materials_tiles.h's, and with them the adapter's
  * routing of a call with gVals[6] (SNAIL_ADAPTER_DEVICE_MATERIALS, snail_adapter.hpp); the transparent kinds and the frames of the
  * transparency continuation are snail_materials_transparency.h's.  The host renderer keeps the transparency continuation together with
- * the bounce, multi-device frames, the heat-map and the ordered launches (dispatch-order feedback) under the bounce.
+ * the bounce, multi-device frames and the ordered launches (dispatch-order feedback) under the bounce; the heat-map (gVals[5]) of full shading,
+ * with and without the bounce, is snail_materials_heatmap.h's.
  */
 #ifndef SNAIL_MATERIALS_BOUNCE_H
 #define SNAIL_MATERIALS_BOUNCE_H

@@ -33,8 +33,8 @@
  *
  * NOT here (the host renderer keeps them): tiles, 4x antialiasing and the tint with the transparency continuation (the transparent kinds and
  * the continuation's plain frames are snail_materials_transparency.h's; a set that can select a transparent lane is refused by the functions here);
- * full-shaded tiles dealt over several devices; the heat-map
- * (gVals[5]) under full shading; the ordered launches (dispatch-order feedback); materials on instanced scenes.
+ * full-shaded tiles dealt over several devices; the ordered launches (dispatch-order feedback); materials on instanced scenes.  The heat-map
+ * (gVals[5]) under full shading is snail_materials_heatmap.h's.
  */
 #ifndef SNAIL_MATERIALS_TILES_H
 #define SNAIL_MATERIALS_TILES_H

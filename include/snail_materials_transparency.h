@@ -11,7 +11,7 @@
  * continuation and continuations inside the bounce, a tree of calls), tiles / 4x antialiasing / the tint with transparency -- so every entry
  * point of snail_materials.h, _bounce.h and _tiles.h refuses a set that can select a transparent lane (below), and the adapter's
  * SNAIL_ADAPTER_DEVICE_MATERIALS routing, which goes through the tile functions, leaves such a set's frames with the reference's own renderer --
- * multi-device frames, the heat-map, MTL / OBJ ingest, the rgba8, DXT and SAT samplers.
+ * multi-device frames, MTL / OBJ ingest, the rgba8, DXT and SAT samplers (the heat-map, gVals[5], of full shading is snail_materials_heatmap.h's).
  */
 #ifndef SNAIL_MATERIALS_TRANSPARENCY_H
 #define SNAIL_MATERIALS_TRANSPARENCY_H

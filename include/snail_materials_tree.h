@@ -37,8 +37,8 @@
  * SNAIL_RENDER_AA4) are bounded per group of intermediates: the packet list runs in slices of whole output packets, back to back on the same
  * stream and arena, sized so that the levels stay within the set's level budget.  Packets are independent: slicing changes no byte and no counter.
  *
- * NOT here (the host renderer keeps them): full-shaded tiles dealt over several devices; the heat-map (gVals[5]) and the ordered launches
- * (dispatch-order feedback) under full shading; materials on instanced scenes (the reference's DBVH::HasShadingData() returns 0); maxDepth
+ * NOT here (the host renderer keeps them): full-shaded tiles dealt over several devices; the ordered launches (dispatch-order feedback) under
+ * full shading (the heat-map, gVals[5], of these frames is snail_materials_heatmap.h); materials on instanced scenes (the reference's DBVH::HasShadingData() returns 0); maxDepth
  * above 8 (the reference has no cut: a frame whose counter moved is not the reference's).
  */
 #ifndef SNAIL_MATERIALS_TREE_H

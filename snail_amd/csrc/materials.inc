@@ -473,7 +473,10 @@ __device__ __forceinline__ void matLoadSamples(const MatArgs &A, const PacketPos
 // one kernel, look-ups checked), and k_inst_light (instances_shade.inc) has the same set-up around the instanced walk.  A change to the shadow
 // packet, to the classify / walkSharedAsm / walk dispatch or to the stats booking belongs in all three.
 // SRC_MIRROR: the nested call's lights on the mirrored packets' samples -- the same shadow packet (the light's shared origin) and walks.
-template <bool DEEP, int SRC>
+// PSTATS: the heat-map launches' instantiation (include/snail_materials_heatmap.h), which also books the (packet, light)'s counters per packet at
+// P.pidx -- a template argument as in snail_dev.inc, so that the other launches' kernels stay the code they were.  A culled pair has returned
+// before the booking: it books nothing.
+template <bool DEEP, int SRC, bool PSTATS = false>
 __device__ __forceinline__ void matLight(const MatArgs &A, float *lds) {
 	const int lane = threadIdx.x & 63;
 	const int li = (int)blockIdx.x, n = (int)blockIdx.y;
@@ -523,6 +526,7 @@ __device__ __forceinline__ void matLight(const MatArgs &A, float *lds) {
 	} else if(mode == M_COH) walkSharedAsm<true, true, false, false, false, false>(A.s.nodes, A.s.tris, 64, lane, lorg, Q, 15u, stid, bu, bv, lds, st, oct);
 	else walkSharedAsm<true, false, false, false, false, false>(A.s.nodes, A.s.tris, 64, lane, lorg, Q, 15u, stid, bu, bv, lds, st, 0);
 	flushStats(A.s.stats, st, rays, lane);
+	if(PSTATS) bookPacketLate<ShadeArgs>(P.pidx, st, rays, lane);
 	*(float4 *)((SRC == SRC_MIRROR ? A.nSDist : A.s.sDist) + ((size_t)n * (size_t)A.s.nPackets + P.pidx) * 256 + (size_t)lane * 4) = make_float4(Q.dist[0], Q.dist[1], Q.dist[2], Q.dist[3]);
 }
 template <bool DEEP>
@@ -534,6 +538,11 @@ template <bool DEEP>
 __global__ __launch_bounds__(64) void k_mat_light_rays(MatArgs A) {
 	__shared__ float lds[LDS_FLOATS_PER_WAVE];
 	matLight<DEEP, SRC_MIRROR>(A, lds);
+}
+template <bool DEEP>
+__global__ __launch_bounds__(64) void k_mat_light_heat(MatArgs A) {
+	__shared__ float lds[LDS_FLOATS_PER_WAVE];
+	matLight<DEEP, SRC_PRIMARY, true>(A, lds);
 }
 
 // ---- one packet: the lights' contributions from the surviving distances, the colour and its store (shadeAndStore with two sample colours) ----
@@ -660,59 +669,17 @@ __global__ __launch_bounds__(64) void k_mat_colour_blend(MatArgs A) { matFinal<S
 // DST_MIRROR> (snail_dev.inc); only the normal's source differs.
 // TWINS: k_mat_mirror_rays (materials_tree.inc) is this body with a level's generic packets (matLoadSamples<SRC_MIRROR>) as its source, under that
 // level's order list; a change to Reflect, the offset, the layout or the booking belongs there too.
+// PSTATS (k_mat_mirror_heat, the heat-map launches of include/snail_materials_heatmap.h): the nested call's TracingRays per packet as well, as
+// matLight's.  The body is materials_mirror_body.inc, included once per kernel.
 __global__ __launch_bounds__(64) void k_mat_mirror(MatArgs A) {
-	const int lane = threadIdx.x & 63;
-	const int li = (int)blockIdx.x;
-	if(li >= A.s.nPackets) return;
-	const PacketPos P = packetOf(A.s, li);
-	const size_t quad = P.pidx * 64 + lane;
-	const float inf = __builtin_inff();
-	Samples S;
-	float d[3][4];
-	matRays(A.s, P, lane, d);
-	matLoadSamples<SRC_PRIMARY>(A, P, lane, S);
-	float rd[3][4], ro[3][4], rdist[4];
-	unsigned sel = 0;
-#pragma unroll
-	for(int l = 0; l < 4; l++) {
-		const float dt = S.nrm[0][l] * d[0][l] + S.nrm[1][l] * d[1][l] + S.nrm[2][l] * d[2][l];
-		const float dt2 = dt + dt;
-#pragma unroll
-		for(int c = 0; c < 3; c++) {
-			const float r = d[c][l] - S.nrm[c][l] * dt2;
-			rd[c][l] = S.hit[l] ? r : 0.0f;
-			ro[c][l] = S.hit[l] ? S.pos[c][l] + r * 0.001f : 0.0f;
-		}
-		rdist[l] = S.hit[l] ? inf : -inf;
-		sel |= S.hit[l] ? (1u << l) : 0u;
-	}
-	float4 *po = (float4 *)(A.s.rOrg + quad * 12), *pd = (float4 *)(A.s.rDir + quad * 12), *pi = (float4 *)(A.s.rIDir + quad * 12);
-#pragma unroll
-	for(int c = 0; c < 3; c++) {
-		po[c] = make_float4(ro[c][0], ro[c][1], ro[c][2], ro[c][3]);
-		pd[c] = make_float4(rd[c][0], rd[c][1], rd[c][2], rd[c][3]);
-	}
-#pragma unroll
-	for(int c = 0; c < 3; c++) {   // SafeInv (src/rtbase.h:117-120); table arithmetic: a component's four look-ups in one batch
-		float x4[4], r4[4];
-#pragma unroll
-		for(int l = 0; l < 4; l++) x4[l] = rd[c][l] + 0.00000001f;
-#if SNAIL_ARITH_SSE
-		InvN<4>(x4, r4);
-#else
-#pragma unroll
-		for(int l = 0; l < 4; l++) r4[l] = Inv(x4[l]);
-#endif
-		pi[c] = make_float4(r4[0], r4[1], r4[2], r4[3]);
-	}
-	A.s.rMask[quad] = (unsigned char)sel;
-	*(float4 *)(A.s.rDist + quad * 4) = make_float4(rdist[0], rdist[1], rdist[2], rdist[3]);
-	*(int4 *)(A.s.rObj + quad * 4) = make_int4(0, 0, 0, 0);
-	unsigned cnt = 0;
-#pragma unroll
-	for(int l = 0; l < 4; l++) cnt += (unsigned)__builtin_popcountll(__builtin_amdgcn_ballot_w64(S.hit[l]));
-	const Counters none = {0, 0, 0, 0, 0};
-	flushStats(A.s.stats, none, cnt, lane);
+#define SNAIL_MIRROR_PSTATS 0
+#include "materials_mirror_body.inc"
+#undef SNAIL_MIRROR_PSTATS
+}
+__global__ __launch_bounds__(64) void k_mat_mirror_heat(MatArgs A) {
+#define SNAIL_MIRROR_PSTATS 1
+#include "materials_mirror_body.inc"
+#undef SNAIL_MIRROR_PSTATS
 }
 
 } // namespace SNAIL_DEV_NS

@@ -56,6 +56,8 @@ struct SnailMaterials {
 		size_t tilesPackets = 0;
 		char *transp = nullptr;   // the per-level intermediates of the transparency frames (materials_transparency_host.inc), only once asked for; sized by
 		size_t transpBytes = 0;   // packets, lights and the depth asked for, grown under the same rule
+		uint32_t *pstats = nullptr;   // snail_materials_heatmap.h: the launch's per-packet TreeStats [packets][4] when the caller keeps none of its own; only
+		size_t pstatsPackets = 0;     // once asked for, grown under the same rule
 		hipEvent_t done = nullptr;
 		bool used = false;
 	};
@@ -276,7 +278,7 @@ int matSetDone(SnailMaterials::Set &W, const char *fn, int rc, hipStream_t st) {
 	// stream) must come after them.  Should the record itself fail, the set is marked grown-from-scratch: its next user synchronises the device.
 	if(hipEventRecord(W.done, st) == hipSuccess) W.used = true;
 	else {
-		W.packets = 0; W.bouncePackets = 0; W.tilesPackets = 0; W.transpBytes = 0; W.used = false;
+		W.packets = 0; W.bouncePackets = 0; W.tilesPackets = 0; W.transpBytes = 0; W.pstatsPackets = 0; W.used = false;
 		if(!rc) { snail_set_error("%s: hipEventRecord failed", fn); return 1; }
 	}
 	return rc;
@@ -502,6 +504,7 @@ void snail_materials_destroy(SnailMaterials *m) {
 		if(W.bounce) (void)hipFree(W.bounce);
 		if(W.tiles) (void)hipFree(W.tiles);
 		if(W.transp) (void)hipFree(W.transp);
+		if(W.pstats) (void)hipFree(W.pstats);
 		if(W.done) (void)hipEventDestroy(W.done);
 	}
 	freeInstTileJob(m->tileJob);

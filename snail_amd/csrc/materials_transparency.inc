@@ -8,7 +8,6 @@
 //   k_mat_continue / k_mat_continue_rays   Scene::TraceTransparency's packets (:620-634) from a level's rays, hits and selector, in the layout of
 //                          k_mat_mirror, + the order word under which launchRays leaves out a packet without a selected lane (orderedSlot)
 // Kernels of their own: the existing sample kernels stay as they are, and a set they can be given never holds these kinds (checkMaterials).
-// BUILD NOTE: the Makefile's source list does not name this file; after editing it alone, touch materials_host.inc (or make clean).
 // TWINS: matSampleTransp is k_mat_sample / k_mat_sample_rays (materials.inc) with the additions marked [T]; a change to the branches, the kinds
 // or the nine planes there belongs here too -- the planes of a set without these kinds are theirs byte for byte.
 namespace SNAIL_DEV_NS {
@@ -220,7 +219,9 @@ __global__ __launch_bounds__(64) void k_mat_sample_transp_rays(TranspArgs T) { m
 // packet goes as RayGroup<0, 0> when all 256 lanes are selected, else as RayGroup<0, 1>: the mask byte says which.
 // TWINS: the output -- layout, zeros for masked lanes (SafeInv(0) in idir), distance inf / -inf (:112-115), object 0, one mask byte per quad, the
 // nested call's TracingRays(CountMaskBits(mask)) (:116-117) -- is k_mat_mirror's (materials.inc) and k_final<SRC_PRIMARY, DST_CONTINUE>'s (snail_dev.inc).
-template <int SRC>
+// PSTATS (k_mat_continue_heat / _rays_heat): the nested call's TracingRays per packet as well (matLight's note, materials.inc); a packet that makes
+// no nested call -- none of its lanes selected, or absent from its level -- books nothing.
+template <int SRC, bool PSTATS = false>
 __device__ __forceinline__ void matContinue(const TranspArgs &T) {
 	const MatArgs &A = T.m;
 	const int lane = threadIdx.x & 63;
@@ -277,9 +278,12 @@ __device__ __forceinline__ void matContinue(const TranspArgs &T) {
 	if(lane == 0) T.order[P.pidx] = cnt ? li : -1;
 	const Counters none = {0, 0, 0, 0, 0};
 	flushStats(A.s.stats, none, cnt, lane);
+	if(PSTATS && cnt) bookPacketLate<ShadeArgs>(P.pidx, none, cnt, lane);
 }
 __global__ __launch_bounds__(64) void k_mat_continue(TranspArgs T) { matContinue<SRC_PRIMARY>(T); }
 __global__ __launch_bounds__(64) void k_mat_continue_rays(TranspArgs T) { matContinue<SRC_MIRROR>(T); }
+__global__ __launch_bounds__(64) void k_mat_continue_heat(TranspArgs T) { matContinue<SRC_PRIMARY, true>(T); }
+__global__ __launch_bounds__(64) void k_mat_continue_rays_heat(TranspArgs T) { matContinue<SRC_MIRROR, true>(T); }
 
 // ---- the way back up (include/snail_materials_transparency.h, frames).  The nested call's lights and outColor are matLight / matFinal of
 // materials.inc on the level's generic packets (SRC_MIRROR: rays, masks, hits, samples and shadow distances of that level), left out for a packet
@@ -291,6 +295,12 @@ __global__ __launch_bounds__(64) void k_mat_light_transp(TranspArgs T) {
 	__shared__ float lds[LDS_FLOATS_PER_WAVE];
 	if((int)blockIdx.x >= T.m.s.nPackets || transpSkipped(T, (int)blockIdx.x)) return;
 	matLight<DEEP, SRC_MIRROR>(T.m, lds);
+}
+template <bool DEEP>
+__global__ __launch_bounds__(64) void k_mat_light_transp_heat(TranspArgs T) {
+	__shared__ float lds[LDS_FLOATS_PER_WAVE];
+	if((int)blockIdx.x >= T.m.s.nPackets || transpSkipped(T, (int)blockIdx.x)) return;
+	matLight<DEEP, SRC_MIRROR, true>(T.m, lds);
 }
 __global__ __launch_bounds__(64) void k_mat_colour_transp(TranspArgs T) {
 	if((int)blockIdx.x >= T.m.s.nPackets || transpSkipped(T, (int)blockIdx.x)) return;

@@ -26,7 +26,9 @@ struct TreeArgs {
 // TWINS: the body -- Reflect, the origin's offset, the layout, zeros for masked lanes, SafeInv one component at a time through InvN<4> in the table
 // arithmetic, distance inf / -inf, object 0, one mask byte per quad and the nested call's TracingRays -- is k_mat_mirror's (materials.inc), which
 // names this kernel's source as its only difference; a change to either belongs in both.
-__global__ __launch_bounds__(64) void k_mat_mirror_rays(TreeArgs G) {
+// PSTATS (k_mat_mirror_rays_heat): the nested call's TracingRays per packet as well, as matMirror's; a packet that is not part of the level books nothing.
+template <bool PSTATS>
+__device__ __forceinline__ void matMirrorRays(const TreeArgs &G) {
 	const TranspArgs &T = G.t;
 	const MatArgs &A = T.m;
 	const int lane = threadIdx.x & 63;
@@ -86,7 +88,10 @@ __global__ __launch_bounds__(64) void k_mat_mirror_rays(TreeArgs G) {
 	for(int l = 0; l < 4; l++) cnt += (unsigned)__builtin_popcountll(__builtin_amdgcn_ballot_w64(S.hit[l]));
 	const Counters none = {0, 0, 0, 0, 0};
 	flushStats(A.s.stats, none, cnt, lane);
+	if(PSTATS) bookPacketLate<ShadeArgs>(P.pidx, none, cnt, lane);
 }
+__global__ __launch_bounds__(64) void k_mat_mirror_rays(TreeArgs G) { matMirrorRays<false>(G); }
+__global__ __launch_bounds__(64) void k_mat_mirror_rays_heat(TreeArgs G) { matMirrorRays<true>(G); }
 
 // ---- one packet: samples[q].diffuse += (reflColor - diffuse) * 0.3 on the hit lanes (= reflSel), specular untouched (src/scene_trace.cpp:462-465),
 // in place in the level's sample buffer T.bSamples, the nested call's outColor in T.bCol (floats [packet][256][3]).  It comes BEFORE

@@ -12,9 +12,18 @@ size_t treeBytes(size_t n, int nLights, int depth, bool refl) { return transpByt
 
 // The stages of one frame over the np packets of dXY (the scene's mu held) into `frame`, packet-major `bgrPackets` or, when colPackets is given,
 // float colours for k_inst_store.  W: level 0; the levels are carved at `arena` (treeBytes).  Without refl the sequence is matShadeTransp's.
+// pstats (a heat-map launch, include/snail_materials_heatmap.h; cleared by the caller): every stage that books into dStats -- the walks, the lights,
+// the generators and the mirrors -- also books per packet there, through its PSTATS / _heat instantiation, at the packet's index in dXY; the stages
+// that only make colours (both blends, the colour stages, k_mat_final) are left out, and frame / bgrPackets / colPackets are not written: no
+// selector, normal or position a counter depends on reads a colour.
+#define SNAIL_TREE_LAUNCH(ARGS_T, GRID, REC, K)                                                                                              \
+	do {                                                                                                                                   \
+		if(pstats) SNAIL_LAUNCH(sse, ARGS_T, GRID, wave, 0, st, REC, K##_heat);                                                            \
+		else SNAIL_LAUNCH(sse, ARGS_T, GRID, wave, 0, st, REC, K);                                                                         \
+	} while(0)
 int matShadeTree(SnailMaterials *m, const char *fn, const float cam[13], int resx, int resy, const int32_t *dXY, int np, const float *lights7, int nLights,
 				 const float ambient[3], uint8_t *frame, int pitch, uint8_t *bgrPackets, float *colPackets, const SnailMaterials::Bufs &W, char *arena, int maxDepth,
-				 bool refl, uint64_t *dTrunc, uint64_t *dStats, hipStream_t st) {
+				 bool refl, uint64_t *dTrunc, uint64_t *dStats, hipStream_t st, uint32_t *pstats = nullptr) {
 	SnailScene *s = m->scene;
 	SceneUse use(s, st);
 	if(use.rc) return use.rc;
@@ -23,7 +32,8 @@ int matShadeTree(SnailMaterials *m, const char *fn, const float cam[13], int res
 	char *p = L[0].carveExtra(arena, (size_t)np);
 	for(int k = 1; k <= D; k++) p = L[k].carve(p, (size_t)np, nLights);
 	if(refl) for(int j = 0; j <= D; j++) p = M[j].carve(p, (size_t)np, nLights);
-	if(int rc = launchPrimary(s, cam, resx, resy, 0, 0, 0, 0, dXY, np, W.hitT, W.hitU, W.hitV, W.hitId, dStats, st)) return rc;
+	if(int rc = launchPrimary(s, cam, resx, resy, 0, 0, 0, 0, dXY, np, W.hitT, W.hitU, W.hitV, W.hitId, dStats, st, nullptr, false, nullptr, nullptr, nullptr, nullptr, 0, pstats))
+		return rc;
 	dev::TreeArgs G;
 	memset(&G, 0, sizeof(G));
 	dev::TranspArgs &T = G.t;
@@ -37,6 +47,7 @@ int matShadeTree(SnailMaterials *m, const char *fn, const float cam[13], int res
 	A.s.frame = frame; A.s.pitch = pitch; A.s.bgrPackets = bgrPackets;
 	A.s.colPackets = colPackets;
 	A.s.stats = (dev::u64 *)dStats;
+	A.s.pstats = pstats;
 	A.rUVStride = 8;
 	T.trunc = (unsigned long long *)dTrunc;
 	const bool sse = s->arith == SNAIL_ARITH_HOST_SSE;
@@ -60,8 +71,8 @@ int matShadeTree(SnailMaterials *m, const char *fn, const float cam[13], int res
 		// the walk reads the barycentrics it was given and writes them back for lanes without a hit: zeros, not what the buffer last held
 		const hipError_t e = hipMemsetAsync(X.R.bary, 0, (size_t)np * 256 * 8, st);
 		if(e != hipSuccess) { snail_set_error("%s: hipMemsetAsync: %s", fn, hipGetErrorString(e)); lrc = 100 + (int)e; return; }
-		if(order) lrc = launchRays(s, false, np, 64, 0, X.R.rOrg, X.R.rDir, X.R.rIDir, X.R.rMask, X.R.rDist, X.R.rObj, X.R.bary, dStats, st, order, nullptr, np);
-		else lrc = launchRays(s, false, np, 64, 0, X.R.rOrg, X.R.rDir, X.R.rIDir, X.R.rMask, X.R.rDist, X.R.rObj, X.R.bary, dStats, st);
+		if(order) lrc = launchRays(s, false, np, 64, 0, X.R.rOrg, X.R.rDir, X.R.rIDir, X.R.rMask, X.R.rDist, X.R.rObj, X.R.bary, dStats, st, order, nullptr, np, nullptr, 0, pstats);
+		else lrc = launchRays(s, false, np, 64, 0, X.R.rOrg, X.R.rDir, X.R.rIDir, X.R.rMask, X.R.rDist, X.R.rObj, X.R.bary, dStats, st, nullptr, nullptr, 0, nullptr, 0, pstats);
 		if(lrc) return;
 		level(X, order);
 		T.opacity = X.opacity; T.sel = X.sel;
@@ -75,7 +86,7 @@ int matShadeTree(SnailMaterials *m, const char *fn, const float cam[13], int res
 		T.order = to.order;
 		T.cT = from.R.rDist; T.cSel = from.sel;
 		T.cOrg = from.R.rOrg; T.cDir = from.R.rDir; T.cIDir = from.R.rIDir;
-		SNAIL_LAUNCH(sse, TranspArgs, grid, wave, 0, st, T, k_mat_continue_rays);
+		SNAIL_TREE_LAUNCH(TranspArgs, grid, T, k_mat_continue_rays);
 		launched("k_mat_continue_rays");
 	};
 	auto truncated = [&](const TranspLevel &X, const int32_t *order) {
@@ -90,17 +101,20 @@ int matShadeTree(SnailMaterials *m, const char *fn, const float cam[13], int res
 	auto lightColour = [&](const TranspLevel &X, const int32_t *order, const TranspLevel *deeper) {
 		if(lrc) return;
 		level(X, order);
-		if(deeper) {
+		if(deeper && !pstats) {
 			T.bSamples = X.R.nSamples; T.bOpacity = X.opacity; T.bSel = X.sel; T.bCol = deeper->R.rCol;
 			SNAIL_LAUNCH(sse, TranspArgs, grid, wave, 0, st, T, k_mat_blend_transp);
 			launched("k_mat_blend_transp");
 		}
 		if(nLights && !lrc) {
-			if(useDeep(s)) SNAIL_LAUNCH(sse, TranspArgs, lgrid, wave, 0, st, T, k_mat_light_transp<true>);
+			if(pstats) {
+				if(useDeep(s)) SNAIL_LAUNCH(sse, TranspArgs, lgrid, wave, 0, st, T, k_mat_light_transp_heat<true>);
+				else SNAIL_LAUNCH(sse, TranspArgs, lgrid, wave, 0, st, T, k_mat_light_transp_heat<false>);
+			} else if(useDeep(s)) SNAIL_LAUNCH(sse, TranspArgs, lgrid, wave, 0, st, T, k_mat_light_transp<true>);
 			else SNAIL_LAUNCH(sse, TranspArgs, lgrid, wave, 0, st, T, k_mat_light_transp<false>);
 			launched("k_mat_light_transp");
 		}
-		if(!lrc) { SNAIL_LAUNCH(sse, TranspArgs, grid, wave, 0, st, T, k_mat_colour_transp); launched("k_mat_colour_transp"); }
+		if(!lrc && !pstats) { SNAIL_LAUNCH(sse, TranspArgs, grid, wave, 0, st, T, k_mat_colour_transp); launched("k_mat_colour_transp"); }
 	};
 
 	// ---- the way down of chain A: sample, then per level generator -> ordered walk -> nested sample ----
@@ -113,7 +127,7 @@ int matShadeTree(SnailMaterials *m, const char *fn, const float cam[13], int res
 			T.order = L[1].order;
 			T.cT = W.hitT; T.cSel = L[0].sel;
 			T.cOrg = T.cDir = T.cIDir = nullptr;
-			SNAIL_LAUNCH(sse, TranspArgs, grid, wave, 0, st, T, k_mat_continue);
+			SNAIL_TREE_LAUNCH(TranspArgs, grid, T, k_mat_continue);
 			launched("k_mat_continue");
 		} else generate(L[k - 1], L[k - 1].order, L[k]);
 		walkSample(L[k], L[k].order);
@@ -139,11 +153,11 @@ int matShadeTree(SnailMaterials *m, const char *fn, const float cam[13], int res
 				level(L[k], aOrder);
 				G.oOrg = M[k].R.rOrg; G.oDir = M[k].R.rDir; G.oIDir = M[k].R.rIDir; G.oDist = M[k].R.rDist; G.oObj = M[k].R.rObj; G.oMask = M[k].R.rMask;
 				G.oOrder = M[k].order;
-				SNAIL_LAUNCH(sse, TreeArgs, grid, wave, 0, st, G, k_mat_mirror_rays);
+				SNAIL_TREE_LAUNCH(TreeArgs, grid, G, k_mat_mirror_rays);
 				launched("k_mat_mirror_rays");
 			} else {
 				level(M[0], nullptr);
-				SNAIL_LAUNCH(sse, MatArgs, grid, wave, 0, st, A, k_mat_mirror);
+				SNAIL_TREE_LAUNCH(MatArgs, grid, A, k_mat_mirror);
 				launched("k_mat_mirror");
 			}
 			walkSample(M[k], bOrder);
@@ -154,7 +168,7 @@ int matShadeTree(SnailMaterials *m, const char *fn, const float cam[13], int res
 			truncated(M[D], D == k ? bOrder : M[D].order);
 			for(int j = D; j >= k; j--) lightColour(M[j], j == k ? bOrder : M[j].order, j < D ? &M[j + 1] : nullptr);
 			// diffuse += (refl - diffuse) * 0.3 on A_k's hit lanes, before its transparency blend
-			if(!lrc) {
+			if(!lrc && !pstats) {
 				if(k) {
 					level(L[k], aOrder);
 					T.bSamples = L[k].R.nSamples; T.bCol = M[k].R.rCol;
@@ -169,26 +183,31 @@ int matShadeTree(SnailMaterials *m, const char *fn, const float cam[13], int res
 		}
 		if(k) lightColour(L[k], aOrder, k < D ? &L[k + 1] : nullptr);
 	}
-	if(!lrc) {
+	if(!lrc && !pstats) {
 		level(L[1], nullptr);   // (the primary stages read none of a level's packets; rCol must not be left on a B level's)
 		T.bSamples = W.samples; T.bOpacity = L[0].opacity; T.bSel = L[0].sel; T.bCol = L[1].R.rCol;
 		SNAIL_LAUNCH(sse, TranspArgs, grid, wave, 0, st, T, k_mat_blend_transp);
 		launched("k_mat_blend_transp");
 	}
-	if(nLights && !lrc) {
+	if(nLights && !lrc && pstats) {
+		if(useDeep(s)) SNAIL_LAUNCH(sse, MatArgs, lgrid, wave, 0, st, A, k_mat_light_heat<true>);
+		else SNAIL_LAUNCH(sse, MatArgs, lgrid, wave, 0, st, A, k_mat_light_heat<false>);
+		launched("k_mat_light");
+	} else if(nLights && !lrc) {
 		if(useDeep(s)) SNAIL_LAUNCH(sse, MatArgs, lgrid, wave, 0, st, A, k_mat_light<true>);
 		else SNAIL_LAUNCH(sse, MatArgs, lgrid, wave, 0, st, A, k_mat_light<false>);
 		launched("k_mat_light");
 	}
 	for(int n = 0; n < nLights; n++)
 		if(relWhich[n] >= 0) { const int urc = relUsed(s, relWhich[n], st); if(!lrc) lrc = urc; }
-	if(lrc) return lrc;
+	if(lrc || pstats) return lrc;
 	// both blends are in the sample buffer: the colour stage without one of its own, bytes or the floats k_inst_store goes on from
 	if(colPackets) SNAIL_LAUNCH(sse, MatArgs, grid, wave, 0, st, A, k_mat_colour);
 	else SNAIL_LAUNCH(sse, MatArgs, grid, wave, 0, st, A, k_mat_final);
 	HIP_TRY(hipGetLastError());
 	return 0;
 }
+#undef SNAIL_TREE_LAUNCH
 
 const int kMatTreeFlags = SNAIL_RENDER_REFLECTIONS | SNAIL_RENDER_DEPTH | SNAIL_RENDER_AA4;
 
@@ -215,14 +234,18 @@ int64_t matTreeLevelBytes(int nLights, int flags, int maxDepth) {
 // the scene's mu held.  The packet list runs in slices of whole output packets, back to back on st over the same intermediates, so that the
 // levels stay within the set's budget (rounding makes the levels of n packets at most n times those of one); the float colours of ALL packets
 // and the sub-packet list are kept, and ONE k_inst_store follows the last slice.
+// heat (include/snail_materials_heatmap.h; never with SNAIL_RENDER_DEPTH): the per-packet TreeStats instead of the colours -- cleared on st in
+// dPacketStats or, when the caller keeps none, in the set's own array; every slice books at its packets' offset in the whole list's array; after
+// the last slice the counters' colours: dev_heat::k_heat_store straight into bgrPackets, or with a tint or tile planes dev_heat::k_heat_colours
+// into the set's float colours and the same ONE k_inst_store.  No output at all: the counters alone.
 int matTreeStore(SnailMaterials *m, const char *fn, const float cam[13], int resx, int resy, const int32_t *dXY, int np, const float *lights7, int nLights,
 				 const float ambient[3], int flags, const float *tint, uint8_t *bgrPackets, const InstTileJob *J, int maxDepth, uint64_t *dTrunc, uint64_t *dStats,
-				 hipStream_t st) {
+				 hipStream_t st, bool heat = false, uint32_t *dPacketStats = nullptr) {
 	if(flags & SNAIL_RENDER_DEPTH)   // gVals[1] returns before the full-shading branch: no level runs
 		return matShadeStore(m, fn, cam, resx, resy, dXY, np, lights7, nLights, ambient, flags, tint, bgrPackets, J, dStats, st);
 	SnailScene *s = m->scene;
 	const bool aa = (flags & SNAIL_RENDER_AA4) != 0, refl = (flags & SNAIL_RENDER_REFLECTIONS) != 0;
-	const bool floats = aa || tint || J;   // otherwise the lit packets as they are: bytes from k_mat_final
+	const bool floats = heat ? (tint || J) : (aa || tint || J);   // otherwise the lit packets as they are: bytes from k_mat_final (k_heat_store)
 	const int q = aa ? 4 : 1;
 	const int rx = aa ? resx * 2 : resx, ry = aa ? resy * 2 : resy;
 	const uint64_t one = (uint64_t)matTreeLevelBytes(nLights, flags, maxDepth);
@@ -248,21 +271,56 @@ int matTreeStore(SnailMaterials *m, const char *fn, const float cam[13], int res
 		HIP_TRY(hipMalloc((void **)&W.transp, want));
 		W.transpBytes = want;
 	}
+	uint32_t *pst = nullptr;
+	if(heat) {
+		if(!dPacketStats && (!W.pstats || W.pstatsPackets < n)) {   // grown under matNextSet's rule
+			HIP_TRY(hipDeviceSynchronize());
+			if(W.pstats) (void)hipFree(W.pstats);
+			const size_t packets = std::max(W.pstatsPackets, n);
+			W.pstats = nullptr; W.pstatsPackets = 0; W.used = false;
+			HIP_TRY(hipMalloc((void **)&W.pstats, packets * 16));
+			W.pstatsPackets = packets;
+		}
+		pst = dPacketStats ? dPacketStats : W.pstats;
+	}
 	SnailMaterials::Bufs B;
 	B.carve(W.base, ns);
 	SnailMaterials::TileBufs T;
 	if(floats) T.carve(W.tiles, n);
 	int rc = 0;
 	const int32_t *list = dXY;
+	if(aa && !floats) {   // (a heat launch without colours to reduce: the sub-packet list needs the tile part's list alone)
+		if(!W.tiles || W.tilesPackets < n) {
+			HIP_TRY(hipDeviceSynchronize());
+			if(W.tiles) (void)hipFree(W.tiles);
+			const size_t packets = std::max(W.tilesPackets, n);
+			W.tiles = nullptr; W.tilesPackets = 0; W.used = false;
+			HIP_TRY(hipMalloc((void **)&W.tiles, SnailMaterials::TileBufs::bytes(packets)));
+			W.tilesPackets = packets;
+		}
+		T.carve(W.tiles, n);
+	}
 	if(aa) {
 		hipLaunchKernelGGL(dev::k_inst_aa_packets, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const int2 *)dXY, np, (int2 *)T.xy2);
 		list = T.xy2;
 	}
+	if(heat) {
+		const hipError_t e = hipMemsetAsync(pst, 0, n * 16, st);
+		if(e != hipSuccess) { snail_set_error("%s: hipMemsetAsync: %s", fn, hipGetErrorString(e)); rc = 100 + (int)e; }
+	}
 	for(int a = 0; a < np && !rc; a += slice) {
 		const int cnt = std::min(slice, np - a);
 		const size_t at = (size_t)a * q;   // the slice's first packet in `list` and in the colours
-		rc = matShadeTree(m, fn, cam, rx, ry, list + at * 2, cnt * q, lights7, nLights, ambient, nullptr, 0, floats ? nullptr : bgrPackets + at * 768,
-						  floats ? T.col + at * 768 : nullptr, B, W.transp, maxDepth, refl, dTrunc, dStats, st);
+		if(heat) rc = matShadeTree(m, fn, cam, rx, ry, list + at * 2, cnt * q, lights7, nLights, ambient, nullptr, 0, nullptr, nullptr, B, W.transp, maxDepth, refl, dTrunc, dStats, st, pst + at * 4);
+		else rc = matShadeTree(m, fn, cam, rx, ry, list + at * 2, cnt * q, lights7, nLights, ambient, nullptr, 0, floats ? nullptr : bgrPackets + at * 768,
+							   floats ? T.col + at * 768 : nullptr, B, W.transp, maxDepth, refl, dTrunc, dStats, st);
+	}
+	if(!rc && heat && (floats || bgrPackets)) {   // no new colour arithmetic: the stores of heatmap.inc
+		if(floats) hipLaunchKernelGGL(dev_heat::k_heat_colours, dim3((unsigned)n), dim3(64), 0, st, (const unsigned *)pst, (int)n, T.col);
+		else if(aa) hipLaunchKernelGGL(dev_heat::k_heat_store<true>, dim3((unsigned)np), dim3(64), 0, st, (const unsigned *)pst, np, bgrPackets);
+		else hipLaunchKernelGGL(dev_heat::k_heat_store<false>, dim3((unsigned)np), dim3(64), 0, st, (const unsigned *)pst, np, bgrPackets);
+		const hipError_t e = hipGetLastError();
+		if(e != hipSuccess) { snail_set_error("%s: the heat store: %s", fn, hipGetErrorString(e)); rc = 100 + (int)e; }
 	}
 	if(!rc && floats) {
 		const bool sse = s->arith == SNAIL_ARITH_HOST_SSE;

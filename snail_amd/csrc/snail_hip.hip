@@ -725,10 +725,18 @@ int launchRays(SnailScene *s, bool shadow, int nPackets, int size, int sharedOri
 			hipLaunchKernelGGL(dev::k_shadow<false>, dim3(blocks), dim3(64), 0, stream, A);
 			hipLaunchKernelGGL(dev::k_shadow_exact<false>, dim3(exactBlocks), dim3(64), 0, stream, A);
 		}
-	} else if(A.pstats) { // the mirrored packets of a heat-map launch (per-ray origins, masks, no barycentrics): the instantiations that book per packet as well
-		if(sharedOrigin || !mask || bary) { snail_set_error("per-packet counters: mirrored packets only"); return 1; }
+	} else if(A.pstats) { // the mirrored packets of a heat-map launch (per-ray origins, masks): the instantiations that book per packet as well
+		if(sharedOrigin || !mask) { snail_set_error("per-packet counters: mirrored packets only"); return 1; }
 		const bool sse = s->arith == SNAIL_ARITH_HOST_SSE;
-		if(useDeep(s)) {
+		if(bary) { // the levels of full shading (materials_tree_host.inc): with barycentrics, under the level's order list -- p is the logical packet there too
+			if(useDeep(s)) {
+				SNAIL_LAUNCH(sse, RaysArgs, dim3(blocks), dim3(64), 0, stream, A, k_rays<false, true, true, true, true>);
+				SNAIL_LAUNCH(sse, RaysArgs, EP.grid, EP.block, EP.lds, stream, A, k_rays_exact<false, true, true, true, true>);
+			} else {
+				SNAIL_LAUNCH(sse, RaysArgs, dim3(blocks), dim3(64), 0, stream, A, k_rays<false, true, false, true, true>);
+				SNAIL_LAUNCH(sse, RaysArgs, EP.grid, EP.block, EP.lds, stream, A, k_rays_exact<false, true, false, true, true>);
+			}
+		} else if(useDeep(s)) {
 			SNAIL_LAUNCH(sse, RaysArgs, dim3(blocks), dim3(64), 0, stream, A, k_rays<false, true, true, false, true>);
 			SNAIL_LAUNCH(sse, RaysArgs, EP.grid, EP.block, EP.lds, stream, A, k_rays_exact<false, true, true, false, true>);
 		} else {
@@ -1806,4 +1814,5 @@ int snail_account_primary(SnailScene *s, const float cam[13], int resx, int resy
 #include "materials_tiles_host.inc"
 #include "materials_transparency_host.inc"
 #include "materials_tree_host.inc"
+#include "materials_heat_host.inc"
 #include "materials_dynamic_host.inc"

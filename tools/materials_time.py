@@ -53,10 +53,19 @@ rebuild and one frame at --res per step, in the same run and alternating:
   repack_alone MaterialSet.update_dev alone (k_shd_pack), device events, launch to launch.
 The two routes' last frames are compared byte for byte first.  No rate is promised: the rows are the record.  --out APPENDS.
 
+--heat [--reflections] [--aa] [--tiles]: the gVals[5] heat-map under full shading (include/snail_materials_heatmap.h) on the `room` case at --res,
+max_depth 8, beside the lit frame it replaces, with the same arguments, in the same run and the same build, the two alternating:
+snail_materials_heat_packets_dev against snail_materials_tree_frame_packets_dev over the frame's packet list, both asynchronous -- device events
+around a window of --frames launches enqueued back to back; with --tiles snail_materials_render_heat_tiles against
+snail_materials_tree_render_tiles over the 16x64 tile map, host calls that return after their device-to-host copy -- host clock, call by call.
+The heat launch runs fewer kernels (no blend, no colour stage) plus a few atomics per wave; the report states both times and their ratio, and
+says so if the heat-map came out slower.  The two launches' TreeStats are compared first.  No gate: a measurement.  --out APPENDS.
+
     python tools/materials_time.py [--res 1920x1080] [--frames 400] [--reps 7] [--parent-lib PATH] [--out profiles/materials.txt] [--trace N] [--reflections]
                                    [--tiles [--aa] [--commit LABEL]] [--transparency N]
                                    [--tree [--reflections] [--aa] [--tiles]]
-                                   [--dynamic [--sheet 180x140]]"""
+                                   [--dynamic [--sheet 180x140]]
+                                   [--heat [--reflections] [--aa] [--tiles]]"""
 import argparse
 import ctypes as C
 import os
@@ -110,6 +119,7 @@ def main():
     ap.add_argument("--transparency", type=int, default=0, metavar="N")
     ap.add_argument("--tree", action="store_true")
     ap.add_argument("--dynamic", action="store_true")
+    ap.add_argument("--heat", action="store_true")
     ap.add_argument("--sheet", default="180x140")
     a = ap.parse_args()
     resx, resy = (int(v) for v in a.res.split("x"))
@@ -119,6 +129,8 @@ def main():
     from tests import materials_cases as K
     if a.transparency:
         return transparency(a)
+    if a.heat:
+        return heat(a, resx, resy)
     if a.tree:
         return tree(a, resx, resy)
     if a.dynamic:
@@ -453,6 +465,89 @@ def tree(a, resx, resy):
     if a.out:
         with open(a.out, "a") as fh:
             fh.write(text + "\n")
+
+
+def heat(a, resx, resy):
+    """--heat: the heat-map of the room case beside the lit frame it replaces, same arguments"""
+    import time
+
+    import torch
+    from snail_amd.render import divide_image
+    from tests import materials_tree_cases as K
+    c = K.room()
+    sc = Scene(HostBVH.build(c["tv"]), 0)
+
+    def material(d):
+        if d[0] == "transp":
+            return P.Material.transparent(d[1], d[2], d[3])
+        if d[0] == "uber":
+            return P.Material.uber(d[1], d[2], d[3])
+        return P.Material.simple(d[1], d[2]) if d[0] == "simple" else P.Material.textured(d[1], d[2])
+    ms = P.MaterialSet(sc, c["uv"], c["nrm"], c["mat_index"], c["flat"], c["material_map"], [material(d) for d in c["descs"]], [P.Texture(t) for t in c["textures"]], transparent=True)
+    flags = (P.RENDER_REFLECTIONS if a.reflections else 0) | (P.RENDER_AA4 if a.aa else 0)
+    pw, ph = (resx + 15) // 16, (resy + 15) // 16
+    xy = torch.tensor([(x * 16, y * 16) for y in range(ph) for x in range(pw)], dtype=torch.int32, device="cuda:0")
+    out = [torch.zeros((pw * ph, 256, 3), dtype=torch.uint8, device="cuda:0") for _ in range(2)]
+    trunc = torch.zeros(1, dtype=torch.int64, device="cuda:0")
+    st = [sc.new_stats(), sc.new_stats()]
+    tl = divide_image(resx, resy)
+    data = np.zeros(int((3 * tl[:, 2].astype(np.int64) * tl[:, 3]).sum()), dtype=np.uint8)
+    htrunc = np.zeros(1, dtype=np.uint64)
+    if a.tiles:
+        variants = {"tree_tiles": lambda s=None: ms.render_tree_tiles_host(c["cam"], resx, resy, tl, lights7=c["lights"], flags=flags, data=data, truncated=htrunc),
+                    "heat_tiles": lambda s=None: ms.render_heat_tiles_host(c["cam"], resx, resy, tl, lights7=c["lights"], flags=flags, data=data, truncated=htrunc)}
+    else:
+        variants = {"tree_packets": lambda s=None: ms.tree_frame_packets(c["cam"], resx, resy, xy, c["lights"], flags=flags, out=out[0], stats=s, truncated=trunc),
+                    "heat_packets": lambda s=None: ms.render_heat_packets(c["cam"], resx, resy, xy, c["lights"], flags=flags, out=out[1], stats=s, truncated=trunc)}
+    for fn in variants.values():        # warm-up: code objects, every group of the set's intermediates at its largest, the cached tile job
+        for _ in range(9):
+            fn()
+    torch.cuda.synchronize()
+    if a.tiles:
+        got = [fn()[2] for fn in variants.values()]
+    else:
+        for fn, s in zip(variants.values(), st):
+            fn(s)
+        torch.cuda.synchronize()
+        got = [s.cpu().numpy() for s in st]
+    same = bool(np.array_equal(got[0], got[1]))
+    times = {k: [] for k in variants}
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    for _ in range(a.reps):
+        for k, fn in variants.items():      # alternating: one window of each per round
+            if a.tiles:
+                t0 = time.perf_counter()
+                for _ in range(a.frames):
+                    fn()
+                times[k].append((time.perf_counter() - t0) * 1e3 / a.frames)
+            else:
+                e0.record()
+                for _ in range(a.frames):
+                    fn()
+                e1.record()
+                e1.synchronize()
+                times[k].append(e0.elapsed_time(e1) / a.frames)
+    med = {k: statistics.median(v) for k, v in times.items()}
+    lit, hm = list(med)
+    ratio = med[hm] / med[lit]
+    lines = ["", "the heat-map under full shading [%s]: room case (%d triangles), its two lights, IEEE, %dx%d (%d packets), flags %s%s, max_depth 8; %d rounds of %d calls per "
+             "variant, alternating, after 9 warm-up calls each; %s, ms per call: median (min .. max)" % (
+                 a.commit, len(c["tv"]), resx, resy, pw * ph, "REFLECTIONS " if a.reflections else "", "AA4" if a.aa else "", a.reps, a.frames,
+                 "host clock, call by call (each call ends in its device-to-host copy)" if a.tiles else "device events around a window enqueued back to back"),
+             "device: %s" % torch.cuda.get_device_name(0),
+             "%s = %s; %s = %s, the same arguments" % ((lit, "snail_materials_tree_render_tiles", hm, "snail_materials_render_heat_tiles") if a.tiles else
+                                                      (lit, "snail_materials_tree_frame_packets_dev", hm, "snail_materials_heat_packets_dev")),
+             "TreeStats of the two launches equal: %s (%s)" % (same, np.asarray(got[1]).tolist())]
+    for k, v in times.items():
+        lines.append("  %-14s %9.3f  (%.3f .. %.3f)" % (k, med[k], min(v), max(v)))
+    lines.append("  %s / %s: %.3f%s" % (hm, lit, ratio, "   -- the heat-map is SLOWER than the frame it replaces" if ratio > 1.0 else ""))
+    text = "\n".join(lines)
+    print(text)
+    if a.out:
+        with open(a.out, "a") as fh:
+            fh.write(text + "\n")
+    if not same:
+        raise SystemExit("the heat launch's TreeStats differ from the lit frame's")
 
 
 def dynamic(a, resx, resy):
