@@ -89,6 +89,8 @@ __device__ __forceinline__ void instLoadSamples(const InstShadeArgs &A, const Pa
 }
 
 // ---- one (packet, light): the shadow packet (src/scene_trace.cpp:538-558) and DBVH::TraverseShadow ----
+// TWINS: k_imat_light (instances_materials.inc) is this kernel with the samples of full shading (matLoadSamples) in place of instLoadSamples; a
+// change to the shadow packet, the walk or the stats flush belongs there too.
 template <bool DEEP, int SRC, bool PSTATS = false>
 __global__ __launch_bounds__(64) void k_inst_light(InstShadeArgs A) {
 	__shared__ float lds[LDS_FLOATS_PER_WAVE];

@@ -162,7 +162,8 @@ __device__ __forceinline__ PacketPos matPacket(const MatArgs &A, int li) {
 	return P;
 }
 
-// (TWINS: k_mat_sample_rays below is this kernel for generic packets; a change to the branches, the kinds or the output belongs in both.)
+// (TWINS: k_mat_sample_rays below is this kernel for generic packets, k_imat_sample (instances_materials.inc) for instanced scenes; a change to
+// the branches, the kinds or the output belongs in all three.)
 __global__ __launch_bounds__(64) void k_mat_sample(MatArgs A) {
 	const int lane = threadIdx.x & 63;
 	const int li = (int)blockIdx.x;
@@ -471,7 +472,8 @@ __device__ __forceinline__ void matLoadSamples(const MatArgs &A, const PacketPos
 // ---- one (packet, light): the shadow packet (src/scene_trace.cpp:538-558) and BVH::TraverseShadow, by the walks of lightPacket ----
 // TWINS: the set-up and the walk selection below are those of lightPacket (snail_dev.inc; its main pass and its deferred M_EXACT pass folded into
 // one kernel, look-ups checked), and k_inst_light (instances_shade.inc) has the same set-up around the instanced walk.  A change to the shadow
-// packet, to the classify / walkSharedAsm / walk dispatch or to the stats booking belongs in all three.
+// packet, to the classify / walkSharedAsm / walk dispatch or to the stats booking belongs in all three.  k_imat_light (instances_materials.inc)
+// is this function's sample load and set-up around k_inst_light's walk: a change to the shadow packet belongs there as well.
 // SRC_MIRROR: the nested call's lights on the mirrored packets' samples -- the same shadow packet (the light's shared origin) and walks.
 // PSTATS: the heat-map launches' instantiation (include/snail_materials_heatmap.h), which also books the (packet, light)'s counters per packet at
 // P.pidx -- a template argument as in snail_dev.inc, so that the other launches' kernels stay the code they were.  A culled pair has returned

@@ -425,14 +425,12 @@ static bool matCheckHost(const char *fn, bool transp, bool dynamic, const void *
 	return true;
 }
 
-// shtris64 null: the records' room is left zeroed (snail_materials_create_dev packs them on the device)
-static SnailMaterials *matUpload(const char *fn, bool canSelect, SnailScene *scene, const void *shtris64, int nTris, const int32_t *matMap, int nMap, const SnailMaterial *mats,
-								 int nMats, const int32_t *opacityTexture, const SnailTexture *textures, int nTex) {
-	if(checkScene(scene, fn)) return nullptr;
-	if(nTris != scene->nTris) { snail_set_error("%s: %d records for a scene of %d triangles", fn, nTris, scene->nTris); return nullptr; }
-
-	// the device copy
-	std::vector<dev::MatRec> recs((size_t)std::max(nMats, 1));
+// The device form of a checked material and texture list (the creators here and snail_instances_materials_create): one MatRec per material, one
+// TexRec per texture with its levels' offsets -> the bytes the texels take, every texture's base set.  opacityTexture: read for the
+// transparent kind alone.
+static size_t matPackLists(const SnailMaterial *mats, int nMats, const int32_t *opacityTexture, const SnailTexture *textures, int nTex, std::vector<dev::MatRec> &recs,
+						   std::vector<dev::TexRec> &trecs) {
+	recs.assign((size_t)std::max(nMats, 1), dev::MatRec());
 	memset(recs.data(), 0, recs.size() * sizeof(dev::MatRec));
 	for(int k = 0; k < nMats; k++) {
 		dev::MatRec &R = recs[k];
@@ -443,7 +441,7 @@ static SnailMaterials *matUpload(const char *fn, bool canSelect, SnailScene *sce
 		for(int c = 0; c < 3; c++) { R.col[c] = mats[k].diffuse[c]; R.spec[c] = mats[k].specular[c]; }
 		if(mats[k].kind == SNAIL_MAT_UBER) std::swap(R.col[0], R.col[2]);   // UberMaterial::UberMaterial: Swap(diffuse.x, diffuse.z)
 	}
-	std::vector<dev::TexRec> trecs((size_t)std::max(nTex, 1));
+	trecs.assign((size_t)std::max(nTex, 1), dev::TexRec());
 	memset(trecs.data(), 0, trecs.size() * sizeof(dev::TexRec));
 	size_t texelBytes = 0;
 	for(int k = 0; k < nTex; k++) {
@@ -453,6 +451,19 @@ static SnailMaterials *matUpload(const char *fn, bool canSelect, SnailScene *sce
 		for(int l = 0; l < T.mips; l++) { T.lvl[l] = (unsigned)off; off += matLevelBytes(T.w, T.h, l); }
 		texelBytes += (off + 4 + 15) & ~(size_t)15;   // 4 bytes of padding: a tap may be read as 4 bytes
 	}
+	return texelBytes;
+}
+
+// shtris64 null: the records' room is left zeroed (snail_materials_create_dev packs them on the device)
+static SnailMaterials *matUpload(const char *fn, bool canSelect, SnailScene *scene, const void *shtris64, int nTris, const int32_t *matMap, int nMap, const SnailMaterial *mats,
+								 int nMats, const int32_t *opacityTexture, const SnailTexture *textures, int nTex) {
+	if(checkScene(scene, fn)) return nullptr;
+	if(nTris != scene->nTris) { snail_set_error("%s: %d records for a scene of %d triangles", fn, nTris, scene->nTris); return nullptr; }
+
+	// the device copy
+	std::vector<dev::MatRec> recs;
+	std::vector<dev::TexRec> trecs;
+	const size_t texelBytes = matPackLists(mats, nMats, opacityTexture, textures, nTex, recs, trecs);
 	typedef HostCallScope H;
 	const size_t oTris = 0, oMap = oTris + H::pad((size_t)nTris * 64), oMats = oMap + H::pad((size_t)nMap * 4), oTex = oMats + H::pad(recs.size() * sizeof(dev::MatRec)),
 				 oTexels = oTex + H::pad(trecs.size() * sizeof(dev::TexRec)), total = oTexels + H::pad(texelBytes + 16);

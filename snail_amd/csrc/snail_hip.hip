@@ -79,6 +79,7 @@ void snail_set_error(const char *fmt, ...) {
 #include "instances.inc"
 #include "instances_shade.inc"
 #include "materials.inc"
+#include "instances_materials.inc"
 #include "materials_transparency.inc"
 #include "materials_tree.inc"
 #undef SNAIL_DEV_NS
@@ -89,6 +90,7 @@ void snail_set_error(const char *fmt, ...) {
 #include "instances.inc"
 #include "instances_shade.inc"
 #include "materials.inc"
+#include "instances_materials.inc"
 #include "materials_transparency.inc"
 #include "materials_tree.inc"
 #undef SNAIL_DEV_NS
@@ -1816,3 +1818,4 @@ int snail_account_primary(SnailScene *s, const float cam[13], int resx, int resy
 #include "materials_tree_host.inc"
 #include "materials_heat_host.inc"
 #include "materials_dynamic_host.inc"
+#include "instances_materials_host.inc"

@@ -33,7 +33,15 @@ instances (default here 1024,10000): host wall ms per frame of each, synchronise
 Alternating runs (each round: update(), one untimed update_dev, the timed update_dev -- the steady state of a loop that stays on the device),
 medians.
 
-    python tools/instances_time.py --rebuild-dev [--rebuild-counts 1024,10000] [--reps 15]"""
+    python tools/instances_time.py --rebuild-dev [--rebuild-counts 1024,10000] [--reps 15]
+
+--materials: what FULL shading costs on an instanced frame (include/snail_instances_materials.h; one light, atrium with procedural uv,
+normals and materials, both arithmetics): host wall ms per frame, synchronised, of
+  full    InstancedMaterialSet.render (snail_instances_render_materials_dev): k_inst_frame, k_imat_sample, k_imat_light, k_mat_final;
+  simple  InstancedScene.render_whitted of the same scene, camera and light (simple shading: one colour, plane normals).
+Alternating runs, medians.
+
+    python tools/instances_time.py --materials [--reps 3]"""
 import argparse
 import json
 import os
@@ -74,6 +82,7 @@ def main():
     ap.add_argument("--rebuild-dev", action="store_true")
     ap.add_argument("--lit", action="store_true")
     ap.add_argument("--tiles", action="store_true")
+    ap.add_argument("--materials", action="store_true")
     ap.add_argument("--baseline-lib", default=None)
     a = ap.parse_args()
     resx, resy = (int(x) for x in a.res.split("x"))
@@ -84,6 +93,8 @@ def main():
         return lit(torch, a, resx, resy)
     if a.tiles:
         return tiles(torch, a, resx, resy)
+    if a.materials:
+        return materials(torch, a, resx, resy)
     rays = resx * resy
     out = {"res": a.res, "unit": "Mrays/s (best of %d launches)" % a.reps, "rows": []}
     meshes = {"atrium": lambda: scenes.atrium(),
@@ -259,6 +270,70 @@ def tiles(torch, a, resx, resy):
         out["rows"].append(row)
         print(json.dumps(row), file=sys.stderr, flush=True)
         isc.close()
+    sc.close()
+    print(json.dumps(out))
+
+
+def procedural_shading(hb, tv, seed=7):
+    """uv, per-vertex normals (the plane normal bent, not normalised again), material index and flat flags of the INPUT triangles, and a
+    material list with every kind the full-shading kernels know: (uv, nrm, mat_index, flat, material_map, materials, textures)"""
+    from snail_amd import materials as P
+    n = len(tv)
+    rng = np.random.RandomState(seed)
+    plane = np.zeros((n, 3), dtype=np.float32)
+    plane[hb.perm] = hb.tris.view(np.float32).reshape(-1, 16)[:, 12:15]
+    plane[~np.isfinite(plane).all(axis=1)] = (0.0, 1.0, 0.0)
+    uv = ((rng.rand(n, 1, 2) * 4.0 - 2.0) + (rng.rand(n, 3, 2) - 0.5)).astype(np.float32)
+    nrm = (plane[:, None, :] + (rng.rand(n, 3, 3) - 0.5) * 0.6).astype(np.float32)
+    ys, xs = np.meshgrid(np.arange(64), np.arange(64), indexing="ij")
+    tex = [np.clip((((xs // 8 + ys // 8) & 1) * 120 + 40)[..., None] + rng.randint(-40, 90, size=(64, 64, 3)), 0, 255).astype(np.uint8),
+           rng.randint(0, 256, size=(8, 32, 3)).astype(np.uint8)]
+    mats = [P.Material.simple((0.3, 0.8, 0.6), False), P.Material.textured(0, True), P.Material.textured(1, False),
+            P.Material.uber((0.9, 0.4, 0.1), (0.2, 0.6, 1.0), 0.0), P.Material.uber((0.2, 0.7, 0.5), (1.0, 0.3, 0.1), 1.0)]
+    # materials in runs of 64 input triangles (neighbouring triangles mostly share one, as in a modelled mesh)
+    return uv, nrm, ((np.arange(n) // 64) % 6).astype(np.int32), (np.arange(n) % 3) == 1, [-1, 0, 1, 2, 3, 4], mats, [P.Texture(t) for t in tex]
+
+
+def materials(torch, a, resx, resy):
+    import statistics
+    import time
+    from snail_amd.instances_materials import InstancedMaterialSet
+    rays = resx * resy
+    tv = scenes.atrium()
+    hb = HostBVH.build(tv)
+    sc = Scene(hb, 0)
+    lo, hi = sc.get_bbox()
+    uv, nrm, mi, flat, mmap, mats, texs = procedural_shading(hb, tv)
+    out = {"res": a.res, "lights": 1, "unit": "host wall ms per frame, synchronised, median of %d alternating runs" % a.reps, "rows": []}
+    for arith in ("ieee", "host_sse"):
+        sc.set_arith(arith)
+        for n in (int(c) for c in a.counts.split(",")):
+            rot, tr, bi = scenes.instance_field(lo, hi, n, seed=1)
+            isc = InstancedScene([sc], rot, tr, bi)
+            ms_set = InstancedMaterialSet(isc, [(uv, nrm, mi, flat, mmap)], mats, texs)
+            nd = isc.nodes()[0]
+            cam = survey_camera(tv) if n == 1 else survey_camera(np.concatenate([nd["bmin"], nd["bmax"], nd["bmin"]]).reshape(1, 9))
+            c, ext = (nd["bmin"] + nd["bmax"]) * 0.5, nd["bmax"] - nd["bmin"]
+            light = np.array([[c[0], c[1] + 0.3 * ext[1], c[2], 1.0, 1.0, 1.0, float(np.linalg.norm(ext))]], dtype=np.float32)
+            frame = torch.zeros((resy, resx, 3), dtype=torch.uint8, device="cuda")
+            runs = {"full": lambda: ms_set.render(cam, resx, resy, light, out=frame), "simple": lambda: isc.render_whitted(cam, resx, resy, light, out=frame)}
+            ms = {k: [] for k in runs}
+            for k, fn in runs.items():      # warm-up: the sets' intermediates, the cached packet lists, first launches
+                fn(); fn(); torch.cuda.synchronize()
+            for _ in range(a.reps):         # alternating
+                for k, fn in runs.items():
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter(); fn(); torch.cuda.synchronize()
+                    ms[k].append((time.perf_counter() - t0) * 1e3)
+            row = {"arith": arith, "instances": n, "nonblack_pixels": int((frame.cpu().numpy() != 0).any(axis=2).sum())}
+            for k in ms:
+                m = statistics.median(ms[k])
+                row[k + "_ms"] = round(m, 3); row[k + "_min_ms"] = round(min(ms[k]), 3); row[k + "_mrays"] = round(rays / m / 1e3, 1)
+            row["full_over_simple"] = round(row["full_ms"] / row["simple_ms"], 3)
+            out["rows"].append(row)
+            print(json.dumps(row), file=sys.stderr, flush=True)
+            ms_set.close()
+            isc.close()
     sc.close()
     print(json.dumps(out))
 
