@@ -57,9 +57,16 @@ void snail_instances_materials_destroy(SnailInstancesMaterials *);
  *   association, texDiff = 0, mip 0).  The "triId 0" quirk becomes the (slot 0, triId 0) quirk: in a quad whose lane 0 missed, a lane that hit
  *   slot 0's triangle 0 keeps the default material and zero normal / texCoord.
  * Material kinds, PointSampler::Sample, the mip choice and the values of lanes that missed are those of snail_materials_shade_packets_dev.
- * The instance records are read at launch: after snail_instances_update / _rebuild_dev the same set shades with the new rotations.  Slots
- * and triIds outside the scene are clamped.  The barycentric deviation of snail_instances.h (u / v stored at the hit's own quad) is
- * inherited. */
+ * The instance records are read at launch: after snail_instances_update / _rebuild_dev the same set shades with the new rotations.
+ * A hit lane's slot or triId outside the scene (a lane that missed carries (0, 0) whatever it holds):
+ *   the slot is clamped to [0, capacity - 1], capacity = the instance records the handle has room for.  That is the instance count unless an
+ *       update shrank it; a slot between the two reads a stale record.
+ *   the triId is clamped below to 0.  The block and quad comparisons and the quirk are taken on (clamped slot, lower-clamped triId): the
+ *       triId's upper bound is its BLAS's nTris, which needs the slot's record, and the comparisons come before any record is read.
+ *   the record read is that of min(triId, nTris - 1) of the slot's BLAS.  Two hit lanes of one slot with triIds nTris + 7 and nTris + 9 read
+ *       the same record and still do not count as a single triangle.
+ * These clamps keep a corrupted hit record from turning into an address; a traversal never produces such records.
+ * The barycentric deviation of snail_instances.h (u / v stored at the hit's own quad) is inherited. */
 int snail_instances_materials_shade_packets_dev(SnailInstancesMaterials *, const float cam[13], int resx, int resy, const int32_t *d_packet_xy, int nPackets,
                                                 const float *d_t, const float *d_u, const float *d_v, const int32_t *d_inst, const int32_t *d_triId,
                                                 float *d_samples, void *stream);

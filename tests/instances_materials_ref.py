@@ -26,6 +26,8 @@ class Diag(M.Diag):
         self.cross_instance_same_tri = 0      # full blocks whose 16 lanes hit the same triId of the same BLAS in at least two slots
         self.shared_material_unmasked = 0     # blocks of (b) ending in the unmasked Shade whose lanes lie in at least two different BLASes
         self.rotated_lanes = 0                # hit lanes whose slot's rotation is not the identity
+        self.cross_blas_same_tri = 0          # full blocks whose 16 lanes carry the same triId in slots of at least two BLASes
+        self.shared_material_unmasked_uber = 0      # ... of shared_material_unmasked, the blocks whose one material is UBER
 
 
 def rot_vec(rot, v):
@@ -90,6 +92,8 @@ class InstMaterialsRef(M.MaterialsRef):
                 obj0, el0 = int(objc[4 * b, 0]), int(elc[4 * b, 0])
                 if full and bool((elc[qs] == el0).all()) and len(np.unique(self.ref.bi[objc[qs]])) == 1 and len(np.unique(objc[qs])) > 1:
                     diag.cross_instance_same_tri += 1
+                if full and bool((elc[qs] == el0).all()) and len(np.unique(self.ref.bi[objc[qs]])) > 1:
+                    diag.cross_blas_same_tri += 1
                 if full and bool(((objc[qs] == obj0) & (elc[qs] == el0)).all()):
                     # (a) 4x4 full, single triangle of a single instance
                     diag.blocks_a += 1
@@ -145,6 +149,7 @@ class InstMaterialsRef(M.MaterialsRef):
                     diag.blocks_b += 1
                     if len(np.unique(self.ref.bi[objc[qs]])) > 1:
                         diag.shared_material_unmasked += 1
+                        diag.shared_material_unmasked_uber += int(self.mat(m0).kind == M.UBER)
                     self.shade(m0, d[qs], nrm[qs], tc[qs], tdiff[qs], None, diffuse[qs], specular[qs], diag)
                 else:
                     ids = []
