@@ -9,8 +9,8 @@
  * GetMaterialId (:246-248), the (object, element) comparisons of Scene::RayTrace under isctFlags & fElement (src/scene_trace.cpp:162,
  * :179-182, :252-253, :263), and the instantiation of Scene<DBVH>::RayTrace (:642-659).
  *
- * NOT here: the mirrored bounce (gVals[7]), the transparency continuation, tile lists, 4x antialiasing and the tint, the heat-map under
- * full shading and multi-device frames of instanced scenes; routing in snail_adapter.hpp (no reference host can reach this branch through
+ * NOT here (the mirrored bounce of gVals[7] is snail_instances_materials_bounce.h's): the transparency continuation, tile lists, 4x
+ * antialiasing and the tint, the heat-map under full shading and multi-device frames of instanced scenes; routing in snail_adapter.hpp (no reference host can reach this branch through
  * HipDBVH); device-packed records for BLASes whose tree is rebuilt on the device (a set made before such a rebuild shades with another
  * triangle's data: build the BLASes from host triangles).
  */

@@ -70,6 +70,8 @@ __device__ __forceinline__ ShTri imatLoadTri(const IMatArgs &A, int slot, int tr
 // TWINS: this kernel is k_mat_sample (materials.inc) for an instanced scene: a block's key is the pair (slot, triId) and a record comes through
 // imatLoadTri; everything else -- blocks, the (slot 0, triId 0) quirk, texDiff, the mip choice, the kinds, the output -- is k_mat_sample's; a
 // change there belongs here too.  A second kernel, not a template argument of k_mat_sample, for the reason k_mat_sample_rays gives.
+// k_imat_sample_rays (instances_materials_bounce.inc) is this kernel for generic packets (k_mat_sample_rays' input side): a change to the keys,
+// their clamps, the quirk or imatLoadTri belongs there too.
 __global__ __launch_bounds__(64) void k_imat_sample(IMatArgs A) {
 	const int lane = threadIdx.x & 63;
 	const int li = (int)blockIdx.x;
@@ -207,7 +209,8 @@ __global__ __launch_bounds__(64) void k_imat_sample(IMatArgs A) {
 
 // ---- one (packet, light): the shadow packet (src/scene_trace.cpp:538-558) on the sample buffer's normals, and DBVH::TraverseShadow ----
 // TWINS: the sample load and the shadow-packet set-up are matLight<DEEP, SRC_PRIMARY>'s (materials.inc), the walk and the stats flush are
-// k_inst_light<DEEP, SRC_PRIMARY>'s (instances_shade.inc); a change to either belongs here too.
+// k_inst_light<DEEP, SRC_PRIMARY>'s (instances_shade.inc); a change to either belongs here too, and a change here in k_imat_light_rays
+// (instances_materials_bounce.inc), which is this kernel on the mirrored packets' samples.
 template <bool DEEP>
 __global__ __launch_bounds__(64) void k_imat_light(IMatArgs A) {
 	__shared__ float lds[LDS_FLOATS_PER_WAVE];

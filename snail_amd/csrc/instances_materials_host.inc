@@ -1,6 +1,7 @@
 // instances_materials_host.inc -- the C-ABI of include/snail_instances_materials.h: the material set of an instanced scene (per-BLAS ShTriangle
 // records and maps, ONE material and texture list) and the staged launches of instances_materials.inc (k_inst_frame with barycentrics ->
-// k_imat_sample -> k_imat_light per (packet, light) -> k_mat_final).  Included after materials_host.inc, whose host-side checks it calls.
+// k_imat_sample -> k_imat_light per (packet, light) -> k_mat_final).  Included after materials_host.inc, whose host-side checks it calls.  With the
+// one mirrored bounce (instances_materials_bounce_host.inc, included next) the nested call stands between the sample stage and the lights.
 #include "../../include/snail_instances_materials.h"
 
 struct SnailInstancesMaterials {
@@ -23,10 +24,28 @@ struct SnailInstancesMaterials {
 			hitTri = (int *)(base + 4 * plane); samples = (float *)(base + 5 * plane); sDist = (float *)(base + 14 * plane);
 		}
 	};
+	// ... and those of the bounce (instances_materials_bounce_host.inc): the mirrored packets (rays, mask, distance, instance slot, triId, bary), the
+	// nested samples, colour and shadow distances.  rTri and bary are neighbours: ONE memset defines both before the walk.
+	struct BounceBufs {
+		float *rOrg = nullptr, *rDir = nullptr, *rIDir = nullptr, *rDist = nullptr, *bary = nullptr, *nSamples = nullptr, *rCol = nullptr, *nSDist = nullptr;
+		int *rInst = nullptr, *rTri = nullptr;
+		unsigned char *rMask = nullptr;
+		static size_t bytes(size_t np, int nLights) { return np * 256 * 4 * (size_t)(26 + (nLights > 0 ? nLights : 0)) + ((np * 64 + 255) & ~(size_t)255); }
+		void carve(char *base, size_t np, int nLights) {
+			const size_t plane = np * 256 * 4;
+			rOrg = (float *)base; rDir = (float *)(base + 3 * plane); rIDir = (float *)(base + 6 * plane); rDist = (float *)(base + 9 * plane);
+			rInst = (int *)(base + 10 * plane); rTri = (int *)(base + 11 * plane); bary = (float *)(base + 12 * plane); nSamples = (float *)(base + 14 * plane);
+			rCol = (float *)(base + 23 * plane); nSDist = (float *)(base + 26 * plane);
+			rMask = (unsigned char *)(base + (size_t)(26 + (nLights > 0 ? nLights : 0)) * plane);
+		}
+	};
 	struct Set {
 		char *base = nullptr;
 		size_t packets = 0;
 		int lights = 0;
+		char *bounce = nullptr;   // allocated only once a bounce has been asked for; grown under the same rule
+		size_t bouncePackets = 0;
+		int bounceLights = 0;
 		hipEvent_t done = nullptr;
 		bool used = false;
 	};
@@ -60,9 +79,16 @@ void imatFillArgs(const SnailInstancesMaterials *m, dev::IMatArgs &A, const dev:
 	A.nSlots = m->inst->instCap;   // (the record count itself is the device's after a rebuild there: a slot is kept inside the buffer)
 }
 
-// the stages of one lit frame over the packet list dXY into `frame` (or packet-major `bgrPackets`), intermediates in W; the handle's mu held
+// instances_materials_bounce_host.inc: the nested call of the one mirrored bounce on the primary samples of A -- mirrored packets, their walk, nested
+// samples, lights and colour -- with its intermediates R entered into A
+int imatNested(SnailInstances *h, const char *fn, dev::IMatArgs &A, const dev::InstArgs &I, bool sse, bool deep, const SnailInstancesMaterials::BounceBufs &R,
+			   hipStream_t st);
+
+// the stages of one lit frame over the packet list dXY into `frame` (or packet-major `bgrPackets`), intermediates in W; the handle's mu held.
+// R (or null): the intermediates of the one mirrored bounce -- the nested call between the sample stage and the primary lights, the blend last.
 int imatShade(SnailInstancesMaterials *m, const char *fn, const float cam[13], int resx, int resy, const int32_t *dXY, int np, const float *lights7, int nLights,
-			  const float ambient[3], uint8_t *frame, int pitch, uint8_t *bgrPackets, const SnailInstancesMaterials::Bufs &W, uint64_t *dStats, hipStream_t st) {
+			  const float ambient[3], uint8_t *frame, int pitch, uint8_t *bgrPackets, const SnailInstancesMaterials::Bufs &W,
+			  const SnailInstancesMaterials::BounceBufs *R, uint64_t *dStats, hipStream_t st) {
 	SnailInstances *h = m->inst;
 	dev::InstArgs I;
 	bool sse, deep;
@@ -88,12 +114,15 @@ int imatShade(SnailInstancesMaterials *m, const char *fn, const float cam[13], i
 	A.m.s.frame = frame; A.m.s.pitch = pitch; A.m.s.bgrPackets = bgrPackets;
 	A.m.s.stats = (dev::u64 *)dStats;
 	SNAIL_IMAT_LAUNCH(sse, grid, st, A, k_imat_sample);
+	if(R) { if(int rc = imatNested(h, fn, A, I, sse, deep, *R, st)) return rc; }
 	if(nLights) {
 		const dim3 lgrid(np, nLights);
 		if(deep) SNAIL_IMAT_LAUNCH(sse, lgrid, st, A, k_imat_light<true>);
 		else SNAIL_IMAT_LAUNCH(sse, lgrid, st, A, k_imat_light<false>);
 	}
-	SNAIL_LAUNCH(sse, MatArgs, grid, dim3(64), 0, st, A.m, k_mat_final);   // (samples, hits and the surviving distances: the plain scenes' colour stage as it is)
+	// (samples, hits and the surviving distances: the plain scenes' colour stage as it is)
+	if(R) SNAIL_LAUNCH(sse, MatArgs, grid, dim3(64), 0, st, A.m, k_mat_final_blend);
+	else SNAIL_LAUNCH(sse, MatArgs, grid, dim3(64), 0, st, A.m, k_mat_final);
 	return instancesEnd(h, st);
 }
 
@@ -119,11 +148,9 @@ int imatFrameList(SnailInstancesMaterials *m, int resx, int resy, const int32_t 
 	return 0;
 }
 
-// snail_instances_render_materials_dev / _packets_dev (the handle's mu held): the next set of intermediates, grown if need be, its previous user
-// waited for on st; the event is recorded also when a stage failed after earlier ones were enqueued (matSetDone's rule)
-int imatShadeDev(SnailInstancesMaterials *m, const char *fn, const float cam[13], int resx, int resy, const int32_t *dXY, int np, const float *lights7, int nLights,
-				 const float ambient[3], uint8_t *frame, int pitch, uint8_t *bgrPackets, uint64_t *dStats, hipStream_t st) {
-	if(!dXY) { if(int rc = imatFrameList(m, resx, resy, &dXY, &np)) return rc; }
+// the next set of intermediates for np packets (the handle's mu held), grown if need be, its previous user waited for on st; refl: with the
+// bounce's part
+int imatNextSet(SnailInstancesMaterials *m, int np, int nLights, bool refl, hipStream_t st, SnailInstancesMaterials::Set **out) {
 	SnailInstancesMaterials::Set &W = m->set[m->setCount++ % SnailInstancesMaterials::kSets];
 	if(!W.base || W.packets < (size_t)np || W.lights < nLights) {   // grown: its previous user may still be running
 		HIP_TRY(hipDeviceSynchronize());
@@ -134,17 +161,43 @@ int imatShadeDev(SnailInstancesMaterials *m, const char *fn, const float cam[13]
 		HIP_TRY(hipMalloc((void **)&W.base, SnailInstancesMaterials::Bufs::bytes(packets, lights)));
 		W.packets = packets; W.lights = lights;
 	}
+	if(refl && (!W.bounce || W.bouncePackets < (size_t)np || W.bounceLights < nLights)) {   // the bounce's part: only when asked for, grown the same way
+		HIP_TRY(hipDeviceSynchronize());
+		if(W.bounce) (void)hipFree(W.bounce);
+		const size_t packets = std::max(W.bouncePackets, (size_t)np);
+		const int lights = std::max(W.bounceLights, nLights);
+		W.bounce = nullptr; W.bouncePackets = 0; W.bounceLights = 0; W.used = false;
+		HIP_TRY(hipMalloc((void **)&W.bounce, SnailInstancesMaterials::BounceBufs::bytes(packets, lights)));
+		W.bouncePackets = packets; W.bounceLights = lights;
+	}
 	if(!W.done) HIP_TRY(hipEventCreateWithFlags(&W.done, hipEventDisableTiming));
 	if(W.used) HIP_TRY(hipStreamWaitEvent(st, W.done, 0));
-	SnailInstancesMaterials::Bufs B;
-	B.carve(W.base, (size_t)np);
-	const int rc = imatShade(m, fn, cam, resx, resy, dXY, np, lights7, nLights, ambient, frame, pitch, bgrPackets, B, dStats, st);
+	*out = &W;
+	return 0;
+}
+// after the set's user has enqueued its stages (rc: how that went): the event is recorded also when a stage failed after earlier ones were
+// enqueued (matSetDone's rule)
+int imatSetDone(SnailInstancesMaterials::Set &W, const char *fn, int rc, hipStream_t st) {
 	if(hipEventRecord(W.done, st) == hipSuccess) W.used = true;
 	else {
-		W.packets = 0; W.used = false;   // its next user synchronises the device
+		W.packets = 0; W.bouncePackets = 0; W.used = false;   // its next user synchronises the device
 		if(!rc) { snail_set_error("%s: hipEventRecord failed", fn); return 1; }
 	}
 	return rc;
+}
+
+// snail_instances_render_materials_dev / _packets_dev and, with refl, snail_instances_materials_bounce_dev / _packets_dev (the handle's mu held)
+int imatShadeDev(SnailInstancesMaterials *m, const char *fn, const float cam[13], int resx, int resy, const int32_t *dXY, int np, const float *lights7, int nLights,
+				 const float ambient[3], uint8_t *frame, int pitch, uint8_t *bgrPackets, uint64_t *dStats, hipStream_t st, bool refl = false) {
+	if(!dXY) { if(int rc = imatFrameList(m, resx, resy, &dXY, &np)) return rc; }
+	SnailInstancesMaterials::Set *Wp = nullptr;
+	if(int rc = imatNextSet(m, np, nLights, refl, st, &Wp)) return rc;
+	SnailInstancesMaterials::Bufs B;
+	B.carve(Wp->base, (size_t)np);
+	SnailInstancesMaterials::BounceBufs RB;
+	if(refl) RB.carve(Wp->bounce, (size_t)np, nLights);
+	const int rc = imatShade(m, fn, cam, resx, resy, dXY, np, lights7, nLights, ambient, frame, pitch, bgrPackets, B, refl ? &RB : nullptr, dStats, st);
+	return imatSetDone(*Wp, fn, rc, st);
 }
 
 } // namespace
@@ -222,6 +275,7 @@ void snail_instances_materials_destroy(SnailInstancesMaterials *m) {
 	(void)hipDeviceSynchronize();
 	for(auto &W : m->set) {
 		if(W.base) (void)hipFree(W.base);
+		if(W.bounce) (void)hipFree(W.bounce);
 		if(W.done) (void)hipEventDestroy(W.done);
 	}
 	for(auto &f : m->frameLists) (void)hipFree(f.d);
@@ -304,7 +358,7 @@ int snail_instances_render_materials_image(SnailInstancesMaterials *m, const flo
 	uint8_t *dImg = (uint8_t *)hc.carve(imgBytes + 4);
 	{
 		std::lock_guard<std::mutex> lock(h->mu);
-		if(int rc = imatShade(m, fn, cam, resx, resy, (const int32_t *)dXY, np, lights7, nLights, ambient, dImg, pitch, nullptr, W, hc.stats(), hc.stream())) return rc;
+		if(int rc = imatShade(m, fn, cam, resx, resy, (const int32_t *)dXY, np, lights7, nLights, ambient, dImg, pitch, nullptr, W, nullptr, hc.stats(), hc.stream())) return rc;
 	}
 	HIP_TRY(hipMemcpy2DAsync(image, (size_t)pitch, dImg, (size_t)pitch, (size_t)resx * 3, (size_t)resy, hipMemcpyDeviceToHost, hc.stream()));
 	return hc.finish(stats);

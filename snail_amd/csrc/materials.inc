@@ -162,8 +162,9 @@ __device__ __forceinline__ PacketPos matPacket(const MatArgs &A, int li) {
 	return P;
 }
 
-// (TWINS: k_mat_sample_rays below is this kernel for generic packets, k_imat_sample (instances_materials.inc) for instanced scenes; a change to
-// the branches, the kinds or the output belongs in all three.)
+// (TWINS: k_mat_sample_rays below is this kernel for generic packets, k_imat_sample (instances_materials.inc) for instanced scenes and
+// k_imat_sample_rays (instances_materials_bounce.inc) for generic packets of instanced scenes; a change to the branches, the kinds or the output
+// belongs in all four.)
 __global__ __launch_bounds__(64) void k_mat_sample(MatArgs A) {
 	const int lane = threadIdx.x & 63;
 	const int li = (int)blockIdx.x;
@@ -299,7 +300,8 @@ __global__ __launch_bounds__(64) void k_mat_sample(MatArgs A) {
 // packet, a hit = t < inf AND the lane's mask bit, and branch (a) shaded with the packet's own hasMask.  A second kernel, not a template
 // argument of k_mat_sample: by the resource report the shared body cost the primary kernel two VGPRs (profiles/materials_resources.txt).
 // TWINS: everything else -- blocks, the triId-0 quirk, texDiff, the mip choice, the kinds, the output -- is k_mat_sample's; a change there
-// belongs in both.
+// belongs in both.  k_imat_sample_rays (instances_materials_bounce.inc) has this kernel's input side -- directions, mask, bary stride, the packet's
+// hasMask -- around k_imat_sample's keys: a change to that side belongs there too.
 __global__ __launch_bounds__(64) void k_mat_sample_rays(MatArgs A) {
 	const int lane = threadIdx.x & 63;
 	const int li = (int)blockIdx.x;
@@ -473,7 +475,8 @@ __device__ __forceinline__ void matLoadSamples(const MatArgs &A, const PacketPos
 // TWINS: the set-up and the walk selection below are those of lightPacket (snail_dev.inc; its main pass and its deferred M_EXACT pass folded into
 // one kernel, look-ups checked), and k_inst_light (instances_shade.inc) has the same set-up around the instanced walk.  A change to the shadow
 // packet, to the classify / walkSharedAsm / walk dispatch or to the stats booking belongs in all three.  k_imat_light (instances_materials.inc)
-// is this function's sample load and set-up around k_inst_light's walk: a change to the shadow packet belongs there as well.
+// is this function's sample load and set-up around k_inst_light's walk, and k_imat_light_rays (instances_materials_bounce.inc) the same with
+// SRC_MIRROR's sample load and the nested distance buffer: a change to the shadow packet belongs in those two as well.
 // SRC_MIRROR: the nested call's lights on the mirrored packets' samples -- the same shadow packet (the light's shared origin) and walks.
 // PSTATS: the heat-map launches' instantiation (include/snail_materials_heatmap.h), which also books the (packet, light)'s counters per packet at
 // P.pidx -- a template argument as in snail_dev.inc, so that the other launches' kernels stay the code they were.  A culled pair has returned

@@ -80,6 +80,7 @@ void snail_set_error(const char *fmt, ...) {
 #include "instances_shade.inc"
 #include "materials.inc"
 #include "instances_materials.inc"
+#include "instances_materials_bounce.inc"
 #include "materials_transparency.inc"
 #include "materials_tree.inc"
 #undef SNAIL_DEV_NS
@@ -91,6 +92,7 @@ void snail_set_error(const char *fmt, ...) {
 #include "instances_shade.inc"
 #include "materials.inc"
 #include "instances_materials.inc"
+#include "instances_materials_bounce.inc"
 #include "materials_transparency.inc"
 #include "materials_tree.inc"
 #undef SNAIL_DEV_NS
@@ -1819,3 +1821,4 @@ int snail_account_primary(SnailScene *s, const float cam[13], int resx, int resy
 #include "materials_heat_host.inc"
 #include "materials_dynamic_host.inc"
 #include "instances_materials_host.inc"
+#include "instances_materials_bounce_host.inc"

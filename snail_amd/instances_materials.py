@@ -5,6 +5,8 @@ of include/snail_instances_materials.h.
                                                                  DBVH::GetMaterialId over Scene::materials
   .shade_packets / .render / .render_packets / .render_image_host   <-> Scene<DBVH>::RayTrace with gVals[6] and HasShadingData() = 1 (this
                                                                  project's completion of the reference's TODO), primary packets and their lights
+  .mirror_packets / .shade_rays, reflections=True           <-> the one mirrored bounce of gVals[7] (Scene::TraceReflection and its nested
+                                                                 RayTrace<0, hasMask>), include/snail_instances_materials_bounce.h
 
 Materials, textures and pack_shtris are snail_amd.materials'."""
 from __future__ import annotations
@@ -15,7 +17,7 @@ import numpy as np
 
 from . import _lib
 from .instances import InstancedScene
-from .materials import SAMPLE_COMPONENTS, _material_records, _texture_array, pack_shtris
+from .materials import RENDER_REFLECTIONS, SAMPLE_COMPONENTS, _material_records, _texture_array, pack_shtris
 from .scene import _stream_ptr, _torch
 
 
@@ -95,38 +97,90 @@ class InstancedMaterialSet:
         _lib.check(rc, "snail_instances_materials_shade_packets_dev")
         return out
 
-    def render(self, cam, resx: int, resy: int, lights7=None, ambient=(0.1, 0.1, 0.1), out=None, stats=None, stream=None, flags: int = 0):
+    def mirror_packets(self, cam, resx: int, resy: int, packet_xy, t, samples, stats=None, stream=None):
+        """Scene::TraceReflection on the primary samples of a packet list (t: the hits' distances [n, 256]; samples: shade_packets' buffer) ->
+        (origin, dir, idir [n, 64, 3, 4] float32, mask [n, 64] uint8, distance [n, 256] float32, object, element [n, 256] int32, bary
+        [n, 64, 2, 4] float32): the mirrored packets as InstancedScene.traverse_primary takes them in and out (object, element and bary zero).
+        snail_instances_materials_mirror_packets_dev."""
+        torch = _torch()
+        n = int(packet_xy.shape[0])
+        dev = self.isc._dev()
+        org, d, idir = (torch.empty((n, 64, 3, 4), dtype=torch.float32, device=dev) for _ in range(3))
+        mask = torch.empty((n, 64), dtype=torch.uint8, device=dev)
+        dist = torch.empty((n, 256), dtype=torch.float32, device=dev)
+        obj, elem = (torch.empty((n, 256), dtype=torch.int32, device=dev) for _ in range(2))
+        bary = torch.empty((n, 64, 2, 4), dtype=torch.float32, device=dev)
+        cam13 = np.ascontiguousarray(cam.as_array13(), dtype=np.float32)
+        rc = _lib.lib().snail_instances_materials_mirror_packets_dev(self._h, _lib.ptr(cam13), resx, resy, _lib.ptr(packet_xy), n, _lib.ptr(t), _lib.ptr(samples),
+                                                                     _lib.ptr(org), _lib.ptr(d), _lib.ptr(idir), _lib.ptr(mask), _lib.ptr(dist), _lib.ptr(obj), _lib.ptr(elem),
+                                                                     _lib.ptr(bary), _lib.ptr(stats), _stream_ptr(stream))
+        _lib.check(rc, "snail_instances_materials_mirror_packets_dev")
+        return org, d, idir, mask, dist, obj, elem, bary
+
+    def shade_rays(self, dirs, mask, t, bary, inst, tri_id, out=None, stream=None):
+        """The samples of generic packets (RayGroup<0, hasMask>): dirs [n, 64, 3, 4], mask [n, 64] uint8 or None (every lane selected), hit
+        records t / inst / tri_id [n, 256] and bary [n, 64, 2, 4] (device tensors: the distance, object, element and bary of
+        InstancedScene.traverse_primary) -> float32 [n, 9, 64, 4].  snail_instances_materials_shade_rays_dev."""
+        torch = _torch()
+        n = int(dirs.shape[0])
+        if out is None:
+            out = torch.empty((n, SAMPLE_COMPONENTS, 64, 4), dtype=torch.float32, device=self.isc._dev())
+        rc = _lib.lib().snail_instances_materials_shade_rays_dev(self._h, n, _lib.ptr(dirs), _lib.ptr(mask), _lib.ptr(t), _lib.ptr(bary), _lib.ptr(inst), _lib.ptr(tri_id),
+                                                                 _lib.ptr(out), _stream_ptr(stream))
+        _lib.check(rc, "snail_instances_materials_shade_rays_dev")
+        return out
+
+    def render(self, cam, resx: int, resy: int, lights7=None, ambient=(0.1, 0.1, 0.1), out=None, stats=None, stream=None, flags: int = 0, reflections: bool = False):
         """The lit frame, [resy, resx, 3] uint8 (B,G,R) (or `out`: a uint8 device tensor [resy, pitch] / [resy, w, 3] whose rows may be wider).
-        snail_instances_render_materials_dev; flags must be 0."""
+        snail_instances_render_materials_dev; flags must be 0.  reflections=True: with the one mirrored bounce of gVals[7]
+        (snail_instances_materials_bounce_dev; `flags` are then that function's)."""
         torch = _torch()
         if out is None:
             out = torch.zeros((resy, resx, 3), dtype=torch.uint8, device=self.isc._dev())
         lights, cam13, amb = self._frame_args(cam, lights7, ambient)
+        if reflections:
+            rc = _lib.lib().snail_instances_materials_bounce_dev(self._h, _lib.ptr(cam13), resx, resy, _lib.ptr(lights) if len(lights) else None, len(lights), _lib.ptr(amb),
+                                                                 int(flags) | RENDER_REFLECTIONS, _lib.ptr(out), int(out.stride(0)), _lib.ptr(stats), _stream_ptr(stream))
+            _lib.check(rc, "snail_instances_materials_bounce_dev")
+            return out
         rc = _lib.lib().snail_instances_render_materials_dev(self._h, _lib.ptr(cam13), resx, resy, _lib.ptr(lights) if len(lights) else None, len(lights), _lib.ptr(amb),
                                                              int(flags), _lib.ptr(out), int(out.stride(0)), _lib.ptr(stats), _stream_ptr(stream))
         _lib.check(rc, "snail_instances_render_materials_dev")
         return out
 
-    def render_packets(self, cam, resx: int, resy: int, packet_xy, lights7=None, ambient=(0.1, 0.1, 0.1), out=None, stats=None, stream=None, flags: int = 0):
+    def render_packets(self, cam, resx: int, resy: int, packet_xy, lights7=None, ambient=(0.1, 0.1, 0.1), out=None, stats=None, stream=None, flags: int = 0,
+                       reflections: bool = False):
         """render for an explicit packet list (int32 [n, 2] device tensor): packet-major [n, 256, 3] uint8 (B,G,R).
-        snail_instances_render_materials_packets_dev."""
+        snail_instances_render_materials_packets_dev.  reflections=True: snail_instances_materials_bounce_packets_dev."""
         torch = _torch()
         n = int(packet_xy.shape[0])
         if out is None:
             out = torch.empty((n, 256, 3), dtype=torch.uint8, device=self.isc._dev())
         lights, cam13, amb = self._frame_args(cam, lights7, ambient)
+        if reflections:
+            rc = _lib.lib().snail_instances_materials_bounce_packets_dev(self._h, _lib.ptr(cam13), resx, resy, _lib.ptr(packet_xy), n, _lib.ptr(lights) if len(lights) else None,
+                                                                         len(lights), _lib.ptr(amb), int(flags) | RENDER_REFLECTIONS, _lib.ptr(out), _lib.ptr(stats),
+                                                                         _stream_ptr(stream))
+            _lib.check(rc, "snail_instances_materials_bounce_packets_dev")
+            return out
         rc = _lib.lib().snail_instances_render_materials_packets_dev(self._h, _lib.ptr(cam13), resx, resy, _lib.ptr(packet_xy), n, _lib.ptr(lights) if len(lights) else None,
                                                                      len(lights), _lib.ptr(amb), int(flags), _lib.ptr(out), _lib.ptr(stats), _stream_ptr(stream))
         _lib.check(rc, "snail_instances_render_materials_packets_dev")
         return out
 
-    def render_image_host(self, cam, resx: int, resy: int, lights7=None, ambient=(0.1, 0.1, 0.1), flags: int = 0, pitch: int | None = None, fill: int = 0):
+    def render_image_host(self, cam, resx: int, resy: int, lights7=None, ambient=(0.1, 0.1, 0.1), flags: int = 0, pitch: int | None = None, fill: int = 0,
+                          reflections: bool = False):
         """snail_instances_render_materials_image: the frame in host memory, uint8 [resy, pitch] (pitch = 3 * resx unless given; bytes past a
-        row's pixels keep `fill`), and the call's TreeStats."""
+        row's pixels keep `fill`), and the call's TreeStats.  reflections=True: snail_instances_materials_bounce_image."""
         pitch = resx * 3 if pitch is None else int(pitch)
         img = np.full((resy, pitch), fill, dtype=np.uint8)
         stats = np.zeros(4, dtype=np.uint64)
         lights, cam13, amb = self._frame_args(cam, lights7, ambient)
+        if reflections:
+            rc = _lib.lib().snail_instances_materials_bounce_image(self._h, _lib.ptr(cam13), resx, resy, _lib.ptr(lights) if len(lights) else None, len(lights), _lib.ptr(amb),
+                                                                   int(flags) | RENDER_REFLECTIONS, _lib.ptr(img), pitch, _lib.ptr(stats))
+            _lib.check(rc, "snail_instances_materials_bounce_image")
+            return img, stats
         rc = _lib.lib().snail_instances_render_materials_image(self._h, _lib.ptr(cam13), resx, resy, _lib.ptr(lights) if len(lights) else None, len(lights), _lib.ptr(amb),
                                                                int(flags), _lib.ptr(img), pitch, _lib.ptr(stats))
         _lib.check(rc, "snail_instances_render_materials_image")

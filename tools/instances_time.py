@@ -39,9 +39,13 @@ medians.
 normals and materials, both arithmetics): host wall ms per frame, synchronised, of
   full    InstancedMaterialSet.render (snail_instances_render_materials_dev): k_inst_frame, k_imat_sample, k_imat_light, k_mat_final;
   simple  InstancedScene.render_whitted of the same scene, camera and light (simple shading: one colour, plane normals).
-Alternating runs, medians.
+Alternating runs, medians.  With --reflections both paths draw the one mirrored bounce of gVals[7]: InstancedMaterialSet.render(reflections=True)
+(snail_instances_materials_bounce_dev: + k_mat_mirror, the mirrored packets' walk, k_imat_sample_rays, k_imat_light_rays, k_mat_colour_rays,
+k_mat_final_blend) beside InstancedScene.render_whitted(reflections=True).  With --plane-normals every record is flat with its triangle's plane
+normal and every material the default: the two paths then draw the same picture from the same rays (the degenerate set of the tests), and
+the ratio is the cost of the full-shading stages alone.
 
-    python tools/instances_time.py --materials [--reps 3]"""
+    python tools/instances_time.py --materials [--reflections] [--plane-normals] [--reps 3]"""
 import argparse
 import json
 import os
@@ -83,6 +87,8 @@ def main():
     ap.add_argument("--lit", action="store_true")
     ap.add_argument("--tiles", action="store_true")
     ap.add_argument("--materials", action="store_true")
+    ap.add_argument("--reflections", action="store_true")
+    ap.add_argument("--plane-normals", action="store_true")
     ap.add_argument("--baseline-lib", default=None)
     a = ap.parse_args()
     resx, resy = (int(x) for x in a.res.split("x"))
@@ -304,7 +310,12 @@ def materials(torch, a, resx, resy):
     sc = Scene(hb, 0)
     lo, hi = sc.get_bbox()
     uv, nrm, mi, flat, mmap, mats, texs = procedural_shading(hb, tv)
-    out = {"res": a.res, "lights": 1, "unit": "host wall ms per frame, synchronised, median of %d alternating runs" % a.reps, "rows": []}
+    if a.plane_normals:
+        plane = np.zeros((len(tv), 3), dtype=np.float32)
+        plane[hb.perm] = hb.tris.view(np.float32).reshape(-1, 16)[:, 12:15]
+        nrm, flat, mi, mmap = np.repeat(plane[:, None, :], 3, axis=1), np.ones(len(tv), dtype=bool), np.zeros(len(tv), dtype=np.int32), [-1]
+    refl = bool(a.reflections)
+    out = {"res": a.res, "lights": 1, "reflections": refl, "plane_normals": bool(a.plane_normals), "unit": "host wall ms per frame, synchronised, median of %d alternating runs" % a.reps, "rows": []}
     for arith in ("ieee", "host_sse"):
         sc.set_arith(arith)
         for n in (int(c) for c in a.counts.split(",")):
@@ -316,7 +327,8 @@ def materials(torch, a, resx, resy):
             c, ext = (nd["bmin"] + nd["bmax"]) * 0.5, nd["bmax"] - nd["bmin"]
             light = np.array([[c[0], c[1] + 0.3 * ext[1], c[2], 1.0, 1.0, 1.0, float(np.linalg.norm(ext))]], dtype=np.float32)
             frame = torch.zeros((resy, resx, 3), dtype=torch.uint8, device="cuda")
-            runs = {"full": lambda: ms_set.render(cam, resx, resy, light, out=frame), "simple": lambda: isc.render_whitted(cam, resx, resy, light, out=frame)}
+            runs = {"full": lambda: ms_set.render(cam, resx, resy, light, out=frame, reflections=refl),
+                    "simple": lambda: isc.render_whitted(cam, resx, resy, light, out=frame, reflections=refl)}
             ms = {k: [] for k in runs}
             for k, fn in runs.items():      # warm-up: the sets' intermediates, the cached packet lists, first launches
                 fn(); fn(); torch.cuda.synchronize()
@@ -326,6 +338,10 @@ def materials(torch, a, resx, resy):
                     t0 = time.perf_counter(); fn(); torch.cuda.synchronize()
                     ms[k].append((time.perf_counter() - t0) * 1e3)
             row = {"arith": arith, "instances": n, "nonblack_pixels": int((frame.cpu().numpy() != 0).any(axis=2).sum())}
+            if a.plane_normals:     # the two paths' last frames, byte for byte
+                fn_full, fn_simple = runs["full"], runs["simple"]
+                fn_full(); full_frame = frame.cpu().numpy().copy()
+                fn_simple(); row["frames_equal"] = bool(np.array_equal(full_frame, frame.cpu().numpy()))
             for k in ms:
                 m = statistics.median(ms[k])
                 row[k + "_ms"] = round(m, 3); row[k + "_min_ms"] = round(min(ms[k]), 3); row[k + "_mrays"] = round(rays / m / 1e3, 1)
