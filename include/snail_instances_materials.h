@@ -9,8 +9,9 @@
  * GetMaterialId (:246-248), the (object, element) comparisons of Scene::RayTrace under isctFlags & fElement (src/scene_trace.cpp:162,
  * :179-182, :252-253, :263), and the instantiation of Scene<DBVH>::RayTrace (:642-659).
  *
- * NOT here (the mirrored bounce of gVals[7] is snail_instances_materials_bounce.h's): the transparency continuation, tile lists, 4x
- * antialiasing and the tint, the heat-map under full shading and multi-device frames of instanced scenes; routing in snail_adapter.hpp (no reference host can reach this branch through
+ * NOT here (the mirrored bounce of gVals[7] is snail_instances_materials_bounce.h's, the transparency continuation
+ * snail_instances_materials_transparency.h's): tile lists, 4x antialiasing and the tint, the heat-map under full shading and multi-device frames
+ * of instanced scenes; routing in snail_adapter.hpp (no reference host can reach this branch through
  * HipDBVH); device-packed records for BLASes whose tree is rebuilt on the device (a set made before such a rebuild shades with another
  * triangle's data: build the BLASes from host triangles).
  */
@@ -31,7 +32,8 @@ extern "C" {
  * entry is shaded unmasked).  Everything is copied; the instances handle and its BLAS scenes must outlive the set.
  * REFUSED (NULL, snail_last_error() says why), before anything touches a device: nBlas different from the handle's, a BLAS whose nTris is
  * not its scene's triangle count, a record whose matId is outside its BLAS's map, a map entry outside -1 .. nMats - 1, a texture index or
- * shape that snail_materials_create refuses, and every material that could select a transparent lane, by snail_materials_create's check. */
+ * shape that snail_materials_create refuses, and every material that could select a transparent lane, by snail_materials_create's check
+ * (snail_instances_materials_transparency.h has the creator that accepts those; its sets are refused by every function below). */
 typedef struct SnailBlasShading {
 	const void *shtris64;
 	int32_t nTris;

@@ -225,6 +225,19 @@ INSTANCES_MATERIALS_BOUNCE_SIGNATURES = {
     "snail_instances_materials_bounce_image": (_I, [_VP, _F13, _I, _I, _VP, _I, _VP, _I, _VP, _I, _VP]),
 }
 
+# include/snail_instances_materials_transparency.h: the transparency continuation under full shading of instanced scenes
+# (tests/c/instances_materials_transparency_c.c enumerates this table)
+INSTANCES_MATERIALS_TRANSPARENCY_SIGNATURES = {
+    "snail_instances_materials_create_transparent": (_VP, [_VP, _VP, _I, _VP, _I, _VP, _VP, _I]),
+    "snail_instances_materials_can_select_transparent": (_I, [_VP]),
+    "snail_instances_materials_shade_packets_transp_dev": (_I, [_VP, _F13, _I, _I, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "snail_instances_materials_shade_rays_transp_dev": (_I, [_VP, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "snail_instances_materials_continue_packets_dev": (_I, [_VP, _F13, _I, _I, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "snail_instances_materials_transparent_dev": (_I, [_VP, _F13, _I, _I, _VP, _I, _VP, _I, _VP, _I, _I, _VP, _VP, _VP]),
+    "snail_instances_materials_transparent_packets_dev": (_I, [_VP, _F13, _I, _I, _VP, _I, _VP, _I, _VP, _I, _VP, _I, _VP, _VP, _VP]),
+    "snail_instances_materials_transparent_image": (_I, [_VP, _F13, _I, _I, _VP, _I, _VP, _I, _VP, _I, _I, _VP, _VP]),
+}
+
 # include/snail_hip_debug.h: the workbench build only (libsnailhip_debug.so, -DSNAIL_DEBUG_API)
 DEBUG_SIGNATURES = {
     "snail_debug_delay_dev": (_I, [C.c_float, _VP]),
@@ -249,7 +262,7 @@ def debug_lib():
         if not os.path.exists(DEBUG_LIB_PATH):
             raise SnailError("workbench library %s is missing: `make -C snail_amd/csrc debug`" % DEBUG_LIB_PATH)
         L = C.CDLL(DEBUG_LIB_PATH)
-        for table in (SIGNATURES, INSTANCES_SIGNATURES, INSTANCES_SHADE_SIGNATURES, INSTANCES_TILES_SIGNATURES, INSTANCES_BUILD_SIGNATURES, BVH_FAST_SIGNATURES, HEATMAP_SIGNATURES, MATERIALS_SIGNATURES, MATERIALS_BOUNCE_SIGNATURES, MATERIALS_TILES_SIGNATURES, MATERIALS_TRANSPARENCY_SIGNATURES, MATERIALS_TREE_SIGNATURES, MATERIALS_HEAT_SIGNATURES, MATERIALS_DYNAMIC_SIGNATURES, INSTANCES_MATERIALS_SIGNATURES, INSTANCES_MATERIALS_BOUNCE_SIGNATURES, DEBUG_SIGNATURES):
+        for table in (SIGNATURES, INSTANCES_SIGNATURES, INSTANCES_SHADE_SIGNATURES, INSTANCES_TILES_SIGNATURES, INSTANCES_BUILD_SIGNATURES, BVH_FAST_SIGNATURES, HEATMAP_SIGNATURES, MATERIALS_SIGNATURES, MATERIALS_BOUNCE_SIGNATURES, MATERIALS_TILES_SIGNATURES, MATERIALS_TRANSPARENCY_SIGNATURES, MATERIALS_TREE_SIGNATURES, MATERIALS_HEAT_SIGNATURES, MATERIALS_DYNAMIC_SIGNATURES, INSTANCES_MATERIALS_SIGNATURES, INSTANCES_MATERIALS_BOUNCE_SIGNATURES, INSTANCES_MATERIALS_TRANSPARENCY_SIGNATURES, DEBUG_SIGNATURES):
             for name, (res, args) in table.items():
                 fn = getattr(L, name)
                 fn.restype = res
@@ -270,7 +283,7 @@ def lib():
             L = C.CDLL(LIB_PATH)
         except OSError as e:  # pragma: no cover - depends on the box
             raise SnailError("cannot load %s: %s" % (LIB_PATH, e)) from e
-        for table in (SIGNATURES, INSTANCES_SIGNATURES, INSTANCES_SHADE_SIGNATURES, INSTANCES_TILES_SIGNATURES, INSTANCES_BUILD_SIGNATURES, BVH_FAST_SIGNATURES, HEATMAP_SIGNATURES, MATERIALS_SIGNATURES, MATERIALS_BOUNCE_SIGNATURES, MATERIALS_TILES_SIGNATURES, MATERIALS_TRANSPARENCY_SIGNATURES, MATERIALS_TREE_SIGNATURES, MATERIALS_HEAT_SIGNATURES, MATERIALS_DYNAMIC_SIGNATURES, INSTANCES_MATERIALS_SIGNATURES, INSTANCES_MATERIALS_BOUNCE_SIGNATURES):
+        for table in (SIGNATURES, INSTANCES_SIGNATURES, INSTANCES_SHADE_SIGNATURES, INSTANCES_TILES_SIGNATURES, INSTANCES_BUILD_SIGNATURES, BVH_FAST_SIGNATURES, HEATMAP_SIGNATURES, MATERIALS_SIGNATURES, MATERIALS_BOUNCE_SIGNATURES, MATERIALS_TILES_SIGNATURES, MATERIALS_TRANSPARENCY_SIGNATURES, MATERIALS_TREE_SIGNATURES, MATERIALS_HEAT_SIGNATURES, MATERIALS_DYNAMIC_SIGNATURES, INSTANCES_MATERIALS_SIGNATURES, INSTANCES_MATERIALS_BOUNCE_SIGNATURES, INSTANCES_MATERIALS_TRANSPARENCY_SIGNATURES):
             for name, (res, args) in table.items():
                 fn = getattr(L, name)
                 fn.restype = res

@@ -303,7 +303,8 @@ __global__ __launch_bounds__(64) void k_inst_frame(InstArgs A) {
 
 // ---- generic packets: DBVH::TraversePrimary<SHARED,MASK>(Context&) ----
 // PSTATS: the heat-map launches' instantiation, which also books per packet (a template argument as in snail_dev.inc: a pointer test here cost the
-// other launches' kernel scalar spills and, in one instantiation, a wave)
+// other launches' kernel scalar spills and, in one instantiation, a wave; for the same reason the walk under an order list is a kernel of its
+// own, k_imat_trace_level in instances_materials_transparency.inc, which repeats the <false, true, DEEP, true> body: a change here belongs there too)
 template <bool SHARED, bool MASK, bool DEEP, bool BARY, bool PSTATS = false>
 __global__ __launch_bounds__(64) void k_inst_trace(InstArgs A) {
 	__shared__ float lds[LDS_FLOATS_PER_WAVE];

@@ -71,7 +71,8 @@ __device__ __forceinline__ ShTri imatLoadTri(const IMatArgs &A, int slot, int tr
 // imatLoadTri; everything else -- blocks, the (slot 0, triId 0) quirk, texDiff, the mip choice, the kinds, the output -- is k_mat_sample's; a
 // change there belongs here too.  A second kernel, not a template argument of k_mat_sample, for the reason k_mat_sample_rays gives.
 // k_imat_sample_rays (instances_materials_bounce.inc) is this kernel for generic packets (k_mat_sample_rays' input side): a change to the keys,
-// their clamps, the quirk or imatLoadTri belongs there too.
+// their clamps, the quirk or imatLoadTri belongs there too -- and in imatSampleTransp (instances_materials_transparency.inc), which is both
+// kernels with the transparent kinds, Sample::opacity and the selector.
 __global__ __launch_bounds__(64) void k_imat_sample(IMatArgs A) {
 	const int lane = threadIdx.x & 63;
 	const int li = (int)blockIdx.x;

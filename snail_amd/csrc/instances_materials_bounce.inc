@@ -22,7 +22,8 @@ struct IMatRaysArgs {
 // TWINS: the input side -- directions, mask, bary stride, the packet's hasMask and where it shows -- is k_mat_sample_rays' (materials.inc); the
 // keys (slot, triId), their clamps, the (slot 0, triId 0) quirk and imatLoadTri are k_imat_sample's (instances_materials.inc); everything else --
 // blocks, texDiff, the mip choice, the kinds, the output -- is k_mat_sample's.  A change to any of the three belongs here too.  A kernel of its
-// own, not a template argument of k_imat_sample, for the reason k_mat_sample_rays gives.
+// own, not a template argument of k_imat_sample, for the reason k_mat_sample_rays gives.  imatSampleTransp
+// (instances_materials_transparency.inc) repeats this kernel's input side: a change here belongs there too.
 __global__ __launch_bounds__(64) void k_imat_sample_rays(IMatRaysArgs B) {
 	const IMatArgs &A = B.a;
 	const int lane = threadIdx.x & 63;
@@ -168,7 +169,8 @@ __global__ __launch_bounds__(64) void k_imat_sample_rays(IMatRaysArgs B) {
 // ---- one (mirrored packet, light): the nested call's shadow packet on the nested samples' normals, and DBVH::TraverseShadow ----
 // TWINS: the sample load (position = reflDir * t + reflOrig, hit = t < inf and the lane's mask bit) and the shadow-packet set-up are
 // matLight<DEEP, SRC_MIRROR>'s (materials.inc), the walk and the stats flush are k_imat_light's (instances_materials.inc), i.e.
-// k_inst_light<DEEP, SRC_MIRROR>'s (instances_shade.inc); a change to any of them belongs here too.
+// k_inst_light<DEEP, SRC_MIRROR>'s (instances_shade.inc); a change to any of them belongs here too, and a change here in k_imat_light_transp
+// (instances_materials_transparency.inc), which is this kernel behind a level's order word.
 template <bool DEEP>
 __global__ __launch_bounds__(64) void k_imat_light_rays(IMatArgs A) {
 	__shared__ float lds[LDS_FLOATS_PER_WAVE];

@@ -8,6 +8,7 @@ struct SnailInstancesMaterials {
 	SnailInstances *inst = nullptr;
 	int device = 0;
 	int nBlas = 0, nMats = 0, nTex = 0;
+	bool canSelectTransparent = false;   // holds SNAIL_MAT_TRANSPARENT or UBER with 0 < dissolve < 1 (snail_instances_materials_create_transparent alone makes such a set)
 	char *dBase = nullptr;   // ONE allocation: the per-BLAS table, every BLAS's records and map, materials, texture descriptors, texels
 	const dev::IMatBlas *dTab = nullptr;
 	const dev::MatRec *dMats = nullptr;
@@ -46,6 +47,8 @@ struct SnailInstancesMaterials {
 		char *bounce = nullptr;   // allocated only once a bounce has been asked for; grown under the same rule
 		size_t bouncePackets = 0;
 		int bounceLights = 0;
+		char *transp = nullptr;   // the levels of the transparency continuation (instances_materials_transparency_host.inc): only once asked for, sized by the depth
+		size_t transpBytes = 0;
 		hipEvent_t done = nullptr;
 		bool used = false;
 	};
@@ -58,9 +61,18 @@ struct SnailInstancesMaterials {
 
 namespace {
 
-int checkIMat(const SnailInstancesMaterials *m, const char *fn) {
+// any set: the entry points of include/snail_instances_materials_transparency.h
+int checkIMatAny(const SnailInstancesMaterials *m, const char *fn) {
 	if(!m || !m->inst || !m->dBase) { snail_set_error("%s: invalid instanced material set handle", fn); return 1; }
 	return checkInstances(m->inst, fn);
+}
+// the entry points of snail_instances_materials.h and _bounce.h: their kernels know neither the transparent kind nor the selector
+int checkIMat(const SnailInstancesMaterials *m, const char *fn) {
+	if(m && m->canSelectTransparent) {
+		snail_set_error("%s: the set holds a material that can select a transparent lane, which this function's kernels do not know (include/snail_instances_materials_transparency.h)", fn);
+		return 1;
+	}
+	return checkIMatAny(m, fn);
 }
 
 #define SNAIL_IMAT_LAUNCH(SSE, GRID, STREAM, A, ...) SNAIL_LAUNCH(SSE, IMatArgs, GRID, dim3(64), 0, STREAM, A, __VA_ARGS__)
@@ -200,23 +212,22 @@ int imatShadeDev(SnailInstancesMaterials *m, const char *fn, const float cam[13]
 	return imatSetDone(*Wp, fn, rc, st);
 }
 
-} // namespace
-
-extern "C" {
-
-SnailInstancesMaterials *snail_instances_materials_create(SnailInstances *h, const SnailBlasShading *perBlas, int nBlas, const SnailMaterial *mats, int nMats,
-														  const SnailTexture *textures, int nTex) {
-	const char *fn = "snail_instances_materials_create";
+// the creators: snail_instances_materials_create (transp = false: its refusals) and snail_instances_materials_create_transparent
+// (include/snail_instances_materials_transparency.h), one body as matCreate is for plain scenes
+SnailInstancesMaterials *imatCreate(const char *fn, bool transp, SnailInstances *h, const SnailBlasShading *perBlas, int nBlas, const SnailMaterial *mats, int nMats,
+									const int32_t *opacityTexture, const SnailTexture *textures, int nTex) {
 	// the caller's HOST data first, by snail_materials_create's own check (once per BLAS: its words name the record, entry, material or texture)
 	if(!perBlas || nBlas <= 0) { snail_set_error("%s: no per-BLAS shading data", fn); return nullptr; }
+	bool canSelectAny = false;
 	for(int b = 0; b < nBlas; b++) {
 		bool canSelect = false;
-		if(!matCheckHost(fn, false, false, perBlas[b].shtris64, perBlas[b].nTris, perBlas[b].matMap, perBlas[b].nMap, mats, nMats, nullptr, textures, nTex, &canSelect)) {
+		if(!matCheckHost(fn, transp, false, perBlas[b].shtris64, perBlas[b].nTris, perBlas[b].matMap, perBlas[b].nMap, mats, nMats, opacityTexture, textures, nTex, &canSelect)) {
 			char why[400];
 			snprintf(why, sizeof(why), "%s", snail_last_error());
 			snail_set_error("%s (the shading data of BLAS %d)", why, b);
 			return nullptr;
 		}
+		canSelectAny = canSelectAny || canSelect;
 	}
 	if(checkInstances(h, fn)) return nullptr;
 	if(nBlas != (int)h->blas.size()) { snail_set_error("%s: shading data of %d BLASes (nBlas) for a handle of %d", fn, nBlas, (int)h->blas.size()); return nullptr; }
@@ -226,10 +237,11 @@ SnailInstancesMaterials *snail_instances_materials_create(SnailInstances *h, con
 		if(perBlas[b].nTris != h->blas[b]->nTris) { snail_set_error("%s: BLAS %d: %d records (nTris) for a scene of %d triangles", fn, b, perBlas[b].nTris, h->blas[b]->nTris); return nullptr; }
 	}
 
-	// the device copy (materials and textures as matUpload lays them out; no transparent kind has passed the check: no opacity maps)
+	// the device copy (materials and textures as matUpload lays them out; opacityTexture is read for the transparent kind alone, which only the
+	// transparent creator's check lets pass)
 	std::vector<dev::MatRec> recs;
 	std::vector<dev::TexRec> trecs;
-	const size_t texelBytes = matPackLists(mats, nMats, nullptr, textures, nTex, recs, trecs);
+	const size_t texelBytes = matPackLists(mats, nMats, opacityTexture, textures, nTex, recs, trecs);
 	typedef HostCallScope H;
 	std::vector<size_t> oTris((size_t)nBlas), oMap((size_t)nBlas);
 	size_t total = H::pad((size_t)nBlas * sizeof(dev::IMatBlas));
@@ -264,9 +276,19 @@ SnailInstancesMaterials *snail_instances_materials_create(SnailInstances *h, con
 	m->inst = h; m->device = h->device;
 	m->nBlas = nBlas; m->nMats = nMats; m->nTex = nTex;
 	m->dBase = base;
+	m->canSelectTransparent = canSelectAny;
 	m->dTab = (const dev::IMatBlas *)base; m->dMats = (const dev::MatRec *)(base + oMats);
 	m->dTex = (const dev::TexRec *)(base + oTex); m->dTexels = (const unsigned char *)(base + oTexels);
 	return m;
+}
+
+} // namespace
+
+extern "C" {
+
+SnailInstancesMaterials *snail_instances_materials_create(SnailInstances *h, const SnailBlasShading *perBlas, int nBlas, const SnailMaterial *mats, int nMats,
+														  const SnailTexture *textures, int nTex) {
+	return imatCreate("snail_instances_materials_create", false, h, perBlas, nBlas, mats, nMats, nullptr, textures, nTex);
 }
 
 void snail_instances_materials_destroy(SnailInstancesMaterials *m) {
@@ -276,6 +298,7 @@ void snail_instances_materials_destroy(SnailInstancesMaterials *m) {
 	for(auto &W : m->set) {
 		if(W.base) (void)hipFree(W.base);
 		if(W.bounce) (void)hipFree(W.bounce);
+		if(W.transp) (void)hipFree(W.transp);
 		if(W.done) (void)hipEventDestroy(W.done);
 	}
 	for(auto &f : m->frameLists) (void)hipFree(f.d);

@@ -9,7 +9,8 @@
 //                          k_mat_mirror, + the order word under which launchRays leaves out a packet without a selected lane (orderedSlot)
 // Kernels of their own: the existing sample kernels stay as they are, and a set they can be given never holds these kinds (checkMaterials).
 // TWINS: matSampleTransp is k_mat_sample / k_mat_sample_rays (materials.inc) with the additions marked [T]; a change to the branches, the kinds
-// or the nine planes there belongs here too -- the planes of a set without these kinds are theirs byte for byte.
+// or the nine planes there belongs here too -- the planes of a set without these kinds are theirs byte for byte.  imatSampleTransp
+// (instances_materials_transparency.inc) carries the same [T] additions for instanced scenes: a change to them belongs there too.
 namespace SNAIL_DEV_NS {
 
 enum { MAT_TRANSPARENT = 3 };

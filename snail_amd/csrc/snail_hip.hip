@@ -82,6 +82,7 @@ void snail_set_error(const char *fmt, ...) {
 #include "instances_materials.inc"
 #include "instances_materials_bounce.inc"
 #include "materials_transparency.inc"
+#include "instances_materials_transparency.inc"
 #include "materials_tree.inc"
 #undef SNAIL_DEV_NS
 #undef SNAIL_ARITH_SSE
@@ -94,6 +95,7 @@ void snail_set_error(const char *fmt, ...) {
 #include "instances_materials.inc"
 #include "instances_materials_bounce.inc"
 #include "materials_transparency.inc"
+#include "instances_materials_transparency.inc"
 #include "materials_tree.inc"
 #undef SNAIL_DEV_NS
 #undef SNAIL_ARITH_SSE
@@ -1822,3 +1824,4 @@ int snail_account_primary(SnailScene *s, const float cam[13], int resx, int resy
 #include "materials_dynamic_host.inc"
 #include "instances_materials_host.inc"
 #include "instances_materials_bounce_host.inc"
+#include "instances_materials_transparency_host.inc"

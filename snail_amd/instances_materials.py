@@ -7,6 +7,10 @@ of include/snail_instances_materials.h.
                                                                  project's completion of the reference's TODO), primary packets and their lights
   .mirror_packets / .shade_rays, reflections=True           <-> the one mirrored bounce of gVals[7] (Scene::TraceReflection and its nested
                                                                  RayTrace<0, hasMask>), include/snail_instances_materials_bounce.h
+  InstancedMaterialSet(..., transparent=True), .can_select_transparent, .shade_packets_transp / .shade_rays_transp / .continue_packets,
+  .render_transparent / .render_transparent_packets / .render_transparent_image_host
+                                                            <-> the transparency continuation (Scene::TraceTransparency and its nested
+                                                                 RayTrace<0, hasMask>, level by level), include/snail_instances_materials_transparency.h
 
 Materials, textures and pack_shtris are snail_amd.materials'."""
 from __future__ import annotations
@@ -25,9 +29,10 @@ class _BlasShading(C.Structure):
     _fields_ = [("shtris64", C.c_void_p), ("nTris", C.c_int32), ("matMap", C.c_void_p), ("nMap", C.c_int32)]
 
 
-def create_instanced_set(instances_handle, shtris_list, map_list, materials, textures):
+def create_instanced_set(instances_handle, shtris_list, map_list, materials, textures, transparent: bool = False):
     """snail_instances_materials_create over raw arguments (per BLAS: uint8 [n, 64] records, int32 map) -> handle (c_void_p); SnailError with
-    the library's text when the set is refused"""
+    the library's text when the set is refused.  transparent=True: snail_instances_materials_create_transparent, with the materials'
+    opacity_texture"""
     sh = [np.ascontiguousarray(s, dtype=np.uint8).reshape(-1, 64) for s in shtris_list]
     mp = [np.ascontiguousarray(m, dtype=np.int32).reshape(-1) for m in map_list]
     if len(sh) != len(mp):
@@ -38,6 +43,14 @@ def create_instanced_set(instances_handle, shtris_list, map_list, materials, tex
         per[b].matMap, per[b].nMap = (mp[b].ctypes.data if len(mp[b]) else None), len(mp[b])
     recs = _material_records(materials)
     tex = _texture_array(textures)
+    if transparent:
+        op = np.ascontiguousarray([getattr(m, "opacity_texture", 0) for m in materials], dtype=np.int32)
+        h = _lib.lib().snail_instances_materials_create_transparent(instances_handle, C.cast(per, C.c_void_p) if len(sh) else None, len(sh),
+                                                                    _lib.ptr(recs) if len(recs) else None, len(recs), _lib.ptr(op) if len(op) else None,
+                                                                    C.cast(tex, C.c_void_p) if len(textures) else None, len(textures))
+        if not h:
+            raise _lib.SnailError("snail_instances_materials_create_transparent: %s" % _lib.lib().snail_last_error().decode())
+        return C.c_void_p(h)
     h = _lib.lib().snail_instances_materials_create(instances_handle, C.cast(per, C.c_void_p) if len(sh) else None, len(sh), _lib.ptr(recs) if len(recs) else None,
                                                     len(recs), C.cast(tex, C.c_void_p) if len(textures) else None, len(textures))
     if not h:
@@ -49,9 +62,11 @@ class InstancedMaterialSet:
     """The shading data of an instanced scene on its GPU.  per_blas[b] = (uv, nrm, mat_index, flat, material_map) of BLAS b's INPUT triangles
     (the order that scene was built from; its bvh.perm permutes them into triId order); a map entry is -1 (the default material) or an index
     into `materials`, ONE list for all BLASes.  The instanced scene (and through it the BLAS scenes) is kept alive by this object.  The
-    instance records are read at every launch: after isc.update / update_dev the same set shades with the new rotations."""
+    instance records are read at every launch: after isc.update / update_dev the same set shades with the new rotations.
+    transparent=True: the materials may be of the kinds that can select a transparent lane (Material.transparent, Material.uber with any
+    dissolve); such a set is shaded by the *_transp / render_transparent* methods alone."""
 
-    def __init__(self, isc: InstancedScene, per_blas, materials=(), textures=()):
+    def __init__(self, isc: InstancedScene, per_blas, materials=(), textures=(), transparent: bool = False):
         self.isc = isc
         self._h = None
         per_blas = list(per_blas)
@@ -65,7 +80,7 @@ class InstancedMaterialSet:
                 raise _lib.SnailError("InstancedMaterialSet: BLAS %d carries no host permutation (BVH slot -> input triangle); build it from host triangles" % b)
             self.shtris.append(pack_shtris(uv, nrm, mat_index, flat, perm))
             maps.append(material_map)
-        self._h = create_instanced_set(isc._h, self.shtris, maps, list(materials), list(textures))
+        self._h = create_instanced_set(isc._h, self.shtris, maps, list(materials), list(textures), transparent)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -185,6 +200,118 @@ class InstancedMaterialSet:
                                                                int(flags), _lib.ptr(img), pitch, _lib.ptr(stats))
         _lib.check(rc, "snail_instances_render_materials_image")
         return img, stats
+
+    # ---- include/snail_instances_materials_transparency.h -----------------------------------------------------------------------------------
+    @property
+    def can_select_transparent(self) -> bool:
+        """whether the set holds a material that can select a transparent lane (Material.transparent, or Material.uber with 0 < dissolve < 1):
+        such a set is refused by every method above this block"""
+        r = _lib.lib().snail_instances_materials_can_select_transparent(self._h)
+        if r < 0:
+            raise _lib.SnailError("snail_instances_materials_can_select_transparent: %s" % _lib.lib().snail_last_error().decode())
+        return bool(r)
+
+    def shade_packets_transp(self, cam, resx: int, resy: int, packet_xy, hits, stream=None):
+        """shade_packets for any set, with Sample::opacity and the transparency selector -> (samples float32 [n, 9, 64, 4], opacity float32
+        [n, 256], sel uint8 [n, 64]: low 4 bits = transSel after the opacity < 1 filter).  snail_instances_materials_shade_packets_transp_dev."""
+        torch = _torch()
+        n = int(packet_xy.shape[0])
+        dev = self.isc._dev()
+        out = torch.empty((n, SAMPLE_COMPONENTS, 64, 4), dtype=torch.float32, device=dev)
+        opacity = torch.empty((n, 256), dtype=torch.float32, device=dev)
+        sel = torch.empty((n, 64), dtype=torch.uint8, device=dev)
+        cam13 = np.ascontiguousarray(cam.as_array13(), dtype=np.float32)
+        rc = _lib.lib().snail_instances_materials_shade_packets_transp_dev(self._h, _lib.ptr(cam13), resx, resy, _lib.ptr(packet_xy), n, _lib.ptr(hits[0]), _lib.ptr(hits[1]),
+                                                                           _lib.ptr(hits[2]), _lib.ptr(hits[3]), _lib.ptr(hits[4]), _lib.ptr(out), _lib.ptr(opacity),
+                                                                           _lib.ptr(sel), _stream_ptr(stream))
+        _lib.check(rc, "snail_instances_materials_shade_packets_transp_dev")
+        return out, opacity, sel
+
+    def shade_rays_transp(self, dirs, mask, t, bary, inst, tri_id, stream=None):
+        """shade_rays for any set -> (samples, opacity, sel) as shade_packets_transp.  snail_instances_materials_shade_rays_transp_dev."""
+        torch = _torch()
+        n = int(dirs.shape[0])
+        dev = self.isc._dev()
+        out = torch.empty((n, SAMPLE_COMPONENTS, 64, 4), dtype=torch.float32, device=dev)
+        opacity = torch.empty((n, 256), dtype=torch.float32, device=dev)
+        sel = torch.empty((n, 64), dtype=torch.uint8, device=dev)
+        rc = _lib.lib().snail_instances_materials_shade_rays_transp_dev(self._h, n, _lib.ptr(dirs), _lib.ptr(mask), _lib.ptr(t), _lib.ptr(bary), _lib.ptr(inst),
+                                                                        _lib.ptr(tri_id), _lib.ptr(out), _lib.ptr(opacity), _lib.ptr(sel), _stream_ptr(stream))
+        _lib.check(rc, "snail_instances_materials_shade_rays_transp_dev")
+        return out, opacity, sel
+
+    def continue_packets(self, t, sel, cam=None, resx: int = 0, resy: int = 0, packet_xy=None, rays=None, stats=None, stream=None):
+        """Scene::TraceTransparency's packets of one level from its hits t [n, 256] and selector sel [n, 64] (device tensors).  The level's rays:
+        cam / resx / resy / packet_xy (the primary level) or rays = (origin, dir, idir) [n, 64, 3, 4] (generic packets) ->
+        (origin, dir, idir [n, 64, 3, 4] float32, mask [n, 64] uint8, distance [n, 256] float32, object, element [n, 256] int32 (zeros), bary
+        [n, 64, 2, 4] float32 (zeros), order [n] int32: the packet's index, or -1 when none of its lanes is selected): the packets as
+        InstancedScene.traverse_primary takes them in and out.  snail_instances_materials_continue_packets_dev."""
+        torch = _torch()
+        n = int(t.shape[0])
+        dev = self.isc._dev()
+        org, d, idir = (torch.empty((n, 64, 3, 4), dtype=torch.float32, device=dev) for _ in range(3))
+        mask = torch.empty((n, 64), dtype=torch.uint8, device=dev)
+        dist = torch.empty((n, 256), dtype=torch.float32, device=dev)
+        obj, elem = (torch.empty((n, 256), dtype=torch.int32, device=dev) for _ in range(2))
+        bary = torch.empty((n, 64, 2, 4), dtype=torch.float32, device=dev)
+        order = torch.empty((n,), dtype=torch.int32, device=dev)
+        cam13 = None if cam is None else np.ascontiguousarray(cam.as_array13(), dtype=np.float32)
+        ro, rd, ri = rays if rays is not None else (None, None, None)
+        rc = _lib.lib().snail_instances_materials_continue_packets_dev(self._h, _lib.ptr(cam13), int(resx), int(resy), _lib.ptr(packet_xy), n, _lib.ptr(ro), _lib.ptr(rd),
+                                                                       _lib.ptr(ri), _lib.ptr(t), _lib.ptr(sel), _lib.ptr(org), _lib.ptr(d), _lib.ptr(idir), _lib.ptr(mask),
+                                                                       _lib.ptr(dist), _lib.ptr(obj), _lib.ptr(elem), _lib.ptr(bary), _lib.ptr(order), _lib.ptr(stats),
+                                                                       _stream_ptr(stream))
+        _lib.check(rc, "snail_instances_materials_continue_packets_dev")
+        return org, d, idir, mask, dist, obj, elem, bary, order
+
+    def _truncated(self, truncated):
+        return truncated if truncated is not None else _torch().zeros(1, dtype=_torch().int64, device=self.isc._dev())
+
+    def render_transparent(self, cam, resx: int, resy: int, lights7=None, ambient=(0.1, 0.1, 0.1), out=None, stats=None, stream=None, flags: int = 0,
+                           max_depth: int = 8, truncated=None):
+        """The lit frame with the transparency continuation, at most max_depth levels deep -> (frame [resy, resx, 3] uint8 (B,G,R) or `out`,
+        truncated: an int64 device tensor of one word, += the lanes level max_depth would still select; 0 = the frame is the reference's).
+        snail_instances_materials_transparent_dev."""
+        torch = _torch()
+        if out is None:
+            out = torch.zeros((resy, resx, 3), dtype=torch.uint8, device=self.isc._dev())
+        truncated = self._truncated(truncated)
+        lights, cam13, amb = self._frame_args(cam, lights7, ambient)
+        rc = _lib.lib().snail_instances_materials_transparent_dev(self._h, _lib.ptr(cam13), resx, resy, _lib.ptr(lights) if len(lights) else None, len(lights), _lib.ptr(amb),
+                                                                  int(flags), _lib.ptr(out), int(out.stride(0)), int(max_depth), _lib.ptr(truncated), _lib.ptr(stats),
+                                                                  _stream_ptr(stream))
+        _lib.check(rc, "snail_instances_materials_transparent_dev")
+        return out, truncated
+
+    def render_transparent_packets(self, cam, resx: int, resy: int, packet_xy, lights7=None, ambient=(0.1, 0.1, 0.1), out=None, stats=None, stream=None,
+                                   flags: int = 0, max_depth: int = 8, truncated=None):
+        """render_transparent for an explicit packet list -> (packet-major [n, 256, 3] uint8 (B,G,R), truncated).
+        snail_instances_materials_transparent_packets_dev."""
+        torch = _torch()
+        n = int(packet_xy.shape[0])
+        if out is None:
+            out = torch.empty((n, 256, 3), dtype=torch.uint8, device=self.isc._dev())
+        truncated = self._truncated(truncated)
+        lights, cam13, amb = self._frame_args(cam, lights7, ambient)
+        rc = _lib.lib().snail_instances_materials_transparent_packets_dev(self._h, _lib.ptr(cam13), resx, resy, _lib.ptr(packet_xy), n,
+                                                                          _lib.ptr(lights) if len(lights) else None, len(lights), _lib.ptr(amb), int(flags), _lib.ptr(out),
+                                                                          int(max_depth), _lib.ptr(truncated), _lib.ptr(stats), _stream_ptr(stream))
+        _lib.check(rc, "snail_instances_materials_transparent_packets_dev")
+        return out, truncated
+
+    def render_transparent_image_host(self, cam, resx: int, resy: int, lights7=None, ambient=(0.1, 0.1, 0.1), flags: int = 0, pitch: int | None = None, fill: int = 0,
+                                      max_depth: int = 8, truncated=None):
+        """snail_instances_materials_transparent_image: the frame in host memory -> (uint8 [resy, pitch], stats uint64 [4], truncated: uint64
+        [1], the caller's array (+=) or a new one)"""
+        pitch = resx * 3 if pitch is None else int(pitch)
+        img = np.full((resy, pitch), fill, dtype=np.uint8)
+        stats = np.zeros(4, dtype=np.uint64)
+        truncated = np.zeros(1, dtype=np.uint64) if truncated is None else truncated
+        lights, cam13, amb = self._frame_args(cam, lights7, ambient)
+        rc = _lib.lib().snail_instances_materials_transparent_image(self._h, _lib.ptr(cam13), resx, resy, _lib.ptr(lights) if len(lights) else None, len(lights),
+                                                                    _lib.ptr(amb), int(flags), _lib.ptr(img), pitch, int(max_depth), _lib.ptr(truncated), _lib.ptr(stats))
+        _lib.check(rc, "snail_instances_materials_transparent_image")
+        return img, stats, truncated
 
 
 __all__ = ["InstancedMaterialSet", "create_instanced_set"]

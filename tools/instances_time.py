@@ -45,7 +45,19 @@ k_mat_final_blend) beside InstancedScene.render_whitted(reflections=True).  With
 normal and every material the default: the two paths then draw the same picture from the same rays (the degenerate set of the tests), and
 the ratio is the cost of the full-shading stages alone.
 
-    python tools/instances_time.py --materials [--reflections] [--plane-normals] [--reps 3]"""
+    python tools/instances_time.py --materials [--reflections] [--plane-normals] [--reps 3]
+
+--materials --transparency N: what the transparency continuation costs on an instanced full-shaded frame
+(include/snail_instances_materials_transparency.h).  The scene of --materials with two of its material classes swapped for kinds that can
+select a transparent lane (the second TEX material -> TRANSPARENT with the first texture's first channel as its opacity map, UBER dissolve 0
+-> UBER dissolve 0.5); host wall ms per frame, synchronised, alternating runs, medians, of
+  transp  InstancedMaterialSet.render_transparent(max_depth=N) (snail_instances_materials_transparent_dev): the way down level by level
+          (k_imat_sample_transp, k_mat_continue[_rays], k_imat_trace_level, k_imat_sample_transp_rays), k_mat_truncated, the way back up
+          (k_mat_blend_transp, k_imat_light_transp, k_mat_colour_transp), k_imat_light, k_mat_final
+  flags0  InstancedMaterialSet.render of the same run: the same scene with the opaque stand-ins the swap replaced
+and the lanes level N would still select (the truncated counter of one frame).  Nobody has measured this before: a record, not a gate.
+
+    python tools/instances_time.py --materials --transparency 4 [--reps 5]"""
 import argparse
 import json
 import os
@@ -89,6 +101,7 @@ def main():
     ap.add_argument("--materials", action="store_true")
     ap.add_argument("--reflections", action="store_true")
     ap.add_argument("--plane-normals", action="store_true")
+    ap.add_argument("--transparency", type=int, default=0, metavar="N")
     ap.add_argument("--baseline-lib", default=None)
     a = ap.parse_args()
     resx, resy = (int(x) for x in a.res.split("x"))
@@ -99,6 +112,8 @@ def main():
         return lit(torch, a, resx, resy)
     if a.tiles:
         return tiles(torch, a, resx, resy)
+    if a.materials and a.transparency:
+        return materials_transparency(torch, a, resx, resy)
     if a.materials:
         return materials(torch, a, resx, resy)
     rays = resx * resy
@@ -349,6 +364,65 @@ def materials(torch, a, resx, resy):
             out["rows"].append(row)
             print(json.dumps(row), file=sys.stderr, flush=True)
             ms_set.close()
+            isc.close()
+    sc.close()
+    print(json.dumps(out))
+
+
+def materials_transparency(torch, a, resx, resy):
+    import statistics
+    import time
+    from snail_amd import materials as P
+    from snail_amd.instances_materials import InstancedMaterialSet
+    rays = resx * resy
+    depth = int(a.transparency)
+    tv = scenes.atrium()
+    hb = HostBVH.build(tv)
+    sc = Scene(hb, 0)
+    lo, hi = sc.get_bbox()
+    uv, nrm, mi, flat, mmap, mats, texs = procedural_shading(hb, tv)
+    capable = list(mats)
+    capable[2] = P.Material.transparent(1, 0, False)                    # TEX over texture 1 -> TRANSPARENT, texture 0's first channel as opacity
+    capable[3] = P.Material.uber((0.9, 0.4, 0.1), (0.2, 0.6, 1.0), 0.5)   # UBER dissolve 0 -> 0.5
+    out = {"res": a.res, "lights": 1, "max_depth": depth, "unit": "host wall ms per frame, synchronised, median of %d alternating runs" % a.reps, "rows": []}
+    for arith in ("ieee", "host_sse"):
+        sc.set_arith(arith)
+        for n in (int(c) for c in a.counts.split(",")):
+            rot, tr, bi = scenes.instance_field(lo, hi, n, seed=1)
+            isc = InstancedScene([sc], rot, tr, bi)
+            opaque_set = InstancedMaterialSet(isc, [(uv, nrm, mi, flat, mmap)], mats, texs)
+            transp_set = InstancedMaterialSet(isc, [(uv, nrm, mi, flat, mmap)], capable, texs, transparent=True)
+            nd = isc.nodes()[0]
+            cam = survey_camera(tv) if n == 1 else survey_camera(np.concatenate([nd["bmin"], nd["bmax"], nd["bmin"]]).reshape(1, 9))
+            c, ext = (nd["bmin"] + nd["bmax"]) * 0.5, nd["bmax"] - nd["bmin"]
+            light = np.array([[c[0], c[1] + 0.3 * ext[1], c[2], 1.0, 1.0, 1.0, float(np.linalg.norm(ext))]], dtype=np.float32)
+            frame = torch.zeros((resy, resx, 3), dtype=torch.uint8, device="cuda")
+            trunc = torch.zeros(1, dtype=torch.int64, device="cuda")
+            runs = {"transp": lambda: transp_set.render_transparent(cam, resx, resy, light, out=frame, max_depth=depth, truncated=trunc),
+                    "flags0": lambda: opaque_set.render(cam, resx, resy, light, out=frame)}
+            ms = {k: [] for k in runs}
+            for k, fn in runs.items():      # warm-up: the sets' intermediates (the levels' part among them), the cached packet lists, first launches
+                fn(); fn(); torch.cuda.synchronize()
+            for _ in range(a.reps):         # alternating
+                for k, fn in runs.items():
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter(); fn(); torch.cuda.synchronize()
+                    ms[k].append((time.perf_counter() - t0) * 1e3)
+            trunc.zero_()
+            st = isc.new_stats()
+            transp_set.render_transparent(cam, resx, resy, light, out=frame, max_depth=depth, truncated=trunc, stats=st)
+            st0 = isc.new_stats()
+            row = {"arith": arith, "instances": n, "nonblack_pixels": int((frame.cpu().numpy() != 0).any(axis=2).sum()), "truncated_lanes": int(trunc.cpu().numpy()[0]),
+                   "traced_rays": int(st.cpu().numpy()[2])}
+            opaque_set.render(cam, resx, resy, light, out=frame, stats=st0)
+            row["flags0_traced_rays"] = int(st0.cpu().numpy()[2])
+            for k in ms:
+                m = statistics.median(ms[k])
+                row[k + "_ms"] = round(m, 3); row[k + "_min_ms"] = round(min(ms[k]), 3); row[k + "_mrays"] = round(rays / m / 1e3, 1)
+            row["transp_over_flags0"] = round(row["transp_ms"] / row["flags0_ms"], 3)
+            out["rows"].append(row)
+            print(json.dumps(row), file=sys.stderr, flush=True)
+            transp_set.close(); opaque_set.close()
             isc.close()
     sc.close()
     print(json.dumps(out))
