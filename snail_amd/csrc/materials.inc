@@ -19,12 +19,12 @@
 // and k_mat_final_blend instead of k_mat_final: diffuse += (colour - diffuse) * 0.3 on the hit lanes, before the lights (:462-465).
 // For the tile renderer (include/snail_materials_tiles.h) the primary colour stage has a float exit: k_mat_colour / k_mat_colour_blend leave outColor
 // as floats [packet][256][3] in ShadeArgs::colPackets, and k_inst_store (instances_shade.inc) goes on from there.
-// The light and colour stages are ONE body each, templated by their source (SRC_PRIMARY: rays from the camera, a hit = t < inf; SRC_MIRROR:
-// rays, masks and hits from the mirrored-packet buffers, a hit = t < inf AND the lane's mask bit: a masked lane carries -inf, not inf); the
-// primary kernels keep their names.
+// The sample, light and colour stages are ONE body each, templated by their source (SRC_PRIMARY: rays from the camera, a hit = t < inf;
+// SRC_MIRROR: rays, masks and hits from the mirrored-packet buffers, a hit = t < inf AND the lane's mask bit: a masked lane carries -inf, not
+// inf); the primary kernels keep their names.  The sample body, matSample, also serves instanced scenes and the transparent kinds.
 namespace SNAIL_DEV_NS {
 
-enum { MAT_SIMPLE = 0, MAT_TEX = 1, MAT_UBER = 2 };
+enum { MAT_SIMPLE = 0, MAT_TEX = 1, MAT_UBER = 2, MAT_TRANSPARENT = 3 };   // (MAT_TRANSPARENT: only in a set made for materials_transparency.inc)
 struct MatRec {            // 48 bytes, read as three dwordx4
 	int kind, ndotr;
 	float col[3], spec[3];
@@ -143,6 +143,9 @@ __device__ __forceinline__ void matSampleTex(const MatArgs &A, int texIdx, float
 
 // broadcast of the block's first lane (lanes 4b .. 4b + 3 -> lane 4b): quad_perm [0, 0, 0, 0]
 __device__ __forceinline__ int blockFirst(int v) { return __builtin_amdgcn_mov_dpp(v, 0x00, 0xf, 0xf, true); }
+// broadcast of lane I of the block (quad_perm [I, I, I, I])
+template <int I>
+__device__ __forceinline__ int blockLane(int v) { return __builtin_amdgcn_mov_dpp(v, I * 0x55, 0xf, 0xf, true); }
 // a predicate over all four lanes of the block
 __device__ __forceinline__ bool blockAll(bool p, int lane) {
 	const unsigned long long b = __builtin_amdgcn_ballot_w64(p);
@@ -162,193 +165,97 @@ __device__ __forceinline__ PacketPos matPacket(const MatArgs &A, int li) {
 	return P;
 }
 
-// (TWINS: k_mat_sample_rays below is this kernel for generic packets, k_imat_sample (instances_materials.inc) for instanced scenes and
-// k_imat_sample_rays (instances_materials_bounce.inc) for generic packets of instanced scenes; a change to the branches, the kinds or the output
-// belongs in all four.)
-__global__ __launch_bounds__(64) void k_mat_sample(MatArgs A) {
+// a level's order list (TranspArgs::inOrder and its kin): a packet whose word is negative is not part of the level; null: every packet
+__device__ __forceinline__ bool orderSkipped(const int *order, int li) { return order && __builtin_amdgcn_readfirstlane(order[li]) < 0; }
+
+// The key of a plain scene's hit: the triId alone, clamped to nTris; the record through loadShTri, its material through matIdOf.  No slot: the
+// constant 0 folds every slot comparison of matSample away.
+struct MatKey {
+	typedef MatArgs Args;
+	enum { SLOTS = 0 };
+	static __device__ __forceinline__ const MatArgs &mat(const MatArgs &A) { return A; }
+	static __device__ __forceinline__ void slots(const MatArgs &, const int *, size_t, int (&s)[4]) { s[0] = s[1] = s[2] = s[3] = 0; }
+	static __device__ __forceinline__ int tri(const MatArgs &A, int id) {
+		const int i = id < 0 ? 0 : id;
+		return i < A.nTris ? i : A.nTris - 1;
+	}
+	static __device__ __forceinline__ ShTri load(const MatArgs &A, int, int tri, int &mat) {
+		const ShTri T = loadShTri(A, tri);
+		mat = matIdOf(A, T.matId);
+		return T;
+	}
+};
+
+// ---- one packet: the sample stage, hit records -> the nine planes of the sample buffer (+ [T] Sample::opacity and the transSel selector) ----
+// ONE body for the eight sample kernels, instantiated over three compile-time axes:
+//   SRC     SRC_PRIMARY: the camera's rays and the primary hits (every lane selected, RayGroup<0, 0>)            k_*_sample, k_*_sample_transp
+//           SRC_MIRROR: GENERIC packets, RayGroup<0, hasMask> (the nested calls of the bounce and of a transparency level): the directions read
+//           from the packet, a hit = t < inf AND the lane's mask bit, the bary stride, the packet's own hasMask   k_*_sample_rays, k_*_sample_transp_rays
+//   KEY     MatKey (above): a plain scene, the key is triId                                                       k_mat_sample*
+//           IMatKey (instances_materials.inc): an instanced scene, the key is the pair (slot, triId) -- every equality of :171-356 is on the
+//           pair (object, element), as the reference compares wherever isctFlags & fElement is set (:162, :179-182, :252-253, :263) --, the
+//           record through imatLoadTri                                                                            k_imat_sample*
+//   TRANSP  the lines marked [T]: the kinds that can select a transparent lane (TransparentMaterial<NDotR>, UberMaterial's dissFactor),
+//           Sample::opacity per ray, the transSel selector after the opacity < 1 filter (:190, :306, :347-349, :472) and the level's order
+//           list (inOrder, opacity, selOut: null without)                                                         k_*_sample_transp*
+// X is the kernel's argument record (KEY::Args, MatArgs inside it), inst the slots of the hits (null for MatKey).
+// The planes of a set without the [T] kinds are the same byte for byte with TRANSP on or off; with it off the code holds no load of
+// MatRec::pad, no second texture sample, no opac / flagged / winner scan and no store of opacity or selector.
+template <int SRC, bool TRANSP, class KEY>
+__device__ __forceinline__ void matSample(const typename KEY::Args &X, const int *inst, const int *inOrder, float *opacity, unsigned char *selOut) {
+	const MatArgs &A = KEY::mat(X);
 	const int lane = threadIdx.x & 63;
 	const int li = (int)blockIdx.x;
-	if(li >= A.s.nPackets) return;
-	const PacketPos P = packetOf(A.s, li);
-	const size_t quad = P.pidx * 64 + lane;
-	const float inf = __builtin_inff();
-	float d[3][4];
-	matRays(A.s, P, lane, d);
-	float bx[4], by[4];
-	bool hit[4];
-	int obj[4];
-	{
-		const float4 tv = *(const float4 *)(A.s.hitT + quad * 4), uv = *(const float4 *)(A.hitU + quad * 4), vv = *(const float4 *)(A.hitV + quad * 4);
-		const int4 iv = *(const int4 *)(A.s.hitId + quad * 4);
-		const float t[4] = {tv.x, tv.y, tv.z, tv.w};
-		const int id[4] = {iv.x, iv.y, iv.z, iv.w};
-		bx[0] = uv.x; bx[1] = uv.y; bx[2] = uv.z; bx[3] = uv.w;
-		by[0] = vv.x; by[1] = vv.y; by[2] = vv.z; by[3] = vv.w;
-#pragma unroll
-		for(int l = 0; l < 4; l++) {
-			hit[l] = t[l] < inf;
-			int i = id[l] < 0 ? 0 : id[l];
-			i = i < A.nTris ? i : A.nTris - 1;
-			obj[l] = hit[l] ? i : 0;       // object = Condition(mask, tObject, 0), :161
-		}
-	}
-	// mask4 == 0x0f0f0f0f, and the 16 objects equal to the block's first (:178-182)
-	const bool full = blockAll(hit[0] && hit[1] && hit[2] && hit[3], lane);
-	const int obj0b = blockFirst(obj[0]);
-	const bool single = blockAll(obj[0] == obj0b && obj[1] == obj0b && obj[2] == obj0b && obj[3] == obj0b, lane) && full;
-
-	float nrm[3][4], tc[2][4], tdx = 0.0f, tdy = 0.0f;
-	int mid[4];
-#pragma unroll
-	for(int l = 0; l < 4; l++) { nrm[0][l] = nrm[1][l] = nrm[2][l] = 0.0f; tc[0][l] = tc[1][l] = 0.0f; mid[l] = -1; }
-	if(single) {
-		// (a): one triangle for the block
-		const ShTri T = loadShTri(A, obj0b);
-		const int m = matIdOf(A, T.matId);
-		const bool flat = T.matId < 0;
-		const bool texd = m >= 0 && A.mats[m].kind == MAT_TEX;     // Material::fTexCoords
-#pragma unroll
-		for(int l = 0; l < 4; l++) {
-			mid[l] = m;
-			if(texd) {
-#pragma unroll
-				for(int c = 0; c < 2; c++) tc[c][l] = lerpL(T.uv[0][c], T.uv[1][c], T.uv[2][c], bx[l], by[l]);
-#pragma unroll
-				for(int c = 0; c < 3; c++) nrm[c][l] = lerpL(T.nrm[0][c], T.nrm[1][c], T.nrm[2][c], bx[l], by[l]);
-			} else {
-#pragma unroll
-				for(int c = 0; c < 3; c++) nrm[c][l] = flat ? T.nrm[0][c] : lerpR(T.nrm[0][c], T.nrm[1][c], T.nrm[2][c], bx[l], by[l]);
-			}
-		}
-		if(texd) {   // texDiff = Maximize(texCoord) - Minimize(texCoord) of the quad (:219; finite values: the fold's order is immaterial)
-			tdx = vmax(vmax(tc[0][0], tc[0][1]), vmax(tc[0][2], tc[0][3])) - vmin(vmin(tc[0][0], tc[0][1]), vmin(tc[0][2], tc[0][3]));
-			tdy = vmax(vmax(tc[1][0], tc[1][1]), vmax(tc[1][2], tc[1][3])) - vmin(vmin(tc[1][0], tc[1][1]), vmin(tc[1][2], tc[1][3]));
-		}
-	} else {
-		// (b): per quad; lane 0's triangle for all four lanes if lane 0 hit, then lanes 1..3 whose triangle differs from obj[0] (0 when lane 0 missed)
-		if(hit[0]) {
-			const ShTri T = loadShTri(A, obj[0]);
-			const int m = matIdOf(A, T.matId);
-#pragma unroll
-			for(int l = 0; l < 4; l++) {
-				mid[l] = hit[l] ? m : -1;
-#pragma unroll
-				for(int c = 0; c < 2; c++) tc[c][l] = lerpL(T.uv[0][c], T.uv[1][c], T.uv[2][c], bx[l], by[l]);
-#pragma unroll
-				for(int c = 0; c < 3; c++) nrm[c][l] = lerpL(T.nrm[0][c], T.nrm[1][c], T.nrm[2][c], bx[l], by[l]);
-			}
-		}
-#pragma unroll
-		for(int l = 1; l < 4; l++)
-			if(hit[l] && obj[l] != obj[0]) {
-				const ShTri T = loadShTri(A, obj[l]);
-				mid[l] = matIdOf(A, T.matId);
-#pragma unroll
-				for(int c = 0; c < 2; c++) tc[c][l] = lerpL(T.uv[0][c], T.uv[1][c], T.uv[2][c], bx[l], by[l]);
-#pragma unroll
-				for(int c = 0; c < 3; c++) nrm[c][l] = lerpL(T.nrm[0][c], T.nrm[1][c], T.nrm[2][c], bx[l], by[l]);
-			}
-	}
-	// One material for 16 hit rays: Shade unmasked (:224, :301-308); otherwise (c) every selected lane by its own material on the masked path
-	// (:310-355).  The per-material masks of (c) are disjoint -- a lane has one matId -- and a masked Shade writes only its own lanes, so the order
-	// in which the reference walks its material list cannot show: shading each lane once by its own material is the same.
-	const int mid0b = blockFirst(mid[0]);
-	const bool unmasked = blockAll(mid[0] == mid0b && mid[1] == mid0b && mid[2] == mid0b && mid[3] == mid0b, lane) && full;
-
-	float diff[3][4], spec[3][4];
-#pragma unroll
-	for(int l = 0; l < 4; l++) {
-		// the lane's material: loaded values of an unrolled loop (compile-time indices), never a runtime-indexed array
-		int kind = MAT_SIMPLE, ndotr = 1, tex = 0;
-		float col[3] = {1.0f, 1.0f, 1.0f}, sp[3] = {0.0f, 0.0f, 0.0f};   // defaultMat = SimpleMaterial<true>(1, 1, 1), src/scene.cpp:6
-		if(mid[l] >= 0) {
-			const uint4 *r = (const uint4 *)(A.mats + mid[l]);
-			const uint4 a = r[0], b = r[1], c = r[2];
-			kind = (int)a.x; ndotr = (int)a.y;
-			col[0] = asf(a.z); col[1] = asf(a.w); col[2] = asf(b.x);
-			sp[0] = asf(b.y); sp[1] = asf(b.z); sp[2] = asf(b.w);
-			tex = (int)c.x;
-		}
-		const float dn = d[0][l] * nrm[0][l] + d[1][l] * nrm[1][l] + d[2][l] * nrm[2][l];
-		const float adn = __builtin_fabsf(dn);
-		float t1[3] = {0.0f, 0.0f, 0.0f};
-		// the kinds present among the wave's lanes: a branch per kind that needs code of its own, skipped when no lane has it
-		if(__builtin_amdgcn_ballot_w64(kind == MAT_TEX && hit[l]) != 0) {
-			if(kind == MAT_TEX && hit[l]) matSampleTex(A, tex, tc[0][l], tc[1][l], tdx, tdy, t1);
-		}
-#pragma unroll
-		for(int c = 0; c < 3; c++) {
-			float df, sf;
-			if(kind == MAT_TEX) { df = ndotr ? t1[c] * dn : t1[c]; sf = df; }
-			else if(kind == MAT_UBER) { df = col[c] * adn; sf = unmasked ? df : sp[c]; }
-			else { df = ndotr ? col[c] * adn : col[c]; sf = df; }
-			diff[c][l] = hit[l] ? df : 0.0f;
-			spec[c][l] = hit[l] ? sf : 0.0f;
-			nrm[c][l] = hit[l] ? nrm[c][l] : 0.0f;
-		}
-	}
-	float4 *o = (float4 *)(A.samples + P.pidx * (9 * 256)) + lane;
-#pragma unroll
-	for(int c = 0; c < 3; c++) {
-		o[(0 + c) * 64] = make_float4(nrm[c][0], nrm[c][1], nrm[c][2], nrm[c][3]);
-		o[(3 + c) * 64] = make_float4(diff[c][0], diff[c][1], diff[c][2], diff[c][3]);
-		o[(6 + c) * 64] = make_float4(spec[c][0], spec[c][1], spec[c][2], spec[c][3]);
-	}
-}
-
-// The sample stage on GENERIC packets, RayGroup<0, hasMask> (the nested call of the bounce): k_mat_sample with the directions read from the
-// packet, a hit = t < inf AND the lane's mask bit, and branch (a) shaded with the packet's own hasMask.  A second kernel, not a template
-// argument of k_mat_sample: by the resource report the shared body cost the primary kernel two VGPRs (profiles/materials_resources.txt).
-// TWINS: everything else -- blocks, the triId-0 quirk, texDiff, the mip choice, the kinds, the output -- is k_mat_sample's; a change there
-// belongs in both.  k_imat_sample_rays (instances_materials_bounce.inc) has this kernel's input side -- directions, mask, bary stride, the packet's
-// hasMask -- around k_imat_sample's keys: a change to that side belongs there too.
-__global__ __launch_bounds__(64) void k_mat_sample_rays(MatArgs A) {
-	const int lane = threadIdx.x & 63;
-	const int li = (int)blockIdx.x;
-	if(li >= A.s.nPackets) return;
-	const PacketPos P = matPacket<SRC_MIRROR>(A, li);
+	if(li >= A.s.nPackets || (TRANSP && orderSkipped(inOrder, li))) return;   // [T] a packet outside its level's call is skipped
+	const PacketPos P = matPacket<SRC>(A, li);
 	const size_t quad = P.pidx * 64 + lane;
 	const float inf = __builtin_inff();
 	float d[3][4];
 	unsigned mask4 = 15u;
-	loadQuad3(A.s.rDir, quad, d);
-	if(A.s.rMask) mask4 = A.s.rMask[quad] & 15u;
-	// hasMask is the PACKET's: RayGroup<0, 0> when all 256 lanes are selected, RayGroup<0, 1> otherwise (src/scene_trace.cpp:615-617)
-	const bool pktMasked = __builtin_amdgcn_ballot_w64(mask4 != 15u) != 0;
+	if(SRC == SRC_MIRROR) {
+		loadQuad3(A.s.rDir, quad, d);
+		if(A.s.rMask) mask4 = A.s.rMask[quad] & 15u;
+	} else matRays(A.s, P, lane, d);
+	// hasMask is the PACKET's: RayGroup<0, 0> when all 256 lanes are selected, RayGroup<0, 1> otherwise (src/scene_trace.cpp:615-617, :631-633)
+	const bool pktMasked = SRC == SRC_MIRROR && __builtin_amdgcn_ballot_w64(mask4 != 15u) != 0;
 	float bx[4], by[4];
 	bool hit[4];
-	int obj[4];
+	int obj[4], slt[4];
 	{
-		const size_t uvq = quad * (size_t)A.rUVStride;
-		const float4 tv = *(const float4 *)(A.s.rDist + quad * 4), uv = *(const float4 *)(A.rU + uvq), vv = *(const float4 *)(A.rV + uvq);
-		const int4 iv = *(const int4 *)(A.s.rObj + quad * 4);
+		const size_t uvq = SRC == SRC_MIRROR ? quad * (size_t)A.rUVStride : quad * 4;
+		const float4 tv = *(const float4 *)((SRC == SRC_MIRROR ? A.s.rDist : A.s.hitT) + quad * 4);
+		const float4 uv = *(const float4 *)((SRC == SRC_MIRROR ? A.rU : A.hitU) + uvq), vv = *(const float4 *)((SRC == SRC_MIRROR ? A.rV : A.hitV) + uvq);
+		const int4 iv = *(const int4 *)((SRC == SRC_MIRROR ? (const int *)A.s.rObj : A.s.hitId) + quad * 4);
 		const float t[4] = {tv.x, tv.y, tv.z, tv.w};
 		const int id[4] = {iv.x, iv.y, iv.z, iv.w};
+		int sl[4];
+		KEY::slots(X, inst, quad, sl);
 		bx[0] = uv.x; bx[1] = uv.y; bx[2] = uv.z; bx[3] = uv.w;
 		by[0] = vv.x; by[1] = vv.y; by[2] = vv.z; by[3] = vv.w;
 #pragma unroll
 		for(int l = 0; l < 4; l++) {
 			hit[l] = t[l] < inf && ((mask4 >> l) & 1u) != 0;   // mask = tDistance < maxDist && selector, :157
-			int i = id[l] < 0 ? 0 : id[l];
-			i = i < A.nTris ? i : A.nTris - 1;
-			obj[l] = hit[l] ? i : 0;       // object = Condition(mask, tObject, 0), :161
+			const int i = KEY::tri(X, id[l]), s = sl[l];   // (scalars, so that both lines below are selects: the hit records stay one dwordx4 load each)
+			slt[l] = hit[l] ? s : 0;       // object = Condition(mask, tObject, 0), :161
+			obj[l] = hit[l] ? i : 0;       // element = Condition(mask, tElement, 0), :162 (a plain scene's object, :161)
 		}
 	}
-	// mask4 == 0x0f0f0f0f, and the 16 objects equal to the block's first (:178-182)
+	// mask4 == 0x0f0f0f0f, and the 16 objects -- (object, element) pairs -- equal to the block's first (:178-182)
 	const bool full = blockAll(hit[0] && hit[1] && hit[2] && hit[3], lane);
-	const int obj0b = blockFirst(obj[0]);
-	const bool single = blockAll(obj[0] == obj0b && obj[1] == obj0b && obj[2] == obj0b && obj[3] == obj0b, lane) && full;
+	const int obj0b = blockFirst(obj[0]), slt0b = KEY::SLOTS ? blockFirst(slt[0]) : 0;
+	const bool single = blockAll(obj[0] == obj0b && obj[1] == obj0b && obj[2] == obj0b && obj[3] == obj0b &&
+								 slt[0] == slt0b && slt[1] == slt0b && slt[2] == slt0b && slt[3] == slt0b, lane) && full;
 
 	float nrm[3][4], tc[2][4], tdx = 0.0f, tdy = 0.0f;
 	int mid[4];
 #pragma unroll
 	for(int l = 0; l < 4; l++) { nrm[0][l] = nrm[1][l] = nrm[2][l] = 0.0f; tc[0][l] = tc[1][l] = 0.0f; mid[l] = -1; }
 	if(single) {
-		// (a): one triangle for the block
-		const ShTri T = loadShTri(A, obj0b);
-		const int m = matIdOf(A, T.matId);
+		// (a): one triangle (of one instance) for the block
+		int m;
+		const ShTri T = KEY::load(X, slt0b, obj0b, m);
 		const bool flat = T.matId < 0;
-		const bool texd = m >= 0 && A.mats[m].kind == MAT_TEX;     // Material::fTexCoords
+		const bool texd = m >= 0 && (A.mats[m].kind == MAT_TEX || (TRANSP && A.mats[m].kind == MAT_TRANSPARENT));   // Material::fTexCoords  [T]: TransparentMaterial carries it too
 #pragma unroll
 		for(int l = 0; l < 4; l++) {
 			mid[l] = m;
@@ -367,10 +274,12 @@ __global__ __launch_bounds__(64) void k_mat_sample_rays(MatArgs A) {
 			tdy = vmax(vmax(tc[1][0], tc[1][1]), vmax(tc[1][2], tc[1][3])) - vmin(vmin(tc[1][0], tc[1][1]), vmin(tc[1][2], tc[1][3]));
 		}
 	} else {
-		// (b): per quad; lane 0's triangle for all four lanes if lane 0 hit, then lanes 1..3 whose triangle differs from obj[0] (0 when lane 0 missed)
+		// (b): per quad; lane 0's triangle for all four lanes if lane 0 hit, then lanes 1..3 whose key differs from lane 0's -- triId 0, or
+		// (slot 0, triId 0), when lane 0 missed or is masked: a lane that hit (slot 0's) triangle 0 beside it keeps the default material and zero
+		// normal / texCoord.  A record is loaded (and transformed) only on lanes that hit.
 		if(hit[0]) {
-			const ShTri T = loadShTri(A, obj[0]);
-			const int m = matIdOf(A, T.matId);
+			int m;
+			const ShTri T = KEY::load(X, slt[0], obj[0], m);
 #pragma unroll
 			for(int l = 0; l < 4; l++) {
 				mid[l] = hit[l] ? m : -1;
@@ -382,28 +291,29 @@ __global__ __launch_bounds__(64) void k_mat_sample_rays(MatArgs A) {
 		}
 #pragma unroll
 		for(int l = 1; l < 4; l++)
-			if(hit[l] && obj[l] != obj[0]) {
-				const ShTri T = loadShTri(A, obj[l]);
-				mid[l] = matIdOf(A, T.matId);
+			if(hit[l] && (obj[l] != obj[0] || slt[l] != slt[0])) {
+				const ShTri T = KEY::load(X, slt[l], obj[l], mid[l]);
 #pragma unroll
 				for(int c = 0; c < 2; c++) tc[c][l] = lerpL(T.uv[0][c], T.uv[1][c], T.uv[2][c], bx[l], by[l]);
 #pragma unroll
 				for(int c = 0; c < 3; c++) nrm[c][l] = lerpL(T.nrm[0][c], T.nrm[1][c], T.nrm[2][c], bx[l], by[l]);
 			}
 	}
-	// One material for 16 hit rays: Shade unmasked (:224, :301-308); otherwise (c) every selected lane by its own material on the masked path
-	// (:310-355).  The per-material masks of (c) are disjoint -- a lane has one matId -- and a masked Shade writes only its own lanes, so the order
-	// in which the reference walks its material list cannot show: shading each lane once by its own material is the same.
+	// One material for 16 hit rays: Shade unmasked (:224, :301-308) -- an instanced scene's ids index ONE scene-wide list, so two BLASes'
+	// triangles of one material meet here --; otherwise (c) every selected lane by its own material on the masked path (:310-355).  The
+	// per-material masks of (c) are disjoint -- a lane has one matId -- and a masked Shade writes only its own lanes, so the order in which the
+	// reference walks its material list cannot show: shading each lane once by its own material is the same.
 	// Branch (a) calls Shade with the packet's own hasMask (:224), (b)'s single-material call is RayGroup<.., 0> whatever the packet is (:308).
 	const int mid0b = blockFirst(mid[0]);
 	const bool unmasked = blockAll(mid[0] == mid0b && mid[1] == mid0b && mid[2] == mid0b && mid[3] == mid0b, lane) && full && !(single && pktMasked);
 
-	float diff[3][4], spec[3][4];
+	float diff[3][4], spec[3][4], opac[4];
+	int flagged[4];   // [T] the lane's material when it carries Material::fTransparency and the lane is selected, else -1
 #pragma unroll
 	for(int l = 0; l < 4; l++) {
 		// the lane's material: loaded values of an unrolled loop (compile-time indices), never a runtime-indexed array
-		int kind = MAT_SIMPLE, ndotr = 1, tex = 0;
-		float col[3] = {1.0f, 1.0f, 1.0f}, sp[3] = {0.0f, 0.0f, 0.0f};   // defaultMat = SimpleMaterial<true>(1, 1, 1), src/scene.cpp:6
+		int kind = MAT_SIMPLE, ndotr = 1, tex = 0, tex2 = 0;
+		float col[3] = {1.0f, 1.0f, 1.0f}, sp[3] = {0.0f, 0.0f, 0.0f}, dissolve = 0.0f;   // defaultMat = SimpleMaterial<true>(1, 1, 1), src/scene.cpp:6
 		if(mid[l] >= 0) {
 			const uint4 *r = (const uint4 *)(A.mats + mid[l]);
 			const uint4 a = r[0], b = r[1], c = r[2];
@@ -411,33 +321,81 @@ __global__ __launch_bounds__(64) void k_mat_sample_rays(MatArgs A) {
 			col[0] = asf(a.z); col[1] = asf(a.w); col[2] = asf(b.x);
 			sp[0] = asf(b.y); sp[1] = asf(b.z); sp[2] = asf(b.w);
 			tex = (int)c.x;
+			if(TRANSP) { tex2 = (int)c.y; dissolve = asf(c.z); }   // [T] MatRec::pad[0], pad[1]: the opacity map, the dissolve factor
 		}
 		const float dn = d[0][l] * nrm[0][l] + d[1][l] * nrm[1][l] + d[2][l] * nrm[2][l];
 		const float adn = __builtin_fabsf(dn);
-		float t1[3] = {0.0f, 0.0f, 0.0f};
+		float t1[3] = {0.0f, 0.0f, 0.0f}, t2[3] = {0.0f, 0.0f, 0.0f};
 		// the kinds present among the wave's lanes: a branch per kind that needs code of its own, skipped when no lane has it
 		if(__builtin_amdgcn_ballot_w64(kind == MAT_TEX && hit[l]) != 0) {
 			if(kind == MAT_TEX && hit[l]) matSampleTex(A, tex, tc[0][l], tc[1][l], tdx, tdy, t1);
 		}
+		// [T] TransparentMaterial::Shade_: both samplers with mipmapping off (Sample(samples, sc, 0)) -- level 0 whatever texDiff says
+		if(TRANSP && __builtin_amdgcn_ballot_w64(kind == MAT_TRANSPARENT && hit[l]) != 0) {
+			if(kind == MAT_TRANSPARENT && hit[l]) {
+				matSampleTex(A, tex, tc[0][l], tc[1][l], 0.0f, 0.0f, t1);
+				matSampleTex(A, tex2, tc[0][l], tc[1][l], 0.0f, 0.0f, t2);
+			}
+		}
 #pragma unroll
 		for(int c = 0; c < 3; c++) {
 			float df, sf;
-			if(kind == MAT_TEX) { df = ndotr ? t1[c] * dn : t1[c]; sf = df; }
+			if(kind == MAT_TEX || (TRANSP && kind == MAT_TRANSPARENT)) { df = ndotr ? t1[c] * dn : t1[c]; sf = df; }
 			else if(kind == MAT_UBER) { df = col[c] * adn; sf = unmasked ? df : sp[c]; }
 			else { df = ndotr ? col[c] * adn : col[c]; sf = df; }
 			diff[c][l] = hit[l] ? df : 0.0f;
 			spec[c][l] = hit[l] ? sf : 0.0f;
 			nrm[c][l] = hit[l] ? nrm[c][l] : 0.0f;
 		}
+		if(TRANSP) {
+			// [T] Sample::opacity: temp1.x of the opacity sampler / dissFactor; the other kinds never write it (read before written: zero)
+			const float op = kind == MAT_TRANSPARENT ? t2[0] : kind == MAT_UBER ? dissolve : 0.0f;
+			opac[l] = hit[l] ? op : 0.0f;
+			const bool fl = kind == MAT_TRANSPARENT || (kind == MAT_UBER && dissolve > 0.0f);   // UberMaterial: fTransparency iff dissolveFactor > 0
+			flagged[l] = (hit[l] && fl) ? mid[l] : -1;
+		}
 	}
-	float4 *o = (float4 *)(A.nSamples + P.pidx * (9 * 256)) + lane;
+	unsigned sel = 0;
+	if(TRANSP) {
+		// [T] transSel.  (a) / (b): the block's one material's flag for the whole block (:190, :306).  (c): for each material of the block's list that
+		// carries the flag, IN THE LIST'S ORDER -- first appearance over the quads, then the lanes, among the selected lanes -- transSel[b4 + q] =
+		// mask[q] is ASSIGNED for all four quads (:347-349): the last flagged material of the list wins.  One rule covers the three branches: the
+		// winner is the flagged material whose first appearance comes latest; a block of one material has one candidate.  A material's identity
+		// in an instanced scene is its index in the ONE scene-wide list: two BLASes' triangles of one entry are one candidate.
+		if(__builtin_amdgcn_ballot_w64((flagged[0] & flagged[1] & flagged[2] & flagged[3]) != -1) != 0) {
+			int e[16];
+#pragma unroll
+			for(int l = 0; l < 4; l++) {
+				e[0 + l] = blockLane<0>(flagged[l]); e[4 + l] = blockLane<1>(flagged[l]);
+				e[8 + l] = blockLane<2>(flagged[l]); e[12 + l] = blockLane<3>(flagged[l]);
+			}
+			int win = -1;
+#pragma unroll
+			for(int p = 0; p < 16; p++) {
+				bool first = e[p] >= 0;
+#pragma unroll
+				for(int k = 0; k < p; k++) first = first && e[k] != e[p];
+				win = first ? e[p] : win;
+			}
+#pragma unroll
+			for(int l = 0; l < 4; l++)
+				sel |= (win >= 0 && flagged[l] == win && opac[l] < 1.0f) ? (1u << l) : 0u;   // transSel[q] &= ForWhich(opacity < 1.0f), :472
+		}
+	}
+	float4 *o = (float4 *)((SRC == SRC_MIRROR ? A.nSamples : A.samples) + P.pidx * (9 * 256)) + lane;
 #pragma unroll
 	for(int c = 0; c < 3; c++) {
 		o[(0 + c) * 64] = make_float4(nrm[c][0], nrm[c][1], nrm[c][2], nrm[c][3]);
 		o[(3 + c) * 64] = make_float4(diff[c][0], diff[c][1], diff[c][2], diff[c][3]);
 		o[(6 + c) * 64] = make_float4(spec[c][0], spec[c][1], spec[c][2], spec[c][3]);
 	}
+	if(TRANSP) {   // [T]
+		*(float4 *)(opacity + quad * 4) = make_float4(opac[0], opac[1], opac[2], opac[3]);
+		selOut[quad] = (unsigned char)sel;
+	}
 }
+__global__ __launch_bounds__(64) void k_mat_sample(MatArgs A) { matSample<SRC_PRIMARY, false, MatKey>(A, nullptr, nullptr, nullptr, nullptr); }
+__global__ __launch_bounds__(64) void k_mat_sample_rays(MatArgs A) { matSample<SRC_MIRROR, false, MatKey>(A, nullptr, nullptr, nullptr, nullptr); }
 
 // position and hit mask as in simple shading (src/scene_trace.cpp:157-165), the normal from the sample buffer.  SRC_MIRROR: the mirrored
 // packet's own rays, position = reflDir * t + reflOrig, hit = t < inf and the lane's mask bit, the normal from the nested sample buffer.
@@ -474,9 +432,8 @@ __device__ __forceinline__ void matLoadSamples(const MatArgs &A, const PacketPos
 // ---- one (packet, light): the shadow packet (src/scene_trace.cpp:538-558) and BVH::TraverseShadow, by the walks of lightPacket ----
 // TWINS: the set-up and the walk selection below are those of lightPacket (snail_dev.inc; its main pass and its deferred M_EXACT pass folded into
 // one kernel, look-ups checked), and k_inst_light (instances_shade.inc) has the same set-up around the instanced walk.  A change to the shadow
-// packet, to the classify / walkSharedAsm / walk dispatch or to the stats booking belongs in all three.  k_imat_light (instances_materials.inc)
-// is this function's sample load and set-up around k_inst_light's walk, and k_imat_light_rays (instances_materials_bounce.inc) the same with
-// SRC_MIRROR's sample load and the nested distance buffer: a change to the shadow packet belongs in those two as well.
+// packet, to the classify / walkSharedAsm / walk dispatch or to the stats booking belongs in all three.  imatLight (instances_materials.inc)
+// is this function's sample load and set-up around k_inst_light's walk: a change to the shadow packet belongs there as well.
 // SRC_MIRROR: the nested call's lights on the mirrored packets' samples -- the same shadow packet (the light's shared origin) and walks.
 // PSTATS: the heat-map launches' instantiation (include/snail_materials_heatmap.h), which also books the (packet, light)'s counters per packet at
 // P.pidx -- a template argument as in snail_dev.inc, so that the other launches' kernels stay the code they were.  A culled pair has returned

@@ -34,7 +34,7 @@ __device__ __forceinline__ void matMirrorRays(const TreeArgs &G) {
 	const int lane = threadIdx.x & 63;
 	const int li = (int)blockIdx.x;
 	if(li >= A.s.nPackets) return;
-	if(transpSkipped(T, li)) {   // (wave-uniform)
+	if(orderSkipped(T.inOrder, li)) {   // (wave-uniform)
 		if(lane == 0) G.oOrder[li] = -1;
 		return;
 	}
@@ -104,7 +104,7 @@ __device__ __forceinline__ void matBlendRefl(const TranspArgs &T) {
 	const MatArgs &A = T.m;
 	const int lane = threadIdx.x & 63;
 	const int li = (int)blockIdx.x;
-	if(li >= A.s.nPackets || transpSkipped(T, li)) return;
+	if(li >= A.s.nPackets || orderSkipped(T.inOrder, li)) return;
 	const size_t quad = (size_t)li * 64 + lane;
 	const float inf = __builtin_inff();
 	const float4 tv = *(const float4 *)((SRC == SRC_MIRROR ? A.s.rDist : A.s.hitT) + quad * 4);

@@ -359,7 +359,7 @@ def materials(torch, a, resx, resy):
                 fn_simple(); row["frames_equal"] = bool(np.array_equal(full_frame, frame.cpu().numpy()))
             for k in ms:
                 m = statistics.median(ms[k])
-                row[k + "_ms"] = round(m, 3); row[k + "_min_ms"] = round(min(ms[k]), 3); row[k + "_mrays"] = round(rays / m / 1e3, 1)
+                row[k + "_ms"] = round(m, 3); row[k + "_min_ms"] = round(min(ms[k]), 3); row[k + "_max_ms"] = round(max(ms[k]), 3); row[k + "_mrays"] = round(rays / m / 1e3, 1)
             row["full_over_simple"] = round(row["full_ms"] / row["simple_ms"], 3)
             out["rows"].append(row)
             print(json.dumps(row), file=sys.stderr, flush=True)
@@ -418,7 +418,7 @@ def materials_transparency(torch, a, resx, resy):
             row["flags0_traced_rays"] = int(st0.cpu().numpy()[2])
             for k in ms:
                 m = statistics.median(ms[k])
-                row[k + "_ms"] = round(m, 3); row[k + "_min_ms"] = round(min(ms[k]), 3); row[k + "_mrays"] = round(rays / m / 1e3, 1)
+                row[k + "_ms"] = round(m, 3); row[k + "_min_ms"] = round(min(ms[k]), 3); row[k + "_max_ms"] = round(max(ms[k]), 3); row[k + "_mrays"] = round(rays / m / 1e3, 1)
             row["transp_over_flags0"] = round(row["transp_ms"] / row["flags0_ms"], 3)
             out["rows"].append(row)
             print(json.dumps(row), file=sys.stderr, flush=True)
