@@ -8,8 +8,9 @@
  * The nested call never bounces again (cache.reflections < 1), and no set snail_instances_materials_create accepts can select a transparent
  * lane, so it takes neither continuation; a set of snail_instances_materials_create_transparent that can is refused by every function here.
  *
- * NOT here: tile lists, 4x antialiasing and the tint with the bounce; the transparency continuation (snail_instances_materials_transparency.h:
- * without the bounce) and the heat-map (gVals[5]) under full shading of instanced scenes; multi-device frames; routing in snail_adapter.hpp (no reference host can reach this branch through HipDBVH);
+ * NOT here: tile lists, 4x antialiasing and the tint with the bounce, and the transparency continuation together with it
+ * (snail_instances_materials_tree.h has them; snail_instances_materials_transparency.h: the continuation without the bounce); the heat-map
+ * (gVals[5]) under full shading of instanced scenes (not on the device); multi-device frames; routing in snail_adapter.hpp (no reference host can reach this branch through HipDBVH);
  * sets for BLASes whose tree is rebuilt on the device (snail_instances_materials.h).
  */
 #ifndef SNAIL_INSTANCES_MATERIALS_BOUNCE_H

@@ -11,7 +11,8 @@
  * as they are.  Plain C.
  *
  * NOT here: the continuation together with the bounce on instanced scenes (with gVals[7] the reference nests a bounce inside every continuation and
- * continuations inside the bounce, a tree of calls); tile lists, 4x antialiasing, the tint and the heat-map (gVals[5]) for instanced full shading;
+ * continuations inside the bounce, a tree of calls), tile lists, 4x antialiasing and the tint: snail_instances_materials_tree.h has them, for any
+ * set, and the frames here keep refusing every nonzero flag; the heat-map (gVals[5]) for instanced full shading (not on the device);
  * multi-device frames; routing in snail_adapter.hpp (no reference host can reach this branch through HipDBVH); device-packed records for BLASes
  * whose tree is rebuilt on the device (snail_instances_materials.h).
  */

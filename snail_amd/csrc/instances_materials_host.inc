@@ -49,6 +49,8 @@ struct SnailInstancesMaterials {
 		int bounceLights = 0;
 		char *transp = nullptr;   // the levels of the transparency continuation (instances_materials_transparency_host.inc): only once asked for, sized by the depth
 		size_t transpBytes = 0;
+		char *tiles = nullptr;    // the tile renderer's part (instances_materials_tree_host.inc): the float colours of a whole packet list and, under 4x
+		size_t tilesPackets = 0;  // antialiasing, its sub-packet list; only once asked for, grown under the same rule
 		hipEvent_t done = nullptr;
 		bool used = false;
 	};
@@ -57,6 +59,13 @@ struct SnailInstancesMaterials {
 	unsigned setCount = 0;
 	struct FrameList { int pw, ph; int32_t *d; };
 	std::vector<FrameList> frameLists;   // a whole frame's packet list, cached by packet-grid size
+	// snail_instances_materials_tree_render_tiles: ONE cached tile job per set (the structure of instances_tiles_host.inc); its calls take turns under
+	// renderMu, which is taken before the instances handle's mu
+	std::mutex renderMu;
+	InstTileJob *tileJob = nullptr;
+	// snail_instances_materials_set_level_budget (instances_materials_tree_host.inc): the bytes the levels of one group of intermediates may take;
+	// 0 = SNAIL_MAT_LEVEL_BUDGET
+	uint64_t levelBudget = 0;
 };
 
 namespace {
@@ -192,7 +201,7 @@ int imatNextSet(SnailInstancesMaterials *m, int np, int nLights, bool refl, hipS
 int imatSetDone(SnailInstancesMaterials::Set &W, const char *fn, int rc, hipStream_t st) {
 	if(hipEventRecord(W.done, st) == hipSuccess) W.used = true;
 	else {
-		W.packets = 0; W.bouncePackets = 0; W.used = false;   // its next user synchronises the device
+		W.packets = 0; W.bouncePackets = 0; W.tilesPackets = 0; W.used = false;   // its next user synchronises the device
 		if(!rc) { snail_set_error("%s: hipEventRecord failed", fn); return 1; }
 	}
 	return rc;
@@ -299,8 +308,10 @@ void snail_instances_materials_destroy(SnailInstancesMaterials *m) {
 		if(W.base) (void)hipFree(W.base);
 		if(W.bounce) (void)hipFree(W.bounce);
 		if(W.transp) (void)hipFree(W.transp);
+		if(W.tiles) (void)hipFree(W.tiles);
 		if(W.done) (void)hipEventDestroy(W.done);
 	}
+	freeInstTileJob(m->tileJob);
 	for(auto &f : m->frameLists) (void)hipFree(f.d);
 	if(m->dBase) (void)hipFree(m->dBase);
 	delete m;

@@ -84,6 +84,7 @@ void snail_set_error(const char *fmt, ...) {
 #include "materials_transparency.inc"
 #include "instances_materials_transparency.inc"
 #include "materials_tree.inc"
+#include "instances_materials_tree.inc"
 #undef SNAIL_DEV_NS
 #undef SNAIL_ARITH_SSE
 #define SNAIL_DEV_NS dev_sse
@@ -97,6 +98,7 @@ void snail_set_error(const char *fmt, ...) {
 #include "materials_transparency.inc"
 #include "instances_materials_transparency.inc"
 #include "materials_tree.inc"
+#include "instances_materials_tree.inc"
 #undef SNAIL_DEV_NS
 #undef SNAIL_ARITH_SSE
 #include "heatmap.inc"           // the heat-map store stage: plain fp32, once for both arithmetics (its C-ABI: heatmap_host.inc)
@@ -1825,3 +1827,4 @@ int snail_account_primary(SnailScene *s, const float cam[13], int resx, int resy
 #include "instances_materials_host.inc"
 #include "instances_materials_bounce_host.inc"
 #include "instances_materials_transparency_host.inc"
+#include "instances_materials_tree_host.inc"

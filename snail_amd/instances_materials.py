@@ -11,6 +11,9 @@ of include/snail_instances_materials.h.
   .render_transparent / .render_transparent_packets / .render_transparent_image_host
                                                             <-> the transparency continuation (Scene::TraceTransparency and its nested
                                                                  RayTrace<0, hasMask>, level by level), include/snail_instances_materials_transparency.h
+  .mirror_rays / .tree_frame_packets / .render_tree_tiles_host / .render_tree_frame_host / .set_level_budget / .level_bytes
+                                                            <-> the continuation TOGETHER with the bounce, tile lists, 4x AA, depth shading and
+                                                                 the tint (RenderTask::Work), include/snail_instances_materials_tree.h
 
 Materials, textures and pack_shtris are snail_amd.materials'."""
 from __future__ import annotations
@@ -312,6 +315,98 @@ class InstancedMaterialSet:
                                                                     _lib.ptr(amb), int(flags), _lib.ptr(img), pitch, int(max_depth), _lib.ptr(truncated), _lib.ptr(stats))
         _lib.check(rc, "snail_instances_materials_transparent_image")
         return img, stats, truncated
+
+    # ---- include/snail_instances_materials_tree.h: the continuation together with the bounce, tile lists, 4x AA, depth shading and the tint; any set ----
+    def _tile_args(self, cam, lights7, ambient, tint):
+        lights, cam13, amb = self._frame_args(cam, lights7, ambient)
+        tnt = None if tint is None else np.ascontiguousarray(tint, dtype=np.float32).reshape(3)
+        return lights, (_lib.ptr(lights) if len(lights) else None), cam13, amb, tnt
+
+    def mirror_rays(self, origin, dirs, mask, t, samples, order_in=None, out=None, stats=None, stream=None):
+        """Scene::TraceReflection from a level's generic packets: origin / dirs [n, 64, 3, 4], mask [n, 64] uint8 or None (every lane selected),
+        t [n, 256], the level's samples [n, 9, 64, 4] (device tensors); order_in [n] int32 or None: the level's own order list ->
+        (origin, dir, idir [n, 64, 3, 4] float32, mask [n, 64] uint8, distance [n, 256] float32, object, element [n, 256] int32 (zeros), bary
+        [n, 64, 2, 4] float32 (zeros), order [n] int32): the mirrored packets as InstancedScene.traverse_primary takes them in and out, or the
+        nine tensors of `out` written in place: a packet whose order_in word is negative gets order -1 and nothing else.
+        snail_instances_materials_mirror_rays_dev."""
+        torch = _torch()
+        n = int(dirs.shape[0])
+        dev = self.isc._dev()
+        if out is None:
+            out = tuple(torch.empty((n, 64, 3, 4), dtype=torch.float32, device=dev) for _ in range(3)) + (
+                torch.empty((n, 64), dtype=torch.uint8, device=dev), torch.empty((n, 256), dtype=torch.float32, device=dev),
+                torch.empty((n, 256), dtype=torch.int32, device=dev), torch.empty((n, 256), dtype=torch.int32, device=dev),
+                torch.empty((n, 64, 2, 4), dtype=torch.float32, device=dev), torch.empty((n,), dtype=torch.int32, device=dev))
+        org, d, idir, msk, dist, obj, elem, bary, order = out
+        rc = _lib.lib().snail_instances_materials_mirror_rays_dev(self._h, n, _lib.ptr(origin), _lib.ptr(dirs), _lib.ptr(mask), _lib.ptr(t), _lib.ptr(samples),
+                                                                  _lib.ptr(order_in), _lib.ptr(org), _lib.ptr(d), _lib.ptr(idir), _lib.ptr(msk), _lib.ptr(dist), _lib.ptr(obj),
+                                                                  _lib.ptr(elem), _lib.ptr(bary), _lib.ptr(order), _lib.ptr(stats), _stream_ptr(stream))
+        _lib.check(rc, "snail_instances_materials_mirror_rays_dev")
+        return out
+
+    def tree_frame_packets(self, cam, resx: int, resy: int, packet_xy, lights7=None, flags: int = 0, tint=None, ambient=(0.1, 0.1, 0.1), out=None, stats=None,
+                           stream=None, max_depth: int = 8, truncated=None):
+        """The lit packets of an explicit packet list for any set, with the transparency continuation at most max_depth levels deep under any
+        of RENDER_REFLECTIONS / RENDER_DEPTH / RENDER_AA4 and the tint -> (packet-major [n, 256, 3] uint8 (B,G,R), truncated: int64 device
+        tensor of one word, +=).  snail_instances_materials_tree_frame_packets_dev."""
+        torch = _torch()
+        n = int(packet_xy.shape[0])
+        if out is None:
+            out = torch.empty((n, 256, 3), dtype=torch.uint8, device=self.isc._dev())
+        truncated = self._truncated(truncated)
+        lights, lp, cam13, amb, tnt = self._tile_args(cam, lights7, ambient, tint)
+        rc = _lib.lib().snail_instances_materials_tree_frame_packets_dev(self._h, _lib.ptr(cam13), resx, resy, _lib.ptr(packet_xy), n, lp, len(lights), _lib.ptr(amb),
+                                                                         int(flags), _lib.ptr(tnt), _lib.ptr(out), int(max_depth), _lib.ptr(truncated), _lib.ptr(stats),
+                                                                         _stream_ptr(stream))
+        _lib.check(rc, "snail_instances_materials_tree_frame_packets_dev")
+        return out, truncated
+
+    def render_tree_tiles_host(self, cam, resx: int, resy: int, tiles, offsets=None, lights7=None, flags: int = 0, tint=None, ambient=(0.1, 0.1, 0.1), data=None,
+                               max_depth: int = 8, truncated=None):
+        """The tile list (tiles: int32 [n, 4] = x, y, w, h; per tile the planes R, G-R, B-R at offsets[k] of data) for any set ->
+        (data, offsets, stats, truncated: uint64 [1], the caller's array (+=) or a new one).  snail_instances_materials_tree_render_tiles."""
+        t = np.ascontiguousarray(tiles, dtype=np.int32).reshape(-1, 4)
+        size = 3 * t[:, 2].astype(np.int64) * t[:, 3]
+        if offsets is None:
+            offsets = np.concatenate([[0], np.cumsum(size)[:-1]]).astype(np.int64)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        if data is None:
+            data = np.zeros(int((offsets + size).max()) if len(t) else 0, dtype=np.uint8)
+        lights, lp, cam13, amb, tnt = self._tile_args(cam, lights7, ambient, tint)
+        stats = np.zeros(4, dtype=np.uint64)
+        truncated = np.zeros(1, dtype=np.uint64) if truncated is None else truncated
+        rc = _lib.lib().snail_instances_materials_tree_render_tiles(self._h, _lib.ptr(cam13), resx, resy, _lib.ptr(t), _lib.ptr(offsets), len(t), lp, len(lights),
+                                                                    _lib.ptr(amb), int(flags), _lib.ptr(tnt), _lib.ptr(data), int(max_depth), _lib.ptr(truncated),
+                                                                    _lib.ptr(stats))
+        _lib.check(rc, "snail_instances_materials_tree_render_tiles")
+        return data, offsets, stats, truncated
+
+    def render_tree_frame_host(self, cam, resx: int, resy: int, lights7=None, flags: int = 0, ambient=(0.1, 0.1, 0.1), pitch: int | None = None, fill: int = 0,
+                               max_depth: int = 8, truncated=None):
+        """The frame in host memory for any set -> (uint8 [resy, pitch], stats, truncated: uint64 [1]).
+        snail_instances_materials_tree_render_frame."""
+        pitch = resx * 3 if pitch is None else int(pitch)
+        img = np.full((resy, pitch), fill, dtype=np.uint8)
+        stats = np.zeros(4, dtype=np.uint64)
+        truncated = np.zeros(1, dtype=np.uint64) if truncated is None else truncated
+        lights, lp, cam13, amb, _ = self._tile_args(cam, lights7, ambient, None)
+        rc = _lib.lib().snail_instances_materials_tree_render_frame(self._h, _lib.ptr(cam13), resx, resy, lp, len(lights), _lib.ptr(amb), int(flags), _lib.ptr(img), pitch,
+                                                                    int(max_depth), _lib.ptr(truncated), _lib.ptr(stats))
+        _lib.check(rc, "snail_instances_materials_tree_render_frame")
+        return img, stats, truncated
+
+    def set_level_budget(self, nbytes: int):
+        """snail_instances_materials_set_level_budget: the bytes the levels of one group of intermediates may take; a call clamps it up to one
+        output packet's worth and runs its packet list in slices that stay within it"""
+        _lib.check(_lib.lib().snail_instances_materials_set_level_budget(self._h, int(nbytes)), "snail_instances_materials_set_level_budget")
+
+    @staticmethod
+    def level_bytes(n_lights: int, flags: int = 0, max_depth: int = 8) -> int:
+        """snail_instances_materials_level_bytes: the bytes of the levels of ONE output packet"""
+        b = _lib.lib().snail_instances_materials_level_bytes(int(n_lights), int(flags), int(max_depth))
+        if b < 0:
+            raise _lib.SnailError("snail_instances_materials_level_bytes: %s" % _lib.lib().snail_last_error().decode())
+        return int(b)
 
 
 __all__ = ["InstancedMaterialSet", "create_instanced_set"]

@@ -57,7 +57,23 @@ select a transparent lane (the second TEX material -> TRANSPARENT with the first
   flags0  InstancedMaterialSet.render of the same run: the same scene with the opaque stand-ins the swap replaced
 and the lanes level N would still select (the truncated counter of one frame).  Nobody has measured this before: a record, not a gate.
 
-    python tools/instances_time.py --materials --transparency 4 [--reps 5]"""
+    python tools/instances_time.py --materials --transparency 4 [--reps 5]
+
+--materials --tree [--reflections] [--aa] [--tiles] [--transparency N]: the transparency continuation together with the bounce, 4x antialiasing
+and tile lists on an instanced full-shaded frame (include/snail_instances_materials_tree.h), the scene and the capable set of --transparency;
+host wall ms per frame, synchronised, median / min / max of the runs, the truncated-lane counter and the number of slices the packet list ran
+in, at maxDepth N (default: 1, 4 and 8).  InstancedMaterialSet.tree_frame_packets, or with --tiles .render_tree_tiles_host over the frame cut
+into 64x64 tiles (the device-to-host copy and the host's scatter included).  First measurements, not targets.
+With --baseline-lib PATH (another build of the library, e.g. the parent commit's) the tool instead starts child processes that alternate between
+this build and that one -- this, that, this, that --, each timing the two frames that had a device path before:
+  transp   the capable set at maxDepth N (default 4), flags 0: tree_frame_packets here, render_transparent_packets (snail_instances_materials_
+           transparent_packets_dev) in the other build -- the same kernels in the same order
+  bounce   the opaque set with the one mirrored bounce: tree_frame_packets(RENDER_REFLECTIONS, maxDepth 1) here, render_packets(reflections=True)
+           (snail_instances_materials_bounce_packets_dev) in the other build
+and prints per row both processes' medians of either build, so that the other build's own run-to-run spread stands beside the difference.
+
+    python tools/instances_time.py --materials --tree --reflections [--aa] [--tiles] [--reps 5]
+    python tools/instances_time.py --materials --tree --baseline-lib parent/libsnailhip.so [--transparency 4] [--reps 7]"""
 import argparse
 import json
 import os
@@ -103,11 +119,16 @@ def main():
     ap.add_argument("--plane-normals", action="store_true")
     ap.add_argument("--transparency", type=int, default=0, metavar="N")
     ap.add_argument("--baseline-lib", default=None)
+    ap.add_argument("--tree", action="store_true")
+    ap.add_argument("--aa", action="store_true")
+    ap.add_argument("--tree-child", default=None, choices=["new", "old"], help=argparse.SUPPRESS)
     a = ap.parse_args()
     resx, resy = (int(x) for x in a.res.split("x"))
     if a.rebuild_dev:
         return rebuild_dev(torch, [int(c) for c in (a.rebuild_counts or "1024,10000").split(",")], a.reps)
     a.rebuild_counts = a.rebuild_counts or "10000"
+    if a.materials and a.tree:
+        return materials_tree_compare(a) if a.baseline_lib and not a.tree_child else materials_tree(torch, a, resx, resy)
     if a.lit:
         return lit(torch, a, resx, resy)
     if a.tiles:
@@ -426,6 +447,133 @@ def materials_transparency(torch, a, resx, resy):
             isc.close()
     sc.close()
     print(json.dumps(out))
+
+
+def tree_scene(a):
+    """the scene of --materials --transparency: the atrium BLAS, its procedural shading, the opaque list and the capable one"""
+    from snail_amd import materials as P
+    tv = scenes.atrium()
+    hb = HostBVH.build(tv)
+    sc = Scene(hb, 0)
+    uv, nrm, mi, flat, mmap, mats, texs = procedural_shading(hb, tv)
+    capable = list(mats)
+    capable[2] = P.Material.transparent(1, 0, False)                    # TEX over texture 1 -> TRANSPARENT, texture 0's first channel as opacity
+    capable[3] = P.Material.uber((0.9, 0.4, 0.1), (0.2, 0.6, 1.0), 0.5)   # UBER dissolve 0 -> 0.5
+    return tv, sc, (uv, nrm, mi, flat, mmap), mats, capable, texs
+
+
+def tree_view(tv, isc, n):
+    nd = isc.nodes()[0]
+    cam = survey_camera(tv) if n == 1 else survey_camera(np.concatenate([nd["bmin"], nd["bmax"], nd["bmin"]]).reshape(1, 9))
+    c, ext = (nd["bmin"] + nd["bmax"]) * 0.5, nd["bmax"] - nd["bmin"]
+    return cam, np.array([[c[0], c[1] + 0.3 * ext[1], c[2], 1.0, 1.0, 1.0, float(np.linalg.norm(ext))]], dtype=np.float32)
+
+
+def tree_times(torch, fn, reps):
+    import statistics
+    import time
+    for _ in range(9):      # warm-up: every one of the set's 8 groups of intermediates has been allocated, the cached lists, first launches
+        fn()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(reps):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter(); fn(); torch.cuda.synchronize()
+        ms.append((time.perf_counter() - t0) * 1e3)
+    return {"ms": round(statistics.median(ms), 3), "min_ms": round(min(ms), 3), "max_ms": round(max(ms), 3)}
+
+
+def materials_tree(torch, a, resx, resy):
+    from snail_amd import _lib
+    from snail_amd import materials as P
+    old = a.tree_child == "old"
+    if old:      # the other build has none of the tree's symbols: bind none (the child calls the older entry points alone)
+        _lib.INSTANCES_MATERIALS_TREE_SIGNATURES.clear()
+    from snail_amd.instances_materials import InstancedMaterialSet
+    tv, sc, per_blas, mats, capable, texs = tree_scene(a)
+    lo, hi = sc.get_bbox()
+    pw, ph = (resx + 15) // 16, (resy + 15) // 16
+    xy = torch.from_numpy(np.array([(x * 16, y * 16) for y in range(ph) for x in range(pw)], dtype=np.int32)).cuda()
+    flags = (P.RENDER_REFLECTIONS if a.reflections else 0) | (P.RENDER_AA4 if a.aa else 0)
+    depths = [int(a.transparency)] if a.transparency else ([4] if a.tree_child else [1, 4, 8])
+    out = {"res": a.res, "lights": 1, "flags": flags, "tiles": bool(a.tiles), "library": a.tree_child or "this build",
+           "unit": "host wall ms per frame, synchronised, median / min / max of %d runs" % a.reps, "rows": []}
+    tiles = np.array([(x, y, 64, 64) for y in range(0, resy, 64) for x in range(0, resx, 64)], dtype=np.int32)
+    for arith in ("ieee", "host_sse"):
+        sc.set_arith(arith)
+        for n in (int(c) for c in a.counts.split(",")):
+            rot, tr, bi = scenes.instance_field(lo, hi, n, seed=1)
+            isc = InstancedScene([sc], rot, tr, bi)
+            cam, light = tree_view(tv, isc, n)
+            bgr = torch.zeros((pw * ph, 256, 3), dtype=torch.uint8, device="cuda")
+            trunc = torch.zeros(1, dtype=torch.int64, device="cuda")
+            transp_set = InstancedMaterialSet(isc, [per_blas], capable, texs, transparent=True)
+            if a.tree_child:      # the two frames that had a device path before, by this build's new entry point or the other build's old one
+                opaque_set = InstancedMaterialSet(isc, [per_blas], mats, texs)
+                d = depths[0]
+                if old:
+                    runs = {"transp": lambda: transp_set.render_transparent_packets(cam, resx, resy, xy, light, out=bgr, max_depth=d, truncated=trunc),
+                            "bounce": lambda: opaque_set.render_packets(cam, resx, resy, xy, light, out=bgr, reflections=True)}
+                else:
+                    runs = {"transp": lambda: transp_set.tree_frame_packets(cam, resx, resy, xy, light, 0, out=bgr, max_depth=d, truncated=trunc),
+                            "bounce": lambda: opaque_set.tree_frame_packets(cam, resx, resy, xy, light, P.RENDER_REFLECTIONS, out=bgr, max_depth=1, truncated=trunc)}
+                row = {"arith": arith, "instances": n, "max_depth": d}
+                for k, fn in runs.items():
+                    row[k] = tree_times(torch, fn, a.reps)
+                    row[k]["checksum"] = int(bgr.sum().item())
+                out["rows"].append(row)
+                print(json.dumps(row), file=sys.stderr, flush=True)
+                opaque_set.close()
+            else:
+                for d in depths:
+                    one = transp_set.level_bytes(1, flags, d)
+                    row = {"arith": arith, "instances": n, "max_depth": d, "slices": -(-(pw * ph) // max(1, min(pw * ph, (1 << 30) // one)))}
+                    if a.tiles:
+                        ht = np.zeros(1, dtype=np.uint64)
+                        fn = lambda: transp_set.render_tree_tiles_host(cam, resx, resy, tiles, None, light, flags, max_depth=d, truncated=ht)      # noqa: E731
+                    else:
+                        fn = lambda: transp_set.tree_frame_packets(cam, resx, resy, xy, light, flags, out=bgr, max_depth=d, truncated=trunc)      # noqa: E731
+                    row.update(tree_times(torch, fn, a.reps))
+                    trunc.zero_()
+                    st = isc.new_stats()
+                    transp_set.tree_frame_packets(cam, resx, resy, xy, light, flags, out=bgr, max_depth=d, truncated=trunc, stats=st)
+                    row["truncated_lanes"] = int(trunc.cpu().numpy()[0]); row["traced_rays"] = int(st.cpu().numpy()[2])
+                    out["rows"].append(row)
+                    print(json.dumps(row), file=sys.stderr, flush=True)
+            transp_set.close()
+            isc.close()
+    sc.close()
+    print(json.dumps(out))
+
+
+def materials_tree_compare(a):
+    """children alternating between this build and --baseline-lib: this, that, this, that; one JSON line with both processes' figures per row"""
+    import subprocess
+    base = [sys.executable, os.path.abspath(__file__), "--materials", "--tree", "--res", a.res, "--reps", str(a.reps), "--counts", a.counts,
+            "--transparency", str(a.transparency or 4), "--baseline-lib", a.baseline_lib]
+    res = {"new": [], "old": []}
+    for which in ("new", "old", "new", "old"):
+        env = dict(os.environ)
+        if which == "old":
+            env["SNAIL_LIB_PATH"] = os.path.abspath(a.baseline_lib)
+        r = subprocess.run(base + ["--tree-child", which], env=env, capture_output=True, text=True, timeout=900)
+        if r.returncode != 0:
+            sys.stderr.write(r.stderr)
+            raise SystemExit("child %s failed with status %d" % (which, r.returncode))
+        res[which].append(json.loads(r.stdout.strip().splitlines()[-1]))
+    rows = []
+    for i, r0 in enumerate(res["new"][0]["rows"]):
+        for k in ("transp", "bounce"):
+            new = [p["rows"][i][k] for p in res["new"]]
+            old = [p["rows"][i][k] for p in res["old"]]
+            row = {"arith": r0["arith"], "instances": r0["instances"], "frame": k, "max_depth": r0["max_depth"] if k == "transp" else 1,
+                   "this_ms": [x["ms"] for x in new], "this_max_ms": [x["max_ms"] for x in new], "other_ms": [x["ms"] for x in old], "other_max_ms": [x["max_ms"] for x in old],
+                   "frames_equal": len({x["checksum"] for x in new + old}) == 1}
+            row["other_spread"] = round(max(row["other_ms"]) / min(row["other_ms"]), 4)
+            row["this_over_other"] = round((sum(row["this_ms"]) / len(new)) / (sum(row["other_ms"]) / len(old)), 4)
+            rows.append(row)
+            print(json.dumps(row), file=sys.stderr, flush=True)
+    print(json.dumps({"res": a.res, "lights": 1, "other": a.baseline_lib, "unit": res["new"][0]["unit"] + "; per build the medians of its two processes", "rows": rows}))
 
 
 def rebuild(torch, sc, counts, reps):
