@@ -249,6 +249,15 @@ INSTANCES_MATERIALS_TREE_SIGNATURES = {
     "snail_instances_materials_level_bytes": (C.c_int64, [_I, _I, _I]),
 }
 
+# include/snail_instances_materials_heatmap.h: per-packet TreeStats and the gVals[5] heat-map under full shading of instanced scenes
+# (tests/c/instances_materials_heat_c.c enumerates this table)
+INSTANCES_MATERIALS_HEAT_SIGNATURES = {
+    "snail_instances_materials_packet_stats_dev": (_I, [_VP, _F13, _I, _I, _VP, _I, _VP, _I, _I, _I, _VP, _VP, _VP, _VP]),
+    "snail_instances_materials_heat_packets_dev": (_I, [_VP, _F13, _I, _I, _VP, _I, _VP, _I, _I, _VP, _VP, _VP, _I, _VP, _VP, _VP]),
+    "snail_instances_materials_render_heat_tiles": (_I, [_VP, _F13, _I, _I, _VP, _VP, _I, _VP, _I, _I, _VP, _VP, _I, _VP, _VP]),
+    "snail_instances_materials_render_heat_frame": (_I, [_VP, _F13, _I, _I, _VP, _I, _I, _VP, _I, _I, _VP, _VP]),
+}
+
 # include/snail_hip_debug.h: the workbench build only (libsnailhip_debug.so, -DSNAIL_DEBUG_API)
 DEBUG_SIGNATURES = {
     "snail_debug_delay_dev": (_I, [C.c_float, _VP]),
@@ -273,7 +282,7 @@ def debug_lib():
         if not os.path.exists(DEBUG_LIB_PATH):
             raise SnailError("workbench library %s is missing: `make -C snail_amd/csrc debug`" % DEBUG_LIB_PATH)
         L = C.CDLL(DEBUG_LIB_PATH)
-        for table in (SIGNATURES, INSTANCES_SIGNATURES, INSTANCES_SHADE_SIGNATURES, INSTANCES_TILES_SIGNATURES, INSTANCES_BUILD_SIGNATURES, BVH_FAST_SIGNATURES, HEATMAP_SIGNATURES, MATERIALS_SIGNATURES, MATERIALS_BOUNCE_SIGNATURES, MATERIALS_TILES_SIGNATURES, MATERIALS_TRANSPARENCY_SIGNATURES, MATERIALS_TREE_SIGNATURES, MATERIALS_HEAT_SIGNATURES, MATERIALS_DYNAMIC_SIGNATURES, INSTANCES_MATERIALS_SIGNATURES, INSTANCES_MATERIALS_BOUNCE_SIGNATURES, INSTANCES_MATERIALS_TRANSPARENCY_SIGNATURES, INSTANCES_MATERIALS_TREE_SIGNATURES, DEBUG_SIGNATURES):
+        for table in (SIGNATURES, INSTANCES_SIGNATURES, INSTANCES_SHADE_SIGNATURES, INSTANCES_TILES_SIGNATURES, INSTANCES_BUILD_SIGNATURES, BVH_FAST_SIGNATURES, HEATMAP_SIGNATURES, MATERIALS_SIGNATURES, MATERIALS_BOUNCE_SIGNATURES, MATERIALS_TILES_SIGNATURES, MATERIALS_TRANSPARENCY_SIGNATURES, MATERIALS_TREE_SIGNATURES, MATERIALS_HEAT_SIGNATURES, MATERIALS_DYNAMIC_SIGNATURES, INSTANCES_MATERIALS_SIGNATURES, INSTANCES_MATERIALS_BOUNCE_SIGNATURES, INSTANCES_MATERIALS_TRANSPARENCY_SIGNATURES, INSTANCES_MATERIALS_TREE_SIGNATURES, INSTANCES_MATERIALS_HEAT_SIGNATURES, DEBUG_SIGNATURES):
             for name, (res, args) in table.items():
                 fn = getattr(L, name)
                 fn.restype = res
@@ -294,7 +303,7 @@ def lib():
             L = C.CDLL(LIB_PATH)
         except OSError as e:  # pragma: no cover - depends on the box
             raise SnailError("cannot load %s: %s" % (LIB_PATH, e)) from e
-        for table in (SIGNATURES, INSTANCES_SIGNATURES, INSTANCES_SHADE_SIGNATURES, INSTANCES_TILES_SIGNATURES, INSTANCES_BUILD_SIGNATURES, BVH_FAST_SIGNATURES, HEATMAP_SIGNATURES, MATERIALS_SIGNATURES, MATERIALS_BOUNCE_SIGNATURES, MATERIALS_TILES_SIGNATURES, MATERIALS_TRANSPARENCY_SIGNATURES, MATERIALS_TREE_SIGNATURES, MATERIALS_HEAT_SIGNATURES, MATERIALS_DYNAMIC_SIGNATURES, INSTANCES_MATERIALS_SIGNATURES, INSTANCES_MATERIALS_BOUNCE_SIGNATURES, INSTANCES_MATERIALS_TRANSPARENCY_SIGNATURES, INSTANCES_MATERIALS_TREE_SIGNATURES):
+        for table in (SIGNATURES, INSTANCES_SIGNATURES, INSTANCES_SHADE_SIGNATURES, INSTANCES_TILES_SIGNATURES, INSTANCES_BUILD_SIGNATURES, BVH_FAST_SIGNATURES, HEATMAP_SIGNATURES, MATERIALS_SIGNATURES, MATERIALS_BOUNCE_SIGNATURES, MATERIALS_TILES_SIGNATURES, MATERIALS_TRANSPARENCY_SIGNATURES, MATERIALS_TREE_SIGNATURES, MATERIALS_HEAT_SIGNATURES, MATERIALS_DYNAMIC_SIGNATURES, INSTANCES_MATERIALS_SIGNATURES, INSTANCES_MATERIALS_BOUNCE_SIGNATURES, INSTANCES_MATERIALS_TRANSPARENCY_SIGNATURES, INSTANCES_MATERIALS_TREE_SIGNATURES, INSTANCES_MATERIALS_HEAT_SIGNATURES):
             for name, (res, args) in table.items():
                 fn = getattr(L, name)
                 fn.restype = res

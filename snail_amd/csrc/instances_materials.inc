@@ -7,6 +7,7 @@
 //                          rotations + ONE scene-wide material and texture list -> 9 floats per ray, the sample buffer of k_mat_sample
 //   k_imat_light<DEEP>     one wave per (packet, light): position + the sample's (interpolated, rotated) normal -> light cull -> shadow packet ->
 //                          DBVH::TraverseShadow -> the surviving distances [light][packet][256]      Scene::TraceLight, src/scene_trace.cpp:523-566
+//   k_imat_light_heat<DEEP>   the same, booking its counters per packet as well (the heat-map launches, include/snail_instances_materials_heatmap.h)
 //   k_mat_final            (materials.inc, unchanged: it reads samples, hits and the surviving distances alone)
 // DBVH::GetSElement(slot, triId) (src/dbvh/tree.h:211-215) = the BLAS's record through ShTriangle::Transform (src/triangle.h:206-219);
 // DBVH::GetMaterialId(idx, slot) (:246-248) = the BLAS's own map entry, an index into the ONE scene-wide list.  Every equality of :171-356 is on
@@ -94,7 +95,13 @@ __global__ __launch_bounds__(64) void k_imat_sample(IMatArgs A) { matSample<SRC_
 // (instances_materials_transparency.inc; SRC_MIRROR behind a level's order list; `order` null: every packet).
 // TWINS: the sample load and the shadow-packet set-up are matLight<DEEP, SRC>'s (materials.inc), the walk and the stats flush are
 // k_inst_light<DEEP, SRC>'s (instances_shade.inc); a change to either belongs here too.
-template <bool DEEP, int SRC>
+// PSTATS: the heat-map launches' instantiation (include/snail_instances_materials_heatmap.h), which also books the (packet, light)'s counters per
+// packet at P.pidx -- a template argument as in matLight and k_inst_light, so that the other launches' kernels stay the code they were.  The array's
+// address is read late, from the kernel-argument segment (bookPacketLate): ShadeArgs opens MatArgs, which opens IMatArgs, which opens ITranspArgs,
+// so ShadeArgs::pstats is at the same offset of the segment in k_imat_light_heat and in k_imat_light_transp_heat.  A culled pair has returned
+// before the booking: it books nothing.
+static_assert(offsetof(IMatArgs, m) == 0 && offsetof(MatArgs, s) == 0, "bookPacketLate<ShadeArgs> reads pstats at the record's offset in the kernel-argument segment");
+template <bool DEEP, int SRC, bool PSTATS = false>
 __device__ __forceinline__ void imatLight(const IMatArgs &A, const int *order, float *lds) {
 	const int lane = threadIdx.x & 63;
 	const int li = (int)blockIdx.x, n = (int)blockIdx.y;
@@ -130,12 +137,18 @@ __device__ __forceinline__ void imatLight(const IMatArgs &A, const int *order, f
 	Counters st = {0, 0, 0, 0, 0};
 	instWalk<true, false, true, false, DEEP>(A.i, 64, lane, lorg, Q.d, Q.id, 15u, Q.dist, obj, elem, bu, bv, lds, st);
 	flushStats(A.m.s.stats, st, rays, lane);
+	if(PSTATS) bookPacketLate<ShadeArgs>(P.pidx, st, rays, lane);
 	*(float4 *)((SRC == SRC_MIRROR ? A.m.nSDist : A.m.s.sDist) + ((size_t)n * (size_t)A.m.s.nPackets + P.pidx) * 256 + (size_t)lane * 4) = make_float4(Q.dist[0], Q.dist[1], Q.dist[2], Q.dist[3]);
 }
 template <bool DEEP>
 __global__ __launch_bounds__(64) void k_imat_light(IMatArgs A) {
 	__shared__ float lds[LDS_FLOATS_PER_WAVE];
 	imatLight<DEEP, SRC_PRIMARY>(A, nullptr, lds);
+}
+template <bool DEEP>
+__global__ __launch_bounds__(64) void k_imat_light_heat(IMatArgs A) {
+	__shared__ float lds[LDS_FLOATS_PER_WAVE];
+	imatLight<DEEP, SRC_PRIMARY, true>(A, nullptr, lds);
 }
 
 } // namespace SNAIL_DEV_NS

@@ -51,6 +51,8 @@ struct SnailInstancesMaterials {
 		size_t transpBytes = 0;
 		char *tiles = nullptr;    // the tile renderer's part (instances_materials_tree_host.inc): the float colours of a whole packet list and, under 4x
 		size_t tilesPackets = 0;  // antialiasing, its sub-packet list; only once asked for, grown under the same rule
+		uint32_t *pstats = nullptr;   // snail_instances_materials_heatmap.h: the launch's per-packet TreeStats [packets][4] when the caller keeps none of its
+		size_t pstatsPackets = 0;     // own; only once asked for, grown under the same rule
 		hipEvent_t done = nullptr;
 		bool used = false;
 	};
@@ -201,7 +203,7 @@ int imatNextSet(SnailInstancesMaterials *m, int np, int nLights, bool refl, hipS
 int imatSetDone(SnailInstancesMaterials::Set &W, const char *fn, int rc, hipStream_t st) {
 	if(hipEventRecord(W.done, st) == hipSuccess) W.used = true;
 	else {
-		W.packets = 0; W.bouncePackets = 0; W.tilesPackets = 0; W.used = false;   // its next user synchronises the device
+		W.packets = 0; W.bouncePackets = 0; W.tilesPackets = 0; W.pstatsPackets = 0; W.used = false;   // its next user synchronises the device
 		if(!rc) { snail_set_error("%s: hipEventRecord failed", fn); return 1; }
 	}
 	return rc;
@@ -309,6 +311,7 @@ void snail_instances_materials_destroy(SnailInstancesMaterials *m) {
 		if(W.bounce) (void)hipFree(W.bounce);
 		if(W.transp) (void)hipFree(W.transp);
 		if(W.tiles) (void)hipFree(W.tiles);
+		if(W.pstats) (void)hipFree(W.pstats);
 		if(W.done) (void)hipEventDestroy(W.done);
 	}
 	freeInstTileJob(m->tileJob);

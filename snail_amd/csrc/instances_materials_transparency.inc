@@ -7,6 +7,7 @@
 //                          can select a transparent lane, Sample::opacity per ray and the transSel selector after the opacity < 1 filter
 //   k_imat_trace_level<DEEP>   DBVH::TraversePrimary<0, 1> of a level's generated packets, with barycentrics, under the generator's order list
 //   k_imat_light_transp<DEEP>  a level's lights: one wave per (packet, light), DBVH::TraverseShadow, under the level's order list
+//   k_imat_trace_level_heat<DEEP> / k_imat_light_transp_heat<DEEP>   the same two, booking their counters per packet as well (the heat-map launches)
 // Unchanged, because they read nothing of the scene: k_mat_continue / k_mat_continue_rays, k_mat_blend_transp, k_mat_colour_transp,
 // k_mat_truncated (materials_transparency.inc); for the primary level k_inst_frame, k_imat_light and k_mat_final.
 // Kernels of their own: the existing sample, walk and light kernels stay the code they are, and a set they can be given never holds these kinds
@@ -35,41 +36,20 @@ __global__ __launch_bounds__(64) void k_imat_sample_transp_rays(ITranspArgs B) {
 // TWINS: the body is k_inst_trace<false, true, DEEP, true>'s (instances.inc: instWalk<false, true, false, true, DEEP>), behind the order word; a
 // change there belongs here too.  A kernel of its own: k_inst_trace itself must not gain a pointer test -- its comment records that one cost the
 // other launches' kernel scalar spills and, in one instantiation, a wave.  A packet that is not walked books no TreeStats and keeps its buffers.
+// PSTATS (k_imat_trace_level_heat, the heat-map launches of include/snail_instances_materials_heatmap.h): the walk's counters per packet as well, at
+// the packet's list position in InstArgs::pstats, as k_inst_trace<.., PSTATS> books them -- decided at compile time, for the reason above.  The body
+// is instances_materials_trace_level_body.inc, included once per kernel.
 template <bool DEEP>
 __global__ __launch_bounds__(64) void k_imat_trace_level(ILevelArgs L) {
-	__shared__ float lds[LDS_FLOATS_PER_WAVE];
-	const InstArgs &A = L.i;
-	const int lane = threadIdx.x & 63;
-	const int p = (int)blockIdx.x;
-	if(p >= A.nPackets || orderSkipped(L.order, p)) return;
-	const int size = A.size;
-	const bool live = lane < size;
-	const size_t q = (size_t)p * size + (live ? lane : 0);
-	float d[3][4], id[3][4], org[3][4];
-	loadQuad3(A.dir, q, d);
-	loadQuad3(A.idir, q, id);
-	loadQuad3(A.origin, q, org);
-	const unsigned mask4 = A.mask[q] & 15u;
-	const float4 dv = *(const float4 *)(A.distance + q * 4);
-	const int4 ov = *(const int4 *)(A.object + q * 4), ev = *(const int4 *)(A.element + q * 4);
-	float dist[4] = {dv.x, dv.y, dv.z, dv.w};
-	int obj[4] = {ov.x, ov.y, ov.z, ov.w}, elem[4] = {ev.x, ev.y, ev.z, ev.w};
-	float bu[4], bv[4];
-	{
-		const float4 b0 = *(const float4 *)(A.bary + q * 8), b1 = *(const float4 *)(A.bary + q * 8 + 4);
-		bu[0] = b0.x; bu[1] = b0.y; bu[2] = b0.z; bu[3] = b0.w;
-		bv[0] = b1.x; bv[1] = b1.y; bv[2] = b1.z; bv[3] = b1.w;
-	}
-	Counters st = {0, 0, 0, 0, 0};
-	instWalk<false, true, false, true, DEEP>(A, size, lane, org, d, id, mask4, dist, obj, elem, bu, bv, lds, st);
-	flushStats(A.stats, st, 0u, lane);
-	if(live) {
-		*(float4 *)(A.distance + q * 4) = make_float4(dist[0], dist[1], dist[2], dist[3]);
-		*(int4 *)(A.object + q * 4) = make_int4(obj[0], obj[1], obj[2], obj[3]);
-		*(int4 *)(A.element + q * 4) = make_int4(elem[0], elem[1], elem[2], elem[3]);
-		*(float4 *)(A.bary + q * 8) = make_float4(bu[0], bu[1], bu[2], bu[3]);
-		*(float4 *)(A.bary + q * 8 + 4) = make_float4(bv[0], bv[1], bv[2], bv[3]);
-	}
+#define SNAIL_TRACE_LEVEL_PSTATS 0
+#include "instances_materials_trace_level_body.inc"
+#undef SNAIL_TRACE_LEVEL_PSTATS
+}
+template <bool DEEP>
+__global__ __launch_bounds__(64) void k_imat_trace_level_heat(ILevelArgs L) {
+#define SNAIL_TRACE_LEVEL_PSTATS 1
+#include "instances_materials_trace_level_body.inc"
+#undef SNAIL_TRACE_LEVEL_PSTATS
 }
 
 // ---- one (level packet, light): the nested call's shadow packet on the level's samples' normals, and DBVH::TraverseShadow: imatLight
@@ -79,6 +59,12 @@ template <bool DEEP>
 __global__ __launch_bounds__(64) void k_imat_light_transp(ITranspArgs B) {
 	__shared__ float lds[LDS_FLOATS_PER_WAVE];
 	imatLight<DEEP, SRC_MIRROR>(B.a, B.inOrder, lds);
+}
+static_assert(offsetof(ITranspArgs, a) == 0, "imatLight's late booking reads ShadeArgs::pstats at offset 0 of this kernel's argument record too");
+template <bool DEEP>
+__global__ __launch_bounds__(64) void k_imat_light_transp_heat(ITranspArgs B) {
+	__shared__ float lds[LDS_FLOATS_PER_WAVE];
+	imatLight<DEEP, SRC_MIRROR, true>(B.a, B.inOrder, lds);
 }
 
 } // namespace SNAIL_DEV_NS

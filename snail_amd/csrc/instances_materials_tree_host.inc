@@ -19,9 +19,27 @@ size_t imatTreeBytes(size_t n, int nLights, int depth, bool refl) {
 // colours for k_inst_store.  W: level 0; the levels are carved at `arena` (imatTreeBytes).  Without refl the sequence is imatShadeTransp's.
 // Every launch is booked through instancesBegin / instancesEnd, so the frame is ordered against snail_instances_update and
 // snail_instances_rebuild_dev as a walk is.
+// pstats (a heat-map launch, include/snail_instances_materials_heatmap.h; cleared by the caller): every stage that books into dStats -- the walks, the
+// lights, the generators and the mirrors -- also books per packet there, through its PSTATS / _heat instantiation (k_inst_frame: through
+// InstArgs::pstats), at the packet's index in dXY; the stages that only make colours (both blends, the colour stages, k_mat_final) are left out, and
+// bgrPackets / colPackets are not written: no selector, normal or position a counter depends on reads a colour.
+#define SNAIL_ITREE_LAUNCH_PSTATS(ARGS_T, GRID, REC, K)                                                                                       \
+	do {                                                                                                                                   \
+		if(pstats) SNAIL_LAUNCH(sse, ARGS_T, GRID, wave, 0, st, REC, K##_heat);                                                            \
+		else SNAIL_LAUNCH(sse, ARGS_T, GRID, wave, 0, st, REC, K);                                                                         \
+	} while(0)
+// (... of a kernel with a <DEEP> argument)
+#define SNAIL_ITREE_LAUNCH_PSTATS_DEEP(ARGS_T, GRID, REC, K)                                                                                  \
+	do {                                                                                                                                   \
+		if(pstats) {                                                                                                                       \
+			if(deep) SNAIL_LAUNCH(sse, ARGS_T, GRID, wave, 0, st, REC, K##_heat<true>);                                                    \
+			else SNAIL_LAUNCH(sse, ARGS_T, GRID, wave, 0, st, REC, K##_heat<false>);                                                       \
+		} else if(deep) SNAIL_LAUNCH(sse, ARGS_T, GRID, wave, 0, st, REC, K<true>);                                                        \
+		else SNAIL_LAUNCH(sse, ARGS_T, GRID, wave, 0, st, REC, K<false>);                                                                  \
+	} while(0)
 int imatShadeTree(SnailInstancesMaterials *m, const char *fn, const float cam[13], int resx, int resy, const int32_t *dXY, int np, const float *lights7, int nLights,
 				  const float ambient[3], uint8_t *bgrPackets, float *colPackets, const SnailInstancesMaterials::Bufs &W, char *arena, int maxDepth, bool refl,
-				  uint64_t *dTrunc, uint64_t *dStats, hipStream_t st) {
+				  uint64_t *dTrunc, uint64_t *dStats, hipStream_t st, uint32_t *pstats = nullptr) {
 	SnailInstances *h = m->inst;
 	dev::InstArgs I;
 	bool sse, deep;
@@ -39,6 +57,7 @@ int imatShadeTree(SnailInstancesMaterials *m, const char *fn, const float cam[13
 	P.packetXY = (const int2 *)dXY; P.nPackets = np;
 	P.t = W.hitT; P.u = W.hitU; P.v = W.hitV; P.instOut = W.hitInst; P.triOut = W.hitTri;
 	P.stats = (dev::u64 *)dStats;
+	P.pstats = pstats;   // (k_inst_frame books per packet whenever it is given the array)
 	if(deep) SNAIL_INST_LAUNCH(sse, grid, st, P, k_inst_frame<true>);
 	else SNAIL_INST_LAUNCH(sse, grid, st, P, k_inst_frame<false>);
 
@@ -53,6 +72,7 @@ int imatShadeTree(SnailInstancesMaterials *m, const char *fn, const float cam[13
 	A.m.samples = W.samples; A.m.s.sDist = W.sDist;
 	A.m.s.bgrPackets = bgrPackets; A.m.s.colPackets = colPackets;
 	A.m.s.stats = (dev::u64 *)dStats;
+	A.m.s.pstats = pstats;   // (T.m and G.t.m are copies of A.m: level() enters it again with everything else)
 	A.m.rUVStride = 8;
 	// the scene-free stages take a TranspArgs (materials_transparency.inc) or a TreeArgs (materials_tree.inc): its MatArgs is the frame's, entered
 	// again whenever a level changes it
@@ -95,9 +115,9 @@ int imatShadeTree(SnailInstancesMaterials *m, const char *fn, const float cam[13
 		V.i.origin = X.R.rOrg; V.i.dir = X.R.rDir; V.i.idir = X.R.rIDir; V.i.mask = X.R.rMask;
 		V.i.distance = X.R.rDist; V.i.object = X.R.rInst; V.i.element = X.R.rTri; V.i.bary = X.R.bary;
 		V.i.stats = (dev::u64 *)dStats;
+		V.i.pstats = pstats;
 		V.order = order;
-		if(deep) SNAIL_LAUNCH(sse, ILevelArgs, grid, wave, 0, st, V, k_imat_trace_level<true>);
-		else SNAIL_LAUNCH(sse, ILevelArgs, grid, wave, 0, st, V, k_imat_trace_level<false>);
+		SNAIL_ITREE_LAUNCH_PSTATS_DEEP(ILevelArgs, grid, V, k_imat_trace_level);
 		level(X, order, false);
 		S.opacity = X.opacity; S.sel = X.sel;
 		SNAIL_ITRANSP_LAUNCH(sse, grid, st, S, k_imat_sample_transp_rays);
@@ -110,7 +130,7 @@ int imatShadeTree(SnailInstancesMaterials *m, const char *fn, const float cam[13
 		T.order = to.order;
 		T.cT = from.R.rDist; T.cSel = from.sel;
 		T.cOrg = from.R.rOrg; T.cDir = from.R.rDir; T.cIDir = from.R.rIDir;
-		SNAIL_LAUNCH(sse, TranspArgs, grid, wave, 0, st, T, k_mat_continue_rays);
+		SNAIL_ITREE_LAUNCH_PSTATS(TranspArgs, grid, T, k_mat_continue_rays);
 	};
 	// the lanes a level D would still select: counted, then treated as not selected
 	auto truncated = [&](const ITranspLevel &X, const int32_t *order) {
@@ -123,15 +143,12 @@ int imatShadeTree(SnailInstancesMaterials *m, const char *fn, const float cam[13
 	auto lightColour = [&](const ITranspLevel &X, const int32_t *order, const ITranspLevel *deeper) {
 		if(me != hipSuccess) return;
 		level(X, order, false);
-		if(deeper) {
+		if(deeper && !pstats) {
 			T.bSamples = X.R.nSamples; T.bOpacity = X.opacity; T.bSel = X.sel; T.bCol = deeper->R.rCol;
 			SNAIL_LAUNCH(sse, TranspArgs, grid, wave, 0, st, T, k_mat_blend_transp);
 		}
-		if(nLights) {
-			if(deep) SNAIL_ITRANSP_LAUNCH(sse, lgrid, st, S, k_imat_light_transp<true>);
-			else SNAIL_ITRANSP_LAUNCH(sse, lgrid, st, S, k_imat_light_transp<false>);
-		}
-		SNAIL_LAUNCH(sse, TranspArgs, grid, wave, 0, st, T, k_mat_colour_transp);
+		if(nLights) SNAIL_ITREE_LAUNCH_PSTATS_DEEP(ITranspArgs, lgrid, S, k_imat_light_transp);
+		if(!pstats) SNAIL_LAUNCH(sse, TranspArgs, grid, wave, 0, st, T, k_mat_colour_transp);
 	};
 
 	// ---- the way down of chain A: sample, then per level generator -> ordered walk -> nested sample ----
@@ -143,7 +160,7 @@ int imatShadeTree(SnailInstancesMaterials *m, const char *fn, const float cam[13
 			T.order = L[1].order;
 			T.cT = W.hitT; T.cSel = L[0].sel;
 			T.cOrg = T.cDir = T.cIDir = nullptr;
-			SNAIL_LAUNCH(sse, TranspArgs, grid, wave, 0, st, T, k_mat_continue);
+			SNAIL_ITREE_LAUNCH_PSTATS(TranspArgs, grid, T, k_mat_continue);
 		} else generate(L[k - 1], L[k - 1].order, L[k]);
 		walkSample(L[k], L[k].order);
 	}
@@ -159,10 +176,10 @@ int imatShadeTree(SnailInstancesMaterials *m, const char *fn, const float cam[13
 				level(L[k], aOrder, false);
 				G.oOrg = M[k].R.rOrg; G.oDir = M[k].R.rDir; G.oIDir = M[k].R.rIDir; G.oDist = M[k].R.rDist; G.oObj = M[k].R.rInst; G.oMask = M[k].R.rMask;
 				G.oOrder = M[k].order;
-				SNAIL_LAUNCH(sse, TreeArgs, grid, wave, 0, st, G, k_mat_mirror_rays);
+				SNAIL_ITREE_LAUNCH_PSTATS(TreeArgs, grid, G, k_mat_mirror_rays);
 			} else {
 				level(M[0], nullptr, true);
-				SNAIL_LAUNCH(sse, MatArgs, grid, wave, 0, st, A.m, k_mat_mirror);
+				SNAIL_ITREE_LAUNCH_PSTATS(MatArgs, grid, A.m, k_mat_mirror);
 			}
 			walkSample(M[k], bOrder);
 			for(int j = k + 1; j <= D; j++) {
@@ -173,15 +190,17 @@ int imatShadeTree(SnailInstancesMaterials *m, const char *fn, const float cam[13
 			for(int j = D; j >= k; j--) lightColour(M[j], j == k ? bOrder : M[j].order, j < D ? &M[j + 1] : nullptr);
 			if(me != hipSuccess) break;
 			// diffuse += (refl - diffuse) * 0.3 on A_k's hit lanes, before its transparency blend
-			if(k) {
-				level(L[k], aOrder, false);
-				T.bSamples = L[k].R.nSamples; T.bCol = M[k].R.rCol;
-				SNAIL_LAUNCH(sse, TranspArgs, grid, wave, 0, st, T, k_mat_blend_refl_rays);
-			} else {
-				T.m = A.m;
-				T.inOrder = nullptr;
-				T.bSamples = W.samples; T.bCol = M[0].R.rCol;
-				SNAIL_LAUNCH(sse, TranspArgs, grid, wave, 0, st, T, k_mat_blend_refl);
+			if(!pstats) {
+				if(k) {
+					level(L[k], aOrder, false);
+					T.bSamples = L[k].R.nSamples; T.bCol = M[k].R.rCol;
+					SNAIL_LAUNCH(sse, TranspArgs, grid, wave, 0, st, T, k_mat_blend_refl_rays);
+				} else {
+					T.m = A.m;
+					T.inOrder = nullptr;
+					T.bSamples = W.samples; T.bCol = M[0].R.rCol;
+					SNAIL_LAUNCH(sse, TranspArgs, grid, wave, 0, st, T, k_mat_blend_refl);
+				}
 			}
 		}
 		if(k) lightColour(L[k], aOrder, k < D ? &L[k + 1] : nullptr);
@@ -189,19 +208,20 @@ int imatShadeTree(SnailInstancesMaterials *m, const char *fn, const float cam[13
 	if(me != hipSuccess) return failed("clearing a level's hit records failed", me);
 	level(L[1], nullptr, false);   // (the primary stages read none of a level's packets; rCol must not be left on a B level's)
 	T.bSamples = W.samples; T.bOpacity = L[0].opacity; T.bSel = L[0].sel; T.bCol = L[1].R.rCol;
-	SNAIL_LAUNCH(sse, TranspArgs, grid, wave, 0, st, T, k_mat_blend_transp);
-	if(nLights) {
-		if(deep) SNAIL_IMAT_LAUNCH(sse, lgrid, st, A, k_imat_light<true>);
-		else SNAIL_IMAT_LAUNCH(sse, lgrid, st, A, k_imat_light<false>);
-	}
+	if(!pstats) SNAIL_LAUNCH(sse, TranspArgs, grid, wave, 0, st, T, k_mat_blend_transp);
+	if(nLights) SNAIL_ITREE_LAUNCH_PSTATS_DEEP(IMatArgs, lgrid, A, k_imat_light);
 	// both blends are in the sample buffer: the colour stage without one of its own, bytes or the floats k_inst_store goes on from
-	if(colPackets) SNAIL_LAUNCH(sse, MatArgs, grid, wave, 0, st, A.m, k_mat_colour);
-	else SNAIL_LAUNCH(sse, MatArgs, grid, wave, 0, st, A.m, k_mat_final);
+	if(!pstats) {   // (a heat launch: the counters alone)
+		if(colPackets) SNAIL_LAUNCH(sse, MatArgs, grid, wave, 0, st, A.m, k_mat_colour);
+		else SNAIL_LAUNCH(sse, MatArgs, grid, wave, 0, st, A.m, k_mat_final);
+	}
 	const hipError_t le = hipGetLastError();
 	const int rc = instancesEnd(h, st);
 	if(le != hipSuccess) { snail_set_error("%s: a stage's launch failed: %s", fn, hipGetErrorString(le)); return 100 + (int)le; }
 	return rc;
 }
+#undef SNAIL_ITREE_LAUNCH_PSTATS
+#undef SNAIL_ITREE_LAUNCH_PSTATS_DEEP
 
 int64_t imatTreeLevelBytes(int nLights, int flags, int maxDepth) {
 	if(flags & SNAIL_RENDER_DEPTH) return 0;
@@ -225,16 +245,20 @@ int imatGrow(SnailInstancesMaterials::Set &W, char *&part, size_t &have, size_t 
 // the handle's mu held.  The packet list runs in slices of whole output packets, back to back on st over the same intermediates, so that the
 // levels stay within the set's budget (rounding makes the levels of n packets at most n times those of one); the float colours of ALL packets
 // and the sub-packet list are kept, and ONE k_inst_store follows the last slice.
+// heat (include/snail_instances_materials_heatmap.h; never with SNAIL_RENDER_DEPTH): the per-packet TreeStats instead of the colours -- cleared on st
+// in dPacketStats or, when the caller keeps none, in the set's own array; every slice books at its packets' offset in the whole list's array; after
+// the last slice the counters' colours: dev_heat::k_heat_store straight into bgrPackets, or with a tint or tile planes dev_heat::k_heat_colours
+// into the set's float colours and the same ONE k_inst_store.  No output at all: the counters alone.
 int imatTreeStore(SnailInstancesMaterials *m, const char *fn, const float cam[13], int resx, int resy, const int32_t *dXY, int np, const float *lights7, int nLights,
 				  const float ambient[3], int flags, const float *tint, uint8_t *bgrPackets, const InstTileJob *J, int maxDepth, uint64_t *dTrunc, uint64_t *dStats,
-				  hipStream_t st) {
+				  hipStream_t st, bool heat = false, uint32_t *dPacketStats = nullptr) {
 	SnailInstances *h = m->inst;
 	if(flags & SNAIL_RENDER_DEPTH) {   // gVals[1] returns before the full-shading branch: the hit distances of k_inst_frame alone, no level runs
 		const float white[3] = {1.0f, 1.0f, 1.0f};
 		return instancesShadeStore(h, fn, cam, resx, resy, dXY, np, nullptr, 0, ambient, white, flags & (SNAIL_RENDER_DEPTH | SNAIL_RENDER_AA4), tint, bgrPackets, J, dStats, st);
 	}
 	const bool aa = (flags & SNAIL_RENDER_AA4) != 0, refl = (flags & SNAIL_RENDER_REFLECTIONS) != 0;
-	const bool floats = aa || tint || J;   // otherwise the lit packets as they are: bytes from k_mat_final
+	const bool floats = heat ? (tint || J) : (aa || tint || J);   // otherwise the lit packets as they are: bytes from k_mat_final (k_heat_store)
 	const int q = aa ? 4 : 1;
 	const int rx = aa ? resx * 2 : resx, ry = aa ? resy * 2 : resy;
 	const uint64_t one = (uint64_t)imatTreeLevelBytes(nLights, flags, maxDepth);
@@ -244,7 +268,7 @@ int imatTreeStore(SnailInstancesMaterials *m, const char *fn, const float cam[13
 	SnailInstancesMaterials::Set *Wp = nullptr;
 	if(int rc = imatNextSet(m, (int)ns, nLights, false, st, &Wp)) return rc;
 	SnailInstancesMaterials::Set &W = *Wp;
-	if(floats) {   // the tile renderer's part for the WHOLE list
+	if(floats || (heat && aa)) {   // the tile renderer's part for the WHOLE list (a heat launch without colours to reduce: for its sub-packet list alone)
 		const size_t packets = std::max(W.tilesPackets, n);
 		if(int rc = imatGrow(W, W.tiles, W.tilesPackets, packets, SnailMaterials::TileBufs::bytes(packets))) return rc;
 	}
@@ -254,19 +278,42 @@ int imatTreeStore(SnailInstancesMaterials *m, const char *fn, const float cam[13
 	}
 	SnailInstancesMaterials::Bufs B;
 	B.carve(W.base, ns);
+	uint32_t *pst = nullptr;
+	if(heat) {
+		if(!dPacketStats) {
+			const size_t packets = std::max(W.pstatsPackets, n);
+			char *part = (char *)W.pstats;
+			const int grc = imatGrow(W, part, W.pstatsPackets, packets, packets * 16);
+			W.pstats = (uint32_t *)part;
+			if(grc) return grc;
+		}
+		pst = dPacketStats ? dPacketStats : W.pstats;
+	}
 	SnailMaterials::TileBufs T;
-	if(floats) T.carve(W.tiles, n);
+	if(floats || (heat && aa)) T.carve(W.tiles, n);
 	int rc = 0;
 	const int32_t *list = dXY;
 	if(aa) {
 		hipLaunchKernelGGL(dev::k_inst_aa_packets, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const int2 *)dXY, np, (int2 *)T.xy2);
 		list = T.xy2;
 	}
+	if(heat) {
+		const hipError_t e = hipMemsetAsync(pst, 0, n * 16, st);
+		if(e != hipSuccess) { snail_set_error("%s: hipMemsetAsync: %s", fn, hipGetErrorString(e)); rc = 100 + (int)e; }
+	}
 	for(int a = 0; a < np && !rc; a += slice) {
 		const int cnt = std::min(slice, np - a);
 		const size_t at = (size_t)a * q;   // the slice's first packet in `list` and in the colours
-		rc = imatShadeTree(m, fn, cam, rx, ry, list + at * 2, cnt * q, lights7, nLights, ambient, floats ? nullptr : bgrPackets + at * 768, floats ? T.col + at * 768 : nullptr, B,
-						   W.transp, maxDepth, refl, dTrunc, dStats, st);
+		if(heat) rc = imatShadeTree(m, fn, cam, rx, ry, list + at * 2, cnt * q, lights7, nLights, ambient, nullptr, nullptr, B, W.transp, maxDepth, refl, dTrunc, dStats, st, pst + at * 4);
+		else rc = imatShadeTree(m, fn, cam, rx, ry, list + at * 2, cnt * q, lights7, nLights, ambient, floats ? nullptr : bgrPackets + at * 768, floats ? T.col + at * 768 : nullptr, B,
+								W.transp, maxDepth, refl, dTrunc, dStats, st);
+	}
+	if(!rc && heat && (floats || bgrPackets)) {   // no new colour arithmetic: the stores of heatmap.inc
+		if(floats) hipLaunchKernelGGL(dev_heat::k_heat_colours, dim3((unsigned)n), dim3(64), 0, st, (const unsigned *)pst, (int)n, T.col);
+		else if(aa) hipLaunchKernelGGL(dev_heat::k_heat_store<true>, dim3((unsigned)np), dim3(64), 0, st, (const unsigned *)pst, np, bgrPackets);
+		else hipLaunchKernelGGL(dev_heat::k_heat_store<false>, dim3((unsigned)np), dim3(64), 0, st, (const unsigned *)pst, np, bgrPackets);
+		const hipError_t e = hipGetLastError();
+		if(e != hipSuccess) { snail_set_error("%s: the heat store: %s", fn, hipGetErrorString(e)); rc = 100 + (int)e; }
 	}
 	if(!rc && floats) {
 		const bool sse = h->blas[0]->arith == SNAIL_ARITH_HOST_SSE;

@@ -1828,3 +1828,4 @@ int snail_account_primary(SnailScene *s, const float cam[13], int resx, int resy
 #include "instances_materials_bounce_host.inc"
 #include "instances_materials_transparency_host.inc"
 #include "instances_materials_tree_host.inc"
+#include "instances_materials_heat_host.inc"

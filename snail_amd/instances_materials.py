@@ -408,5 +408,73 @@ class InstancedMaterialSet:
             raise _lib.SnailError("snail_instances_materials_level_bytes: %s" % _lib.lib().snail_last_error().decode())
         return int(b)
 
+    # ---- include/snail_instances_materials_heatmap.h: per-packet TreeStats and the gVals[5] heat-map under full shading; any set ----
+    def packet_stats(self, cam, resx: int, resy: int, packet_xy=None, lights7=None, reflections: bool = False, out=None, stats=None, stream=None, flags: int = 0,
+                     max_depth: int = 8, truncated=None):
+        """snail_instances_materials_packet_stats_dev: the TreeStats {intersects, iterations, rays, skips} of every packet's RayTrace call
+        under full shading -- the whole tree of nested calls -- -> (int32 device tensor [n, 4] holding uint32 words, truncated: int64 device
+        tensor of one word, +=).  packet_xy = int32 device tensor [n, 2], or None = the frame's grid, row-major."""
+        torch = _torch()
+        n = int(packet_xy.shape[0]) if packet_xy is not None else ((resx + 15) // 16) * ((resy + 15) // 16)
+        if out is None:
+            out = torch.zeros((n, 4), dtype=torch.int32, device=self.isc._dev())
+        truncated = self._truncated(truncated)
+        lights, lp, cam13, _, _ = self._tile_args(cam, lights7, (0.0, 0.0, 0.0), None)
+        rc = _lib.lib().snail_instances_materials_packet_stats_dev(self._h, _lib.ptr(cam13), resx, resy, _lib.ptr(packet_xy), n, lp, len(lights),
+                                                                   int(flags) | (RENDER_REFLECTIONS if reflections else 0), int(max_depth), _lib.ptr(out),
+                                                                   _lib.ptr(truncated), _lib.ptr(stats), _stream_ptr(stream))
+        _lib.check(rc, "snail_instances_materials_packet_stats_dev")
+        return out, truncated
+
+    def render_heat_packets(self, cam, resx: int, resy: int, packet_xy=None, lights7=None, flags: int = 0, tint=None, out=None, packet_stats=None, stats=None,
+                            stream=None, max_depth: int = 8, truncated=None):
+        """snail_instances_materials_heat_packets_dev: the heat-map of the packets -> (packet-major [n, 256, 3] uint8 (B,G,R), truncated).
+        flags: RENDER_REFLECTIONS, RENDER_AA4; tint = three factors (gVals[8]) or None; packet_stats (optional) int32 device tensor [n, 4]
+        ([n, 4, 4] with RENDER_AA4)."""
+        torch = _torch()
+        n = int(packet_xy.shape[0]) if packet_xy is not None else ((resx + 15) // 16) * ((resy + 15) // 16)
+        if out is None:
+            out = torch.empty((n, 256, 3), dtype=torch.uint8, device=self.isc._dev())
+        truncated = self._truncated(truncated)
+        lights, lp, cam13, _, tnt = self._tile_args(cam, lights7, (0.0, 0.0, 0.0), tint)
+        rc = _lib.lib().snail_instances_materials_heat_packets_dev(self._h, _lib.ptr(cam13), resx, resy, _lib.ptr(packet_xy), n, lp, len(lights), int(flags),
+                                                                   _lib.ptr(tnt), _lib.ptr(out), _lib.ptr(packet_stats), int(max_depth), _lib.ptr(truncated),
+                                                                   _lib.ptr(stats), _stream_ptr(stream))
+        _lib.check(rc, "snail_instances_materials_heat_packets_dev")
+        return out, truncated
+
+    def render_heat_tiles_host(self, cam, resx: int, resy: int, tiles, offsets=None, lights7=None, flags: int = 0, tint=None, data=None, max_depth: int = 8,
+                               truncated=None):
+        """snail_instances_materials_render_heat_tiles: render_tree_tiles_host with gVals[5] -> (data, offsets, stats, truncated: uint64 [1],
+        the caller's array (+=) or a new one)."""
+        t = np.ascontiguousarray(tiles, dtype=np.int32).reshape(-1, 4)
+        size = 3 * t[:, 2].astype(np.int64) * t[:, 3]
+        if offsets is None:
+            offsets = np.concatenate([[0], np.cumsum(size)[:-1]]).astype(np.int64)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        if data is None:
+            data = np.zeros(int((offsets + size).max()) if len(t) else 0, dtype=np.uint8)
+        lights, lp, cam13, _, tnt = self._tile_args(cam, lights7, (0.0, 0.0, 0.0), tint)
+        stats = np.zeros(4, dtype=np.uint64)
+        truncated = np.zeros(1, dtype=np.uint64) if truncated is None else truncated
+        rc = _lib.lib().snail_instances_materials_render_heat_tiles(self._h, _lib.ptr(cam13), resx, resy, _lib.ptr(t), _lib.ptr(offsets), len(t), lp, len(lights),
+                                                                    int(flags), _lib.ptr(tnt), _lib.ptr(data), int(max_depth), _lib.ptr(truncated), _lib.ptr(stats))
+        _lib.check(rc, "snail_instances_materials_render_heat_tiles")
+        return data, offsets, stats, truncated
+
+    def render_heat_frame_host(self, cam, resx: int, resy: int, lights7=None, flags: int = 0, pitch: int | None = None, fill: int = 0, max_depth: int = 8,
+                               truncated=None):
+        """snail_instances_materials_render_heat_frame: render_tree_frame_host with gVals[5] -> (uint8 [resy, pitch] (B,G,R rows; pitch =
+        3 * resx unless given, bytes past a row's pixels keep `fill`), stats, truncated: uint64 [1])."""
+        pitch = resx * 3 if pitch is None else int(pitch)
+        img = np.full((resy, max(pitch, 0)), fill, dtype=np.uint8)
+        stats = np.zeros(4, dtype=np.uint64)
+        truncated = np.zeros(1, dtype=np.uint64) if truncated is None else truncated
+        lights, lp, cam13, _, _ = self._tile_args(cam, lights7, (0.0, 0.0, 0.0), None)
+        rc = _lib.lib().snail_instances_materials_render_heat_frame(self._h, _lib.ptr(cam13), resx, resy, lp, len(lights), int(flags), _lib.ptr(img), pitch,
+                                                                    int(max_depth), _lib.ptr(truncated), _lib.ptr(stats))
+        _lib.check(rc, "snail_instances_materials_render_heat_frame")
+        return img, stats, truncated
+
 
 __all__ = ["InstancedMaterialSet", "create_instanced_set"]

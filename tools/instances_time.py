@@ -73,7 +73,20 @@ this build and that one -- this, that, this, that --, each timing the two frames
 and prints per row both processes' medians of either build, so that the other build's own run-to-run spread stands beside the difference.
 
     python tools/instances_time.py --materials --tree --reflections [--aa] [--tiles] [--reps 5]
-    python tools/instances_time.py --materials --tree --baseline-lib parent/libsnailhip.so [--transparency 4] [--reps 7]"""
+    python tools/instances_time.py --materials --tree --baseline-lib parent/libsnailhip.so [--transparency 4] [--reps 7]
+
+--materials --heat [--reflections] [--aa] [--tiles] [--transparency N]: the gVals[5] heat-map of an instanced full-shaded frame
+(include/snail_instances_materials_heatmap.h) beside the lit frame it replaces, the same arguments, the scene, the capable set and the view of
+--materials --tree, the first of --counts instances, maxDepth N (default 4).  ONE process, alternating rounds of --frames calls per variant:
+  heat_packets    snail_instances_materials_heat_packets_dev              (with --tiles: heat_tiles, snail_instances_materials_render_heat_tiles)
+  tree_packets    snail_instances_materials_tree_frame_packets_dev of this build: the yardstick, its kernels are the parent commit's
+  parent_packets  with --baseline-lib PATH: the same call in that build of the library (e.g. the parent commit's), on handles of its own made
+                  from the same arrays -- this build's lit call must lie within the run's own min .. max spread of it
+Device events around a window enqueued back to back (--tiles: the host clock, call by call); ms per call: median (min .. max); the two launches'
+TreeStats are compared first.  The heat launch runs fewer kernels (no blend, no colour stage) plus four atomics per booking wave.  No ratio is a
+target: a measurement.  --out PATH appends the report (profiles/instances_materials_heat.txt).
+
+    python tools/instances_time.py --materials --heat [--reflections] [--aa] [--tiles] [--counts 64] [--frames 20] [--reps 5] [--baseline-lib PATH] [--out PATH]"""
 import argparse
 import json
 import os
@@ -121,12 +134,17 @@ def main():
     ap.add_argument("--baseline-lib", default=None)
     ap.add_argument("--tree", action="store_true")
     ap.add_argument("--aa", action="store_true")
+    ap.add_argument("--heat", action="store_true")
+    ap.add_argument("--frames", type=int, default=20)
+    ap.add_argument("--out", default=None)
     ap.add_argument("--tree-child", default=None, choices=["new", "old"], help=argparse.SUPPRESS)
     a = ap.parse_args()
     resx, resy = (int(x) for x in a.res.split("x"))
     if a.rebuild_dev:
         return rebuild_dev(torch, [int(c) for c in (a.rebuild_counts or "1024,10000").split(",")], a.reps)
     a.rebuild_counts = a.rebuild_counts or "10000"
+    if a.materials and a.heat:
+        return materials_heat(torch, a, resx, resy)
     if a.materials and a.tree:
         return materials_tree_compare(a) if a.baseline_lib and not a.tree_child else materials_tree(torch, a, resx, resy)
     if a.lit:
@@ -574,6 +592,147 @@ def materials_tree_compare(a):
             rows.append(row)
             print(json.dumps(row), file=sys.stderr, flush=True)
     print(json.dumps({"res": a.res, "lights": 1, "other": a.baseline_lib, "unit": res["new"][0]["unit"] + "; per build the medians of its two processes", "rows": rows}))
+
+
+class OtherBuild:
+    """Another build of the library (--baseline-lib) in THIS process: bound with this build's signature tables as far as it exports them, and
+    swapped in as snail_amd._lib's library while its handles are made, called or closed."""
+
+    def __init__(self, path):
+        import ctypes as C
+
+        from snail_amd import _lib
+        self._lib = _lib
+        self.L = C.CDLL(os.path.abspath(path))
+        for key, table in vars(_lib).items():
+            if key.endswith("SIGNATURES"):
+                for name, (res, args) in table.items():
+                    fn = getattr(self.L, name, None)
+                    if fn is not None:
+                        fn.restype, fn.argtypes = res, args
+
+    def __enter__(self):
+        self.prev = self._lib.lib()
+        self._lib._lib = self.L
+        return self
+
+    def __exit__(self, *exc):
+        self._lib._lib = self.prev
+
+
+def materials_heat(torch, a, resx, resy):
+    """--materials --heat: the heat-map beside the lit frame it replaces, and beside the same lit call of --baseline-lib"""
+    import statistics
+    import time
+
+    from snail_amd import materials as P
+    from snail_amd.instances_materials import InstancedMaterialSet
+    if not torch.cuda.is_available():
+        raise SystemExit("instances_time.py measures on the GPU; there is none here")
+    flags = (P.RENDER_REFLECTIONS if a.reflections else 0) | (P.RENDER_AA4 if a.aa else 0)
+    depth = int(a.transparency) if a.transparency else 4
+    n = int(a.counts.split(",")[0])
+    pw, ph = (resx + 15) // 16, (resy + 15) // 16
+    xy = torch.from_numpy(np.array([(x * 16, y * 16) for y in range(ph) for x in range(pw)], dtype=np.int32)).cuda()
+    tiles = np.array([(x, y, 64, 64) for y in range(0, resy, 64) for x in range(0, resx, 64)], dtype=np.int32)
+    data = np.zeros(int((3 * tiles[:, 2].astype(np.int64) * tiles[:, 3]).sum()), dtype=np.uint8)
+
+    def build():
+        """the scene, the instances and the capable set in whichever build is snail_amd._lib's at the moment"""
+        tv, sc, per_blas, mats, capable, texs = tree_scene(a)
+        lo, hi = sc.get_bbox()
+        rot, tr, bi = scenes.instance_field(lo, hi, n, seed=1)
+        isc = InstancedScene([sc], rot, tr, bi)
+        cam, light = tree_view(tv, isc, n)
+        return sc, isc, InstancedMaterialSet(isc, [per_blas], capable, texs, transparent=True), cam, light, len(tv)
+
+    sc, isc, ms, cam, light, ntris = build()
+    other = OtherBuild(a.baseline_lib) if a.baseline_lib else None
+    if other:
+        with other:
+            osc, oisc, oms, _, _, _ = build()
+    out = [torch.zeros((pw * ph, 256, 3), dtype=torch.uint8, device="cuda") for _ in range(3)]
+    trunc = torch.zeros(1, dtype=torch.int64, device="cuda")
+    htrunc = np.zeros(1, dtype=np.uint64)
+
+    def in_other(fn):
+        def run(s=None):
+            with other:
+                return fn(s)
+        return run
+    if a.tiles:
+        variants = {"tree_tiles": lambda s=None: ms.render_tree_tiles_host(cam, resx, resy, tiles, None, light, flags, data=data, max_depth=depth, truncated=htrunc),
+                    "heat_tiles": lambda s=None: ms.render_heat_tiles_host(cam, resx, resy, tiles, None, light, flags, data=data, max_depth=depth, truncated=htrunc)}
+        if other:
+            variants["parent_tiles"] = in_other(lambda s=None: oms.render_tree_tiles_host(cam, resx, resy, tiles, None, light, flags, data=data, max_depth=depth, truncated=htrunc))
+    else:
+        variants = {"tree_packets": lambda s=None: ms.tree_frame_packets(cam, resx, resy, xy, light, flags, out=out[0], stats=s, max_depth=depth, truncated=trunc),
+                    "heat_packets": lambda s=None: ms.render_heat_packets(cam, resx, resy, xy, light, flags, out=out[1], stats=s, max_depth=depth, truncated=trunc)}
+        if other:
+            variants["parent_packets"] = in_other(lambda s=None: oms.tree_frame_packets(cam, resx, resy, xy, light, flags, out=out[2], stats=s, max_depth=depth, truncated=trunc))
+    for fn in variants.values():        # warm-up: code objects, every group of the set's intermediates at its largest, the cached lists and tile job
+        for _ in range(9):
+            fn()
+    torch.cuda.synchronize()
+    if a.tiles:
+        got = [np.asarray(fn()[2]) for fn in variants.values()]
+    else:
+        st = [isc.new_stats() for _ in variants]
+        for fn, s in zip(variants.values(), st):
+            fn(s)
+        torch.cuda.synchronize()
+        got = [s.cpu().numpy() for s in st]
+    same = all(bool(np.array_equal(got[0], g)) for g in got[1:])
+    lit_equal = (not other) or a.tiles or bool(torch.equal(out[0], out[2]))
+    times = {k: [] for k in variants}
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    for _ in range(a.reps):
+        for k, fn in variants.items():      # alternating: one window of each per round
+            if a.tiles:
+                t0 = time.perf_counter()
+                for _ in range(a.frames):
+                    fn()
+                times[k].append((time.perf_counter() - t0) * 1e3 / a.frames)
+            else:
+                e0.record()
+                for _ in range(a.frames):
+                    fn()
+                e1.record()
+                e1.synchronize()
+                times[k].append(e0.elapsed_time(e1) / a.frames)
+    med = {k: statistics.median(v) for k, v in times.items()}
+    names = list(med)
+    lit, hm = names[0], names[1]
+    ratio = med[hm] / med[lit]
+    what = ("snail_instances_materials_tree_render_tiles", "snail_instances_materials_render_heat_tiles") if a.tiles else (
+        "snail_instances_materials_tree_frame_packets_dev", "snail_instances_materials_heat_packets_dev")
+    lines = ["", "the heat-map under full shading of an instanced scene: atrium BLAS (%d triangles) x %d instances, the capable set of --materials --tree, one light, IEEE, "
+             "%dx%d (%d packets), flags %s%s, max_depth %d; %d rounds of %d calls per variant, alternating, after 9 warm-up calls each; %s, ms per call: median (min .. max)" % (
+                 ntris, n, resx, resy, pw * ph, "REFLECTIONS " if a.reflections else "", "AA4" if a.aa else "", depth, a.reps, a.frames,
+                 "host clock, call by call (each call ends in its device-to-host copy)" if a.tiles else "device events around a window enqueued back to back"),
+             "device: %s" % torch.cuda.get_device_name(0),
+             "%s = %s; %s = %s, the same arguments%s" % (lit, what[0], hm, what[1], "; %s = %s of the parent commit's build, in the same process" % (names[2], what[0]) if other else ""),
+             "TreeStats of the launches equal: %s (%s)%s" % (same, np.asarray(got[1]).tolist(), "" if a.tiles or not other else "; lit bytes of the two builds equal: %s" % lit_equal)]
+    for k, v in times.items():
+        lines.append("  %-15s %9.3f  (%.3f .. %.3f)" % (k, med[k], min(v), max(v)))
+    lines.append("  %s / %s: %.3f%s" % (hm, lit, ratio, "   -- the heat-map is SLOWER than the frame it replaces" if ratio > 1.0 else ""))
+    if other:
+        pk = names[2]
+        lo_, hi_ = min(min(times[pk]), min(times[lit])), max(max(times[pk]), max(times[lit]))
+        inside = min(times[pk]) <= med[lit] <= max(times[pk]) or min(times[lit]) <= med[pk] <= max(times[lit])
+        lines.append("  %s / %s: %.4f; the run's own spread of the two lit calls: %.3f .. %.3f (max / min %.4f); one build's median within the other's min .. max: %s" % (
+            lit, pk, med[lit] / med[pk], lo_, hi_, hi_ / lo_, inside))
+    text = "\n".join(lines)
+    print(text)
+    if a.out:
+        with open(a.out, "a") as fh:
+            fh.write(text + "\n")
+    if other:
+        with other:
+            oms.close(); oisc.close(); osc.close()
+    ms.close(); isc.close(); sc.close()
+    if not same or not lit_equal:
+        raise SystemExit("the heat launch's TreeStats differ from the lit frame's, or the two builds' lit frames differ")
 
 
 def rebuild(torch, sc, counts, reps):
