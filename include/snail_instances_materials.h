@@ -12,8 +12,9 @@
  * NOT here (the mirrored bounce of gVals[7] is snail_instances_materials_bounce.h's, the transparency continuation
  * snail_instances_materials_transparency.h's): tile lists, 4x antialiasing and the tint, the heat-map under full shading and multi-device frames
  * of instanced scenes; routing in snail_adapter.hpp (no reference host can reach this branch through
- * HipDBVH); device-packed records for BLASes whose tree is rebuilt on the device (a set made before such a rebuild shades with another
- * triangle's data: build the BLASes from host triangles).
+ * HipDBVH); device-packed records for BLASes whose tree is rebuilt on the device (a set made here before such a rebuild would shade with
+ * another triangle's data, so this creator refuses such a BLAS: snail_instances_materials_dynamic.h has the creator that takes it, and the
+ * calls that pack its records again behind every rebuild).
  */
 #ifndef SNAIL_INSTANCES_MATERIALS_H
 #define SNAIL_INSTANCES_MATERIALS_H

@@ -11,7 +11,7 @@
  * NOT here: tile lists, 4x antialiasing and the tint with the bounce, and the transparency continuation together with it
  * (snail_instances_materials_tree.h has them; snail_instances_materials_transparency.h: the continuation without the bounce); the heat-map
  * (gVals[5]) under full shading of instanced scenes (not on the device); multi-device frames; routing in snail_adapter.hpp (no reference host can reach this branch through HipDBVH);
- * sets for BLASes whose tree is rebuilt on the device (snail_instances_materials.h).
+ * creating sets for BLASes whose tree is rebuilt on the device (snail_instances_materials_dynamic.h has that; its sets are taken here).
  */
 #ifndef SNAIL_INSTANCES_MATERIALS_BOUNCE_H
 #define SNAIL_INSTANCES_MATERIALS_BOUNCE_H

@@ -33,7 +33,8 @@
  * slices, each of which books at its packets' place in the whole list's counters.  Slicing changes no counter and no byte.
  *
  * NOT here (the host renderer keeps them): full-shaded tiles dealt over several devices; the ordered launches (dispatch-order feedback) under
- * full shading; routing in snail_adapter.hpp (no reference host can reach this branch through HipDBVH).
+ * full shading; routing in snail_adapter.hpp (no reference host can reach this branch through HipDBVH); creating sets for BLASes whose tree is
+ * rebuilt on the device (snail_instances_materials_dynamic.h has that; its sets are taken here).
  */
 #ifndef SNAIL_INSTANCES_MATERIALS_HEATMAP_H
 #define SNAIL_INSTANCES_MATERIALS_HEATMAP_H

@@ -14,7 +14,7 @@
  * continuations inside the bounce, a tree of calls), tile lists, 4x antialiasing and the tint: snail_instances_materials_tree.h has them, for any
  * set, and the frames here keep refusing every nonzero flag; the heat-map (gVals[5]) for instanced full shading (not on the device);
  * multi-device frames; routing in snail_adapter.hpp (no reference host can reach this branch through HipDBVH); device-packed records for BLASes
- * whose tree is rebuilt on the device (snail_instances_materials.h).
+ * whose tree is rebuilt on the device (snail_instances_materials_dynamic.h has them; its sets are taken here).
  */
 #ifndef SNAIL_INSTANCES_MATERIALS_TRANSPARENCY_H
 #define SNAIL_INSTANCES_MATERIALS_TRANSPARENCY_H

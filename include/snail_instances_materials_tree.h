@@ -40,8 +40,8 @@
  * records are read at launch.
  *
  * NOT here (the host renderer keeps them): the heat-map (gVals[5]) and per-packet TreeStats of these frames; frames dealt over several devices;
- * the ordered launches; routing in snail_adapter.hpp (no reference host can reach this branch through HipDBVH); sets for BLASes whose tree is
- * rebuilt on the device (snail_instances_materials.h); maxDepth above 8 (the reference has no cut: a frame whose counter moved is not the
+ * the ordered launches; routing in snail_adapter.hpp (no reference host can reach this branch through HipDBVH); creating sets for BLASes whose tree is
+ * rebuilt on the device (snail_instances_materials_dynamic.h has that; its sets are taken here); maxDepth above 8 (the reference has no cut: a frame whose counter moved is not the
  * reference's).
  */
 #ifndef SNAIL_INSTANCES_MATERIALS_TREE_H

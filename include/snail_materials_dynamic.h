@@ -32,7 +32,8 @@
  *
  * Conventions are those of snail_hip.h: 0 = success, otherwise snail_last_error() holds the message and nothing was enqueued.
  * NOT here: smooth normals averaged over shared vertices (the caller supplies them through d_nrm9, as the reference takes them from vn);
- * changing uv or the material assignment after creation; instanced scenes; OBJ / MTL ingest.
+ * changing uv or the material assignment after creation; instanced scenes (snail_instances_materials_dynamic.h has them: the same records
+ * per BLAS, several BLASes packed in one launch); OBJ / MTL ingest.
  */
 #ifndef SNAIL_MATERIALS_DYNAMIC_H
 #define SNAIL_MATERIALS_DYNAMIC_H

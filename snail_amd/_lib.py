@@ -258,6 +258,14 @@ INSTANCES_MATERIALS_HEAT_SIGNATURES = {
     "snail_instances_materials_render_heat_frame": (_I, [_VP, _F13, _I, _I, _VP, _I, _I, _VP, _I, _I, _VP, _VP]),
 }
 
+# include/snail_instances_materials_dynamic.h: an instanced set whose BLASes deform on the device -- per-BLAS records packed on the device and packed
+# again behind every rebuild of a BLAS (tests/c/instances_materials_dynamic_c.c enumerates this table)
+INSTANCES_MATERIALS_DYNAMIC_SIGNATURES = {
+    "snail_instances_materials_create_dev": (_VP, [_VP, _VP, _I, _VP, _I, _VP, _VP, _I, _VP]),
+    "snail_instances_materials_rebuild_dev": (_I, [_VP, _VP, _I, _VP]),
+    "snail_instances_materials_update_dev": (_I, [_VP, _VP, _I, _VP]),
+}
+
 # include/snail_hip_debug.h: the workbench build only (libsnailhip_debug.so, -DSNAIL_DEBUG_API)
 DEBUG_SIGNATURES = {
     "snail_debug_delay_dev": (_I, [C.c_float, _VP]),
@@ -282,7 +290,7 @@ def debug_lib():
         if not os.path.exists(DEBUG_LIB_PATH):
             raise SnailError("workbench library %s is missing: `make -C snail_amd/csrc debug`" % DEBUG_LIB_PATH)
         L = C.CDLL(DEBUG_LIB_PATH)
-        for table in (SIGNATURES, INSTANCES_SIGNATURES, INSTANCES_SHADE_SIGNATURES, INSTANCES_TILES_SIGNATURES, INSTANCES_BUILD_SIGNATURES, BVH_FAST_SIGNATURES, HEATMAP_SIGNATURES, MATERIALS_SIGNATURES, MATERIALS_BOUNCE_SIGNATURES, MATERIALS_TILES_SIGNATURES, MATERIALS_TRANSPARENCY_SIGNATURES, MATERIALS_TREE_SIGNATURES, MATERIALS_HEAT_SIGNATURES, MATERIALS_DYNAMIC_SIGNATURES, INSTANCES_MATERIALS_SIGNATURES, INSTANCES_MATERIALS_BOUNCE_SIGNATURES, INSTANCES_MATERIALS_TRANSPARENCY_SIGNATURES, INSTANCES_MATERIALS_TREE_SIGNATURES, INSTANCES_MATERIALS_HEAT_SIGNATURES, DEBUG_SIGNATURES):
+        for table in (SIGNATURES, INSTANCES_SIGNATURES, INSTANCES_SHADE_SIGNATURES, INSTANCES_TILES_SIGNATURES, INSTANCES_BUILD_SIGNATURES, BVH_FAST_SIGNATURES, HEATMAP_SIGNATURES, MATERIALS_SIGNATURES, MATERIALS_BOUNCE_SIGNATURES, MATERIALS_TILES_SIGNATURES, MATERIALS_TRANSPARENCY_SIGNATURES, MATERIALS_TREE_SIGNATURES, MATERIALS_HEAT_SIGNATURES, MATERIALS_DYNAMIC_SIGNATURES, INSTANCES_MATERIALS_SIGNATURES, INSTANCES_MATERIALS_BOUNCE_SIGNATURES, INSTANCES_MATERIALS_TRANSPARENCY_SIGNATURES, INSTANCES_MATERIALS_TREE_SIGNATURES, INSTANCES_MATERIALS_HEAT_SIGNATURES, INSTANCES_MATERIALS_DYNAMIC_SIGNATURES, DEBUG_SIGNATURES):
             for name, (res, args) in table.items():
                 fn = getattr(L, name)
                 fn.restype = res
@@ -303,7 +311,7 @@ def lib():
             L = C.CDLL(LIB_PATH)
         except OSError as e:  # pragma: no cover - depends on the box
             raise SnailError("cannot load %s: %s" % (LIB_PATH, e)) from e
-        for table in (SIGNATURES, INSTANCES_SIGNATURES, INSTANCES_SHADE_SIGNATURES, INSTANCES_TILES_SIGNATURES, INSTANCES_BUILD_SIGNATURES, BVH_FAST_SIGNATURES, HEATMAP_SIGNATURES, MATERIALS_SIGNATURES, MATERIALS_BOUNCE_SIGNATURES, MATERIALS_TILES_SIGNATURES, MATERIALS_TRANSPARENCY_SIGNATURES, MATERIALS_TREE_SIGNATURES, MATERIALS_HEAT_SIGNATURES, MATERIALS_DYNAMIC_SIGNATURES, INSTANCES_MATERIALS_SIGNATURES, INSTANCES_MATERIALS_BOUNCE_SIGNATURES, INSTANCES_MATERIALS_TRANSPARENCY_SIGNATURES, INSTANCES_MATERIALS_TREE_SIGNATURES, INSTANCES_MATERIALS_HEAT_SIGNATURES):
+        for table in (SIGNATURES, INSTANCES_SIGNATURES, INSTANCES_SHADE_SIGNATURES, INSTANCES_TILES_SIGNATURES, INSTANCES_BUILD_SIGNATURES, BVH_FAST_SIGNATURES, HEATMAP_SIGNATURES, MATERIALS_SIGNATURES, MATERIALS_BOUNCE_SIGNATURES, MATERIALS_TILES_SIGNATURES, MATERIALS_TRANSPARENCY_SIGNATURES, MATERIALS_TREE_SIGNATURES, MATERIALS_HEAT_SIGNATURES, MATERIALS_DYNAMIC_SIGNATURES, INSTANCES_MATERIALS_SIGNATURES, INSTANCES_MATERIALS_BOUNCE_SIGNATURES, INSTANCES_MATERIALS_TRANSPARENCY_SIGNATURES, INSTANCES_MATERIALS_TREE_SIGNATURES, INSTANCES_MATERIALS_HEAT_SIGNATURES, INSTANCES_MATERIALS_DYNAMIC_SIGNATURES):
             for name, (res, args) in table.items():
                 fn = getattr(L, name)
                 fn.restype = res

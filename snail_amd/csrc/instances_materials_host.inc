@@ -4,13 +4,16 @@
 // one mirrored bounce (instances_materials_bounce_host.inc, included next) the nested call stands between the sample stage and the lights.
 #include "../../include/snail_instances_materials.h"
 
+struct SnailInstancesMaterialsDyn;   // instances_materials_dynamic_host.inc: what a set of snail_instances_materials_create_dev carries besides
 struct SnailInstancesMaterials {
 	SnailInstances *inst = nullptr;
+	SnailInstancesMaterialsDyn *dyn = nullptr;   // (null: no BLAS whose records are packed on the device -- the two older creators' sets)
 	int device = 0;
 	int nBlas = 0, nMats = 0, nTex = 0;
 	bool canSelectTransparent = false;   // holds SNAIL_MAT_TRANSPARENT or UBER with 0 < dissolve < 1 (snail_instances_materials_create_transparent alone makes such a set)
 	char *dBase = nullptr;   // ONE allocation: the per-BLAS table, every BLAS's records and map, materials, texture descriptors, texels
 	const dev::IMatBlas *dTab = nullptr;
+	std::vector<dev::IMatBlas> hTab;   // the host's copy of dTab (device addresses): where a BLAS's records stand, for the device pack
 	const dev::MatRec *dMats = nullptr;
 	const dev::TexRec *dTex = nullptr;
 	const unsigned char *dTexels = nullptr;
@@ -72,10 +75,16 @@ struct SnailInstancesMaterials {
 
 namespace {
 
+// instances_materials_dynamic_host.inc: whether the records of every dynamic BLAS are those of the tree that BLAS holds now (a refusal that names
+// the rebuild otherwise), and the end of what the set carries for them
+int imatDynCheckFresh(const SnailInstancesMaterials *m, const char *fn);
+void imatDynFree(SnailInstancesMaterialsDyn *d);
+
 // any set: the entry points of include/snail_instances_materials_transparency.h
 int checkIMatAny(const SnailInstancesMaterials *m, const char *fn) {
 	if(!m || !m->inst || !m->dBase) { snail_set_error("%s: invalid instanced material set handle", fn); return 1; }
-	return checkInstances(m->inst, fn);
+	if(int rc = checkInstances(m->inst, fn)) return rc;
+	return m->dyn ? imatDynCheckFresh(m, fn) : 0;
 }
 // the entry points of snail_instances_materials.h and _bounce.h: their kernels know neither the transparent kind nor the selector
 int checkIMat(const SnailInstancesMaterials *m, const char *fn) {
@@ -225,6 +234,8 @@ int imatShadeDev(SnailInstancesMaterials *m, const char *fn, const float cam[13]
 
 // the creators: snail_instances_materials_create (transp = false: its refusals) and snail_instances_materials_create_transparent
 // (include/snail_instances_materials_transparency.h), one body as matCreate is for plain scenes
+SnailInstancesMaterials *imatUpload(const char *fn, bool canSelectAny, SnailInstances *h, const SnailBlasShading *perBlas, int nBlas, const SnailMaterial *mats,
+									int nMats, const int32_t *opacityTexture, const SnailTexture *textures, int nTex);
 SnailInstancesMaterials *imatCreate(const char *fn, bool transp, SnailInstances *h, const SnailBlasShading *perBlas, int nBlas, const SnailMaterial *mats, int nMats,
 									const int32_t *opacityTexture, const SnailTexture *textures, int nTex) {
 	// the caller's HOST data first, by snail_materials_create's own check (once per BLAS: its words name the record, entry, material or texture)
@@ -247,7 +258,13 @@ SnailInstancesMaterials *imatCreate(const char *fn, bool transp, SnailInstances 
 		if(h->blas[b]->fast) { snail_set_error("%s: BLAS %d is rebuilt on the device, which renumbers its triangles: no records for such a BLAS here", fn, b); return nullptr; }
 		if(perBlas[b].nTris != h->blas[b]->nTris) { snail_set_error("%s: BLAS %d: %d records (nTris) for a scene of %d triangles", fn, b, perBlas[b].nTris, h->blas[b]->nTris); return nullptr; }
 	}
+	return imatUpload(fn, canSelectAny, h, perBlas, nBlas, mats, nMats, opacityTexture, textures, nTex);
+}
 
+// the second half of the creators, after every check: the set on the device.  A BLAS with shtris64 == NULL (snail_instances_materials_create_dev's
+// alone: the checks above let none pass) gets zeroed records, which that creator packs on the device
+SnailInstancesMaterials *imatUpload(const char *fn, bool canSelectAny, SnailInstances *h, const SnailBlasShading *perBlas, int nBlas, const SnailMaterial *mats,
+									int nMats, const int32_t *opacityTexture, const SnailTexture *textures, int nTex) {
 	// the device copy (materials and textures as matUpload lays them out; opacityTexture is read for the transparent kind alone, which only the
 	// transparent creator's check lets pass)
 	std::vector<dev::MatRec> recs;
@@ -270,7 +287,7 @@ SnailInstancesMaterials *imatCreate(const char *fn, bool transp, SnailInstances 
 	for(int b = 0; b < nBlas && e == hipSuccess; b++) {
 		tab[b].shtris = (const uint4 *)(base + oTris[b]); tab[b].matMap = (const int *)(base + oMap[b]);
 		tab[b].nTris = perBlas[b].nTris; tab[b].nMap = perBlas[b].nMap;
-		e = hipMemcpy(base + oTris[b], perBlas[b].shtris64, (size_t)perBlas[b].nTris * 64, hipMemcpyHostToDevice);
+		if(perBlas[b].shtris64) e = hipMemcpy(base + oTris[b], perBlas[b].shtris64, (size_t)perBlas[b].nTris * 64, hipMemcpyHostToDevice);
 		if(e == hipSuccess) e = hipMemcpy(base + oMap[b], perBlas[b].matMap, (size_t)perBlas[b].nMap * 4, hipMemcpyHostToDevice);
 	}
 	if(e == hipSuccess) e = hipMemcpy(base, tab.data(), tab.size() * sizeof(dev::IMatBlas), hipMemcpyHostToDevice);
@@ -288,6 +305,7 @@ SnailInstancesMaterials *imatCreate(const char *fn, bool transp, SnailInstances 
 	m->nBlas = nBlas; m->nMats = nMats; m->nTex = nTex;
 	m->dBase = base;
 	m->canSelectTransparent = canSelectAny;
+	m->hTab = tab;
 	m->dTab = (const dev::IMatBlas *)base; m->dMats = (const dev::MatRec *)(base + oMats);
 	m->dTex = (const dev::TexRec *)(base + oTex); m->dTexels = (const unsigned char *)(base + oTexels);
 	return m;
@@ -317,6 +335,7 @@ void snail_instances_materials_destroy(SnailInstancesMaterials *m) {
 	freeInstTileJob(m->tileJob);
 	for(auto &f : m->frameLists) (void)hipFree(f.d);
 	if(m->dBase) (void)hipFree(m->dBase);
+	imatDynFree(m->dyn);
 	delete m;
 }
 

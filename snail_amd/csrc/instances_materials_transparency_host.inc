@@ -187,6 +187,7 @@ SnailInstancesMaterials *snail_instances_materials_create_transparent(SnailInsta
 
 int snail_instances_materials_can_select_transparent(const SnailInstancesMaterials *m) {
 	if(!m) { snail_set_error("snail_instances_materials_can_select_transparent: invalid instanced material set handle"); return -1; }
+	if(m->dyn && imatDynCheckFresh(m, "snail_instances_materials_can_select_transparent")) return -1;   // (include/snail_instances_materials_dynamic.h, "staleness")
 	return m->canSelectTransparent ? 1 : 0;
 }
 

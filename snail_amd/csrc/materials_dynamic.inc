@@ -5,6 +5,7 @@
 //   k_shd_check   creation only: uv finite and below 2^20, matIdx inside the map, perm inside the triangles -> the first offender
 //   k_shd_pack    record i <- input triangle perm[i]; under a rebuild only when the build's status word (k_fast_commit's info) is 0
 //   k_shd_info    the caller's info words, after the pack (one thread)
+// The per-record body and the info words are __device__ functions: the batched kernels of instances_materials_dynamic.inc call the same ones.
 namespace devshd {
 
 struct PackArgs {
@@ -36,9 +37,8 @@ __global__ void k_shd_check(PackArgs A) {
 	if(code) { atomicMax(&A.check[0], code); atomicMin(&A.check[1], i); }
 }
 
-__global__ void k_shd_pack(PackArgs A) {
-	const int i = blockIdx.x * blockDim.x + threadIdx.x;
-	if(i >= A.n) return;
+// record i of one set (i < A.n): the ONE body of k_shd_pack and of the batched devshd::k_ishd_pack (instances_materials_dynamic.inc)
+__device__ __forceinline__ void shdPackRecord(const PackArgs &A, const int i) {
 	const int src = A.perm[i];
 	if(A.permOut) A.permOut[i] = src;
 	if(A.build && A.build[0] != 0) return;   // the tree was not committed: neither are the records
@@ -80,9 +80,15 @@ __global__ void k_shd_pack(PackArgs A) {
 	o[3] = make_uint4(__float_as_uint(r[12]), __float_as_uint(r[13]), __float_as_uint(r[14]), id);
 }
 
+__global__ void k_shd_pack(PackArgs A) {
+	const int i = blockIdx.x * blockDim.x + threadIdx.x;
+	if(i >= A.n) return;
+	shdPackRecord(A, i);
+}
+
 // rebuild (build given): {status, nNodes, depth, n, committed, zeroed}; update: {1, zeroed}
-__global__ void k_shd_info(PackArgs A) {
-	if(blockIdx.x != 0 || threadIdx.x != 0 || !A.info) return;
+__device__ __forceinline__ void shdInfoWords(const PackArgs &A) {
+	if(!A.info) return;
 	if(A.build) {
 		for(int k = 0; k < 4; k++) A.info[k] = A.build[k];
 		A.info[4] = A.build[0] == 0 ? 1 : 0;
@@ -91,6 +97,10 @@ __global__ void k_shd_info(PackArgs A) {
 		A.info[0] = 1;
 		A.info[1] = *A.zeroed;
 	}
+}
+__global__ void k_shd_info(PackArgs A) {
+	if(blockIdx.x != 0 || threadIdx.x != 0) return;
+	shdInfoWords(A);
 }
 
 } // namespace devshd

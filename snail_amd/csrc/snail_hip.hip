@@ -105,6 +105,7 @@ void snail_set_error(const char *fmt, ...) {
 #include "build_common.inc"      // the device builders: plain fp32, once for both arithmetics
 #include "instances_build.inc"   // ... of the top-level tree over instances (bvh_fast.inc, of a plain scene, follows lbvh.inc)
 #include "materials_dynamic.inc"  // the ShTriangle records of a material set packed on the device: plain fp32, once for both arithmetics
+#include "instances_materials_dynamic.inc"  // ... of several BLASes of an instanced set in one launch
 
 // A launch in the scene's arithmetic: dev::K, or dev_sse::K with the same argument record (the two namespaces are the same text, so the
 // records have the same layout; they are distinct types, hence the copy).  K comes last because its template arguments hold commas.
@@ -1825,6 +1826,7 @@ int snail_account_primary(SnailScene *s, const float cam[13], int resx, int resy
 #include "materials_heat_host.inc"
 #include "materials_dynamic_host.inc"
 #include "instances_materials_host.inc"
+#include "instances_materials_dynamic_host.inc"
 #include "instances_materials_bounce_host.inc"
 #include "instances_materials_transparency_host.inc"
 #include "instances_materials_tree_host.inc"

@@ -15,6 +15,10 @@ of include/snail_instances_materials.h.
                                                             <-> the continuation TOGETHER with the bounce, tile lists, 4x AA, depth shading and
                                                                  the tint (RenderTask::Work), include/snail_instances_materials_tree.h
 
+  InstancedMaterialSet.from_dev(isc, per_blas, ...), DevBlasShading, .rebuild_blas_dev / .update_blas_dev
+                                                            <-> an animated instanced scene: BLASes of Scene.from_fast_dev whose records are packed
+                                                                 on the device and follow their rebuilds, include/snail_instances_materials_dynamic.h
+
 Materials, textures and pack_shtris are snail_amd.materials'."""
 from __future__ import annotations
 
@@ -24,12 +28,35 @@ import numpy as np
 
 from . import _lib
 from .instances import InstancedScene
+from . import materials as P
 from .materials import RENDER_REFLECTIONS, SAMPLE_COMPONENTS, _material_records, _texture_array, pack_shtris
 from .scene import _stream_ptr, _torch
 
 
 class _BlasShading(C.Structure):
     _fields_ = [("shtris64", C.c_void_p), ("nTris", C.c_int32), ("matMap", C.c_void_p), ("nMap", C.c_int32)]
+
+
+class _BlasShadingDev(C.Structure):
+    _fields_ = _BlasShading._fields_ + [("d_uv6", C.c_void_p), ("d_matIdx", C.c_void_p), ("d_flat", C.c_void_p), ("d_perm", C.c_void_p), ("d_nrm9", C.c_void_p),
+                                        ("d_verts9", C.c_void_p)]
+
+
+class _BlasRebuild(C.Structure):
+    _fields_ = [("blas", C.c_int32), ("d_verts9", C.c_void_p), ("d_nrm9", C.c_void_p), ("d_perm", C.c_void_p), ("d_info", C.c_void_p)]
+
+
+class DevBlasShading:
+    """The shading data of a Scene.from_fast_dev BLAS for InstancedMaterialSet.from_dev: device tensors on the scene's device describing the
+    INPUT triangles -- d_uv float32 [n, 3, 2], d_mat_index int32 [n], d_flat uint8 [n] or None (none flat) -- the BLAS's material_map (host),
+    and the normals: d_nrm float32 [n, 3, 3], or None for face normals of d_verts float32 [n, 3, 3]."""
+
+    def __init__(self, d_uv, d_mat_index, d_flat, material_map, d_nrm=None, d_verts=None):
+        self.d_uv, self.d_mat_index, self.d_flat, self.material_map, self.d_nrm, self.d_verts = d_uv, d_mat_index, d_flat, material_map, d_nrm, d_verts
+
+
+def _addr(t):
+    return None if t is None else (t.data_ptr() if hasattr(t, "data_ptr") else t.ctypes.data)
 
 
 def create_instanced_set(instances_handle, shtris_list, map_list, materials, textures, transparent: bool = False):
@@ -84,6 +111,119 @@ class InstancedMaterialSet:
             self.shtris.append(pack_shtris(uv, nrm, mat_index, flat, perm))
             maps.append(material_map)
         self._h = create_instanced_set(isc._h, self.shtris, maps, list(materials), list(textures), transparent)
+
+    # ---- include/snail_instances_materials_dynamic.h: BLASes that deform on the device ---------------------------------------------------------
+    @classmethod
+    def from_dev(cls, isc: InstancedScene, per_blas, materials=(), textures=(), transparent: bool = False, stream=None):
+        """The set of an instanced scene with Scene.from_fast_dev BLASes (snail_instances_materials_create_dev).  per_blas[b] is the
+        constructor's host 5-tuple for a BLAS built from host triangles and a DevBlasShading for a Scene.from_fast_dev BLAS, whose records are
+        packed on the device through that scene's d_perm and packed again by rebuild_blas_dev / update_blas_dev.  The device tensors of uv,
+        material index and flat are copied: they need not outlive the call."""
+        torch = _torch()
+        per_blas = list(per_blas)
+        if len(per_blas) != len(isc.blas):
+            raise _lib.SnailError("InstancedMaterialSet.from_dev: shading data of %d BLASes for an instanced scene of %d" % (len(per_blas), len(isc.blas)))
+        self = cls.__new__(cls)
+        self.isc, self._h, self.shtris, self._dynamic = isc, None, [], True
+        per = (_BlasShadingDev * max(len(per_blas), 1))()
+        keep = []
+        for b, pb in enumerate(per_blas):
+            sc = isc.blas[b]
+            fast = getattr(sc, "_fast_dev", False)
+            if isinstance(pb, DevBlasShading) != bool(fast):
+                raise _lib.SnailError("InstancedMaterialSet.from_dev: BLAS %d: a Scene.from_fast_dev BLAS takes a DevBlasShading, a BLAS built from host "
+                                      "triangles the host tuple (uv, nrm, mat_index, flat, material_map)" % b)
+            if fast:
+                n, d = sc._fast_n, sc._dev()
+                P.MaterialSet._check_dev("d_uv", pb.d_uv, torch.float32, n * 6, d)
+                P.MaterialSet._check_dev("d_mat_index", pb.d_mat_index, torch.int32, n, d)
+                P.MaterialSet._check_dev("d_flat", pb.d_flat, torch.uint8, n, d, optional=True)
+                P.MaterialSet._check_dev("d_nrm", pb.d_nrm, torch.float32, n * 9, d, optional=True)
+                P.MaterialSet._check_dev("d_verts", pb.d_verts, torch.float32, n * 9, d, optional=True)
+                mp = np.ascontiguousarray(pb.material_map, dtype=np.int32).reshape(-1)
+                per[b].nTris = n
+                per[b].d_uv6, per[b].d_matIdx, per[b].d_flat, per[b].d_perm = _addr(pb.d_uv), _addr(pb.d_mat_index), _addr(pb.d_flat), _addr(sc.d_perm)
+                per[b].d_nrm9, per[b].d_verts9 = _addr(pb.d_nrm), _addr(pb.d_verts)
+                self.shtris.append(None)
+            else:
+                uv, nrm, mat_index, flat, material_map = pb
+                perm = getattr(sc.bvh, "perm", None)
+                if perm is None:
+                    raise _lib.SnailError("InstancedMaterialSet.from_dev: BLAS %d carries no host permutation (BVH slot -> input triangle)" % b)
+                sh = np.ascontiguousarray(pack_shtris(uv, nrm, mat_index, flat, perm), dtype=np.uint8).reshape(-1, 64)
+                mp = np.ascontiguousarray(material_map, dtype=np.int32).reshape(-1)
+                per[b].shtris64, per[b].nTris = (sh.ctypes.data if len(sh) else None), len(sh)
+                self.shtris.append(sh)
+            per[b].matMap, per[b].nMap = (mp.ctypes.data if len(mp) else None), len(mp)
+            keep.append(mp)
+        materials, textures = list(materials), list(textures)
+        recs = _material_records(materials)
+        tex = _texture_array(textures)
+        op = np.ascontiguousarray([getattr(m, "opacity_texture", 0) for m in materials] or [0], dtype=np.int32) if transparent else None
+        h = _lib.lib().snail_instances_materials_create_dev(isc._h, C.cast(per, C.c_void_p) if len(per_blas) else None, len(per_blas), _lib.ptr(recs) if len(recs) else None,
+                                                            len(recs), _lib.ptr(op), C.cast(tex, C.c_void_p) if len(textures) else None, len(textures), _stream_ptr(stream))
+        if not h:
+            raise _lib.SnailError("snail_instances_materials_create_dev: %s" % _lib.lib().snail_last_error().decode())
+        self._h = C.c_void_p(h)
+        return self
+
+    def _blas_list(self, what, entries, words, stream):
+        """the SnailBlasRebuild list of rebuild_blas_dev / update_blas_dev -> (array, info tensor [k, words], [(b, scene, d_verts, d_nrm)])"""
+        if not getattr(self, "_dynamic", False):
+            raise _lib.SnailError("%s: the set was not made by InstancedMaterialSet.from_dev" % what)
+        torch = _torch()
+        items = list(entries.items())
+        d = self.isc._dev()
+        info = torch.empty((len(items), words), dtype=torch.int32, device=d)
+        if stream is not None:
+            info.record_stream(stream)
+        arr = (_BlasRebuild * max(len(items), 1))()
+        for k, (b, _) in enumerate(items):
+            b = int(b)
+            if not (0 <= b < len(self.isc.blas)) or not getattr(self.isc.blas[b], "_fast_dev", False):
+                raise _lib.SnailError("%s: BLAS %d is out of range, or not a Scene.from_fast_dev BLAS (a BLAS built from host triangles is never rebuilt)" % (what, b))
+            arr[k].blas = b
+            arr[k].d_perm = _addr(self.isc.blas[b].d_perm)
+            arr[k].d_info = info.data_ptr() + k * words * 4
+        return arr, info, items
+
+    def rebuild_blas_dev(self, entries, stream=None):
+        """entries = {b: (d_verts, d_nrm or None)}: rebuild every listed Scene.from_fast_dev BLAS from its new vertices, as Scene.rebuild_fast_dev
+        does, and pack the records of all of them again through the new permutations in one launch on the same stream
+        (snail_instances_materials_rebuild_dev); face normals of d_verts where d_nrm is None.  No host wait.  -> int32 [k, 6] device tensor, a
+        row per entry in the dictionary's order: the build's {status, nNodes, depth, n}, then {records committed (0 / 1), zeroed triangles}.
+        A BLAS whose status is not 0 keeps tree, perm and records.  Each scene's d_perm is written.  The top-level tree is NOT touched: follow
+        with isc.update_dev (or isc.update) before the next frame.  The tensors must stay alive and unchanged until the work has run."""
+        arr, info, items = self._blas_list("rebuild_blas_dev", entries, 6, stream)
+        torch = _torch()
+        for k, (b, (d_verts, d_nrm)) in enumerate(items):
+            sc = self.isc.blas[int(b)]
+            if sc._check_verts(d_verts, sc._dev()) != sc._fast_n:
+                raise ValueError("BLAS %d: d_verts must hold %d triangles" % (int(b), sc._fast_n))
+            P.MaterialSet._check_dev("d_nrm", d_nrm, torch.float32, sc._fast_n * 9, sc._dev(), optional=True)
+            arr[k].d_verts9, arr[k].d_nrm9 = _addr(d_verts), _addr(d_nrm)
+        _lib.check(_lib.lib().snail_instances_materials_rebuild_dev(self._h, C.cast(arr, C.c_void_p) if items else None, len(items), _stream_ptr(stream)),
+                   "snail_instances_materials_rebuild_dev")
+        for k, (b, _) in enumerate(items):
+            sc = self.isc.blas[int(b)]
+            sc.d_info = info[k, :4]
+            sc._stale = True           # .bvh / .perm / .depth are read back when next asked, as after Scene.rebuild_fast_dev
+        return info
+
+    def update_blas_dev(self, entries, stream=None):
+        """entries = {b: (d_nrm or None, d_verts or None)}: pack the records of the listed BLASes again through each scene's d_perm, and nothing
+        else (snail_instances_materials_update_dev): after a BLAS scene was rebuilt by Scene.rebuild_fast_dev or through another set, or for
+        new normals alone.  -> int32 [k, 2] device tensor, rows {1, zeroed triangles}."""
+        arr, info, items = self._blas_list("update_blas_dev", entries, 2, stream)
+        torch = _torch()
+        for k, (b, (d_nrm, d_verts)) in enumerate(items):
+            sc = self.isc.blas[int(b)]
+            P.MaterialSet._check_dev("d_nrm", d_nrm, torch.float32, sc._fast_n * 9, sc._dev(), optional=True)
+            P.MaterialSet._check_dev("d_verts", d_verts, torch.float32, sc._fast_n * 9, sc._dev(), optional=True)
+            arr[k].d_verts9, arr[k].d_nrm9 = _addr(d_verts), _addr(d_nrm)
+        _lib.check(_lib.lib().snail_instances_materials_update_dev(self._h, C.cast(arr, C.c_void_p) if items else None, len(items), _stream_ptr(stream)),
+                   "snail_instances_materials_update_dev")
+        return info
 
     def close(self):
         if getattr(self, "_h", None):
@@ -477,4 +617,4 @@ class InstancedMaterialSet:
         return img, stats, truncated
 
 
-__all__ = ["InstancedMaterialSet", "create_instanced_set"]
+__all__ = ["InstancedMaterialSet", "DevBlasShading", "create_instanced_set"]

@@ -86,7 +86,22 @@ Device events around a window enqueued back to back (--tiles: the host clock, ca
 TreeStats are compared first.  The heat launch runs fewer kernels (no blend, no colour stage) plus four atomics per booking wave.  No ratio is a
 target: a measurement.  --out PATH appends the report (profiles/instances_materials_heat.txt).
 
-    python tools/instances_time.py --materials --heat [--reflections] [--aa] [--tiles] [--counts 64] [--frames 20] [--reps 5] [--baseline-lib PATH] [--out PATH]"""
+    python tools/instances_time.py --materials --heat [--reflections] [--aa] [--tiles] [--counts 64] [--frames 20] [--reps 5] [--baseline-lib PATH] [--out PATH]
+
+--materials --dynamic: what a frame of k DEFORMING BLASes costs under full shading (include/snail_instances_materials_dynamic.h): k bumpy
+sheets of --dyn-tris triangles each (Scene.from_fast_dev), one instance per sheet, one InstancedMaterialSet.from_dev; per frame, ms, median
+(min .. max) over --reps windows of --frames back-to-back steps between two device events:
+  rebuild_batched   rebuild_blas_dev of all k (k fast builds, ONE k_ishd_pack launch)
+  pack_batched      update_blas_dev of all k in one call: the pack alone (one k_ishd_pack + one k_ishd_info launch)
+  pack_single       update_blas_dev k times with one entry each: the pack alone, k times two launches -- what batching is measured against
+  top_level         isc.update_dev, which follows every BLAS rebuild
+  frame             InstancedMaterialSet.render at --res with one light
+  host_route        what a host had to do without the header, on the HOST clock per step: wait for the device, download the k perms,
+                    pack_shtris on the CPU, create a set of host records (over a host-built twin of the same trees: the older creator
+                    refuses a device-built BLAS) and destroy the previous one
+No threshold: a record.  --commit names what was timed; --out PATH writes the report (profiles/instances_materials_dynamic.txt).
+
+    python tools/instances_time.py --materials --dynamic [--dyn-blas 4,16] [--dyn-tris 2048,20000] [--frames 20] [--reps 5] [--commit ID] [--out PATH]"""
 import argparse
 import json
 import os
@@ -137,12 +152,18 @@ def main():
     ap.add_argument("--heat", action="store_true")
     ap.add_argument("--frames", type=int, default=20)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--dynamic", action="store_true")
+    ap.add_argument("--dyn-blas", default="4,16")
+    ap.add_argument("--dyn-tris", default="2048,20000")
+    ap.add_argument("--commit", default=None)
     ap.add_argument("--tree-child", default=None, choices=["new", "old"], help=argparse.SUPPRESS)
     a = ap.parse_args()
     resx, resy = (int(x) for x in a.res.split("x"))
     if a.rebuild_dev:
         return rebuild_dev(torch, [int(c) for c in (a.rebuild_counts or "1024,10000").split(",")], a.reps)
     a.rebuild_counts = a.rebuild_counts or "10000"
+    if a.materials and a.dynamic:
+        return materials_dynamic(torch, a, resx, resy)
     if a.materials and a.heat:
         return materials_heat(torch, a, resx, resy)
     if a.materials and a.tree:
@@ -733,6 +754,136 @@ def materials_heat(torch, a, resx, resy):
     ms.close(); isc.close(); sc.close()
     if not same or not lit_equal:
         raise SystemExit("the heat launch's TreeStats differ from the lit frame's, or the two builds' lit frames differ")
+
+
+def bumpy_sheet(n_tris, phase, amp=0.25):
+    """a g x g grid of quads (2 g^2 >= n_tris triangles, cut to n_tris) over [-1, 1]^2, z a smooth function of the position and the phase"""
+    g = int(np.ceil(np.sqrt(n_tris / 2.0)))
+    u = np.linspace(-1.0, 1.0, g + 1)
+    x, y = np.meshgrid(u, u, indexing="ij")
+    z = amp * np.sin(2.3 * x + phase) * np.cos(1.7 * y - 0.5 * phase)
+    p = np.stack([x, y, z], axis=-1).astype(np.float32)
+    a, b, c, d = p[:-1, :-1], p[1:, :-1], p[1:, 1:], p[:-1, 1:]
+    tris = np.stack([np.stack([a, b, c], axis=2), np.stack([a, c, d], axis=2)], axis=2).reshape(-1, 3, 3)
+    return np.ascontiguousarray(tris[:n_tris], dtype=np.float32)
+
+
+def materials_dynamic(torch, a, resx, resy):
+    import statistics
+    import subprocess
+    import time
+    from snail_amd import materials as P
+    from snail_amd.instances_materials import DevBlasShading, InstancedMaterialSet
+    commit = a.commit
+    if commit is None:
+        try:
+            commit = subprocess.run(["git", "-C", ROOT, "describe", "--always", "--dirty"], capture_output=True, text=True, check=True).stdout.strip()
+        except Exception:
+            commit = "unknown"
+    dv = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to("cuda:0")      # noqa: E731
+    lines = ["instanced full shading of k deforming BLASes (tools/instances_time.py --materials --dynamic), one MI355X, commit %s" % commit,
+             "frame %dx%d, one light; ms per step: median (min .. max) of %d windows of %d back-to-back steps between device events; host_route on the host clock" % (resx, resy, a.reps, a.frames),
+             ""]
+    rows = []
+
+    def window(step):
+        step(); torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        ms = []
+        for _ in range(a.reps):
+            e0.record()
+            for f in range(a.frames):
+                step(f)
+            e1.record()
+            e1.synchronize()
+            ms.append(e0.elapsed_time(e1) / a.frames)
+        return ms
+
+    for n_tris in (int(c) for c in a.dyn_tris.split(",")):
+        for k in (int(c) for c in a.dyn_blas.split(",")):
+            rng = np.random.RandomState(5)
+            tv = [[bumpy_sheet(n_tris, ph + 0.37 * b) for ph in (0.0, 0.9)] for b in range(k)]
+            n = len(tv[0][0])
+            uv = ((rng.rand(n, 1, 2) * 4.0 - 2.0) + (rng.rand(n, 3, 2) - 0.5)).astype(np.float32)
+            mi = ((np.arange(n) // 64) % 6).astype(np.int32)
+            flat = ((np.arange(n) % 3) == 1).astype(np.uint8)
+            ys, xs = np.meshgrid(np.arange(64), np.arange(64), indexing="ij")
+            texs = [P.Texture(np.clip((((xs // 8 + ys // 8) & 1) * 120 + 40)[..., None] + rng.randint(-40, 90, size=(64, 64, 3)), 0, 255).astype(np.uint8))]
+            mats = [P.Material.simple((0.3, 0.8, 0.6), False), P.Material.textured(0, True), P.Material.simple((0.8, 0.3, 0.2), True),
+                    P.Material.uber((0.9, 0.4, 0.1), (0.2, 0.6, 1.0), 0.0), P.Material.uber((0.2, 0.7, 0.5), (1.0, 0.3, 0.1), 1.0)]
+            mmap = [-1, 0, 1, 2, 3, 4]
+            d_tv = [[dv(t) for t in pair] for pair in tv]
+            scs = [Scene.from_fast_dev(d_tv[b][0], 0) for b in range(k)]
+            side = int(np.ceil(np.sqrt(k)))
+            tr = np.array([[2.2 * (b % side), 2.2 * (b // side), 0.0] for b in range(k)], dtype=np.float32)
+            rot = np.stack([np.eye(3, dtype=np.float32)] * k)
+            bi = np.arange(k, dtype=np.int32)
+            isc = InstancedScene(scs, rot, tr, bi)
+            d_uv, d_mi, d_flat = dv(uv), dv(mi), dv(flat)
+            ms_set = InstancedMaterialSet.from_dev(isc, [DevBlasShading(d_uv, d_mi, d_flat, mmap, d_verts=d_tv[b][0]) for b in range(k)], mats, texs)
+            d_xf, d_bi = dv(np.concatenate([rot.reshape(k, 9), tr], axis=1).astype(np.float32)), dv(bi)
+            isc.update_dev(d_xf, d_bi)
+            nd = isc.nodes()[0]
+            cam = survey_camera(np.concatenate([nd["bmin"], nd["bmax"], nd["bmin"]]).reshape(1, 9))
+            c, ext = (nd["bmin"] + nd["bmax"]) * 0.5, nd["bmax"] - nd["bmin"]
+            light = np.array([[c[0], c[1], c[2] - 1.5 * float(np.linalg.norm(ext)), 1.0, 1.0, 1.0, 4.0 * float(np.linalg.norm(ext))]], dtype=np.float32)
+            frame = torch.zeros((resy, resx, 3), dtype=torch.uint8, device="cuda:0")
+            steps = {
+                "rebuild_batched": lambda f=0: ms_set.rebuild_blas_dev({b: (d_tv[b][f & 1], None) for b in range(k)}),
+                "pack_batched": lambda f=0: ms_set.update_blas_dev({b: (None, d_tv[b][1]) for b in range(k)}),
+                "pack_single": lambda f=0: [ms_set.update_blas_dev({b: (None, d_tv[b][1])}) for b in range(k)],
+                "top_level": lambda f=0: isc.update_dev(d_xf, d_bi),
+                "frame": lambda f=0: ms_set.render(cam, resx, resy, light, out=frame),
+            }
+            row = {"k": k, "tris_per_blas": n}
+            for name, step in steps.items():
+                if name == "pack_batched":      # (the packs run on the last pose the rebuilds left: pose index (frames - 1) & 1 = 1 for an even count)
+                    ms_set.rebuild_blas_dev({b: (d_tv[b][1], None) for b in range(k)})
+                ms = window(step)
+                row[name] = (statistics.median(ms), min(ms), max(ms))
+            row["nonblack_pixels"] = int((frame.cpu().numpy() != 0).any(axis=2).sum())
+            # the host route, over a host-built twin of the trees the handle holds now (pose 1)
+            tw = [Scene.from_fast(tv[b][1], 0) for b in range(k)]
+            tisc = InstancedScene(tw, rot, tr, bi)
+            nrm = [np.repeat(np.cross(t[:, 1] - t[:, 0], t[:, 2] - t[:, 0])[:, None, :], 3, axis=1).astype(np.float32) for t in (tv[b][1] for b in range(k))]
+            prev, host = None, []
+            for _ in range(max(a.reps, 3)):
+                t0 = time.perf_counter()
+                torch.cuda.synchronize()
+                perms = [scs[b].d_perm.cpu().numpy() for b in range(k)]
+                sh = [P.pack_shtris(uv, nrm[b], mi, flat, perms[b]) for b in range(k)]
+                new = InstancedMaterialSet.__new__(InstancedMaterialSet)
+                new.isc, new.shtris = tisc, sh
+                from snail_amd.instances_materials import create_instanced_set
+                new._h = create_instanced_set(tisc._h, sh, [mmap] * k, mats, texs)
+                if prev is not None:
+                    prev.close()
+                prev = new
+                host.append((time.perf_counter() - t0) * 1e3)
+            prev.close()
+            row["host_route"] = (statistics.median(host), min(host), max(host))
+            rows.append(row)
+            print(json.dumps({kk: ([round(x, 4) for x in v] if isinstance(v, tuple) else v) for kk, v in row.items()}), file=sys.stderr, flush=True)
+            tisc.close()
+            for s in tw:
+                s.close()
+            ms_set.close(); isc.close()
+            for s in scs:
+                s.close()
+    cols = ["rebuild_batched", "pack_batched", "pack_single", "top_level", "frame", "host_route"]
+    lines.append("%4s %9s  " % ("k", "tris/BLAS") + "  ".join("%-26s" % c for c in cols))
+    for r in rows:
+        lines.append("%4d %9d  " % (r["k"], r["tris_per_blas"]) + "  ".join("%-26s" % ("%.3f (%.3f .. %.3f)" % r[c]) for c in cols))
+    lines.append("")
+    for r in rows:
+        lines.append("k = %d, %d triangles each: k single-entry packs take %.2f x the batched pack (%.3f ms against %.3f ms per frame); the pack is %.1f %% of the "
+                     "batched rebuild; %d non-black pixels in the frame" % (r["k"], r["tris_per_blas"], r["pack_single"][0] / r["pack_batched"][0], r["pack_single"][0],
+                                                                            r["pack_batched"][0], 100.0 * r["pack_batched"][0] / r["rebuild_batched"][0], r["nonblack_pixels"]))
+    text = "\n".join(lines) + "\n"
+    print(text)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(text)
 
 
 def rebuild(torch, sc, counts, reps):
