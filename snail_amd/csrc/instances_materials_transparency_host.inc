@@ -1,9 +1,9 @@
 // instances_materials_transparency_host.inc -- the C-ABI of include/snail_instances_materials_transparency.h: the creator that accepts the kinds which
 // can select a transparent lane (one body with snail_instances_materials_create: imatCreate, instances_materials_host.inc), the query, the launches
 // of instances_materials_transparency.inc on their own (k_imat_sample_transp / _rays) and of the scene-free generator (k_mat_continue / _rays,
-// materials_transparency.inc), and the frames that run them level by level (imatShadeTransp, beside imatShade: way down with
-// k_imat_trace_level, truncation count, way back up with k_mat_blend_transp / k_imat_light_transp / k_mat_colour_transp and the primary
-// k_imat_light / k_mat_final).  These entry points take ANY set (checkIMatAny); the older ones refuse a set that answers the query with 1
+// materials_transparency.inc), and the frames that run them level by level (shadeLevels, materials_levels_host.inc, without the
+// bounce, beside imatShade: way down with k_imat_trace_level, truncation count, way back up with k_mat_blend_transp / k_imat_light_transp /
+// k_mat_colour_transp and the primary k_imat_light / k_mat_final), with IMatLevels, what the level driver asks of an instanced scene.  These entry points take ANY set (checkIMatAny); the older ones refuse a set that answers the query with 1
 // (checkIMat).  Included after instances_materials_bounce_host.inc and materials_transparency_host.inc, whose checkTranspFrameArgs and
 // matAligned16 it calls.
 #include "../../include/snail_instances_materials_transparency.h"
@@ -12,148 +12,98 @@ namespace {
 
 #define SNAIL_ITRANSP_LAUNCH(SSE, GRID, STREAM, A, ...) SNAIL_LAUNCH(SSE, ITranspArgs, GRID, dim3(64), 0, STREAM, A, __VA_ARGS__)
 
-// One level's intermediates: the generic packets and everything of the bounce's part (SnailInstancesMaterials::BounceBufs: rays, mask, hits with
-// instance slot and triId, barycentrics, samples, colour, shadow distances) + opacity, selector and the level's order list.  Level 0 (the primary
-// packets, SnailInstancesMaterials::Bufs) has the last three alone.
-struct ITranspLevel {
-	SnailInstancesMaterials::BounceBufs R;
-	float *opacity = nullptr;
-	unsigned char *sel = nullptr;
-	int32_t *order = nullptr;
-	static size_t extra(size_t np) { return np * 1024 + ((np * 64 + 255) & ~(size_t)255) + ((np * 4 + 255) & ~(size_t)255); }
-	static size_t bytes(size_t np, int nLights) { return ((SnailInstancesMaterials::BounceBufs::bytes(np, nLights) + 255) & ~(size_t)255) + extra(np); }
-	char *carveExtra(char *p, size_t np) {
-		opacity = (float *)p; p += np * 1024;
-		sel = (unsigned char *)p; p += (np * 64 + 255) & ~(size_t)255;
-		order = (int32_t *)p; p += (np * 4 + 255) & ~(size_t)255;
-		return p;
-	}
-	char *carve(char *p, size_t np, int nLights) {
-		R.carve(p, np, nLights);
-		return carveExtra(p + ((SnailInstancesMaterials::BounceBufs::bytes(np, nLights) + 255) & ~(size_t)255), np);
-	}
-};
-size_t imatTranspBytes(size_t np, int nLights, int depth) { return ITranspLevel::extra(np) + (size_t)depth * ITranspLevel::bytes(np, nLights); }
-
-// the stages of one frame with the continuation over the packet list dXY (the handle's mu held); W: level 0, the maxDepth levels carved at `arena`
-int imatShadeTransp(SnailInstancesMaterials *m, const char *fn, const float cam[13], int resx, int resy, const int32_t *dXY, int np, const float *lights7, int nLights,
-					const float ambient[3], uint8_t *frame, int pitch, uint8_t *bgrPackets, const SnailInstancesMaterials::Bufs &W, char *arena, int maxDepth,
-					uint64_t *dTrunc, uint64_t *dStats, hipStream_t st) {
-	SnailInstances *h = m->inst;
+// The instanced scene's kind of the level driver (materials_levels_host.inc); the handle's mu held.  Every launch is booked through
+// instancesBegin / instancesEnd, so the frame is ordered against snail_instances_update and snail_instances_rebuild_dev as a walk is.  The sample
+// and light stages take an ITranspArgs of the kind's own: its MatArgs is the frame's, copied into the scene-free stages' record whenever a level
+// changes it.
+struct IMatLevels : LevelsFrame {
+	typedef SnailInstancesMaterials Handle;
+	typedef SnailInstancesMaterials::Bufs Bufs;
+	typedef SnailInstancesMaterials::BounceBufs BounceBufs;
+	typedef SnailInstancesMaterials::Set Set;
+	SnailInstancesMaterials *m;
+	SnailInstances *h;
 	dev::InstArgs I;
-	bool sse, deep;
-	if(int rc = instancesBegin(h, fn, I, &sse, &deep, st)) return rc;
-	ITranspLevel L[SNAIL_MAT_TRANSP_MAX_DEPTH + 1];
-	char *p = L[0].carveExtra(arena, (size_t)np);
-	for(int k = 1; k <= maxDepth; k++) p = L[k].carve(p, (size_t)np, nLights);
-	const dim3 grid(np), wave(64), lgrid(np, nLights > 0 ? nLights : 1);
-	// primary hits, with their barycentrics
-	dev::InstArgs P = I;
-	P.g = makeGen(cam, resx, resy);
-	P.resx = resx; P.resy = resy;
-	P.packetXY = (const int2 *)dXY; P.nPackets = np;
-	P.t = W.hitT; P.u = W.hitU; P.v = W.hitV; P.instOut = W.hitInst; P.triOut = W.hitTri;
-	P.stats = (dev::u64 *)dStats;
-	if(deep) SNAIL_INST_LAUNCH(sse, grid, st, P, k_inst_frame<true>);
-	else SNAIL_INST_LAUNCH(sse, grid, st, P, k_inst_frame<false>);
-
 	dev::ITranspArgs S;
-	memset(&S, 0, sizeof(S));
-	dev::IMatArgs &A = S.a;
-	imatFillArgs(m, A, I, cam, resx, resy, dXY, np);
-	A.m.s.nLights = nLights;
-	for(int n = 0; n < nLights; n++) for(int k = 0; k < 7; k++) A.m.s.lights[n][k] = lights7[n * 7 + k];
-	for(int c = 0; c < 3; c++) { A.m.s.ambient[c] = ambient[c]; A.m.s.color[c] = 1.0f; }
-	A.m.s.hitT = W.hitT; A.m.s.hitId = W.hitTri; A.m.hitU = W.hitU; A.m.hitV = W.hitV; A.hitInst = W.hitInst;
-	A.m.samples = W.samples; A.m.s.sDist = W.sDist;
-	A.m.s.frame = frame; A.m.s.pitch = pitch; A.m.s.bgrPackets = bgrPackets;
-	A.m.s.stats = (dev::u64 *)dStats;
-	A.m.rUVStride = 8;
-	// the scene-free stages of materials_transparency.inc take a TranspArgs: its MatArgs is the frame's, entered again whenever a level changes it
-	dev::TranspArgs T;
-	memset(&T, 0, sizeof(T));
-	// a level's generic packets as the stages' source; the object of the walk is the instance slot, the sample stages' rObj the triIds
-	auto level = [&](int k, bool slotAsObject) {
-		const SnailInstancesMaterials::BounceBufs &R = L[k].R;
-		A.m.s.rOrg = R.rOrg; A.m.s.rDir = R.rDir; A.m.s.rIDir = R.rIDir; A.m.s.rMask = R.rMask; A.m.s.rDist = R.rDist; A.m.s.rCol = R.rCol;
-		A.m.s.rObj = slotAsObject ? R.rInst : R.rTri;
-		A.m.rU = R.bary; A.m.rV = R.bary + 4;
-		A.m.nSamples = R.nSamples; A.m.nSDist = R.nSDist;
-		S.rInst = R.rInst;
-		S.inOrder = L[k].order;
-		T.m = A.m;
-		T.inOrder = L[k].order;
-	};
-	int rc = 0;
+	IMatLevels(SnailInstancesMaterials *m_, const char *fn_, hipStream_t st_, uint32_t *pstats_, int np_, int nLights) : LevelsFrame(fn_, st_, pstats_, np_, nLights), m(m_), h(m_->inst) {}
+	int begin() { return instancesBegin(h, fn, I, &sse, &deep, st); }
 	// (the stages enqueued so far are booked as every launch of the handle is, whatever failed)
-	auto failed = [&](const char *what, hipError_t e) {
-		(void)instancesEnd(h, st);
-		snail_set_error("%s: %s: %s", fn, what, hipGetErrorString(e));
-		return 100 + (int)e;
-	};
-	// ---- the way down: sample, then per level generator -> ordered walk -> nested sample ----
-	S.opacity = L[0].opacity; S.sel = L[0].sel; S.inOrder = nullptr;
-	SNAIL_ITRANSP_LAUNCH(sse, grid, st, S, k_imat_sample_transp);
-	for(int k = 1; k <= maxDepth; k++) {
-		// generator: from level k - 1 (its rays, hits, selector and own order list) into level k's packets and order list; it zeroes the object
-		// (here: the instance slot)
-		level(k, true);
-		T.order = L[k].order;
-		T.cT = k == 1 ? W.hitT : L[k - 1].R.rDist; T.cSel = L[k - 1].sel;
-		T.inOrder = k == 1 ? nullptr : L[k - 1].order;
-		if(k == 1) { T.cOrg = T.cDir = T.cIDir = nullptr; SNAIL_LAUNCH(sse, TranspArgs, grid, wave, 0, st, T, k_mat_continue); }
-		else {
-			T.cOrg = L[k - 1].R.rOrg; T.cDir = L[k - 1].R.rDir; T.cIDir = L[k - 1].R.rIDir;
-			SNAIL_LAUNCH(sse, TranspArgs, grid, wave, 0, st, T, k_mat_continue_rays);
-		}
+	int end() { return instancesEnd(h, st); }
+	int primary(const float cam[13], int resx, int resy, const int32_t *dXY, const Bufs &W, uint64_t *dStats) {
+		dev::InstArgs P = I;
+		P.g = makeGen(cam, resx, resy);
+		P.resx = resx; P.resy = resy;
+		P.packetXY = (const int2 *)dXY; P.nPackets = np;
+		P.t = W.hitT; P.u = W.hitU; P.v = W.hitV; P.instOut = W.hitInst; P.triOut = W.hitTri;
+		P.stats = (dev::u64 *)dStats;
+		P.pstats = pstats;   // (k_inst_frame books per packet whenever it is given the array)
+		if(deep) SNAIL_INST_LAUNCH(sse, grid, st, P, k_inst_frame<true>);
+		else SNAIL_INST_LAUNCH(sse, grid, st, P, k_inst_frame<false>);
+		return launched("k_inst_frame");
+	}
+	dev::MatArgs &frameArgs(dev::TreeArgs &, const float cam[13], int resx, int resy, const int32_t *dXY, const Bufs &W) {
+		memset(&S, 0, sizeof(S));
+		imatFillArgs(m, S.a, I, cam, resx, resy, dXY, np);
+		S.a.m.s.hitId = W.hitTri; S.a.hitInst = W.hitInst;
+		return S.a.m;
+	}
+	// the object of the walk, of the generator and of the mirror stage is the instance slot, the sample stages' rObj the triIds
+	static int *object(const BounceBufs &R) { return R.rInst; }
+	void level(dev::TreeArgs &G, const BounceBufs &R, const int32_t *order, bool slotAsObject) {
+		S.a.m.s.rObj = slotAsObject ? R.rInst : R.rTri;
+		S.rInst = R.rInst;
+		S.inOrder = order;
+		G.t.m = S.a.m;
+	}
+	int walk(const BounceBufs &R, const int32_t *order, uint64_t *dStats) {
 		// the walk leaves element and barycentrics of a lane without a hit as it found them: zeros, not what the buffers last held (rTri and bary
 		// are neighbours: ONE memset, as imatNested's)
-		const hipError_t e = hipMemsetAsync(L[k].R.rTri, 0, (size_t)np * 256 * 12, st);
-		if(e != hipSuccess) return failed("clearing a level's hit records failed", e);
+		const hipError_t e = hipMemsetAsync(R.rTri, 0, (size_t)np * 256 * 12, st);
+		if(e != hipSuccess) return failed("clearing a level's hit records", e);
 		dev::ILevelArgs V;
 		memset(&V, 0, sizeof(V));
 		V.i = I;
 		V.i.nPackets = np; V.i.size = 64;
-		V.i.origin = L[k].R.rOrg; V.i.dir = L[k].R.rDir; V.i.idir = L[k].R.rIDir; V.i.mask = L[k].R.rMask;
-		V.i.distance = L[k].R.rDist; V.i.object = L[k].R.rInst; V.i.element = L[k].R.rTri; V.i.bary = L[k].R.bary;
+		V.i.origin = R.rOrg; V.i.dir = R.rDir; V.i.idir = R.rIDir; V.i.mask = R.rMask;
+		V.i.distance = R.rDist; V.i.object = R.rInst; V.i.element = R.rTri; V.i.bary = R.bary;
 		V.i.stats = (dev::u64 *)dStats;
-		V.order = L[k].order;
-		if(deep) SNAIL_LAUNCH(sse, ILevelArgs, grid, wave, 0, st, V, k_imat_trace_level<true>);
-		else SNAIL_LAUNCH(sse, ILevelArgs, grid, wave, 0, st, V, k_imat_trace_level<false>);
-		level(k, false);
-		S.opacity = L[k].opacity; S.sel = L[k].sel;
+		V.i.pstats = pstats;
+		V.order = order;
+		SNAIL_LEVELS_LAUNCH_DEEP(ILevelArgs, grid, V, k_imat_trace_level);
+		return launched("k_imat_trace_level");
+	}
+	int samplePrimary(dev::TreeArgs &, float *opacity, unsigned char *sel) {
+		S.opacity = opacity; S.sel = sel;
+		SNAIL_ITRANSP_LAUNCH(sse, grid, st, S, k_imat_sample_transp);
+		return launched("k_imat_sample_transp");
+	}
+	int sampleRays(dev::TreeArgs &, float *opacity, unsigned char *sel) {
+		S.opacity = opacity; S.sel = sel;
 		SNAIL_ITRANSP_LAUNCH(sse, grid, st, S, k_imat_sample_transp_rays);
+		return launched("k_imat_sample_transp_rays");
 	}
-	// the lanes the deepest level would still select: counted, then treated as not selected
-	level(maxDepth, false);
-	T.bSel = L[maxDepth].sel; T.trunc = (unsigned long long *)dTrunc;
-	SNAIL_LAUNCH(sse, TranspArgs, grid, wave, 0, st, T, k_mat_truncated);
-	// ---- the way back up: per level (blend from the deeper level,) nested lights, nested colour; then the primary blend, lights and store ----
-	for(int k = maxDepth; k >= 1; k--) {
-		level(k, false);
-		if(k < maxDepth) {
-			T.bSamples = L[k].R.nSamples; T.bOpacity = L[k].opacity; T.bSel = L[k].sel; T.bCol = L[k + 1].R.rCol;
-			SNAIL_LAUNCH(sse, TranspArgs, grid, wave, 0, st, T, k_mat_blend_transp);
-		}
-		if(nLights) {
-			if(deep) SNAIL_ITRANSP_LAUNCH(sse, lgrid, st, S, k_imat_light_transp<true>);
-			else SNAIL_ITRANSP_LAUNCH(sse, lgrid, st, S, k_imat_light_transp<false>);
-		}
-		SNAIL_LAUNCH(sse, TranspArgs, grid, wave, 0, st, T, k_mat_colour_transp);
+	int lightsBegin(dev::MatArgs &, int) { return 0; }   // (the instanced lights walk the BLASes' own records: no origin-relative copy is taken)
+	int nestedLights(dev::TreeArgs &) {
+		SNAIL_LEVELS_LAUNCH_DEEP(ITranspArgs, lgrid, S, k_imat_light_transp);
+		return launched("k_imat_light_transp");
 	}
-	T.inOrder = nullptr;
-	T.bSamples = W.samples; T.bOpacity = L[0].opacity; T.bSel = L[0].sel; T.bCol = L[1].R.rCol;
-	SNAIL_LAUNCH(sse, TranspArgs, grid, wave, 0, st, T, k_mat_blend_transp);
-	if(nLights) {
-		if(deep) SNAIL_IMAT_LAUNCH(sse, lgrid, st, A, k_imat_light<true>);
-		else SNAIL_IMAT_LAUNCH(sse, lgrid, st, A, k_imat_light<false>);
+	int lights(dev::TreeArgs &) {
+		SNAIL_LEVELS_LAUNCH_DEEP(IMatArgs, lgrid, S.a, k_imat_light);
+		return launched("k_imat_light");
 	}
-	SNAIL_LAUNCH(sse, MatArgs, grid, wave, 0, st, A.m, k_mat_final);
-	const hipError_t le = hipGetLastError();
-	rc = instancesEnd(h, st);
-	if(le != hipSuccess) { snail_set_error("%s: a stage's launch failed: %s", fn, hipGetErrorString(le)); return 100 + (int)le; }
-	return rc;
-}
+	// the handle's part of levelsStore and of the host calls
+	static int nextSet(SnailInstancesMaterials *m, int np, int nLights, hipStream_t st, Set **out) { return imatNextSet(m, np, nLights, false, st, out); }
+	static int setDone(Set &W, const char *fn, int rc, hipStream_t st) { return imatSetDone(W, fn, rc, st); }
+	// (the hit distances of k_inst_frame alone)
+	static int depthStore(SnailInstancesMaterials *m, const char *fn, const float cam[13], int resx, int resy, const int32_t *dXY, int np, const float *, int,
+						  const float ambient[3], int flags, const float *tint, uint8_t *bgrPackets, const InstTileJob *J, uint64_t *dStats, hipStream_t st) {
+		const float white[3] = {1.0f, 1.0f, 1.0f};
+		return instancesShadeStore(m->inst, fn, cam, resx, resy, dXY, np, nullptr, 0, ambient, white, flags & (SNAIL_RENDER_DEPTH | SNAIL_RENDER_AA4), tint, bgrPackets, J, dStats, st);
+	}
+	static SnailScene *scene(SnailInstancesMaterials *m) { return m->inst->blas[0]; }   // (the arithmetic and its tables are the BLAS scenes'; it lends a host call its free list)
+	static std::mutex &mu(SnailInstancesMaterials *m) { return m->inst->mu; }
+	static int frameList(SnailInstancesMaterials *m, int resx, int resy, const int32_t **dXY, int *np) { return imatFrameList(m, resx, resy, dXY, np); }
+};
 
 // _dev / _packets_dev (the handle's mu held): the next group of intermediates with its levels' part, grown if need be
 int imatTranspDev(SnailInstancesMaterials *m, const char *fn, const float cam[13], int resx, int resy, const int32_t *dXY, int np, const float *lights7, int nLights,
@@ -162,17 +112,11 @@ int imatTranspDev(SnailInstancesMaterials *m, const char *fn, const float cam[13
 	SnailInstancesMaterials::Set *Wp = nullptr;
 	if(int rc = imatNextSet(m, np, nLights, false, st, &Wp)) return rc;
 	SnailInstancesMaterials::Set &W = *Wp;
-	const size_t want = imatTranspBytes((size_t)np, nLights, maxDepth);
-	if(!W.transp || W.transpBytes < want) {   // grown: its previous user may still be running
-		HIP_TRY(hipDeviceSynchronize());
-		if(W.transp) (void)hipFree(W.transp);
-		W.transp = nullptr; W.transpBytes = 0; W.used = false;
-		HIP_TRY(hipMalloc((void **)&W.transp, want));
-		W.transpBytes = want;
-	}
+	const size_t want = levelsBytes<SnailInstancesMaterials::BounceBufs>((size_t)np, nLights, maxDepth, false);
+	if(int rc = levelsGrow(W, W.transp, W.transpBytes, want, want)) return rc;
 	SnailInstancesMaterials::Bufs B;
 	B.carve(W.base, (size_t)np);
-	const int rc = imatShadeTransp(m, fn, cam, resx, resy, dXY, np, lights7, nLights, ambient, frame, pitch, bgrPackets, B, W.transp, maxDepth, dTrunc, dStats, st);
+	const int rc = shadeLevels<IMatLevels>(m, fn, cam, resx, resy, dXY, np, lights7, nLights, ambient, frame, pitch, bgrPackets, nullptr, B, W.transp, maxDepth, false, dTrunc, dStats, st);
 	return imatSetDone(W, fn, rc, st);
 }
 
@@ -337,7 +281,7 @@ int snail_instances_materials_transparent_image(SnailInstancesMaterials *m, cons
 		for(int x = 0; x < pw; x++) { xy[((size_t)y * pw + x) * 2] = x * 16; xy[((size_t)y * pw + x) * 2 + 1] = y * 16; }
 	typedef HostCallScope H;
 	const size_t imgBytes = (size_t)pitch * resy, bufBytes = SnailInstancesMaterials::Bufs::bytes((size_t)np, nLights),
-				 levelBytes = imatTranspBytes((size_t)np, nLights, maxDepth);
+				 levelBytes = levelsBytes<SnailInstancesMaterials::BounceBufs>((size_t)np, nLights, maxDepth, false);
 	if(int rc = hc.reserve(H::pad(xy.size() * 4) + H::pad(bufBytes) + H::pad(levelBytes) + H::pad(imgBytes + 4) + H::pad(8))) return rc;
 	void *dXY = nullptr;
 	if(int rc = hc.put(&dXY, xy.data(), xy.size() * 4)) return rc;
@@ -349,7 +293,8 @@ int snail_instances_materials_transparent_image(SnailInstancesMaterials *m, cons
 	HIP_TRY(hipMemsetAsync(dTrunc, 0, 8, hc.stream()));
 	{
 		std::lock_guard<std::mutex> lock(h->mu);
-		if(int rc = imatShadeTransp(m, fn, cam, resx, resy, (const int32_t *)dXY, np, lights7, nLights, ambient, dImg, pitch, nullptr, W, arena, maxDepth, dTrunc, hc.stats(), hc.stream()))
+		if(int rc = shadeLevels<IMatLevels>(m, fn, cam, resx, resy, (const int32_t *)dXY, np, lights7, nLights, ambient, dImg, pitch, nullptr, nullptr, W, arena, maxDepth, false, dTrunc,
+											hc.stats(), hc.stream()))
 			return rc;
 	}
 	HIP_TRY(hipMemcpy2DAsync(image, (size_t)pitch, dImg, (size_t)pitch, (size_t)resx * 3, (size_t)resy, hipMemcpyDeviceToHost, hc.stream()));

@@ -1,9 +1,9 @@
 // materials_transparency_host.inc -- the C-ABI of include/snail_materials_transparency.h: the creator that accepts the kinds which can select a
 // transparent lane (one body with snail_materials_create: matCreate, materials_host.inc), the query, and the launches of
-// materials_transparency.inc (k_mat_sample_transp / _rays, k_mat_continue / _rays), and the frames that run them level by level (matShadeTransp:
-// way down, truncation count, way back up with k_mat_blend_transp / k_mat_light_transp / k_mat_colour_transp and the primary k_mat_light /
-// k_mat_final).  These entry points take ANY set (checkMaterialsAny); the older ones refuse a set that answers the query with 1 (checkMaterials).
-// BUILD NOTE: the Makefile's source list does not name this file; after editing it alone, touch materials_host.inc (or make clean).
+// materials_transparency.inc (k_mat_sample_transp / _rays, k_mat_continue / _rays), and the frames that run them level by level (shadeLevels,
+// materials_levels_host.inc, without the bounce: way down, truncation count, way back up with k_mat_blend_transp / k_mat_light_transp /
+// k_mat_colour_transp and the primary k_mat_light / k_mat_final), with MatLevels, what the level driver asks of a plain scene.
+// These entry points take ANY set (checkMaterialsAny); the older ones refuse a set that answers the query with 1 (checkMaterials).
 #include "../../include/snail_materials_transparency.h"
 
 namespace {
@@ -13,30 +13,6 @@ bool matAligned16(std::initializer_list<const void *> ps) {
 	for(const void *p : ps) a |= (unsigned long long)p;
 	return (a & 15) == 0;
 }
-
-// ---- frames: the levels of the transparency continuation -----------------------------------------------------------------------------------
-// One level's intermediates: the generic packets and everything of the bounce's part (BounceBufs: rays, mask, hits, barycentrics, samples,
-// colour, shadow distances) + opacity, selector and the level's order list.  Level 0 (the primary packets, SnailMaterials::Bufs) has the
-// last three alone.
-struct TranspLevel {
-	SnailMaterials::BounceBufs R;
-	float *opacity = nullptr;
-	unsigned char *sel = nullptr;
-	int32_t *order = nullptr;
-	static size_t extra(size_t np) { return np * 1024 + ((np * 64 + 255) & ~(size_t)255) + ((np * 4 + 255) & ~(size_t)255); }
-	static size_t bytes(size_t np, int nLights) { return ((SnailMaterials::BounceBufs::bytes(np, nLights) + 255) & ~(size_t)255) + extra(np); }
-	char *carveExtra(char *p, size_t np) {
-		opacity = (float *)p; p += np * 1024;
-		sel = (unsigned char *)p; p += (np * 64 + 255) & ~(size_t)255;
-		order = (int32_t *)p; p += (np * 4 + 255) & ~(size_t)255;
-		return p;
-	}
-	char *carve(char *p, size_t np, int nLights) {
-		R.carve(p, np, nLights);
-		return carveExtra(p + ((SnailMaterials::BounceBufs::bytes(np, nLights) + 255) & ~(size_t)255), np);
-	}
-};
-size_t transpBytes(size_t np, int nLights, int depth) { return TranspLevel::extra(np) + (size_t)depth * TranspLevel::bytes(np, nLights); }
 
 int checkTranspFrameArgs(const char *fn, const float cam[13], int resx, int resy, const float *lights7, int nLights, const float ambient[3], int flags, int maxDepth,
 						 const uint64_t *trunc) {
@@ -49,113 +25,84 @@ int checkTranspFrameArgs(const char *fn, const float cam[13], int resx, int resy
 	return checkMatFrameArgs(fn, cam, resx, resy, lights7, nLights, ambient, 0);
 }
 
-// the stages of one frame with the continuation over the packet list dXY (the scene's mu held); W: level 0, `levels`: maxDepth levels carved at `arena`
-int matShadeTransp(SnailMaterials *m, const char *fn, const float cam[13], int resx, int resy, const int32_t *dXY, int np, const float *lights7, int nLights,
-				   const float ambient[3], uint8_t *frame, int pitch, uint8_t *bgrPackets, const SnailMaterials::Bufs &W, char *arena, int maxDepth, uint64_t *dTrunc,
-				   uint64_t *dStats, hipStream_t st) {
-	SnailScene *s = m->scene;
-	SceneUse use(s, st);
-	if(use.rc) return use.rc;
-	TranspLevel L[SNAIL_MAT_TRANSP_MAX_DEPTH + 1];
-	char *p = L[0].carveExtra(arena, (size_t)np);
-	for(int k = 1; k <= maxDepth; k++) p = L[k].carve(p, (size_t)np, nLights);
-	if(int rc = launchPrimary(s, cam, resx, resy, 0, 0, 0, 0, dXY, np, W.hitT, W.hitU, W.hitV, W.hitId, dStats, st)) return rc;
-	dev::TranspArgs T;
-	memset(&T, 0, sizeof(T));
-	dev::MatArgs &A = T.m;
-	matFillArgs(m, A, cam, resx, resy, dXY, np);
-	A.s.nLights = nLights;
-	for(int n = 0; n < nLights; n++) for(int k = 0; k < 7; k++) A.s.lights[n][k] = lights7[n * 7 + k];
-	for(int c = 0; c < 3; c++) { A.s.ambient[c] = ambient[c]; A.s.color[c] = 1.0f; }
-	A.s.hitT = W.hitT; A.s.hitId = W.hitId; A.hitU = W.hitU; A.hitV = W.hitV;
-	A.samples = W.samples; A.s.sDist = W.sDist;
-	A.s.frame = frame; A.s.pitch = pitch; A.s.bgrPackets = bgrPackets;
-	A.s.stats = (dev::u64 *)dStats;
-	A.rUVStride = 8;
-	const bool sse = s->arith == SNAIL_ARITH_HOST_SSE;
-	const dim3 grid(np), wave(64);
-	// a level's generic packets as the stages' source
-	auto level = [&](int k) {
-		const SnailMaterials::BounceBufs &R = L[k].R;
-		A.s.rOrg = R.rOrg; A.s.rDir = R.rDir; A.s.rIDir = R.rIDir; A.s.rMask = R.rMask; A.s.rDist = R.rDist; A.s.rObj = R.rObj; A.s.rCol = R.rCol;
-		A.rU = R.bary; A.rV = R.bary + 4;
-		A.nSamples = R.nSamples; A.nSDist = R.nSDist;
-		T.inOrder = L[k].order;
-	};
-	// ---- the way down: sample, then per level generator -> ordered walk -> nested sample ----
-	T.opacity = L[0].opacity; T.sel = L[0].sel; T.inOrder = nullptr;
-	SNAIL_LAUNCH(sse, TranspArgs, grid, wave, 0, st, T, k_mat_sample_transp);
-	HIP_TRY(hipGetLastError());
-	for(int k = 1; k <= maxDepth; k++) {
-		// generator: from level k - 1 (its rays, hits, selector and own order list) into level k's packets and order list
-		level(k);
-		T.order = L[k].order;
-		T.cT = k == 1 ? W.hitT : L[k - 1].R.rDist; T.cSel = L[k - 1].sel;
-		T.inOrder = k == 1 ? nullptr : L[k - 1].order;
-		if(k == 1) { T.cOrg = T.cDir = T.cIDir = nullptr; SNAIL_LAUNCH(sse, TranspArgs, grid, wave, 0, st, T, k_mat_continue); }
-		else {
-			T.cOrg = L[k - 1].R.rOrg; T.cDir = L[k - 1].R.rDir; T.cIDir = L[k - 1].R.rIDir;
-			SNAIL_LAUNCH(sse, TranspArgs, grid, wave, 0, st, T, k_mat_continue_rays);
-		}
-		HIP_TRY(hipGetLastError());
+// The plain scene's kind of the level driver (materials_levels_host.inc); the scene's mu held.  The scene-free stages' TreeArgs is the only
+// argument record: its MatArgs is the frame's, and the sample and light stages take its TranspArgs.
+struct MatLevels : LevelsFrame {
+	typedef SnailMaterials Handle;
+	typedef SnailMaterials::Bufs Bufs;
+	typedef SnailMaterials::BounceBufs BounceBufs;
+	typedef SnailMaterials::Set Set;
+	SnailMaterials *m;
+	SnailScene *s;
+	SceneUse use;
+	int relWhich[SNAIL_MAX_LIGHTS];   // the origin-relative copies taken by lightsBegin
+	MatLevels(SnailMaterials *m_, const char *fn_, hipStream_t st_, uint32_t *pstats_, int np_, int nLights) : LevelsFrame(fn_, st_, pstats_, np_, nLights), m(m_), s(m_->scene), use(s, st_) {
+		for(int n = 0; n < SNAIL_MAX_LIGHTS; n++) relWhich[n] = -1;
+	}
+	int begin() {
+		sse = s->arith == SNAIL_ARITH_HOST_SSE; deep = useDeep(s);
+		return use.rc;
+	}
+	// every origin-relative copy taken is booked as used on st on EVERY way out, first error kept (matShade's rule)
+	int end() {
+		int rc = 0;
+		for(int n = 0; n < SNAIL_MAX_LIGHTS; n++)
+			if(relWhich[n] >= 0) { const int urc = relUsed(s, relWhich[n], st); if(!rc) rc = urc; }
+		return rc;
+	}
+	int primary(const float cam[13], int resx, int resy, const int32_t *dXY, const Bufs &W, uint64_t *dStats) {
+		return launchPrimary(s, cam, resx, resy, 0, 0, 0, 0, dXY, np, W.hitT, W.hitU, W.hitV, W.hitId, dStats, st, nullptr, false, nullptr, nullptr, nullptr, nullptr, 0, pstats);
+	}
+	dev::MatArgs &frameArgs(dev::TreeArgs &G, const float cam[13], int resx, int resy, const int32_t *dXY, const Bufs &W) {
+		dev::MatArgs &A = G.t.m;
+		matFillArgs(m, A, cam, resx, resy, dXY, np);
+		A.s.hitId = W.hitId;
+		return A;
+	}
+	static int *object(const BounceBufs &R) { return R.rObj; }
+	void level(dev::TreeArgs &G, const BounceBufs &R, const int32_t *, bool) { G.t.m.s.rObj = R.rObj; }
+	int walk(const BounceBufs &R, const int32_t *order, uint64_t *dStats) {
 		// the walk reads the barycentrics it was given and writes them back for lanes without a hit: zeros, not what the buffer last held
-		HIP_TRY(hipMemsetAsync(L[k].R.bary, 0, (size_t)np * 256 * 8, st));
-		if(int rc = launchRays(s, false, np, 64, 0, L[k].R.rOrg, L[k].R.rDir, L[k].R.rIDir, L[k].R.rMask, L[k].R.rDist, L[k].R.rObj, L[k].R.bary, dStats, st, L[k].order, nullptr, np))
-			return rc;
-		level(k);
-		T.opacity = L[k].opacity; T.sel = L[k].sel;
-		SNAIL_LAUNCH(sse, TranspArgs, grid, wave, 0, st, T, k_mat_sample_transp_rays);
-		HIP_TRY(hipGetLastError());
+		const hipError_t e = hipMemsetAsync(R.bary, 0, (size_t)np * 256 * 8, st);
+		if(e != hipSuccess) return failed("hipMemsetAsync", e);
+		return launchRays(s, false, np, 64, 0, R.rOrg, R.rDir, R.rIDir, R.rMask, R.rDist, R.rObj, R.bary, dStats, st, order, nullptr, order ? np : 0, nullptr, 0, pstats);
 	}
-	// the lanes the deepest level would still select: counted, then treated as not selected
-	level(maxDepth);
-	T.bSel = L[maxDepth].sel; T.trunc = (unsigned long long *)dTrunc;
-	SNAIL_LAUNCH(sse, TranspArgs, grid, wave, 0, st, T, k_mat_truncated);
-	HIP_TRY(hipGetLastError());
-	// ---- the way back up: per level (blend from the deeper level,) nested lights, nested colour; then the primary blend, lights and store ----
-	int relWhich[SNAIL_MAX_LIGHTS];
-	for(int n = 0; n < SNAIL_MAX_LIGHTS; n++) { relWhich[n] = -1; A.s.relLight[n] = nullptr; }
-	int lrc = 0;
-	// (every origin-relative copy taken here is booked as used on st on EVERY way out, first error kept: matShade's rule)
-	if(nLights && A.s.pack && !useDeep(s))
-		for(int n = 0; n < nLights && !lrc; n++) lrc = relFor(s, A.s.lights[n], st, &A.s.relLight[n], &relWhich[n]);
-	const dim3 lgrid(np, nLights > 0 ? nLights : 1);
-	auto launched = [&](const char *what) {
-		const hipError_t e = hipGetLastError();
-		if(e != hipSuccess && !lrc) { snail_set_error("%s: %s: %s", fn, what, hipGetErrorString(e)); lrc = 100 + (int)e; }
-	};
-	for(int k = maxDepth; k >= 1 && !lrc; k--) {
-		level(k);
-		if(k < maxDepth) {
-			T.bSamples = L[k].R.nSamples; T.bOpacity = L[k].opacity; T.bSel = L[k].sel; T.bCol = L[k + 1].R.rCol;
-			SNAIL_LAUNCH(sse, TranspArgs, grid, wave, 0, st, T, k_mat_blend_transp);
-			launched("k_mat_blend_transp");
-		}
-		if(nLights && !lrc) {
-			if(useDeep(s)) SNAIL_LAUNCH(sse, TranspArgs, lgrid, wave, 0, st, T, k_mat_light_transp<true>);
-			else SNAIL_LAUNCH(sse, TranspArgs, lgrid, wave, 0, st, T, k_mat_light_transp<false>);
-			launched("k_mat_light_transp");
-		}
-		if(!lrc) { SNAIL_LAUNCH(sse, TranspArgs, grid, wave, 0, st, T, k_mat_colour_transp); launched("k_mat_colour_transp"); }
+	int samplePrimary(dev::TreeArgs &G, float *opacity, unsigned char *sel) {
+		G.t.opacity = opacity; G.t.sel = sel;
+		SNAIL_LAUNCH(sse, TranspArgs, grid, dim3(64), 0, st, G.t, k_mat_sample_transp);
+		return launched("k_mat_sample_transp");
 	}
-	if(!lrc) {
-		T.inOrder = nullptr;
-		T.bSamples = W.samples; T.bOpacity = L[0].opacity; T.bSel = L[0].sel; T.bCol = L[1].R.rCol;
-		SNAIL_LAUNCH(sse, TranspArgs, grid, wave, 0, st, T, k_mat_blend_transp);
-		launched("k_mat_blend_transp");
+	int sampleRays(dev::TreeArgs &G, float *opacity, unsigned char *sel) {
+		G.t.opacity = opacity; G.t.sel = sel;
+		SNAIL_LAUNCH(sse, TranspArgs, grid, dim3(64), 0, st, G.t, k_mat_sample_transp_rays);
+		return launched("k_mat_sample_transp_rays");
 	}
-	if(nLights && !lrc) {
-		if(useDeep(s)) SNAIL_LAUNCH(sse, MatArgs, lgrid, wave, 0, st, A, k_mat_light<true>);
-		else SNAIL_LAUNCH(sse, MatArgs, lgrid, wave, 0, st, A, k_mat_light<false>);
-		launched("k_mat_light");
+	// (the lights of every level of both chains walk from the same origins: the same copies)
+	int lightsBegin(dev::MatArgs &A, int nLights) {
+		int rc = 0;
+		if(nLights && A.s.pack && !deep)
+			for(int n = 0; n < nLights && !rc; n++) rc = relFor(s, A.s.lights[n], st, &A.s.relLight[n], &relWhich[n]);
+		return rc;
 	}
-	for(int n = 0; n < nLights; n++)
-		if(relWhich[n] >= 0) { const int urc = relUsed(s, relWhich[n], st); if(!lrc) lrc = urc; }
-	if(lrc) return lrc;
-	SNAIL_LAUNCH(sse, MatArgs, grid, wave, 0, st, A, k_mat_final);
-	HIP_TRY(hipGetLastError());
-	return 0;
-}
+	int nestedLights(dev::TreeArgs &G) {
+		SNAIL_LEVELS_LAUNCH_DEEP(TranspArgs, lgrid, G.t, k_mat_light_transp);
+		return launched("k_mat_light_transp");
+	}
+	int lights(dev::TreeArgs &G) {
+		SNAIL_LEVELS_LAUNCH_DEEP(MatArgs, lgrid, G.t.m, k_mat_light);
+		return launched("k_mat_light");
+	}
+	// the handle's part of levelsStore and of the host calls
+	static int nextSet(SnailMaterials *m, int np, int nLights, hipStream_t st, Set **out) { return matNextSet(m, np, nLights, false, false, st, out); }
+	static int setDone(Set &W, const char *fn, int rc, hipStream_t st) { return matSetDone(W, fn, rc, st); }
+	static int depthStore(SnailMaterials *m, const char *fn, const float cam[13], int resx, int resy, const int32_t *dXY, int np, const float *lights7, int nLights,
+						  const float ambient[3], int flags, const float *tint, uint8_t *bgrPackets, const InstTileJob *J, uint64_t *dStats, hipStream_t st) {
+		return matShadeStore(m, fn, cam, resx, resy, dXY, np, lights7, nLights, ambient, flags, tint, bgrPackets, J, dStats, st);
+	}
+	static SnailScene *scene(SnailMaterials *m) { return m->scene; }
+	static std::mutex &mu(SnailMaterials *m) { return m->scene->mu; }
+	static int frameList(SnailMaterials *m, int resx, int resy, const int32_t **dXY, int *np) { return matFrameList(m, resx, resy, dXY, np); }
+};
 
 // _dev / _packets_dev (the scene's mu held): the next group of intermediates with its fourth part, grown if need be
 int matTranspDev(SnailMaterials *m, const char *fn, const float cam[13], int resx, int resy, const int32_t *dXY, int np, const float *lights7, int nLights,
@@ -164,17 +111,11 @@ int matTranspDev(SnailMaterials *m, const char *fn, const float cam[13], int res
 	SnailMaterials::Set *Wp = nullptr;
 	if(int rc = matNextSet(m, np, nLights, false, false, st, &Wp)) return rc;
 	SnailMaterials::Set &W = *Wp;
-	const size_t want = transpBytes((size_t)np, nLights, maxDepth);
-	if(!W.transp || W.transpBytes < want) {   // grown: its previous user may still be running
-		HIP_TRY(hipDeviceSynchronize());
-		if(W.transp) (void)hipFree(W.transp);
-		W.transp = nullptr; W.transpBytes = 0; W.used = false;
-		HIP_TRY(hipMalloc((void **)&W.transp, want));
-		W.transpBytes = want;
-	}
+	const size_t want = levelsBytes<SnailMaterials::BounceBufs>((size_t)np, nLights, maxDepth, false);
+	if(int rc = levelsGrow(W, W.transp, W.transpBytes, want, want)) return rc;
 	SnailMaterials::Bufs B;
 	B.carve(W.base, (size_t)np);
-	const int rc = matShadeTransp(m, fn, cam, resx, resy, dXY, np, lights7, nLights, ambient, frame, pitch, bgrPackets, B, W.transp, maxDepth, dTrunc, dStats, st);
+	const int rc = shadeLevels<MatLevels>(m, fn, cam, resx, resy, dXY, np, lights7, nLights, ambient, frame, pitch, bgrPackets, nullptr, B, W.transp, maxDepth, false, dTrunc, dStats, st);
 	return matSetDone(W, fn, rc, st);
 }
 
@@ -313,7 +254,8 @@ int snail_materials_transparent_image(SnailMaterials *m, const float cam[13], in
 	for(int y = 0; y < ph; y++)
 		for(int x = 0; x < pw; x++) { xy[((size_t)y * pw + x) * 2] = x * 16; xy[((size_t)y * pw + x) * 2 + 1] = y * 16; }
 	typedef HostCallScope H;
-	const size_t imgBytes = (size_t)pitch * resy, bufBytes = SnailMaterials::Bufs::bytes((size_t)np, nLights), levelBytes = transpBytes((size_t)np, nLights, maxDepth);
+	const size_t imgBytes = (size_t)pitch * resy, bufBytes = SnailMaterials::Bufs::bytes((size_t)np, nLights),
+				 levelBytes = levelsBytes<SnailMaterials::BounceBufs>((size_t)np, nLights, maxDepth, false);
 	if(int rc = hc.reserve(H::pad(xy.size() * 4) + H::pad(bufBytes) + H::pad(levelBytes) + H::pad(imgBytes + 4) + H::pad(8))) return rc;
 	void *dXY = nullptr;
 	if(int rc = hc.put(&dXY, xy.data(), xy.size() * 4)) return rc;
@@ -325,7 +267,8 @@ int snail_materials_transparent_image(SnailMaterials *m, const float cam[13], in
 	HIP_TRY(hipMemsetAsync(dTrunc, 0, 8, hc.stream()));
 	{
 		SNAIL_LOCK(m->scene);
-		if(int rc = matShadeTransp(m, fn, cam, resx, resy, (const int32_t *)dXY, np, lights7, nLights, ambient, dImg, pitch, nullptr, W, arena, maxDepth, dTrunc, hc.stats(), hc.stream()))
+		if(int rc = shadeLevels<MatLevels>(m, fn, cam, resx, resy, (const int32_t *)dXY, np, lights7, nLights, ambient, dImg, pitch, nullptr, nullptr, W, arena, maxDepth, false, dTrunc,
+										   hc.stats(), hc.stream()))
 			return rc;
 	}
 	HIP_TRY(hipMemcpy2DAsync(image, (size_t)pitch, dImg, (size_t)pitch, (size_t)resx * 3, (size_t)resy, hipMemcpyDeviceToHost, hc.stream()));

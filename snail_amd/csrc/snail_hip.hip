@@ -1821,6 +1821,7 @@ int snail_account_primary(SnailScene *s, const float cam[13], int resx, int resy
 #include "heatmap_host.inc"
 #include "materials_host.inc"
 #include "materials_tiles_host.inc"
+#include "materials_levels_host.inc"
 #include "materials_transparency_host.inc"
 #include "materials_tree_host.inc"
 #include "materials_heat_host.inc"
