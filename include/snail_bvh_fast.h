@@ -53,7 +53,8 @@ SnailScene *snail_scene_create_fast_dev(const float *d_verts9, int nTris, int de
  *   status 3 when the handle was created with records the fast arithmetic paths accept (snail_scene_flags: fastOK) and a rebuilt record
  *            is outside their range (a zero-area triangle, a coordinate beyond 1e9).  A handle created without fastOK takes any finite mesh.
  * A SnailInstances handle records its BLAS root boxes at creation: a BLAS rebuilt under live instances needs
- * snail_instances_rebuild_dev afterwards (instanced launches themselves are ordered against the BLAS rebuild like any other launch). */
+ * snail_instances_rebuild_dev afterwards (instanced launches themselves are ordered against the BLAS rebuild like any other launch).
+ * Several handles in one batched pass, with these semantics per handle: snail_scenes_rebuild_fast_dev (snail_bvh_fast_batch.h). */
 int snail_scene_rebuild_fast_dev(SnailScene *, const float *d_verts9, int nTris, int32_t *d_perm, int32_t *d_info, void *stream);
 
 #ifdef __cplusplus

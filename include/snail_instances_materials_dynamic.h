@@ -32,7 +32,7 @@
  * Conventions are those of snail_hip.h: 0 = success, otherwise snail_last_error() holds the message and nothing was enqueued -- except that
  * a HIP error in the middle of a list leaves the BLASes rebuilt before it stale (an _update_dev brings them back).
  * NOT here: a snail::HipDBVH route in snail_adapter.hpp (no reference host reaches the branch); changing uv or the material assignment after
- * creation; one call that rebuilds BLASes and the top-level tree.
+ * creation.  The one call that rebuilds BLASes and the top-level tree is snail_instances_materials_rebuild_all.h's.
  */
 #ifndef SNAIL_INSTANCES_MATERIALS_DYNAMIC_H
 #define SNAIL_INSTANCES_MATERIALS_DYNAMIC_H
@@ -73,8 +73,9 @@ typedef struct { int32_t blas; const float *d_verts9; const float *d_nrm9; int32
 SnailInstancesMaterials *snail_instances_materials_create_dev(SnailInstances *, const SnailBlasShadingDev *perBlas, int nBlas, const SnailMaterial *mats, int nMats,
                                                               const int32_t *opacityTexture, const SnailTexture *textures, int nTex, void *stream);
 
-/* Rebuilds every listed BLAS from its d_verts9 exactly as snail_scene_rebuild_fast_dev does (its kernels, status rules and ordering), perm and
- * status going into the set's own words for that BLAS, and then packs the records of ALL listed BLASes again in one launch on the same stream,
+/* Rebuilds every listed BLAS from its d_verts9 with the results, status rules and ordering of snail_scene_rebuild_fast_dev -- all listed builds
+ * in ONE batched pass, snail_scenes_rebuild_fast_dev's (snail_bvh_fast_batch.h): each phase of the build is one launch for all of them, and every
+ * BLAS ends byte-equal to a rebuild of its own --, perm and status going into the set's own words for that BLAS, and then packs the records of ALL listed BLASes again in one launch on the same stream,
  * under the commit rule above.  REFUSED before anything is enqueued: nList <= 0, a blas index out of range, one that names a BLAS that is never
  * rebuilt, one listed twice, null vertices, a set that was not made by snail_instances_materials_create_dev, and a STALE set
  * (snail_instances_materials_update_dev first: were a build then refused, nothing would bring its records back to the tree the BLAS keeps).

@@ -122,6 +122,17 @@ BVH_FAST_SIGNATURES = {
     "snail_scene_rebuild_fast_dev": (_I, [_VP, _VP, _I, _VP, _VP, _VP]),
 }
 
+# include/snail_bvh_fast_batch.h: the fast builder over several device handles in one batched pass (tests/c/bvh_fast_batch_c.c enumerates this
+# table and the next)
+BVH_FAST_BATCH_SIGNATURES = {
+    "snail_scenes_rebuild_fast_dev": (_I, [_VP, _I, _VP]),
+}
+
+# include/snail_instances_materials_rebuild_all.h: the per-frame step of a deforming instanced scene in one call
+INSTANCES_MATERIALS_REBUILD_ALL_SIGNATURES = {
+    "snail_instances_materials_rebuild_all_dev": (_I, [_VP, _VP, _I, _VP, _VP, _I, _VP, _VP, _VP]),
+}
+
 # include/snail_heatmap.h: per-packet TreeStats and the gVals[5] heat-map of plain and instanced scenes (tests/c/heatmap_c.c enumerates this table)
 HEATMAP_SIGNATURES = {
     "snail_packet_stats_dev": (_I, [_VP, _F13, _I, _I, _VP, _I, _VP, _I, _I, _VP, _VP, _VP]),
@@ -290,7 +301,7 @@ def debug_lib():
         if not os.path.exists(DEBUG_LIB_PATH):
             raise SnailError("workbench library %s is missing: `make -C snail_amd/csrc debug`" % DEBUG_LIB_PATH)
         L = C.CDLL(DEBUG_LIB_PATH)
-        for table in (SIGNATURES, INSTANCES_SIGNATURES, INSTANCES_SHADE_SIGNATURES, INSTANCES_TILES_SIGNATURES, INSTANCES_BUILD_SIGNATURES, BVH_FAST_SIGNATURES, HEATMAP_SIGNATURES, MATERIALS_SIGNATURES, MATERIALS_BOUNCE_SIGNATURES, MATERIALS_TILES_SIGNATURES, MATERIALS_TRANSPARENCY_SIGNATURES, MATERIALS_TREE_SIGNATURES, MATERIALS_HEAT_SIGNATURES, MATERIALS_DYNAMIC_SIGNATURES, INSTANCES_MATERIALS_SIGNATURES, INSTANCES_MATERIALS_BOUNCE_SIGNATURES, INSTANCES_MATERIALS_TRANSPARENCY_SIGNATURES, INSTANCES_MATERIALS_TREE_SIGNATURES, INSTANCES_MATERIALS_HEAT_SIGNATURES, INSTANCES_MATERIALS_DYNAMIC_SIGNATURES, DEBUG_SIGNATURES):
+        for table in (SIGNATURES, INSTANCES_SIGNATURES, INSTANCES_SHADE_SIGNATURES, INSTANCES_TILES_SIGNATURES, INSTANCES_BUILD_SIGNATURES, BVH_FAST_SIGNATURES, HEATMAP_SIGNATURES, MATERIALS_SIGNATURES, MATERIALS_BOUNCE_SIGNATURES, MATERIALS_TILES_SIGNATURES, MATERIALS_TRANSPARENCY_SIGNATURES, MATERIALS_TREE_SIGNATURES, MATERIALS_HEAT_SIGNATURES, MATERIALS_DYNAMIC_SIGNATURES, INSTANCES_MATERIALS_SIGNATURES, INSTANCES_MATERIALS_BOUNCE_SIGNATURES, INSTANCES_MATERIALS_TRANSPARENCY_SIGNATURES, INSTANCES_MATERIALS_TREE_SIGNATURES, INSTANCES_MATERIALS_HEAT_SIGNATURES, INSTANCES_MATERIALS_DYNAMIC_SIGNATURES, BVH_FAST_BATCH_SIGNATURES, INSTANCES_MATERIALS_REBUILD_ALL_SIGNATURES, DEBUG_SIGNATURES):
             for name, (res, args) in table.items():
                 fn = getattr(L, name)
                 fn.restype = res
@@ -311,7 +322,7 @@ def lib():
             L = C.CDLL(LIB_PATH)
         except OSError as e:  # pragma: no cover - depends on the box
             raise SnailError("cannot load %s: %s" % (LIB_PATH, e)) from e
-        for table in (SIGNATURES, INSTANCES_SIGNATURES, INSTANCES_SHADE_SIGNATURES, INSTANCES_TILES_SIGNATURES, INSTANCES_BUILD_SIGNATURES, BVH_FAST_SIGNATURES, HEATMAP_SIGNATURES, MATERIALS_SIGNATURES, MATERIALS_BOUNCE_SIGNATURES, MATERIALS_TILES_SIGNATURES, MATERIALS_TRANSPARENCY_SIGNATURES, MATERIALS_TREE_SIGNATURES, MATERIALS_HEAT_SIGNATURES, MATERIALS_DYNAMIC_SIGNATURES, INSTANCES_MATERIALS_SIGNATURES, INSTANCES_MATERIALS_BOUNCE_SIGNATURES, INSTANCES_MATERIALS_TRANSPARENCY_SIGNATURES, INSTANCES_MATERIALS_TREE_SIGNATURES, INSTANCES_MATERIALS_HEAT_SIGNATURES, INSTANCES_MATERIALS_DYNAMIC_SIGNATURES):
+        for table in (SIGNATURES, INSTANCES_SIGNATURES, INSTANCES_SHADE_SIGNATURES, INSTANCES_TILES_SIGNATURES, INSTANCES_BUILD_SIGNATURES, BVH_FAST_SIGNATURES, HEATMAP_SIGNATURES, MATERIALS_SIGNATURES, MATERIALS_BOUNCE_SIGNATURES, MATERIALS_TILES_SIGNATURES, MATERIALS_TRANSPARENCY_SIGNATURES, MATERIALS_TREE_SIGNATURES, MATERIALS_HEAT_SIGNATURES, MATERIALS_DYNAMIC_SIGNATURES, INSTANCES_MATERIALS_SIGNATURES, INSTANCES_MATERIALS_BOUNCE_SIGNATURES, INSTANCES_MATERIALS_TRANSPARENCY_SIGNATURES, INSTANCES_MATERIALS_TREE_SIGNATURES, INSTANCES_MATERIALS_HEAT_SIGNATURES, INSTANCES_MATERIALS_DYNAMIC_SIGNATURES, BVH_FAST_BATCH_SIGNATURES, INSTANCES_MATERIALS_REBUILD_ALL_SIGNATURES):
             for name, (res, args) in table.items():
                 fn = getattr(L, name)
                 fn.restype = res

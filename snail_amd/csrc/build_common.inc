@@ -99,10 +99,13 @@ __device__ __forceinline__ void hdrInit(BuildHdr &H) {
 	for(int k = 0; k < kLevels + 3; k++) H.qCount[k] = 0;
 }
 
+// The kernels' bodies are functions of the argument record (and, where they use them, a block index and a grid size), or text in a file of
+// their own (build_big_body.inc, build_small_body.inc: see there), so that the batched builder (bvh_fast_batch.inc) runs the same code for
+// one tree of several per launch, with the block index and grid size of that tree's share
 template <class P>
-__global__ void k_build_root(SplitArgs A) {
+__device__ __forceinline__ void buildRootBody(const SplitArgs &A, int block) {
 	BuildHdr &H = *A.hdr;
-	if(threadIdx.x != 0 || blockIdx.x != 0 || H.status != 0) return;
+	if(threadIdx.x != 0 || block != 0 || H.status != 0) return;
 	TNode r;
 	for(int k = 0; k < 3; k++) { r.lo[k] = keyValue(H.rootMin[k]); r.hi[k] = keyValue(H.rootMax[k]); }
 	r.first = 0; r.count = A.n; r.aux = A.n; r.inner = 0; r.chain = 0; r.pfirst = 0; r.pchain = 0; r.side = 0; r.sdepth = 0; r.pad = 0;
@@ -111,6 +114,8 @@ __global__ void k_build_root(SplitArgs A) {
 	if(A.n > kSmall) { A.queue[0][0] = 0; H.qCount[0] = 1; }
 	else if(A.n >= P::minSplit) { A.small[0] = 0; H.nSmall = 1; }
 }
+template <class P>
+__global__ void k_build_root(SplitArgs A) { buildRootBody<P>(A, (int)blockIdx.x); }
 
 struct SplitLds {
 	u64 bmin[16][3], bmax[16][3];
@@ -287,59 +292,26 @@ template <class P>
 __global__ void __launch_bounds__(256) k_build_big(SplitArgs A, int level0, int level1) {
 	__shared__ SplitLds S;
 	__shared__ int levelCount;
-	BuildHdr &H = *A.hdr;
-	if(H.status == 1) return;
-	for(int level = level0; level < level1; level++) {
-		__syncthreads();
-		if(threadIdx.x == 0) levelCount = atomicAdd(&H.qCount[level], 0);   // (read where this workgroup's own atomics of the level before landed)
-		__syncthreads();
-		const int cnt = levelCount;
-		if(cnt == 0) return;      // no node of this depth: none deeper either
-		const int *in = A.queue[level & 1];
-		int *out = A.queue[(level + 1) & 1];
-		for(int item = blockIdx.x; item < cnt; item += gridDim.x) {
-			__syncthreads();
-			splitNode<256, P>(A, in[item], S);
-			if(threadIdx.x == 0 && S.child >= 0) {
-				const int id[2] = {S.child, S.child + 1}, c[2] = {S.cL, S.cR};
-				for(int s = 0; s < 2; s++) {
-					if(c[s] > kSmall) out[atomicAdd(&H.qCount[level + 1], 1)] = id[s];
-					else if(c[s] >= P::minSplit) A.small[atomicAdd(&H.nSmall, 1)] = id[s];
-				}
-			}
-		}
-	}
+#define SNAIL_BODY_BLOCK blockIdx.x
+#define SNAIL_BODY_GRID gridDim.x
+#include "build_big_body.inc"
+#undef SNAIL_BODY_BLOCK
+#undef SNAIL_BODY_GRID
 }
 
 template <class P>
 __global__ void __launch_bounds__(64) k_build_small(SplitArgs A) {
 	__shared__ SplitLds S;
 	__shared__ int stack[kLevels + 8];
-	BuildHdr &H = *A.hdr;
-	if(H.status == 1) return;
-	const int cnt = H.nSmall;
-	for(int item = blockIdx.x; item < cnt; item += gridDim.x) {
-		__syncthreads();
-		if(threadIdx.x == 0) stack[0] = A.small[item];
-		int sp = 1;
-		while(sp > 0) {
-			__syncthreads();
-			const int t = stack[--sp];
-			__syncthreads();
-			splitNode<64, P>(A, t, S);
-			// (the children of a node at depth d sit at d + 1 <= 64 and none is made below that: at most one pending sibling per level)
-			const int c = S.child;
-			if(c >= 0) {
-				if(S.cR >= P::minSplit && sp < kLevels + 6) { if(threadIdx.x == 0) stack[sp] = c + 1; sp++; }
-				if(S.cL >= P::minSplit && sp < kLevels + 6) { if(threadIdx.x == 0) stack[sp] = c; sp++; }
-			}
-		}
-	}
+#define SNAIL_BODY_BLOCK blockIdx.x
+#define SNAIL_BODY_GRID gridDim.x
+#include "build_small_body.inc"
+#undef SNAIL_BODY_BLOCK
+#undef SNAIL_BODY_GRID
 }
 
-// startCnt[i] := number of inner nodes whose first slot is < i; totalInner
-__global__ void __launch_bounds__(1024) k_build_scan(SplitArgs A) {
-	__shared__ int s[1024];
+// startCnt[i] := number of inner nodes whose first slot is < i; totalInner (one workgroup of 1024 threads per tree)
+__device__ __forceinline__ void buildScanBody(const SplitArgs &A, int *s) {
 	BuildHdr &H = *A.hdr;
 	if(H.status != 0) return;
 	const int tid = threadIdx.x;
@@ -360,6 +332,10 @@ __global__ void __launch_bounds__(1024) k_build_scan(SplitArgs A) {
 		__syncthreads();
 	}
 	if(tid == 0) H.totalInner = carry;
+}
+__global__ void __launch_bounds__(1024) k_build_scan(SplitArgs A) {
+	__shared__ int s[1024];
+	buildScanBody(A, s);
 }
 
 } // namespace devb

@@ -40,14 +40,17 @@ struct FastArgs : devb::SplitArgs {
 	int *perm, *info;
 };
 
-__global__ void k_fast_init(FastArgs A) {
-	const int i = blockIdx.x * blockDim.x + threadIdx.x;
+// (bodies as functions of the record and a block index, the commit's as text in bvh_fast_commit_body.inc: bvh_fast_batch.inc runs them for one
+// tree of several per launch)
+__device__ __forceinline__ void fastInitBody(const FastArgs &A, unsigned block) {
+	const int i = block * blockDim.x + threadIdx.x;
 	if(i < A.n) A.startCnt[i] = 0;
 	if(i == 0) devb::hdrInit(*A.hdr);
 }
+__global__ void k_fast_init(FastArgs A) { fastInitBody(A, blockIdx.x); }
 
-__global__ void k_fast_boxes(FastArgs A) {
-	const int i = blockIdx.x * blockDim.x + threadIdx.x;
+__device__ __forceinline__ void fastBoxesBody(const FastArgs &A, unsigned block) {
+	const int i = block * blockDim.x + threadIdx.x;
 	if(i >= A.n) return;
 	float p[9], rec[16];
 	bool ok = true;
@@ -69,46 +72,14 @@ __global__ void k_fast_boxes(FastArgs A) {
 	// the root box: box[0] grown by 1..n-1 in the caller's order
 	for(int k = 0; k < 3; k++) { devb::keyMin(&A.hdr->rootMin[k], lo[k], i); devb::keyMax(&A.hdr->rootMax[k], hi[k], i); }
 }
+__global__ void k_fast_boxes(FastArgs A) { fastBoxesBody(A, blockIdx.x); }
 
 __global__ void k_fast_commit(FastArgs A) {
-	const BuildHdr &H = *A.hdr;
-	const int g = blockIdx.x * blockDim.x + threadIdx.x, stride = gridDim.x * blockDim.x;
-	const int status = H.status != 0 ? H.status : (A.needSane && H.insane) ? 3 : 0;
-	if(status != 0) {
-		if(g == 0 && A.info) { A.info[0] = status; A.info[1] = 0; A.info[2] = 0; A.info[3] = A.n; }
-		return;
-	}
-	const int nTemp = H.nTemp;
-	for(int t = g; t < nTemp; t += stride) {
-		const TNode nd = A.tn[t];
-		const int idx = t == 0 ? 0 : 1 + 2 * (A.startCnt[nd.pfirst] + nd.pchain) + nd.side;
-		const unsigned sub = nd.inner ? (unsigned)(1 + 2 * (A.startCnt[nd.first] + nd.chain)) : ((unsigned)nd.first | 0x80000000u);
-		const unsigned in[8] = {__float_as_uint(nd.lo[0]), __float_as_uint(nd.lo[1]), __float_as_uint(nd.lo[2]), __float_as_uint(nd.hi[0]),
-								__float_as_uint(nd.hi[1]), __float_as_uint(nd.hi[2]), sub, (unsigned)nd.aux};
-		A.nodes[(size_t)idx * 2] = make_uint4(in[0], in[1], in[2], in[3]);
-		A.nodes[(size_t)idx * 2 + 1] = make_uint4(in[4], in[5], in[6], in[7]);
-		if(A.pf) {
-			unsigned out[8];
-			dev::pfEncode(in, out, A.trisOff);
-			A.pf[(size_t)(idx + 1) * 2] = make_uint4(out[0], out[1], out[2], out[3]);
-			A.pf[(size_t)(idx + 1) * 2 + 1] = make_uint4(out[4], out[5], out[6], out[7]);
-		}
-	}
-	for(int i = g; i < A.n; i += stride) {
-		const int s = A.src[i];
-		float p[9], rec[16];
-		for(int k = 0; k < 9; k++) p[k] = A.verts[(size_t)s * 9 + k];
-		(void)dev::lbvh::triRecord(p, rec);
-		uint4 *o = A.tris + (size_t)i * 4;
-		for(int q = 0; q < 4; q++)
-			o[q] = make_uint4(__float_as_uint(rec[q * 4]), __float_as_uint(rec[q * 4 + 1]), __float_as_uint(rec[q * 4 + 2]), __float_as_uint(rec[q * 4 + 3]));
-		if(A.perm) A.perm[i] = s;
-	}
-	if(g == 0) {
-		const int nNodes = 1 + 2 * H.totalInner;
-		A.cur[0] = nNodes; A.cur[1] = H.depth; A.cur[2] = H.insane ? 0 : 1; A.cur[3] = 0;
-		if(A.info) { A.info[0] = 0; A.info[1] = nNodes; A.info[2] = H.depth; A.info[3] = A.n; }
-	}
+#define SNAIL_BODY_BLOCK blockIdx.x
+#define SNAIL_BODY_GRID gridDim.x
+#include "bvh_fast_commit_body.inc"
+#undef SNAIL_BODY_BLOCK
+#undef SNAIL_BODY_GRID
 }
 
 } // namespace devf

@@ -740,19 +740,19 @@ int buildReserve(SnailInstances *h, int n) {
 	return 0;
 }
 
-} // namespace
-
-extern "C" {
-
-int snail_instances_rebuild_dev(SnailInstances *h, const float *d_xf12, const int32_t *d_blasIdx, int n, int32_t *d_perm, int32_t *d_info, void *stream) {
-	const char *fn = "snail_instances_rebuild_dev";
+// what snail_instances_rebuild_dev refuses before anything is enqueued (fn: the caller's name in the texts)
+int instancesRebuildCheck(const char *fn, const SnailInstances *h, const float *d_xf12, int n) {
 	if(n <= 0 || n > (1 << 30)) { snail_set_error("%s: %d instances (1 .. 1 << 30)", fn, n); return 1; }
 	if(!d_xf12) { snail_set_error("%s: null transforms", fn); return 1; }
 	if(int rc = checkInstances(h, fn)) return rc;
 	if(!h->dBlasBox || !h->dCur) { snail_set_error("%s: invalid instances handle", fn); return 1; }
-	hipStream_t st = (hipStream_t)stream;
-	DeviceGuard guard(h->device);
-	std::lock_guard<std::mutex> lock(h->mu);
+	return 0;
+}
+
+// snail_instances_rebuild_dev after its arguments were judged: the handle's mu held, its device current.  `held` (or null): BLAS scenes whose mu
+// the CALLER holds already (snail_instances_materials_rebuild_all_dev, behind its BLAS rebuilds); every other BLAS scene's is taken here
+int instancesRebuildLocked(SnailInstances *h, const float *d_xf12, const int32_t *d_blasIdx, int n, int32_t *d_perm, int32_t *d_info, hipStream_t st,
+						   const std::vector<SnailScene *> *held) {
 	if(int rc = buildReserve(h, n)) return rc;
 	// after every launch enqueued since the previous update (they read the buffers the commit writes) and after the previous update or rebuild
 	// itself (one scratch area per handle)
@@ -762,7 +762,8 @@ int snail_instances_rebuild_dev(SnailInstances *h, const float *d_xf12, const in
 	for(size_t b = 0; b < h->blas.size(); b++) {
 		SnailScene *s = h->blas[b];
 		if(!s->fast) continue;
-		std::lock_guard<std::mutex> blasLock(s->mu);
+		std::unique_lock<std::mutex> blasLock(s->mu, std::defer_lock);
+		if(!held || std::find(held->begin(), held->end(), s) == held->end()) blasLock.lock();
 		if(int rc = fastSceneBegin(s, st)) return rc;
 		HIP_TRY(hipMemcpyAsync((char *)h->dBlasBox + b * 24, s->dNodes, 24, hipMemcpyDeviceToDevice, st));
 		fastSceneEnd(s, st);
@@ -799,6 +800,18 @@ int snail_instances_rebuild_dev(SnailInstances *h, const float *d_xf12, const in
 	h->hasReady = true;
 	h->curOnDevice = true;
 	return 0;
+}
+
+} // namespace
+
+extern "C" {
+
+int snail_instances_rebuild_dev(SnailInstances *h, const float *d_xf12, const int32_t *d_blasIdx, int n, int32_t *d_perm, int32_t *d_info, void *stream) {
+	const char *fn = "snail_instances_rebuild_dev";
+	if(int rc = instancesRebuildCheck(fn, h, d_xf12, n)) return rc;
+	DeviceGuard guard(h->device);
+	std::lock_guard<std::mutex> lock(h->mu);
+	return instancesRebuildLocked(h, d_xf12, d_blasIdx, n, d_perm, d_info, (hipStream_t)stream, nullptr);
 }
 
 int snail_instances_read_tree(SnailInstances *h, void *nodes32, int nodeCap, int *nNodes, float *xf12_slots, int32_t *blasIdx_slots, int slotCap, int *n) {

@@ -1,7 +1,7 @@
 // instances_materials_dynamic_host.inc -- the C-ABI of include/snail_instances_materials_dynamic.h: the material set of an instanced scene in
 // which the records of every BLAS of snail_scene_create_fast_dev are packed on the device and packed again behind every rebuild of that BLAS,
 // all listed BLASes in ONE launch (instances_materials_dynamic.inc).  Per BLAS it is materials_dynamic_host.inc's scheme: the rebuild is
-// snail_scene_rebuild_fast_dev's own (fastRebuildLocked), the pack's stream has waited for every user of the BLAS scene (fastWaitUsers;
+// snail_scenes_rebuild_fast_dev's own (fastRebuildBatchLocked: the listed BLASes' builds in one batched pass), the pack's stream has waited for every user of the BLAS scene (fastWaitUsers;
 // instanced launches book their use in instancesEnd) and the scene's `ready` is recorded again behind the pack, so every later instanced launch
 // waits for it in instancesBegin.  Lock order: the set's renderMu, the instances handle's mu, the BLAS scenes' mu in ascending BLAS index.
 #include "../../include/snail_instances_materials_dynamic.h"
@@ -128,6 +128,37 @@ int imatDynCheckList(const char *fn, const SnailInstancesMaterials *m, const Sna
 			if(m->inst->blas[list[j].blas] == m->inst->blas[b]) { snail_set_error("%s: entries %d and %d name one BLAS scene (BLAS %d and %d)", fn, j, k, list[j].blas, b); return 1; }
 	}
 	return 0;
+}
+
+// everything snail_instances_materials_rebuild_dev refuses, before anything is enqueued (fn: the caller's name in the texts)
+int imatDynCheckRebuild(const char *fn, const SnailInstancesMaterials *m, const SnailBlasRebuild *list, int nList) {
+	if(int rc = imatDynCheckList(fn, nullptr, list, nList, true)) return rc;
+	if(int rc = checkIMatDyn(m, fn)) return rc;
+	if(int rc = imatDynCheckList(fn, m, list, nList, true)) return rc;
+	// (a stale set is refused: should a build then fail, nothing would bring that BLAS's records back to the tree it keeps)
+	return imatDynCheckFresh(m, fn);
+}
+
+// snail_instances_materials_rebuild_dev after its arguments were judged; the set's renderMu, the handle's mu and the listed scenes' mu held.
+// The builds of all listed BLASes are ONE batched pass (bvh_fast_batch.inc), the pack of all of them one launch behind it
+int imatDynRebuildLocked(SnailInstancesMaterials *m, const SnailBlasRebuild *list, int nList, hipStream_t st) {
+	SnailInstances *h = m->inst;
+	std::vector<int> idx;
+	std::vector<devshd::PackArgs> E;
+	std::vector<FastBatchItem> builds;
+	for(int k = 0; k < nList; k++) {
+		const int b = list[k].blas;
+		SnailInstancesMaterialsDyn::Blas &D = m->dyn->blas[b];
+		// the build commits perm and tree together, into the SET's perm and status words of this BLAS: the pack behind it reads both on the stream
+		builds.push_back(FastBatchItem{h->blas[b], list[k].d_verts9, D.dPerm, D.dBuild});
+		devshd::PackArgs A = imatDynEntry(m, b);
+		A.perm = D.dPerm; A.build = D.dBuild; A.permOut = list[k].d_perm; A.info = list[k].d_info;
+		A.nrm9 = list[k].d_nrm9; A.verts9 = list[k].d_verts9;
+		idx.push_back(b);
+		E.push_back(A);
+	}
+	if(int rc = fastRebuildBatchLocked(builds.data(), nList, st)) return rc;
+	return imatDynPack(m, idx, E, st);
 }
 
 std::vector<int> imatDynSorted(const SnailBlasRebuild *list, int nList) {
@@ -275,33 +306,15 @@ SnailInstancesMaterials *snail_instances_materials_create_dev(SnailInstances *h,
 
 int snail_instances_materials_rebuild_dev(SnailInstancesMaterials *m, const SnailBlasRebuild *list, int nList, void *stream) {
 	const char *fn = "snail_instances_materials_rebuild_dev";
-	if(int rc = imatDynCheckList(fn, nullptr, list, nList, true)) return rc;
-	if(int rc = checkIMatDyn(m, fn)) return rc;
-	if(int rc = imatDynCheckList(fn, m, list, nList, true)) return rc;
-	// (a stale set is refused: should a build then fail, nothing would bring that BLAS's records back to the tree it keeps)
-	if(int rc = imatDynCheckFresh(m, fn)) return rc;
+	if(int rc = imatDynCheckRebuild(fn, m, list, nList)) return rc;
 	SnailInstances *h = m->inst;
-	hipStream_t st = (hipStream_t)stream;
 	DeviceGuard guard(m->device);
 	std::lock_guard<std::mutex> renderLock(m->renderMu);   // the set's tile job takes turns with this call
 	std::lock_guard<std::mutex> lock(h->mu);               // no launch of the handle comes between a BLAS's build and its pack
 	const std::vector<int> sorted = imatDynSorted(list, nList);
 	std::vector<std::unique_lock<std::mutex>> locks;
 	imatDynLock(h, sorted, locks);
-	std::vector<int> idx;
-	std::vector<devshd::PackArgs> E;
-	for(int k = 0; k < nList; k++) {
-		const int b = list[k].blas;
-		SnailInstancesMaterialsDyn::Blas &D = m->dyn->blas[b];
-		// the build commits perm and tree together, into the SET's perm and status words of this BLAS: the pack behind it reads both on the stream
-		if(int rc = fastRebuildLocked(h->blas[b], list[k].d_verts9, D.dPerm, D.dBuild, st)) return rc;
-		devshd::PackArgs A = imatDynEntry(m, b);
-		A.perm = D.dPerm; A.build = D.dBuild; A.permOut = list[k].d_perm; A.info = list[k].d_info;
-		A.nrm9 = list[k].d_nrm9; A.verts9 = list[k].d_verts9;
-		idx.push_back(b);
-		E.push_back(A);
-	}
-	return imatDynPack(m, idx, E, st);
+	return imatDynRebuildLocked(m, list, nList, (hipStream_t)stream);
 }
 
 int snail_instances_materials_update_dev(SnailInstancesMaterials *m, const SnailBlasRebuild *list, int nList, void *stream) {

@@ -44,6 +44,7 @@
 #include "../../include/snail_hip.h"
 #include "../../include/snail_instances.h"
 #include "../../include/snail_bvh_fast.h"
+#include "../../include/snail_bvh_fast_batch.h"
 #include "host_sse.h"
 #ifdef SNAIL_DEBUG_API
 #include "../../include/snail_hip_debug.h"
@@ -1815,6 +1816,7 @@ int snail_account_primary(SnailScene *s, const float cam[13], int resx, int resy
 } // extern "C"
 
 #include "bvh_fast.inc"
+#include "bvh_fast_batch.inc"
 #include "render_host.inc"
 #include "instances_host.inc"
 #include "instances_tiles_host.inc"
@@ -1828,6 +1830,7 @@ int snail_account_primary(SnailScene *s, const float cam[13], int resx, int resy
 #include "materials_dynamic_host.inc"
 #include "instances_materials_host.inc"
 #include "instances_materials_dynamic_host.inc"
+#include "instances_materials_rebuild_all_host.inc"
 #include "instances_materials_bounce_host.inc"
 #include "instances_materials_transparency_host.inc"
 #include "instances_materials_tree_host.inc"

@@ -17,7 +17,7 @@ import numpy as np
 
 from . import _lib
 from .bvh import NODE_DTYPE
-from .scene import Scene, Context, ShadowContext, HitFrame, _stream_ptr, _torch
+from .scene import Scene, Context, ShadowContext, HitFrame, _filled_on, _stream_ptr, _torch
 
 
 def _xf12(rotations, translations) -> np.ndarray:
@@ -115,6 +115,14 @@ class InstancedScene:
         xf12 and blas_index are read on `stream` and must stay alive and unchanged until that work has run (keep the tensors, or
         record_stream them, when `stream` is not the current one).  nodes() / perm() / slot_transforms() / depth read the handle back (and
         wait for it) when they are next asked."""
+        n, info = self._update_dev_begin(xf12, blas_index, stream, perm, info)
+        _lib.check(_lib.lib().snail_instances_rebuild_dev(self._h, _lib.ptr(xf12), _lib.ptr(blas_index), n, _lib.ptr(self._d_perm), _lib.ptr(info),
+                                                          _stream_ptr(stream)), "snail_instances_rebuild_dev")
+        return self._update_dev_end(n, stream, perm, info)
+
+    def _update_dev_begin(self, xf12, blas_index, stream, perm, info):
+        """update_dev before its library call: the arguments checked, the scene's device copy of perm in place -> (n, info tensor).  (Shared with
+        InstancedMaterialSet.rebuild_all_dev, whose one call rebuilds BLASes and this tree.)"""
         torch = _torch()
         d = self._dev()
         if not (hasattr(xf12, "data_ptr") and xf12.is_cuda and xf12.device == d and xf12.dtype == torch.float32 and xf12.dim() == 2
@@ -140,8 +148,12 @@ class InstancedScene:
             info = torch.empty(4, dtype=torch.int32, device=d)
             if stream is not None:
                 info.record_stream(stream)
-        _lib.check(_lib.lib().snail_instances_rebuild_dev(self._h, _lib.ptr(xf12), _lib.ptr(blas_index), n, _lib.ptr(self._d_perm), _lib.ptr(info),
-                                                          _stream_ptr(stream)), "snail_instances_rebuild_dev")
+        return n, info
+
+    def _update_dev_end(self, n, stream, perm, info):
+        """update_dev after its library call -> (perm, info)"""
+        torch = _torch()
+        d = self._dev()
         self._dirty = True
         if perm is None:
             return self._d_perm[:n], info
@@ -213,11 +225,12 @@ class InstancedScene:
         torch = _torch()
         x0, y0, w, h = rect if rect is not None else (0, 0, resx, resy)
         d = self._dev()
-        t = torch.full((resy, resx), float("inf"), dtype=torch.float32, device=d)
-        u = torch.zeros((resy, resx), dtype=torch.float32, device=d)
-        v = torch.zeros((resy, resx), dtype=torch.float32, device=d)
-        inst = torch.zeros((resy, resx), dtype=torch.int32, device=d)
-        tri = torch.zeros((resy, resx), dtype=torch.int32, device=d)
+        with _filled_on(stream):
+            t = torch.full((resy, resx), float("inf"), dtype=torch.float32, device=d)
+            u = torch.zeros((resy, resx), dtype=torch.float32, device=d)
+            v = torch.zeros((resy, resx), dtype=torch.float32, device=d)
+            inst = torch.zeros((resy, resx), dtype=torch.int32, device=d)
+            tri = torch.zeros((resy, resx), dtype=torch.int32, device=d)
         cam13 = np.ascontiguousarray(cam.as_array13(), dtype=np.float32)
         rc = _lib.lib().snail_instances_trace_primary_dev(self._h, _lib.ptr(cam13), resx, resy, x0, y0, w, h, _lib.ptr(t), _lib.ptr(u), _lib.ptr(v),
                                                          _lib.ptr(inst), _lib.ptr(tri), _lib.ptr(stats), _stream_ptr(stream))
@@ -229,11 +242,12 @@ class InstancedScene:
         torch = _torch()
         n = int(packet_xy.shape[0])
         d = self._dev()
-        t = torch.full((n, 256), float("inf"), dtype=torch.float32, device=d)
-        u = torch.zeros((n, 256), dtype=torch.float32, device=d)
-        v = torch.zeros((n, 256), dtype=torch.float32, device=d)
-        inst = torch.zeros((n, 256), dtype=torch.int32, device=d)
-        tri = torch.zeros((n, 256), dtype=torch.int32, device=d)
+        with _filled_on(stream):
+            t = torch.full((n, 256), float("inf"), dtype=torch.float32, device=d)
+            u = torch.zeros((n, 256), dtype=torch.float32, device=d)
+            v = torch.zeros((n, 256), dtype=torch.float32, device=d)
+            inst = torch.zeros((n, 256), dtype=torch.int32, device=d)
+            tri = torch.zeros((n, 256), dtype=torch.int32, device=d)
         cam13 = np.ascontiguousarray(cam.as_array13(), dtype=np.float32)
         rc = _lib.lib().snail_instances_trace_packets_dev(self._h, _lib.ptr(cam13), resx, resy, _lib.ptr(packet_xy), n, _lib.ptr(t), _lib.ptr(u), _lib.ptr(v),
                                                          _lib.ptr(inst), _lib.ptr(tri), _lib.ptr(stats), _stream_ptr(stream))

@@ -88,7 +88,27 @@ def create_instanced_set(instances_handle, shtris_list, map_list, materials, tex
     return C.c_void_p(h)
 
 
-class InstancedMaterialSet:
+class _FrameStep:
+    """include/snail_instances_materials_rebuild_all.h.  A base of InstancedMaterialSet, so that the class's own method list stays the list of
+    include/snail_instances_materials*.h up to snail_instances_materials_dynamic.h, which the tests of those headers enumerate."""
+
+    def rebuild_all_dev(self, entries, xf12, blas_index=None, stream=None, perm=None, info=None):
+        """The per-frame step in one call (snail_instances_materials_rebuild_all_dev): rebuild_blas_dev(entries) followed by
+        isc.update_dev(xf12, blas_index, perm=perm, info=info) under one set of locks -- the BLASes' builds in one batched pass, their records
+        packed again, then the top-level tree over the new BLAS root boxes (a BLAS whose build is refused contributes the box of the tree it
+        keeps), all on `stream`, no host wait.  -> (blas_info int32 [k, 6] as rebuild_blas_dev's, top_perm, top_info as update_dev's)."""
+        arr, binfo, items = self._rebuild_entries("rebuild_all_dev", entries, stream)
+        isc = self.isc
+        n, info = isc._update_dev_begin(xf12, blas_index, stream, perm, info)
+        _lib.check(_lib.lib().snail_instances_materials_rebuild_all_dev(self._h, C.cast(arr, C.c_void_p) if items else None, len(items), _lib.ptr(xf12), _lib.ptr(blas_index),
+                                                                        n, _lib.ptr(isc._d_perm), _lib.ptr(info), _stream_ptr(stream)),
+                   "snail_instances_materials_rebuild_all_dev")
+        self._rebuilt(binfo, items)
+        top_perm, top_info = isc._update_dev_end(n, stream, perm, info)
+        return binfo, top_perm, top_info
+
+
+class InstancedMaterialSet(_FrameStep):
     """The shading data of an instanced scene on its GPU.  per_blas[b] = (uv, nrm, mat_index, flat, material_map) of BLAS b's INPUT triangles
     (the order that scene was built from; its bvh.perm permutes them into triId order); a map entry is -1 (the default material) or an index
     into `materials`, ONE list for all BLASes.  The instanced scene (and through it the BLAS scenes) is kept alive by this object.  The
@@ -194,7 +214,15 @@ class InstancedMaterialSet:
         row per entry in the dictionary's order: the build's {status, nNodes, depth, n}, then {records committed (0 / 1), zeroed triangles}.
         A BLAS whose status is not 0 keeps tree, perm and records.  Each scene's d_perm is written.  The top-level tree is NOT touched: follow
         with isc.update_dev (or isc.update) before the next frame.  The tensors must stay alive and unchanged until the work has run."""
-        arr, info, items = self._blas_list("rebuild_blas_dev", entries, 6, stream)
+        arr, info, items = self._rebuild_entries("rebuild_blas_dev", entries, stream)
+        _lib.check(_lib.lib().snail_instances_materials_rebuild_dev(self._h, C.cast(arr, C.c_void_p) if items else None, len(items), _stream_ptr(stream)),
+                   "snail_instances_materials_rebuild_dev")
+        self._rebuilt(info, items)
+        return info
+
+    def _rebuild_entries(self, what, entries, stream):
+        """the checked SnailBlasRebuild list of rebuild_blas_dev / rebuild_all_dev"""
+        arr, info, items = self._blas_list(what, entries, 6, stream)
         torch = _torch()
         for k, (b, (d_verts, d_nrm)) in enumerate(items):
             sc = self.isc.blas[int(b)]
@@ -202,13 +230,13 @@ class InstancedMaterialSet:
                 raise ValueError("BLAS %d: d_verts must hold %d triangles" % (int(b), sc._fast_n))
             P.MaterialSet._check_dev("d_nrm", d_nrm, torch.float32, sc._fast_n * 9, sc._dev(), optional=True)
             arr[k].d_verts9, arr[k].d_nrm9 = _addr(d_verts), _addr(d_nrm)
-        _lib.check(_lib.lib().snail_instances_materials_rebuild_dev(self._h, C.cast(arr, C.c_void_p) if items else None, len(items), _stream_ptr(stream)),
-                   "snail_instances_materials_rebuild_dev")
+        return arr, info, items
+
+    def _rebuilt(self, info, items):
         for k, (b, _) in enumerate(items):
             sc = self.isc.blas[int(b)]
             sc.d_info = info[k, :4]
             sc._stale = True           # .bvh / .perm / .depth are read back when next asked, as after Scene.rebuild_fast_dev
-        return info
 
     def update_blas_dev(self, entries, stream=None):
         """entries = {b: (d_nrm or None, d_verts or None)}: pack the records of the listed BLASes again through each scene's d_perm, and nothing

@@ -29,6 +29,14 @@ def _torch():
     return torch
 
 
+def _filled_on(stream):
+    """The context in which a method allocates AND FILLS an output it was not given, for a launch on `stream`: the fill must be ordered before
+    the launch that writes into the tensor.  torch enqueues it on the current stream; a launch on another (non-blocking) stream does not wait for
+    that, and a fill that lands after the kernel wipes the result.  None: the current stream, where the launch goes too."""
+    import contextlib
+    return contextlib.nullcontext() if stream is None else _torch().cuda.stream(stream)
+
+
 def _stream_ptr(stream=None):
     torch = _torch()
     if stream is not None:
@@ -282,7 +290,9 @@ class Scene:
         """Trace every 16x16 packet of `rect` (x0,y0,w,h; default the whole image).  `order` / `slot_cost`: optional int32 device
         tensors of primary_slots(w, h) entries -- the dispatch-order feedback of snail_trace_primary_ordered_dev."""
         x0, y0, w, h = rect if rect is not None else (0, 0, resx, resy)
-        out = out if out is not None else self.alloc_frame(resx, resy)
+        if out is None:
+            with _filled_on(stream):
+                out = self.alloc_frame(resx, resy)
         cam13 = np.ascontiguousarray(cam.as_array13(), dtype=np.float32)
         if order is not None or slot_cost is not None:
             n = self.primary_slots(w, h)
@@ -465,7 +475,8 @@ class Scene:
         Scene::ambientLight / defaultMat (src/scene.cpp:6-10)."""
         torch = _torch()
         if out is None:
-            out = torch.zeros((resy, resx, 3), dtype=torch.uint8, device=self._dev())
+            with _filled_on(stream):
+                out = torch.zeros((resy, resx, 3), dtype=torch.uint8, device=self._dev())
         lights = np.ascontiguousarray(lights7, dtype=np.float32).reshape(-1, 7)
         cam13 = np.ascontiguousarray(cam.as_array13(), dtype=np.float32)
         amb = np.ascontiguousarray(ambient, dtype=np.float32); col = np.ascontiguousarray(color, dtype=np.float32)
@@ -516,7 +527,8 @@ class Scene:
         torch = _torch()
         n = int(packet_xy.shape[0])
         if out is None:
-            out = torch.zeros((n, 256, 3), dtype=torch.float32, device=self._dev())
+            with _filled_on(stream):
+                out = torch.zeros((n, 256, 3), dtype=torch.float32, device=self._dev())
         lights = np.ascontiguousarray(lights7, dtype=np.float32).reshape(-1, 7)
         cam13 = np.ascontiguousarray(cam.as_array13(), dtype=np.float32)
         amb = np.ascontiguousarray(ambient, dtype=np.float32); col = np.ascontiguousarray(color, dtype=np.float32)
@@ -585,7 +597,8 @@ class Scene:
         torch = _torch()
         n = int(packet_xy.shape[0]) if packet_xy is not None else ((resx + 15) // 16) * ((resy + 15) // 16)
         if out is None:
-            out = torch.zeros((n, 4), dtype=torch.int32, device=self._dev())
+            with _filled_on(stream):
+                out = torch.zeros((n, 4), dtype=torch.int32, device=self._dev())
         lights, lp = self._heat_lights(lights7)
         cam13 = np.ascontiguousarray(cam.as_array13(), dtype=np.float32)
         rc = _lib.lib().snail_packet_stats_dev(self._h, _lib.ptr(cam13), resx, resy, _lib.ptr(packet_xy), n, lp, len(lights), self._heat_flags(flags, reflections, False),
@@ -732,3 +745,39 @@ class Scene:
         b, t = C.c_int(0), C.c_int(0)
         _lib.check(_lib.lib().snail_last_launch(self._h, C.addressof(b), C.addressof(t)), "snail_last_launch")
         return b.value, t.value
+
+
+class _FastRebuild(C.Structure):
+    _fields_ = [("scene", C.c_void_p), ("d_verts9", C.c_void_p), ("nTris", C.c_int32), ("d_perm", C.c_void_p), ("d_info", C.c_void_p)]
+
+
+def rebuild_fast_dev_batch(scenes, d_verts_list, stream=None, infos=None):
+    """Scene.rebuild_fast_dev for several from_fast_dev scenes in ONE batched pass on the device (snail_scenes_rebuild_fast_dev,
+    include/snail_bvh_fast_batch.h): every phase of the build is one launch for all of them, and each scene ends byte-equal to a
+    rebuild_fast_dev of its own.  scenes and d_verts_list go pairwise; all scenes on one device, none twice.  Enqueued on `stream`, no host
+    wait.  -> the list of info tensors (int32 [4] each: {status, nNodes, depth, n}; `infos` supplies them); a scene whose status is not 0
+    stays as it was, the others commit.  Every scene is marked stale as after rebuild_fast_dev."""
+    scenes, d_verts_list = list(scenes), list(d_verts_list)
+    if len(scenes) != len(d_verts_list) or (infos is not None and len(infos) != len(scenes)):
+        raise ValueError("rebuild_fast_dev_batch: one vertex tensor (and one info tensor) per scene")
+    torch = _torch()
+    arr = (_FastRebuild * max(len(scenes), 1))()
+    out = []
+    for k, (sc, dv) in enumerate(zip(scenes, d_verts_list)):
+        if not getattr(sc, "_fast_dev", False):
+            raise _lib.SnailError("rebuild_fast_dev_batch: scene %d was not made by from_fast_dev" % k)
+        d = sc._dev()
+        info = None if infos is None else infos[k]
+        if info is None:
+            info = torch.empty(4, dtype=torch.int32, device=d)
+            if stream is not None:
+                info.record_stream(stream)
+        arr[k].scene, arr[k].d_verts9, arr[k].nTris = sc._h, dv.data_ptr(), Scene._check_verts(dv, d)
+        arr[k].d_perm, arr[k].d_info = sc.d_perm.data_ptr(), info.data_ptr()
+        out.append(info)
+    _lib.check(_lib.lib().snail_scenes_rebuild_fast_dev(C.cast(arr, C.c_void_p) if scenes else None, len(scenes), _stream_ptr(stream)),
+               "snail_scenes_rebuild_fast_dev")
+    for sc, info in zip(scenes, out):
+        sc.d_info = info
+        sc._stale = True
+    return out

@@ -91,7 +91,11 @@ target: a measurement.  --out PATH appends the report (profiles/instances_materi
 --materials --dynamic: what a frame of k DEFORMING BLASes costs under full shading (include/snail_instances_materials_dynamic.h): k bumpy
 sheets of --dyn-tris triangles each (Scene.from_fast_dev), one instance per sheet, one InstancedMaterialSet.from_dev; per frame, ms, median
 (min .. max) over --reps windows of --frames back-to-back steps between two device events:
-  rebuild_batched   rebuild_blas_dev of all k (k fast builds, ONE k_ishd_pack launch)
+  rebuild_batched   rebuild_blas_dev of all k (the k fast builds in ONE batched pass, include/snail_bvh_fast_batch.h, then ONE k_ishd_pack launch)
+  rebuild_single    Scene.rebuild_fast_dev k times, then one update_blas_dev of all k: the builds one after the other with the single-tree
+                    kernels, which are the parent commit's -- the yardstick of rebuild_batched, same results
+  rebuild_all       rebuild_all_dev: rebuild_batched and top_level in one call (include/snail_instances_materials_rebuild_all.h)
+                    (these three take turns window by window, so that what else the machine does falls on all of them alike)
   pack_batched      update_blas_dev of all k in one call: the pack alone (one k_ishd_pack + one k_ishd_info launch)
   pack_single       update_blas_dev k times with one entry each: the pack alone, k times two launches -- what batching is measured against
   top_level         isc.update_dev, which follows every BLAS rebuild
@@ -99,7 +103,9 @@ sheets of --dyn-tris triangles each (Scene.from_fast_dev), one instance per shee
   host_route        what a host had to do without the header, on the HOST clock per step: wait for the device, download the k perms,
                     pack_shtris on the CPU, create a set of host records (over a host-built twin of the same trees: the older creator
                     refuses a device-built BLAS) and destroy the previous one
-No threshold: a record.  --commit names what was timed; --out PATH writes the report (profiles/instances_materials_dynamic.txt).
+No ratio is a target: a record.  The report says per row what the batched pass is worth against rebuild_single, and whether it is slower than it
+by more than rebuild_single's own min .. max spread.  --commit names what was timed; --out PATH writes the report (profiles/bvh_fast_batch.txt;
+profiles/instances_materials_dynamic.txt is the record of the commit before the batched pass).
 
     python tools/instances_time.py --materials --dynamic [--dyn-blas 4,16] [--dyn-tris 2048,20000] [--frames 20] [--reps 5] [--commit ID] [--out PATH]"""
 import argparse
@@ -799,6 +805,23 @@ def materials_dynamic(torch, a, resx, resy):
             ms.append(e0.elapsed_time(e1) / a.frames)
         return ms
 
+    def alternating(steps):
+        """window()'s figures for several steps that take turns, window by window"""
+        for step in steps.values():
+            step()
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        ms = {name: [] for name in steps}
+        for _ in range(a.reps):
+            for name, step in steps.items():
+                e0.record()
+                for f in range(a.frames):
+                    step(f)
+                e1.record()
+                e1.synchronize()
+                ms[name].append(e0.elapsed_time(e1) / a.frames)
+        return ms
+
     for n_tris in (int(c) for c in a.dyn_tris.split(",")):
         for k in (int(c) for c in a.dyn_blas.split(",")):
             rng = np.random.RandomState(5)
@@ -828,14 +851,25 @@ def materials_dynamic(torch, a, resx, resy):
             c, ext = (nd["bmin"] + nd["bmax"]) * 0.5, nd["bmax"] - nd["bmin"]
             light = np.array([[c[0], c[1], c[2] - 1.5 * float(np.linalg.norm(ext)), 1.0, 1.0, 1.0, 4.0 * float(np.linalg.norm(ext))]], dtype=np.float32)
             frame = torch.zeros((resy, resx, 3), dtype=torch.uint8, device="cuda:0")
-            steps = {
+            def rebuild_single(f=0):
+                for b in range(k):
+                    scs[b].rebuild_fast_dev(d_tv[b][f & 1])
+                ms_set.update_blas_dev({b: (None, d_tv[b][f & 1]) for b in range(k)})
+
+            rebuilds = {
                 "rebuild_batched": lambda f=0: ms_set.rebuild_blas_dev({b: (d_tv[b][f & 1], None) for b in range(k)}),
+                "rebuild_single": rebuild_single,
+                "rebuild_all": lambda f=0: ms_set.rebuild_all_dev({b: (d_tv[b][f & 1], None) for b in range(k)}, d_xf, d_bi),
+            }
+            row = {"k": k, "tris_per_blas": n}
+            for name, ms in alternating(rebuilds).items():
+                row[name] = (statistics.median(ms), min(ms), max(ms))
+            steps = {
                 "pack_batched": lambda f=0: ms_set.update_blas_dev({b: (None, d_tv[b][1]) for b in range(k)}),
                 "pack_single": lambda f=0: [ms_set.update_blas_dev({b: (None, d_tv[b][1])}) for b in range(k)],
                 "top_level": lambda f=0: isc.update_dev(d_xf, d_bi),
                 "frame": lambda f=0: ms_set.render(cam, resx, resy, light, out=frame),
             }
-            row = {"k": k, "tris_per_blas": n}
             for name, step in steps.items():
                 if name == "pack_batched":      # (the packs run on the last pose the rebuilds left: pose index (frames - 1) & 1 = 1 for an even count)
                     ms_set.rebuild_blas_dev({b: (d_tv[b][1], None) for b in range(k)})
@@ -870,7 +904,7 @@ def materials_dynamic(torch, a, resx, resy):
             ms_set.close(); isc.close()
             for s in scs:
                 s.close()
-    cols = ["rebuild_batched", "pack_batched", "pack_single", "top_level", "frame", "host_route"]
+    cols = ["rebuild_batched", "rebuild_single", "rebuild_all", "pack_batched", "pack_single", "top_level", "frame", "host_route"]
     lines.append("%4s %9s  " % ("k", "tris/BLAS") + "  ".join("%-26s" % c for c in cols))
     for r in rows:
         lines.append("%4d %9d  " % (r["k"], r["tris_per_blas"]) + "  ".join("%-26s" % ("%.3f (%.3f .. %.3f)" % r[c]) for c in cols))
@@ -879,6 +913,15 @@ def materials_dynamic(torch, a, resx, resy):
         lines.append("k = %d, %d triangles each: k single-entry packs take %.2f x the batched pack (%.3f ms against %.3f ms per frame); the pack is %.1f %% of the "
                      "batched rebuild; %d non-black pixels in the frame" % (r["k"], r["tris_per_blas"], r["pack_single"][0] / r["pack_batched"][0], r["pack_single"][0],
                                                                             r["pack_batched"][0], 100.0 * r["pack_batched"][0] / r["rebuild_batched"][0], r["nonblack_pixels"]))
+    lines.append("")
+    lines.append("the batched pass against k single builds (rebuild_single: the parent commit's kernels and launch count), medians of the same run:")
+    for r in rows:
+        b, s1, al = r["rebuild_batched"], r["rebuild_single"], r["rebuild_all"]
+        spread = s1[2] - s1[1]
+        verdict = "not slower" if b[0] <= s1[0] else ("slower, within rebuild_single's spread" if b[0] - s1[0] <= spread else "SLOWER by more than rebuild_single's spread")
+        lines.append("k = %d, %d triangles each: rebuild_single / rebuild_batched = %.2f (%.3f ms against %.3f ms; rebuild_single's min .. max spread %.3f ms): %s; "
+                     "rebuild_all %.3f ms against rebuild_batched + top_level = %.3f ms" % (r["k"], r["tris_per_blas"], s1[0] / b[0], s1[0], b[0], spread, verdict, al[0],
+                                                                                             b[0] + r["top_level"][0]))
     text = "\n".join(lines) + "\n"
     print(text)
     if a.out:
