@@ -63,6 +63,7 @@
 #include "snail_materials_tree.h"
 #include "snail_materials_heatmap.h"
 #include "snail_materials_dynamic.h"
+#include "snail_wide.h"
 
 #ifndef SNAIL_CHECK
 #define SNAIL_CHECK(expr)                                                                              \
@@ -229,6 +230,20 @@ public:
 		uint64_t st[4] = {0, 0, 0, 0};
 		SNAIL_CHECK(snail_trace_shadow(scene, 1, c.Size(), org, (const float *)c.rays.DirPtr(), (const float *)c.rays.IDirPtr(), (float *)c.distance, st));
 		if(c.stats) { c.stats->Intersection((unsigned)st[0]); c.stats->LoopIteration((unsigned)st[1]); c.stats->Skip((unsigned)st[3]); }
+	}
+
+	// BVH::WideTrace (src/bvh/traverse.cpp:197-225) with the reference's signature, so that TracePhotons (src/photons.cpp:239) compiles
+	// against this class unchanged: the listed rays walk the tree one ray per lane (include/snail_wide.h) and dist[] of exactly those rays is
+	// updated.  Vec3T = the reference's Vec3f (three packed floats), IndexT = its u16.  The arrays are read up to the largest listed index.
+	template <class Vec3T, class IndexT>
+	void WideTrace(const Vec3T *origin, const Vec3T *dir, const Vec3T *idir, IndexT *indices, float *dist, unsigned count, unsigned nodeIdx = 0) const {
+		static_assert(sizeof(Vec3T) == 12, "Vec3f is three packed floats");
+		if(!count) return;
+		std::vector<int32_t> idx(count);
+		int32_t last = 0;
+		for(unsigned n = 0; n < count; n++) { idx[n] = (int32_t)indices[n]; if(idx[n] > last) last = idx[n]; }
+		SNAIL_CHECK(snail_wide_trace(scene, last + 1, (const float *)origin, (const float *)dir, (const float *)idir, idx.data(), (int)count, dist,
+									 (int)nodeIdx, nullptr, nullptr));
 	}
 
 	SnailScene *Handle() const { return scene; }

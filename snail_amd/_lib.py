@@ -128,6 +128,14 @@ BVH_FAST_BATCH_SIGNATURES = {
     "snail_scenes_rebuild_fast_dev": (_I, [_VP, _I, _VP]),
 }
 
+# include/snail_wide.h: BVH::WideTrace with one ray per lane and the photon pass (tests/c/wide_c.c enumerates this table)
+WIDE_SIGNATURES = {
+    "snail_wide_trace_dev": (_I, [_VP, _I, _VP, _VP, _VP, _VP, _I, _VP, _I, _VP, _VP, _VP]),
+    "snail_wide_trace": (_I, [_VP, _I, _VP, _VP, _VP, _VP, _I, _VP, _I, _VP, _VP]),
+    "snail_photons_trace_dev": (_I, [_VP, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "snail_photons_trace": (_I, [_VP, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP]),
+}
+
 # include/snail_instances_materials_rebuild_all.h: the per-frame step of a deforming instanced scene in one call
 INSTANCES_MATERIALS_REBUILD_ALL_SIGNATURES = {
     "snail_instances_materials_rebuild_all_dev": (_I, [_VP, _VP, _I, _VP, _VP, _I, _VP, _VP, _VP]),
@@ -301,7 +309,7 @@ def debug_lib():
         if not os.path.exists(DEBUG_LIB_PATH):
             raise SnailError("workbench library %s is missing: `make -C snail_amd/csrc debug`" % DEBUG_LIB_PATH)
         L = C.CDLL(DEBUG_LIB_PATH)
-        for table in (SIGNATURES, INSTANCES_SIGNATURES, INSTANCES_SHADE_SIGNATURES, INSTANCES_TILES_SIGNATURES, INSTANCES_BUILD_SIGNATURES, BVH_FAST_SIGNATURES, HEATMAP_SIGNATURES, MATERIALS_SIGNATURES, MATERIALS_BOUNCE_SIGNATURES, MATERIALS_TILES_SIGNATURES, MATERIALS_TRANSPARENCY_SIGNATURES, MATERIALS_TREE_SIGNATURES, MATERIALS_HEAT_SIGNATURES, MATERIALS_DYNAMIC_SIGNATURES, INSTANCES_MATERIALS_SIGNATURES, INSTANCES_MATERIALS_BOUNCE_SIGNATURES, INSTANCES_MATERIALS_TRANSPARENCY_SIGNATURES, INSTANCES_MATERIALS_TREE_SIGNATURES, INSTANCES_MATERIALS_HEAT_SIGNATURES, INSTANCES_MATERIALS_DYNAMIC_SIGNATURES, BVH_FAST_BATCH_SIGNATURES, INSTANCES_MATERIALS_REBUILD_ALL_SIGNATURES, DEBUG_SIGNATURES):
+        for table in (SIGNATURES, INSTANCES_SIGNATURES, INSTANCES_SHADE_SIGNATURES, INSTANCES_TILES_SIGNATURES, INSTANCES_BUILD_SIGNATURES, BVH_FAST_SIGNATURES, HEATMAP_SIGNATURES, MATERIALS_SIGNATURES, MATERIALS_BOUNCE_SIGNATURES, MATERIALS_TILES_SIGNATURES, MATERIALS_TRANSPARENCY_SIGNATURES, MATERIALS_TREE_SIGNATURES, MATERIALS_HEAT_SIGNATURES, MATERIALS_DYNAMIC_SIGNATURES, INSTANCES_MATERIALS_SIGNATURES, INSTANCES_MATERIALS_BOUNCE_SIGNATURES, INSTANCES_MATERIALS_TRANSPARENCY_SIGNATURES, INSTANCES_MATERIALS_TREE_SIGNATURES, INSTANCES_MATERIALS_HEAT_SIGNATURES, INSTANCES_MATERIALS_DYNAMIC_SIGNATURES, BVH_FAST_BATCH_SIGNATURES, INSTANCES_MATERIALS_REBUILD_ALL_SIGNATURES, WIDE_SIGNATURES, DEBUG_SIGNATURES):
             for name, (res, args) in table.items():
                 fn = getattr(L, name)
                 fn.restype = res
@@ -322,7 +330,7 @@ def lib():
             L = C.CDLL(LIB_PATH)
         except OSError as e:  # pragma: no cover - depends on the box
             raise SnailError("cannot load %s: %s" % (LIB_PATH, e)) from e
-        for table in (SIGNATURES, INSTANCES_SIGNATURES, INSTANCES_SHADE_SIGNATURES, INSTANCES_TILES_SIGNATURES, INSTANCES_BUILD_SIGNATURES, BVH_FAST_SIGNATURES, HEATMAP_SIGNATURES, MATERIALS_SIGNATURES, MATERIALS_BOUNCE_SIGNATURES, MATERIALS_TILES_SIGNATURES, MATERIALS_TRANSPARENCY_SIGNATURES, MATERIALS_TREE_SIGNATURES, MATERIALS_HEAT_SIGNATURES, MATERIALS_DYNAMIC_SIGNATURES, INSTANCES_MATERIALS_SIGNATURES, INSTANCES_MATERIALS_BOUNCE_SIGNATURES, INSTANCES_MATERIALS_TRANSPARENCY_SIGNATURES, INSTANCES_MATERIALS_TREE_SIGNATURES, INSTANCES_MATERIALS_HEAT_SIGNATURES, INSTANCES_MATERIALS_DYNAMIC_SIGNATURES, BVH_FAST_BATCH_SIGNATURES, INSTANCES_MATERIALS_REBUILD_ALL_SIGNATURES):
+        for table in (SIGNATURES, INSTANCES_SIGNATURES, INSTANCES_SHADE_SIGNATURES, INSTANCES_TILES_SIGNATURES, INSTANCES_BUILD_SIGNATURES, BVH_FAST_SIGNATURES, HEATMAP_SIGNATURES, MATERIALS_SIGNATURES, MATERIALS_BOUNCE_SIGNATURES, MATERIALS_TILES_SIGNATURES, MATERIALS_TRANSPARENCY_SIGNATURES, MATERIALS_TREE_SIGNATURES, MATERIALS_HEAT_SIGNATURES, MATERIALS_DYNAMIC_SIGNATURES, INSTANCES_MATERIALS_SIGNATURES, INSTANCES_MATERIALS_BOUNCE_SIGNATURES, INSTANCES_MATERIALS_TRANSPARENCY_SIGNATURES, INSTANCES_MATERIALS_TREE_SIGNATURES, INSTANCES_MATERIALS_HEAT_SIGNATURES, INSTANCES_MATERIALS_DYNAMIC_SIGNATURES, BVH_FAST_BATCH_SIGNATURES, INSTANCES_MATERIALS_REBUILD_ALL_SIGNATURES, WIDE_SIGNATURES):
             for name, (res, args) in table.items():
                 fn = getattr(L, name)
                 fn.restype = res

@@ -45,6 +45,7 @@
 #include "../../include/snail_instances.h"
 #include "../../include/snail_bvh_fast.h"
 #include "../../include/snail_bvh_fast_batch.h"
+#include "../../include/snail_wide.h"
 #include "host_sse.h"
 #ifdef SNAIL_DEBUG_API
 #include "../../include/snail_hip_debug.h"
@@ -107,6 +108,7 @@ void snail_set_error(const char *fmt, ...) {
 #include "instances_build.inc"   // ... of the top-level tree over instances (bvh_fast.inc, of a plain scene, follows lbvh.inc)
 #include "materials_dynamic.inc"  // the ShTriangle records of a material set packed on the device: plain fp32, once for both arithmetics
 #include "instances_materials_dynamic.inc"  // ... of several BLASes of an instanced set in one launch
+#include "wide.inc"               // BVH::WideTrace, one ray per lane, and the photon records: scalar IEEE fp32, once for both arithmetics
 
 // A launch in the scene's arithmetic: dev::K, or dev_sse::K with the same argument record (the two namespaces are the same text, so the
 // records have the same layout; they are distinct types, hence the copy).  K comes last because its template arguments hold commas.
@@ -193,6 +195,9 @@ struct SnailScene {
 	// deferred-packet lists of snail_trace_rays*, same slot discipline
 	struct RayDefer { int *p = nullptr; size_t cap = 0; hipEvent_t done = nullptr; bool used = false; } rayDefer[kDeferSlots];
 	unsigned rayCount = 0;
+	// distances and block counts of snail_photons_trace_dev (wide_host.inc), same slot discipline
+	struct WideScratch { char *p = nullptr; size_t cap = 0; hipEvent_t done = nullptr; bool used = false; } wide[kDeferSlots];
+	unsigned wideCount = 0;
 	// ---- concurrency (include/snail_hip.h, "Concurrency"): the reference hands ONE const Scene<AccStruct> to `threads` pthread workers, each of which
 	// calls TraversePrimary / TraverseShadow on it (src/render.cpp:214-267, src/thread_pool.cpp:151-180, src/scene_trace.cpp:119-120,:560-563) ----
 	// mu: everything a launch books in this handle -- the slot rotations above, the origin-relative node cache, scratch growth, lastBlocks, arith.
@@ -1002,6 +1007,8 @@ void snail_scene_destroy(SnailScene *s) {
 	for(int k = 0; k < SnailScene::kDeferSlots; k++) {
 		if(s->rayDefer[k].p) (void)hipFree(s->rayDefer[k].p);
 		if(s->rayDefer[k].done) (void)hipEventDestroy(s->rayDefer[k].done);
+		if(s->wide[k].p) (void)hipFree(s->wide[k].p);
+		if(s->wide[k].done) (void)hipEventDestroy(s->wide[k].done);
 		if(s->deferDone[k]) (void)hipEventDestroy(s->deferDone[k]);
 		if(s->shade[k].done) (void)hipEventDestroy(s->shade[k].done);
 	}
@@ -1817,6 +1824,7 @@ int snail_account_primary(SnailScene *s, const float cam[13], int resx, int resy
 
 #include "bvh_fast.inc"
 #include "bvh_fast_batch.inc"
+#include "wide_host.inc"
 #include "render_host.inc"
 #include "instances_host.inc"
 #include "instances_tiles_host.inc"

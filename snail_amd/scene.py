@@ -701,6 +701,71 @@ class Scene:
         _lib.check(rc, "snail_trace_shadow")
         return stats
 
+    # ---- rays that form no packets (include/snail_wide.h) -------------------------------------
+    def wide_trace(self, origin, dir, dist, idir=None, indices=None, start_node: int = 0, visits=None, stats=None, stream=None):
+        """BVH::WideTrace with one ray per lane (snail_wide_trace_dev): origin / dir / idir = float32 device tensors [n, 3] (idir None =
+        1 / dir), dist = float32 [n], IN/OUT (the walk prunes against it).  indices = int32 device tensor of distinct ray numbers (None = all
+        rays); rays not listed keep their dist.  visits = int32 [n, 2], per ray {box tests, triangle tests}; stats = int64 [2] device
+        accumulator of the same.  -> dist."""
+        n = int(dist.numel())
+        for name, a in (("origin", origin), ("dir", dir), ("idir", idir)):
+            if a is not None and int(a.numel()) != 3 * n:
+                raise ValueError("wide_trace: %s must hold 3 values per ray (%d rays)" % (name, n))
+        if visits is not None and int(visits.numel()) != 2 * n:
+            raise ValueError("wide_trace: visits must hold 2 values per ray (%d rays)" % n)
+        if indices is not None and int(indices.numel()) == 0:
+            return dist      # (an empty tensor has no address: the C-ABI would read NULL = all rays)
+        rc =_lib.lib().snail_wide_trace_dev(self._h, n, _lib.ptr(origin), _lib.ptr(dir), _lib.ptr(idir), _lib.ptr(indices),
+                                             0 if indices is None else int(indices.numel()), _lib.ptr(dist), int(start_node), _lib.ptr(visits),
+                                             _lib.ptr(stats), _stream_ptr(stream))
+        _lib.check(rc, "snail_wide_trace_dev")
+        return dist
+
+    def wide_trace_host(self, origin, dir, dist, idir=None, indices=None, start_node: int = 0, visits=None):
+        """The same on NumPy arrays (snail_wide_trace); dist (and visits) are updated in place.  -> uint64[2] {box tests, triangle tests}."""
+        stats = np.zeros(2, dtype=np.uint64)
+        rc = _lib.lib().snail_wide_trace(self._h, int(dist.size), _lib.ptr(origin), _lib.ptr(dir), _lib.ptr(idir), _lib.ptr(indices),
+                                         0 if indices is None else int(indices.size), _lib.ptr(dist), int(start_node), _lib.ptr(visits), _lib.ptr(stats))
+        _lib.check(rc, "snail_wide_trace")
+        return stats
+
+    def trace_photons(self, origin, dir, lights7, count: int, out=None, n_photons=None, stats=None, stream=None):
+        """The photon pass of TracePhotons (snail_photons_trace_dev): ray l * count + n is photon n of light l; origin / dir = float32 device
+        tensors [n_lights * count, 3], lights7 = host array [n_lights, 7] (read for the colours).  -> (out, n_photons): out = uint8 device
+        tensor [n_lights * count, 32] viewed as photons.PHOTON records after .cpu().numpy(), of which the first n_photons (int32 device tensor
+        [1]) were written, in ray order; the rest of `out` is not touched."""
+        torch = _torch()
+        l7 = np.ascontiguousarray(lights7, dtype=np.float32).reshape(-1, 7)
+        n = len(l7) * int(count)
+        if int(origin.numel()) != 3 * n or int(dir.numel()) != 3 * n:
+            raise ValueError("trace_photons: origin and dir must hold 3 values for each of the %d x %d rays" % (len(l7), count))
+        with _filled_on(stream):
+            if out is None:
+                out = torch.zeros((max(n, 1), 32), dtype=torch.uint8, device=self._dev())
+            if n_photons is None:
+                n_photons = torch.zeros(1, dtype=torch.int32, device=self._dev())
+        rc = _lib.lib().snail_photons_trace_dev(self._h, len(l7), int(count), _lib.ptr(origin), _lib.ptr(dir), _lib.ptr(l7), _lib.ptr(out),
+                                                _lib.ptr(n_photons), _lib.ptr(stats), _stream_ptr(stream))
+        _lib.check(rc, "snail_photons_trace_dev")
+        return out, n_photons
+
+    def trace_photons_host(self, origin, dir, lights7, count: int):
+        """The same on NumPy arrays (snail_photons_trace).  -> (photons.PHOTON records [n_photons], uint64[2] {box tests, triangle tests})."""
+        from .photons import PHOTON
+        l7 = np.ascontiguousarray(lights7, dtype=np.float32).reshape(-1, 7)
+        n = len(l7) * int(count)
+        o = np.ascontiguousarray(origin, dtype=np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(dir, dtype=np.float32).reshape(-1, 3)
+        if len(o) != n or len(d) != n:
+            raise ValueError("trace_photons_host: origin and dir must hold 3 values for each of the %d x %d rays" % (len(l7), count))
+        out = np.zeros(max(n, 1), dtype=PHOTON)
+        got = C.c_int32(0)
+        stats = np.zeros(2, dtype=np.uint64)
+        rc = _lib.lib().snail_photons_trace(self._h, len(l7), int(count), _lib.ptr(o), _lib.ptr(d), _lib.ptr(l7), _lib.ptr(out), C.addressof(got),
+                                            _lib.ptr(stats))
+        _lib.check(rc, "snail_photons_trace")
+        return out[:got.value], stats
+
     # ---- measurement --------------------------------------------------------------------------
     def account_primary(self, cam: Camera, resx: int, resy: int, rect=None) -> np.ndarray:
         """{rays, sum V_n, sum V_t, hits} of the single-ray accounting walk."""
