@@ -116,7 +116,7 @@ int instHeatArgsOk(const char *fn, const SnailInstances *h, const float *cam, in
 // output is given -- through k_inst_store into packet-major bytes (bgrPackets) or the planes of J's tiles.  mu held.
 int instancesHeat(SnailInstances *h, const char *fn, const float cam[13], int resx, int resy, const int32_t *dXY, int np, const float *lights7, int nLights, int flags,
 				  const float *tint, uint8_t *bgrPackets, const InstTileJob *J, uint32_t *dPacketStats, uint64_t *dStats, hipStream_t st) {
-	if(!dXY) { if(int rc = instancesFrameList(h, resx, resy, &dXY, &np)) return rc; }
+	if(!dXY) { if(int rc = h->frameLists.get(resx, resy, &dXY, &np)) return rc; }
 	if(np > (1 << 24)) { snail_set_error("%s: more than 2^24 packets", fn); return 1; }
 	const bool aa = (flags & SNAIL_RENDER_AA4) != 0, refl = (flags & SNAIL_RENDER_REFLECTIONS) != 0;
 	const size_t n = aa ? (size_t)np * 4 : (size_t)np;
@@ -235,7 +235,7 @@ int snail_instances_render_heat_frame(SnailInstances *h, const float cam[13], in
 		std::lock_guard<std::mutex> lock(h->mu);
 		const int32_t *dXY = nullptr;
 		int n = 0;
-		if(int rc = instancesFrameList(h, resx, resy, &dXY, &n)) return rc;
+		if(int rc = h->frameLists.get(resx, resy, &dXY, &n)) return rc;
 		if(int rc = instancesHeat(h, fn, cam, resx, resy, dXY, np, lights7, nLights, flags, nullptr, bgr, nullptr, nullptr, stats ? hc.stats() : nullptr, hc.stream())) return rc;
 		// (under mu: the cached frame list may be dropped by a later call, which first waits for everything enqueued)
 		if(int rc = snail_packets_bgr_to_frame_dev(dXY, np, resx, resy, bgr, dImg, (int)row, hc.stream())) return rc;

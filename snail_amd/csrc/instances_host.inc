@@ -1,7 +1,6 @@
 // instances_host.inc -- host side of the two-level instanced scenes (include/snail_instances.h); included at
 // the end of snail_hip.hip.  The build is in dbvh_build.cpp, the kernels in instances.inc.
 
-namespace { struct InstTileJob; void freeInstTileJob(InstTileJob *); } // instances_tiles_host.inc: the cached lists of snail_instances_render_tiles
 struct SnailInstances {
 	int device = 0;
 	std::vector<SnailScene *> blas;
@@ -77,8 +76,7 @@ struct SnailInstances {
 	} shade[kShadeSets];
 	unsigned shadeCount = 0;
 	// packet lists of whole frames (row-major over the 16x16 packet grid), by grid size; built once each
-	struct FrameList { int pw, ph; int32_t *d; };
-	std::vector<FrameList> frameLists;
+	FrameLists frameLists;
 	// snail_instances_render_tiles: ONE cached tile job per handle, whose calls take turns
 	std::mutex renderMu;
 	InstTileJob *tileJob = nullptr;
@@ -286,9 +284,7 @@ static int instancesFramePackets(SnailInstances *h, const char *fn, HostCallScop
 								 float **dT, float **dU, float **dV, int32_t **dI, int32_t **dTri, int *nPackets) {
 	if(!cam || resx <= 0 || resy <= 0) { snail_set_error("%s: bad camera or resolution", fn); return 1; }
 	const int pw = (resx + 15) / 16, ph = (resy + 15) / 16, np = pw * ph;
-	std::vector<int32_t> xy((size_t)np * 2);
-	for(int y = 0; y < ph; y++)
-		for(int x = 0; x < pw; x++) { xy[((size_t)y * pw + x) * 2] = x * 16; xy[((size_t)y * pw + x) * 2 + 1] = y * 16; }
+	const std::vector<int32_t> xy = frameGrid(pw, ph);
 	typedef HostCallScope H;
 	const size_t rays = (size_t)np * 256;
 	if(int rc = hc.reserve(H::pad(xy.size() * 4) + (all ? 5 : 1) * H::pad(rays * 4) + H::pad(rays * 3))) return rc;
@@ -384,28 +380,6 @@ int instancesShade(SnailInstances *h, const char *fn, const float cam[13], int r
 	return instancesEnd(h, st);
 }
 
-// the packet list of a whole frame, cached in the handle by packet-grid size (mu held)
-int instancesFrameList(SnailInstances *h, int resx, int resy, const int32_t **dXY, int *np) {
-	const int pw = (resx + 15) / 16, ph = (resy + 15) / 16;
-	*np = pw * ph;
-	for(auto &f : h->frameLists)
-		if(f.pw == pw && f.ph == ph) { *dXY = f.d; return 0; }
-	if(h->frameLists.size() >= 16) { // (a host that keeps changing its resolution: start over once nothing reads the old lists)
-		HIP_TRY(hipDeviceSynchronize());
-		for(auto &f : h->frameLists) (void)hipFree(f.d);
-		h->frameLists.clear();
-	}
-	std::vector<int32_t> xy((size_t)pw * ph * 2);
-	for(int y = 0; y < ph; y++)
-		for(int x = 0; x < pw; x++) { xy[((size_t)y * pw + x) * 2] = x * 16; xy[((size_t)y * pw + x) * 2 + 1] = y * 16; }
-	SnailInstances::FrameList f = {pw, ph, nullptr};
-	HIP_TRY(hipMalloc((void **)&f.d, xy.size() * 4));
-	if(hipMemcpy(f.d, xy.data(), xy.size() * 4, hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(f.d); snail_set_error("frame packet list: upload failed"); return 1; }
-	h->frameLists.push_back(f);
-	*dXY = f.d;
-	return 0;
-}
-
 // the next set of intermediates of the handle, grown if need be, its previous user's last kernel waited for on `st` (mu held).  tiles: with the
 // float colours and the double-resolution packet list of snail_instances_tiles.h
 int instancesNextSet(SnailInstances *h, size_t np, bool refl, bool tiles, hipStream_t st, SnailInstances::ShadeSet **out) {
@@ -429,7 +403,7 @@ int instancesNextSet(SnailInstances *h, size_t np, bool refl, bool tiles, hipStr
 int instancesShadeDev(SnailInstances *h, const char *fn, const float cam[13], int resx, int resy, const int32_t *dXY, int np, const float *lights7, int nLights,
 					  const float ambient[3], const float color[3], int flags, uint8_t *frame, int pitch, uint8_t *bgrPackets, uint64_t *dStats, hipStream_t st) {
 	const bool refl = (flags & SNAIL_WHITTED_REFLECTIONS) != 0;
-	if(!dXY) { if(int rc = instancesFrameList(h, resx, resy, &dXY, &np)) return rc; }
+	if(!dXY) { if(int rc = h->frameLists.get(resx, resy, &dXY, &np)) return rc; }
 	SnailInstances::ShadeSet *Wp = nullptr;
 	if(int rc = instancesNextSet(h, (size_t)np, refl, false, st, &Wp)) return rc;
 	SnailInstances::ShadeSet &W = *Wp;
@@ -507,7 +481,7 @@ void snail_instances_destroy(SnailInstances *h) {
 		if(w.base) (void)hipFree(w.base);
 		if(w.done) (void)hipEventDestroy(w.done);
 	}
-	for(auto &f : h->frameLists) (void)hipFree(f.d);
+	h->frameLists.release();
 	freeInstTileJob(h->tileJob);
 	delete h;
 }
@@ -685,9 +659,7 @@ int snail_instances_render_image(SnailInstances *h, const float cam[13], int res
 	if(hc.rc) return hc.rc;
 	if(int rc = hc.zeroStats()) return rc;
 	const int pw = (resx + 15) / 16, ph = (resy + 15) / 16, np = pw * ph;
-	std::vector<int32_t> xy((size_t)np * 2);
-	for(int y = 0; y < ph; y++)
-		for(int x = 0; x < pw; x++) { xy[((size_t)y * pw + x) * 2] = x * 16; xy[((size_t)y * pw + x) * 2 + 1] = y * 16; }
+	const std::vector<int32_t> xy = frameGrid(pw, ph);
 	typedef HostCallScope H;
 	const size_t imgBytes = (size_t)pitch * resy;
 	if(int rc = hc.reserve(H::pad(xy.size() * 4) + H::pad(SnailInstances::ShadeBufs::bytes((size_t)np, nLights, refl)) + H::pad(imgBytes + 4))) return rc;

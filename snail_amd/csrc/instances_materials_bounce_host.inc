@@ -131,9 +131,7 @@ int snail_instances_materials_bounce_dev(SnailInstancesMaterials *m, const float
 	if(int rc = checkIMatBounceFrameArgs(fn, cam, resx, resy, lights7, nLights, ambient, flags)) return rc;
 	if(int rc = checkIMat(m, fn)) return rc;
 	if(!frame || pitch < resx * 3) { snail_set_error("%s: null frame or a pitch below 3 * resx", fn); return 1; }
-	DeviceGuard guard(m->device);
-	std::lock_guard<std::mutex> lock(m->inst->mu);
-	return imatShadeDev(m, fn, cam, resx, resy, nullptr, 0, lights7, nLights, ambient, frame, pitch, nullptr, dStats, (hipStream_t)stream, (flags & SNAIL_RENDER_REFLECTIONS) != 0);
+	return frameDev<IMatLevels>(m, fn, cam, resx, resy, lights7, nLights, ambient, (flags & SNAIL_RENDER_REFLECTIONS) != 0, 0, frame, pitch, nullptr, dStats, stream);
 }
 
 int snail_instances_materials_bounce_packets_dev(SnailInstancesMaterials *m, const float cam[13], int resx, int resy, const int32_t *dPacketXY, int nPackets,
@@ -145,10 +143,7 @@ int snail_instances_materials_bounce_packets_dev(SnailInstancesMaterials *m, con
 	if(!dPacketXY && nPackets > 0) { snail_set_error("%s: null packet list", fn); return 1; }
 	if(nPackets <= 0) return 0;
 	if(!bgrPackets || ((unsigned long long)bgrPackets & 3)) { snail_set_error("%s: null or unaligned output", fn); return 1; }
-	DeviceGuard guard(m->device);
-	std::lock_guard<std::mutex> lock(m->inst->mu);
-	return imatShadeDev(m, fn, cam, resx, resy, dPacketXY, nPackets, lights7, nLights, ambient, nullptr, 0, bgrPackets, dStats, (hipStream_t)stream,
-						(flags & SNAIL_RENDER_REFLECTIONS) != 0);
+	return framePacketsDev<IMatLevels>(m, fn, cam, resx, resy, dPacketXY, nPackets, lights7, nLights, ambient, (flags & SNAIL_RENDER_REFLECTIONS) != 0, 0, bgrPackets, nullptr, dStats, stream);
 }
 
 int snail_instances_materials_bounce_image(SnailInstancesMaterials *m, const float cam[13], int resx, int resy, const float *lights7, int nLights,
@@ -157,33 +152,7 @@ int snail_instances_materials_bounce_image(SnailInstancesMaterials *m, const flo
 	if(int rc = checkIMatBounceFrameArgs(fn, cam, resx, resy, lights7, nLights, ambient, flags)) return rc;
 	if(int rc = checkIMat(m, fn)) return rc;
 	if(!image || pitch < resx * 3) { snail_set_error("%s: null image or a pitch below 3 * resx", fn); return 1; }
-	const bool refl = (flags & SNAIL_RENDER_REFLECTIONS) != 0;
-	SnailInstances *h = m->inst;
-	DeviceGuard guard(m->device);
-	HostCallScope hc(h->blas[0], fn);   // (a stream, counters and staging arena of the call's own; the BLAS handle only lends its free list)
-	if(hc.rc) return hc.rc;
-	if(int rc = hc.zeroStats()) return rc;
-	const int pw = (resx + 15) / 16, ph = (resy + 15) / 16, np = pw * ph;
-	std::vector<int32_t> xy((size_t)np * 2);
-	for(int y = 0; y < ph; y++)
-		for(int x = 0; x < pw; x++) { xy[((size_t)y * pw + x) * 2] = x * 16; xy[((size_t)y * pw + x) * 2 + 1] = y * 16; }
-	typedef HostCallScope H;
-	const size_t imgBytes = (size_t)pitch * resy, bufBytes = SnailInstancesMaterials::Bufs::bytes((size_t)np, nLights),
-				 bounceBytes = refl ? SnailInstancesMaterials::BounceBufs::bytes((size_t)np, nLights) : 0;
-	if(int rc = hc.reserve(H::pad(xy.size() * 4) + H::pad(bufBytes) + (refl ? H::pad(bounceBytes) : 0) + H::pad(imgBytes + 4))) return rc;
-	void *dXY = nullptr;
-	if(int rc = hc.put(&dXY, xy.data(), xy.size() * 4)) return rc;
-	SnailInstancesMaterials::Bufs W;
-	W.carve((char *)hc.carve(bufBytes), (size_t)np);
-	SnailInstancesMaterials::BounceBufs RB;
-	if(refl) RB.carve((char *)hc.carve(bounceBytes), (size_t)np, nLights);
-	uint8_t *dImg = (uint8_t *)hc.carve(imgBytes + 4);
-	{
-		std::lock_guard<std::mutex> lock(h->mu);
-		if(int rc = imatShade(m, fn, cam, resx, resy, (const int32_t *)dXY, np, lights7, nLights, ambient, dImg, pitch, nullptr, W, refl ? &RB : nullptr, hc.stats(), hc.stream())) return rc;
-	}
-	HIP_TRY(hipMemcpy2DAsync(image, (size_t)pitch, dImg, (size_t)pitch, (size_t)resx * 3, (size_t)resy, hipMemcpyDeviceToHost, hc.stream()));
-	return hc.finish(stats);
+	return frameImage<IMatLevels>(m, fn, cam, resx, resy, lights7, nLights, ambient, (flags & SNAIL_RENDER_REFLECTIONS) != 0, 0, image, pitch, nullptr, stats);
 }
 
 } // extern "C"

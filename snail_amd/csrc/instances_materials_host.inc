@@ -2,10 +2,12 @@
 // records and maps, ONE material and texture list) and the staged launches of instances_materials.inc (k_inst_frame with barycentrics ->
 // k_imat_sample -> k_imat_light per (packet, light) -> k_mat_final).  Included after materials_host.inc, whose host-side checks it calls.  With the
 // one mirrored bounce (instances_materials_bounce_host.inc, included next) the nested call stands between the sample stage and the lights.
+// The handle's sets of intermediates and frame lists are shading_sets_host.inc's; the frames' bodies from DeviceGuard on are materials_levels_host.inc's
+// (frameDev, framePacketsDev, frameImage) over IMatLevels, the instanced scene's kind, defined here beside imatShade.
 #include "../../include/snail_instances_materials.h"
 
 struct SnailInstancesMaterialsDyn;   // instances_materials_dynamic_host.inc: what a set of snail_instances_materials_create_dev carries besides
-struct SnailInstancesMaterials {
+struct SnailInstancesMaterials : ShadeSets {   // (shading_sets_host.inc: the sets of intermediates, the frame lists, the tile job, the level budget)
 	SnailInstances *inst = nullptr;
 	SnailInstancesMaterialsDyn *dyn = nullptr;   // (null: no BLAS whose records are packed on the device -- the two older creators' sets)
 	int device = 0;
@@ -17,7 +19,7 @@ struct SnailInstancesMaterials {
 	const dev::MatRec *dMats = nullptr;
 	const dev::TexRec *dTex = nullptr;
 	const unsigned char *dTexels = nullptr;
-	// intermediates of the lit frames, one set per launch in flight (round-robin, each guarded by an event; booked under the instances handle's mu)
+	// a set's base part: the intermediates of the lit frames
 	struct Bufs {
 		float *hitT = nullptr, *hitU = nullptr, *hitV = nullptr, *samples = nullptr, *sDist = nullptr;
 		int *hitInst = nullptr, *hitTri = nullptr;
@@ -43,34 +45,7 @@ struct SnailInstancesMaterials {
 			rMask = (unsigned char *)(base + (size_t)(26 + (nLights > 0 ? nLights : 0)) * plane);
 		}
 	};
-	struct Set {
-		char *base = nullptr;
-		size_t packets = 0;
-		int lights = 0;
-		char *bounce = nullptr;   // allocated only once a bounce has been asked for; grown under the same rule
-		size_t bouncePackets = 0;
-		int bounceLights = 0;
-		char *transp = nullptr;   // the levels of the transparency continuation (instances_materials_transparency_host.inc): only once asked for, sized by the depth
-		size_t transpBytes = 0;
-		char *tiles = nullptr;    // the tile renderer's part (instances_materials_tree_host.inc): the float colours of a whole packet list and, under 4x
-		size_t tilesPackets = 0;  // antialiasing, its sub-packet list; only once asked for, grown under the same rule
-		uint32_t *pstats = nullptr;   // snail_instances_materials_heatmap.h: the launch's per-packet TreeStats [packets][4] when the caller keeps none of its
-		size_t pstatsPackets = 0;     // own; only once asked for, grown under the same rule
-		hipEvent_t done = nullptr;
-		bool used = false;
-	};
-	enum { kSets = 8 };
-	Set set[kSets];
-	unsigned setCount = 0;
-	struct FrameList { int pw, ph; int32_t *d; };
-	std::vector<FrameList> frameLists;   // a whole frame's packet list, cached by packet-grid size
-	// snail_instances_materials_tree_render_tiles: ONE cached tile job per set (the structure of instances_tiles_host.inc); its calls take turns under
-	// renderMu, which is taken before the instances handle's mu
-	std::mutex renderMu;
-	InstTileJob *tileJob = nullptr;
-	// snail_instances_materials_set_level_budget (instances_materials_tree_host.inc): the bytes the levels of one group of intermediates may take;
-	// 0 = SNAIL_MAT_LEVEL_BUDGET
-	uint64_t levelBudget = 0;
+	typedef SnailMaterials::TileBufs TileBufs;   // (the tile renderer's part holds colours and a sub-packet list: no instance data)
 };
 
 namespace {
@@ -158,79 +133,100 @@ int imatShade(SnailInstancesMaterials *m, const char *fn, const float cam[13], i
 	return instancesEnd(h, st);
 }
 
-// the packet list of a whole frame, cached in the set by packet-grid size as instancesFrameList caches it in the handle (the handle's mu held)
-int imatFrameList(SnailInstancesMaterials *m, int resx, int resy, const int32_t **dXY, int *np) {
-	const int pw = (resx + 15) / 16, ph = (resy + 15) / 16;
-	*np = pw * ph;
-	for(auto &f : m->frameLists)
-		if(f.pw == pw && f.ph == ph) { *dXY = f.d; return 0; }
-	if(m->frameLists.size() >= 16) {
-		HIP_TRY(hipDeviceSynchronize());
-		for(auto &f : m->frameLists) (void)hipFree(f.d);
-		m->frameLists.clear();
-	}
-	std::vector<int32_t> xy((size_t)pw * ph * 2);
-	for(int y = 0; y < ph; y++)
-		for(int x = 0; x < pw; x++) { xy[((size_t)y * pw + x) * 2] = x * 16; xy[((size_t)y * pw + x) * 2 + 1] = y * 16; }
-	SnailInstancesMaterials::FrameList f = {pw, ph, nullptr};
-	HIP_TRY(hipMalloc((void **)&f.d, xy.size() * 4));
-	if(hipMemcpy(f.d, xy.data(), xy.size() * 4, hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(f.d); snail_set_error("frame packet list: upload failed"); return 1; }
-	m->frameLists.push_back(f);
-	*dXY = f.d;
-	return 0;
-}
+#define SNAIL_ITRANSP_LAUNCH(SSE, GRID, STREAM, A, ...) SNAIL_LAUNCH(SSE, ITranspArgs, GRID, dim3(64), 0, STREAM, A, __VA_ARGS__)
 
-// the next set of intermediates for np packets (the handle's mu held), grown if need be, its previous user waited for on st; refl: with the
-// bounce's part
-int imatNextSet(SnailInstancesMaterials *m, int np, int nLights, bool refl, hipStream_t st, SnailInstancesMaterials::Set **out) {
-	SnailInstancesMaterials::Set &W = m->set[m->setCount++ % SnailInstancesMaterials::kSets];
-	if(!W.base || W.packets < (size_t)np || W.lights < nLights) {   // grown: its previous user may still be running
-		HIP_TRY(hipDeviceSynchronize());
-		if(W.base) (void)hipFree(W.base);
-		const size_t packets = std::max(W.packets, (size_t)np);
-		const int lights = std::max(W.lights, nLights);
-		W.base = nullptr; W.packets = 0; W.lights = 0; W.used = false;
-		HIP_TRY(hipMalloc((void **)&W.base, SnailInstancesMaterials::Bufs::bytes(packets, lights)));
-		W.packets = packets; W.lights = lights;
+// The instanced scene's kind of the frame bodies and the level driver (materials_levels_host.inc); the handle's mu held.  Every launch is booked through
+// instancesBegin / instancesEnd, so the frame is ordered against snail_instances_update and snail_instances_rebuild_dev as a walk is.  The sample
+// and light stages take an ITranspArgs of the kind's own: its MatArgs is the frame's, copied into the scene-free stages' record whenever a level
+// changes it.
+struct IMatLevels : LevelsFrame {
+	typedef SnailInstancesMaterials Handle;
+	typedef SnailInstancesMaterials::Bufs Bufs;
+	typedef SnailInstancesMaterials::BounceBufs BounceBufs;
+	SnailInstancesMaterials *m;
+	SnailInstances *h;
+	dev::InstArgs I;
+	dev::ITranspArgs S;
+	IMatLevels(SnailInstancesMaterials *m_, const char *fn_, hipStream_t st_, uint32_t *pstats_, int np_, int nLights) : LevelsFrame(fn_, st_, pstats_, np_, nLights), m(m_), h(m_->inst) {}
+	int begin() { return instancesBegin(h, fn, I, &sse, &deep, st); }
+	// (the stages enqueued so far are booked as every launch of the handle is, whatever failed)
+	int end() { return instancesEnd(h, st); }
+	int primary(const float cam[13], int resx, int resy, const int32_t *dXY, const Bufs &W, uint64_t *dStats) {
+		dev::InstArgs P = I;
+		P.g = makeGen(cam, resx, resy);
+		P.resx = resx; P.resy = resy;
+		P.packetXY = (const int2 *)dXY; P.nPackets = np;
+		P.t = W.hitT; P.u = W.hitU; P.v = W.hitV; P.instOut = W.hitInst; P.triOut = W.hitTri;
+		P.stats = (dev::u64 *)dStats;
+		P.pstats = pstats;   // (k_inst_frame books per packet whenever it is given the array)
+		if(deep) SNAIL_INST_LAUNCH(sse, grid, st, P, k_inst_frame<true>);
+		else SNAIL_INST_LAUNCH(sse, grid, st, P, k_inst_frame<false>);
+		return launched("k_inst_frame");
 	}
-	if(refl && (!W.bounce || W.bouncePackets < (size_t)np || W.bounceLights < nLights)) {   // the bounce's part: only when asked for, grown the same way
-		HIP_TRY(hipDeviceSynchronize());
-		if(W.bounce) (void)hipFree(W.bounce);
-		const size_t packets = std::max(W.bouncePackets, (size_t)np);
-		const int lights = std::max(W.bounceLights, nLights);
-		W.bounce = nullptr; W.bouncePackets = 0; W.bounceLights = 0; W.used = false;
-		HIP_TRY(hipMalloc((void **)&W.bounce, SnailInstancesMaterials::BounceBufs::bytes(packets, lights)));
-		W.bouncePackets = packets; W.bounceLights = lights;
+	dev::MatArgs &frameArgs(dev::TreeArgs &, const float cam[13], int resx, int resy, const int32_t *dXY, const Bufs &W) {
+		memset(&S, 0, sizeof(S));
+		imatFillArgs(m, S.a, I, cam, resx, resy, dXY, np);
+		S.a.m.s.hitId = W.hitTri; S.a.hitInst = W.hitInst;
+		return S.a.m;
 	}
-	if(!W.done) HIP_TRY(hipEventCreateWithFlags(&W.done, hipEventDisableTiming));
-	if(W.used) HIP_TRY(hipStreamWaitEvent(st, W.done, 0));
-	*out = &W;
-	return 0;
-}
-// after the set's user has enqueued its stages (rc: how that went): the event is recorded also when a stage failed after earlier ones were
-// enqueued (matSetDone's rule)
-int imatSetDone(SnailInstancesMaterials::Set &W, const char *fn, int rc, hipStream_t st) {
-	if(hipEventRecord(W.done, st) == hipSuccess) W.used = true;
-	else {
-		W.packets = 0; W.bouncePackets = 0; W.tilesPackets = 0; W.pstatsPackets = 0; W.used = false;   // its next user synchronises the device
-		if(!rc) { snail_set_error("%s: hipEventRecord failed", fn); return 1; }
+	// the object of the walk, of the generator and of the mirror stage is the instance slot, the sample stages' rObj the triIds
+	static int *object(const BounceBufs &R) { return R.rInst; }
+	void level(dev::TreeArgs &G, const BounceBufs &R, const int32_t *order, bool slotAsObject) {
+		S.a.m.s.rObj = slotAsObject ? R.rInst : R.rTri;
+		S.rInst = R.rInst;
+		S.inOrder = order;
+		G.t.m = S.a.m;
 	}
-	return rc;
-}
-
-// snail_instances_render_materials_dev / _packets_dev and, with refl, snail_instances_materials_bounce_dev / _packets_dev (the handle's mu held)
-int imatShadeDev(SnailInstancesMaterials *m, const char *fn, const float cam[13], int resx, int resy, const int32_t *dXY, int np, const float *lights7, int nLights,
-				 const float ambient[3], uint8_t *frame, int pitch, uint8_t *bgrPackets, uint64_t *dStats, hipStream_t st, bool refl = false) {
-	if(!dXY) { if(int rc = imatFrameList(m, resx, resy, &dXY, &np)) return rc; }
-	SnailInstancesMaterials::Set *Wp = nullptr;
-	if(int rc = imatNextSet(m, np, nLights, refl, st, &Wp)) return rc;
-	SnailInstancesMaterials::Bufs B;
-	B.carve(Wp->base, (size_t)np);
-	SnailInstancesMaterials::BounceBufs RB;
-	if(refl) RB.carve(Wp->bounce, (size_t)np, nLights);
-	const int rc = imatShade(m, fn, cam, resx, resy, dXY, np, lights7, nLights, ambient, frame, pitch, bgrPackets, B, refl ? &RB : nullptr, dStats, st);
-	return imatSetDone(*Wp, fn, rc, st);
-}
+	int walk(const BounceBufs &R, const int32_t *order, uint64_t *dStats) {
+		// the walk leaves element and barycentrics of a lane without a hit as it found them: zeros, not what the buffers last held (rTri and bary
+		// are neighbours: ONE memset, as imatNested's)
+		const hipError_t e = hipMemsetAsync(R.rTri, 0, (size_t)np * 256 * 12, st);
+		if(e != hipSuccess) return failed("clearing a level's hit records", e);
+		dev::ILevelArgs V;
+		memset(&V, 0, sizeof(V));
+		V.i = I;
+		V.i.nPackets = np; V.i.size = 64;
+		V.i.origin = R.rOrg; V.i.dir = R.rDir; V.i.idir = R.rIDir; V.i.mask = R.rMask;
+		V.i.distance = R.rDist; V.i.object = R.rInst; V.i.element = R.rTri; V.i.bary = R.bary;
+		V.i.stats = (dev::u64 *)dStats;
+		V.i.pstats = pstats;
+		V.order = order;
+		SNAIL_LEVELS_LAUNCH_DEEP(ILevelArgs, grid, V, k_imat_trace_level);
+		return launched("k_imat_trace_level");
+	}
+	int samplePrimary(dev::TreeArgs &, float *opacity, unsigned char *sel) {
+		S.opacity = opacity; S.sel = sel;
+		SNAIL_ITRANSP_LAUNCH(sse, grid, st, S, k_imat_sample_transp);
+		return launched("k_imat_sample_transp");
+	}
+	int sampleRays(dev::TreeArgs &, float *opacity, unsigned char *sel) {
+		S.opacity = opacity; S.sel = sel;
+		SNAIL_ITRANSP_LAUNCH(sse, grid, st, S, k_imat_sample_transp_rays);
+		return launched("k_imat_sample_transp_rays");
+	}
+	int lightsBegin(dev::MatArgs &, int) { return 0; }   // (the instanced lights walk the BLASes' own records: no origin-relative copy is taken)
+	int nestedLights(dev::TreeArgs &) {
+		SNAIL_LEVELS_LAUNCH_DEEP(ITranspArgs, lgrid, S, k_imat_light_transp);
+		return launched("k_imat_light_transp");
+	}
+	int lights(dev::TreeArgs &) {
+		SNAIL_LEVELS_LAUNCH_DEEP(IMatArgs, lgrid, S.a, k_imat_light);
+		return launched("k_imat_light");
+	}
+	// the handle's part of the frame bodies, of levelsStore and of the host calls
+	static int opaque(SnailInstancesMaterials *m, const char *fn, const float cam[13], int resx, int resy, const int32_t *dXY, int np, const float *lights7, int nLights,
+					  const float ambient[3], uint8_t *frame, int pitch, uint8_t *bgrPackets, const Bufs &W, const BounceBufs *R, uint64_t *dStats, hipStream_t st) {
+		return imatShade(m, fn, cam, resx, resy, dXY, np, lights7, nLights, ambient, frame, pitch, bgrPackets, W, R, dStats, st);
+	}
+	// (the hit distances of k_inst_frame alone)
+	static int depthStore(SnailInstancesMaterials *m, const char *fn, const float cam[13], int resx, int resy, const int32_t *dXY, int np, const float *, int,
+						  const float ambient[3], int flags, const float *tint, uint8_t *bgrPackets, const InstTileJob *J, uint64_t *dStats, hipStream_t st) {
+		const float white[3] = {1.0f, 1.0f, 1.0f};
+		return instancesShadeStore(m->inst, fn, cam, resx, resy, dXY, np, nullptr, 0, ambient, white, flags & (SNAIL_RENDER_DEPTH | SNAIL_RENDER_AA4), tint, bgrPackets, J, dStats, st);
+	}
+	static SnailScene *scene(SnailInstancesMaterials *m) { return m->inst->blas[0]; }   // (the arithmetic and its tables are the BLAS scenes'; it lends a host call its free list)
+	static std::mutex &mu(SnailInstancesMaterials *m) { return m->inst->mu; }
+};
 
 // the creators: snail_instances_materials_create (transp = false: its refusals) and snail_instances_materials_create_transparent
 // (include/snail_instances_materials_transparency.h), one body as matCreate is for plain scenes
@@ -324,16 +320,7 @@ void snail_instances_materials_destroy(SnailInstancesMaterials *m) {
 	if(!m) return;
 	DeviceGuard guard(m->device);
 	(void)hipDeviceSynchronize();
-	for(auto &W : m->set) {
-		if(W.base) (void)hipFree(W.base);
-		if(W.bounce) (void)hipFree(W.bounce);
-		if(W.transp) (void)hipFree(W.transp);
-		if(W.tiles) (void)hipFree(W.tiles);
-		if(W.pstats) (void)hipFree(W.pstats);
-		if(W.done) (void)hipEventDestroy(W.done);
-	}
-	freeInstTileJob(m->tileJob);
-	for(auto &f : m->frameLists) (void)hipFree(f.d);
+	m->release();
 	if(m->dBase) (void)hipFree(m->dBase);
 	imatDynFree(m->dyn);
 	delete m;
@@ -370,9 +357,7 @@ int snail_instances_render_materials_dev(SnailInstancesMaterials *m, const float
 	if(int rc = checkMatFrameArgs(fn, cam, resx, resy, lights7, nLights, ambient, flags)) return rc;
 	if(int rc = checkIMat(m, fn)) return rc;
 	if(!frame || pitch < resx * 3) { snail_set_error("%s: null frame or a pitch below 3 * resx", fn); return 1; }
-	DeviceGuard guard(m->device);
-	std::lock_guard<std::mutex> lock(m->inst->mu);
-	return imatShadeDev(m, fn, cam, resx, resy, nullptr, 0, lights7, nLights, ambient, frame, pitch, nullptr, dStats, (hipStream_t)stream);
+	return frameDev<IMatLevels>(m, fn, cam, resx, resy, lights7, nLights, ambient, false, 0, frame, pitch, nullptr, dStats, stream);
 }
 
 int snail_instances_render_materials_packets_dev(SnailInstancesMaterials *m, const float cam[13], int resx, int resy, const int32_t *dPacketXY, int nPackets,
@@ -384,9 +369,7 @@ int snail_instances_render_materials_packets_dev(SnailInstancesMaterials *m, con
 	if(!dPacketXY && nPackets > 0) { snail_set_error("%s: null packet list", fn); return 1; }
 	if(nPackets <= 0) return 0;
 	if(!bgrPackets || ((unsigned long long)bgrPackets & 3)) { snail_set_error("%s: null or unaligned output", fn); return 1; }
-	DeviceGuard guard(m->device);
-	std::lock_guard<std::mutex> lock(m->inst->mu);
-	return imatShadeDev(m, fn, cam, resx, resy, dPacketXY, nPackets, lights7, nLights, ambient, nullptr, 0, bgrPackets, dStats, (hipStream_t)stream);
+	return framePacketsDev<IMatLevels>(m, fn, cam, resx, resy, dPacketXY, nPackets, lights7, nLights, ambient, false, 0, bgrPackets, nullptr, dStats, stream);
 }
 
 int snail_instances_render_materials_image(SnailInstancesMaterials *m, const float cam[13], int resx, int resy, const float *lights7, int nLights,
@@ -395,29 +378,7 @@ int snail_instances_render_materials_image(SnailInstancesMaterials *m, const flo
 	if(int rc = checkMatFrameArgs(fn, cam, resx, resy, lights7, nLights, ambient, flags)) return rc;
 	if(int rc = checkIMat(m, fn)) return rc;
 	if(!image || pitch < resx * 3) { snail_set_error("%s: null image or a pitch below 3 * resx", fn); return 1; }
-	SnailInstances *h = m->inst;
-	DeviceGuard guard(m->device);
-	HostCallScope hc(h->blas[0], fn);   // (a stream, counters and staging arena of the call's own; the BLAS handle only lends its free list)
-	if(hc.rc) return hc.rc;
-	if(int rc = hc.zeroStats()) return rc;
-	const int pw = (resx + 15) / 16, ph = (resy + 15) / 16, np = pw * ph;
-	std::vector<int32_t> xy((size_t)np * 2);
-	for(int y = 0; y < ph; y++)
-		for(int x = 0; x < pw; x++) { xy[((size_t)y * pw + x) * 2] = x * 16; xy[((size_t)y * pw + x) * 2 + 1] = y * 16; }
-	typedef HostCallScope H;
-	const size_t imgBytes = (size_t)pitch * resy, bufBytes = SnailInstancesMaterials::Bufs::bytes((size_t)np, nLights);
-	if(int rc = hc.reserve(H::pad(xy.size() * 4) + H::pad(bufBytes) + H::pad(imgBytes + 4))) return rc;
-	void *dXY = nullptr;
-	if(int rc = hc.put(&dXY, xy.data(), xy.size() * 4)) return rc;
-	SnailInstancesMaterials::Bufs W;
-	W.carve((char *)hc.carve(bufBytes), (size_t)np);
-	uint8_t *dImg = (uint8_t *)hc.carve(imgBytes + 4);
-	{
-		std::lock_guard<std::mutex> lock(h->mu);
-		if(int rc = imatShade(m, fn, cam, resx, resy, (const int32_t *)dXY, np, lights7, nLights, ambient, dImg, pitch, nullptr, W, nullptr, hc.stats(), hc.stream())) return rc;
-	}
-	HIP_TRY(hipMemcpy2DAsync(image, (size_t)pitch, dImg, (size_t)pitch, (size_t)resx * 3, (size_t)resy, hipMemcpyDeviceToHost, hc.stream()));
-	return hc.finish(stats);
+	return frameImage<IMatLevels>(m, fn, cam, resx, resy, lights7, nLights, ambient, false, 0, image, pitch, nullptr, stats);
 }
 
 } // extern "C"

@@ -1,7 +1,7 @@
 // instances_materials_tree_host.inc -- the C-ABI of include/snail_instances_materials_tree.h: the transparency continuation of an instanced scene
 // together with the mirrored bounce, the tile renderer, 4x antialiasing, depth shading and the tint; included by snail_hip.hip after
 // instances_materials_transparency_host.inc.  The frames are the level driver's (materials_levels_host.inc) for an instanced scene (IMatLevels,
-// instances_materials_transparency_host.inc): shadeLevels with chain B under SNAIL_RENDER_REFLECTIONS, run by levelsStore over a packet list in
+// instances_materials_host.inc): shadeLevels with chain B under SNAIL_RENDER_REFLECTIONS, run by levelsStore over a packet list in
 // slices that keep the levels within the set's budget.  No stage is new: the kernels are those of instances*.inc, materials*.inc and
 // instances_shade.inc, unchanged (instances_materials_tree.inc).  The arguments are judged by matTreeArgsOk (materials_tree_host.inc).
 #include "../../include/snail_instances_materials_tree.h"
@@ -73,7 +73,7 @@ int snail_instances_materials_tree_render_tiles(SnailInstancesMaterials *m, cons
 	if(int rc = tileRectsOk(fn, coords, nTiles)) return rc;
 	if(int rc = checkIMatAny(m, fn)) return rc;
 	if(nTiles <= 0) return 0;
-	return renderTilesHost<IMatLevels>(m, fn, cam, resx, resy, coords, offsets, nTiles, lights7, nLights, ambient, flags, tint, data, maxDepth, truncated, stats, false);
+	return renderTilesHost<IMatLevels>(m, fn, cam, resx, resy, coords, offsets, nTiles, lights7, nLights, ambient, flags, tint, data, maxDepth, truncated, stats, false, levelsStore<IMatLevels>);
 }
 
 int snail_instances_materials_tree_render_frame(SnailInstancesMaterials *m, const float cam[13], int resx, int resy, const float *lights7, int nLights,
@@ -82,7 +82,7 @@ int snail_instances_materials_tree_render_frame(SnailInstancesMaterials *m, cons
 	if(int rc = matTreeArgsOk(fn, cam, resx, resy, lights7, nLights, ambient, flags, nullptr, maxDepth, truncated)) return rc;
 	if(!image || pitch < resx * 3) { snail_set_error("%s: null image or a pitch below 3 * resx", fn); return 1; }
 	if(int rc = checkIMatAny(m, fn)) return rc;
-	return renderFrameHost<IMatLevels>(m, fn, cam, resx, resy, lights7, nLights, ambient, flags, image, pitch, maxDepth, truncated, stats, false);
+	return renderFrameHost<IMatLevels>(m, fn, cam, resx, resy, lights7, nLights, ambient, flags, image, pitch, maxDepth, truncated, stats, false, levelsStore<IMatLevels>);
 }
 
 int snail_instances_materials_set_level_budget(SnailInstancesMaterials *m, uint64_t bytes) {

@@ -227,7 +227,7 @@ int snail_instances_render_frame(SnailInstances *h, const float cam[13], int res
 	{
 		std::lock_guard<std::mutex> lock(h->mu);
 		int n = 0;
-		if(int rc = instancesFrameList(h, resx, resy, &dXY, &n)) return rc;
+		if(int rc = h->frameLists.get(resx, resy, &dXY, &n)) return rc;
 		if(int rc = instancesShadeStore(h, fn, cam, resx, resy, dXY, np, lights7, nLights, ambient, color, flags, nullptr, bgr, nullptr, stats ? hc.stats() : nullptr, hc.stream()))
 			return rc;
 		// (under mu: the cached frame list may be dropped by a later call, which first waits for everything enqueued)

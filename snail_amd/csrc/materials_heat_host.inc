@@ -30,7 +30,7 @@ int matHeatDev(SnailMaterials *m, const char *fn, const float cam[13], int resx,
 			   const float *tint, uint8_t *bgrPackets, uint32_t *dPacketStats, int maxDepth, uint64_t *dTrunc, uint64_t *dStats, hipStream_t st) {
 	DeviceGuard guard(m->device);
 	SNAIL_LOCK(m->scene);
-	if(!dXY) { if(int rc = matFrameList(m, resx, resy, &dXY, &np)) return rc; }
+	if(!dXY) { if(int rc = m->frameLists.get(resx, resy, &dXY, &np)) return rc; }
 	if(np > (1 << 24)) { snail_set_error("%s: more than 2^24 packets", fn); return 1; }
 	return levelsStore<MatLevels>(m, fn, cam, resx, resy, dXY, np, lights7, nLights, kMatHeatNoColour, flags, tint, bgrPackets, nullptr, maxDepth, dTrunc, dStats, st, true, dPacketStats);
 }
@@ -73,7 +73,7 @@ int snail_materials_render_heat_tiles(SnailMaterials *m, const float cam[13], in
 	if(int rc = tileRectsOk(fn, coords, nTiles)) return rc;
 	if(int rc = checkMaterialsAny(m, fn)) return rc;
 	if(nTiles <= 0) return 0;
-	return renderTilesHost<MatLevels>(m, fn, cam, resx, resy, coords, offsets, nTiles, lights7, nLights, kMatHeatNoColour, flags, tint, data, maxDepth, truncated, stats, true);
+	return renderTilesHost<MatLevels>(m, fn, cam, resx, resy, coords, offsets, nTiles, lights7, nLights, kMatHeatNoColour, flags, tint, data, maxDepth, truncated, stats, true, levelsStore<MatLevels>);
 }
 
 int snail_materials_render_heat_frame(SnailMaterials *m, const float cam[13], int resx, int resy, const float *lights7, int nLights, int flags, uint8_t *image, int pitch,
@@ -82,7 +82,7 @@ int snail_materials_render_heat_frame(SnailMaterials *m, const float cam[13], in
 	if(int rc = matHeatArgsOk(fn, cam, resx, resy, lights7, nLights, flags, SNAIL_RENDER_REFLECTIONS | SNAIL_RENDER_AA4, nullptr, maxDepth, truncated)) return rc;
 	if(!image || pitch < resx * 3) { snail_set_error("%s: null image or a pitch below 3 * resx", fn); return 1; }
 	if(int rc = checkMaterialsAny(m, fn)) return rc;
-	return renderFrameHost<MatLevels>(m, fn, cam, resx, resy, lights7, nLights, kMatHeatNoColour, flags, image, pitch, maxDepth, truncated, stats, true);
+	return renderFrameHost<MatLevels>(m, fn, cam, resx, resy, lights7, nLights, kMatHeatNoColour, flags, image, pitch, maxDepth, truncated, stats, true, levelsStore<MatLevels>);
 }
 
 } // extern "C"

@@ -2,13 +2,15 @@
 // scene, and the staged launches of materials.inc (primary hits -> k_mat_sample -> k_mat_light per (packet, light) -> k_mat_final); and the
 // C-ABI of include/snail_materials_bounce.h: the same frames with the one mirrored bounce of gVals[7] (-> k_mat_mirror -> launchRays with
 // barycentrics -> k_mat_sample_rays -> k_mat_light_rays -> k_mat_colour_rays between the sample stage and the primary lights, k_mat_final_blend last).
+// The handle's sets of intermediates and frame lists are shading_sets_host.inc's; the frames' bodies from DeviceGuard on are materials_levels_host.inc's
+// (frameDev, framePacketsDev, frameImage), included ahead of this file, over MatLevels, the plain scene's kind, defined here beside matShade.
 #include "../../include/snail_materials.h"
 #include "../../include/snail_materials_bounce.h"
 #include "../../include/snail_materials_tiles.h"
 
 struct SnailMaterialsDyn;   // materials_dynamic_host.inc: what a set of snail_materials_create_dev carries besides the set
 namespace { int dynCheckFresh(const SnailMaterials *, const char *fn); void dynFree(SnailMaterialsDyn *); }
-struct SnailMaterials {
+struct SnailMaterials : ShadeSets {   // (shading_sets_host.inc: the sets of intermediates, the frame lists, the tile job, the level budget)
 	SnailScene *scene = nullptr;
 	SnailMaterialsDyn *dyn = nullptr;   // snail_materials_create_dev: the records are packed on the device and follow the scene's rebuilds
 	int device = 0;
@@ -20,7 +22,7 @@ struct SnailMaterials {
 	const dev::MatRec *dMats = nullptr;
 	const dev::TexRec *dTex = nullptr;
 	const unsigned char *dTexels = nullptr;
-	// intermediates of the lit frames, one set per launch in flight (round-robin, each guarded by an event; booked under the scene's lock)
+	// a set's base part: the intermediates of the lit frames
 	struct Bufs {
 		float *hitT = nullptr, *hitU = nullptr, *hitV = nullptr, *samples = nullptr, *sDist = nullptr;
 		int *hitId = nullptr;
@@ -45,40 +47,13 @@ struct SnailMaterials {
 			rMask = (unsigned char *)(base + (size_t)(25 + (nLights > 0 ? nLights : 0)) * plane);
 		}
 	};
-	struct Set {
-		char *base = nullptr;
-		size_t packets = 0;
-		int lights = 0;
-		char *bounce = nullptr;   // allocated only once a bounce has been asked for; grown under the same rule
-		size_t bouncePackets = 0;
-		int bounceLights = 0;
-		char *tiles = nullptr;    // the tile renderer's part (Set::TileBufs), only once it was asked for; grown under the same rule
-		size_t tilesPackets = 0;
-		char *transp = nullptr;   // the per-level intermediates of the transparency frames (materials_transparency_host.inc), only once asked for; sized by
-		size_t transpBytes = 0;   // packets, lights and the depth asked for, grown under the same rule
-		uint32_t *pstats = nullptr;   // snail_materials_heatmap.h: the launch's per-packet TreeStats [packets][4] when the caller keeps none of its own; only
-		size_t pstatsPackets = 0;     // once asked for, grown under the same rule
-		hipEvent_t done = nullptr;
-		bool used = false;
-	};
-	// ... and those of the tile renderer (materials_tiles_host.inc): the packets' float colours and, under 4x antialiasing, the sub-packet list
+	// ... and the tile renderer's (materials_tiles_host.inc, levelsStore): the packets' float colours and, under 4x antialiasing, the sub-packet list
 	struct TileBufs {
 		float *col = nullptr;
 		int32_t *xy2 = nullptr;
 		static size_t bytes(size_t np) { return np * 256 * 12 + np * 8; }
 		void carve(char *base, size_t np) { col = (float *)base; xy2 = (int32_t *)(base + np * 256 * 12); }
 	};
-	enum { kSets = 8 };
-	Set set[kSets];
-	unsigned setCount = 0;
-	struct FrameList { int pw, ph; int32_t *d; };
-	std::vector<FrameList> frameLists;   // a whole frame's packet list, cached by packet-grid size
-	// snail_materials_render_tiles: ONE cached tile job per set (the structure of instances_tiles_host.inc); its calls take turns under renderMu,
-	// which is taken before the scene's mu
-	std::mutex renderMu;
-	InstTileJob *tileJob = nullptr;
-	// snail_materials_set_level_budget (materials_tree_host.inc): the bytes the levels of one group of intermediates may take; 0 = SNAIL_MAT_LEVEL_BUDGET
-	uint64_t levelBudget = 0;
 };
 
 namespace {
@@ -215,88 +190,88 @@ int matShade(SnailMaterials *m, const char *fn, const float cam[13], int resx, i
 	return 0;
 }
 
-// the packet list of a whole frame, cached in the set by packet-grid size (the scene's mu held)
-int matFrameList(SnailMaterials *m, int resx, int resy, const int32_t **dXY, int *np) {
-	const int pw = (resx + 15) / 16, ph = (resy + 15) / 16;
-	*np = pw * ph;
-	for(auto &f : m->frameLists)
-		if(f.pw == pw && f.ph == ph) { *dXY = f.d; return 0; }
-	if(m->frameLists.size() >= 16) {
-		HIP_TRY(hipDeviceSynchronize());
-		for(auto &f : m->frameLists) (void)hipFree(f.d);
-		m->frameLists.clear();
-	}
-	std::vector<int32_t> xy((size_t)pw * ph * 2);
-	for(int y = 0; y < ph; y++)
-		for(int x = 0; x < pw; x++) { xy[((size_t)y * pw + x) * 2] = x * 16; xy[((size_t)y * pw + x) * 2 + 1] = y * 16; }
-	SnailMaterials::FrameList f = {pw, ph, nullptr};
-	HIP_TRY(hipMalloc((void **)&f.d, xy.size() * 4));
-	if(hipMemcpy(f.d, xy.data(), xy.size() * 4, hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(f.d); snail_set_error("frame packet list: upload failed"); return 1; }
-	m->frameLists.push_back(f);
-	*dXY = f.d;
-	return 0;
-}
+// materials_tiles_host.inc: the opaque stages with any flags and tint into packet-major bytes or a tile job's planes
+int matShadeStore(SnailMaterials *m, const char *fn, const float cam[13], int resx, int resy, const int32_t *dXY, int np, const float *lights7, int nLights,
+				  const float ambient[3], int flags, const float *tint, uint8_t *bgrPackets, const InstTileJob *J, uint64_t *dStats, hipStream_t st);
 
-// snail_render_materials_dev / _packets_dev (the scene's mu held): the next set of intermediates, grown if need be, its previous user waited for on st
-// the next set of intermediates for np packets (the scene's mu held); tiles: with the tile renderer's part
-int matNextSet(SnailMaterials *m, int np, int nLights, bool refl, bool tiles, hipStream_t st, SnailMaterials::Set **out) {
-	SnailMaterials::Set &W = m->set[m->setCount++ % SnailMaterials::kSets];
-	if(!W.base || W.packets < (size_t)np || W.lights < nLights) {   // grown: its previous user may still be running
-		HIP_TRY(hipDeviceSynchronize());
-		if(W.base) (void)hipFree(W.base);
-		const size_t packets = std::max(W.packets, (size_t)np);
-		const int lights = std::max(W.lights, nLights);
-		W.base = nullptr; W.packets = 0; W.lights = 0; W.used = false;
-		HIP_TRY(hipMalloc((void **)&W.base, SnailMaterials::Bufs::bytes(packets, lights)));
-		W.packets = packets; W.lights = lights;
+// The plain scene's kind of the frame bodies and the level driver (materials_levels_host.inc); the scene's mu held.  The scene-free stages'
+// TreeArgs is the only argument record: its MatArgs is the frame's, and the sample and light stages take its TranspArgs.
+struct MatLevels : LevelsFrame {
+	typedef SnailMaterials Handle;
+	typedef SnailMaterials::Bufs Bufs;
+	typedef SnailMaterials::BounceBufs BounceBufs;
+	SnailMaterials *m;
+	SnailScene *s;
+	SceneUse use;
+	int relWhich[SNAIL_MAX_LIGHTS];   // the origin-relative copies taken by lightsBegin
+	MatLevels(SnailMaterials *m_, const char *fn_, hipStream_t st_, uint32_t *pstats_, int np_, int nLights) : LevelsFrame(fn_, st_, pstats_, np_, nLights), m(m_), s(m_->scene), use(s, st_) {
+		for(int n = 0; n < SNAIL_MAX_LIGHTS; n++) relWhich[n] = -1;
 	}
-	if(refl && (!W.bounce || W.bouncePackets < (size_t)np || W.bounceLights < nLights)) {   // the bounce's part: only when asked for, grown the same way
-		HIP_TRY(hipDeviceSynchronize());
-		if(W.bounce) (void)hipFree(W.bounce);
-		const size_t packets = std::max(W.bouncePackets, (size_t)np);
-		const int lights = std::max(W.bounceLights, nLights);
-		W.bounce = nullptr; W.bouncePackets = 0; W.bounceLights = 0; W.used = false;
-		HIP_TRY(hipMalloc((void **)&W.bounce, SnailMaterials::BounceBufs::bytes(packets, lights)));
-		W.bouncePackets = packets; W.bounceLights = lights;
+	int begin() {
+		sse = s->arith == SNAIL_ARITH_HOST_SSE; deep = useDeep(s);
+		return use.rc;
 	}
-	if(tiles && (!W.tiles || W.tilesPackets < (size_t)np)) {
-		HIP_TRY(hipDeviceSynchronize());
-		if(W.tiles) (void)hipFree(W.tiles);
-		const size_t packets = std::max(W.tilesPackets, (size_t)np);
-		W.tiles = nullptr; W.tilesPackets = 0; W.used = false;
-		HIP_TRY(hipMalloc((void **)&W.tiles, SnailMaterials::TileBufs::bytes(packets)));
-		W.tilesPackets = packets;
+	// every origin-relative copy taken is booked as used on st on EVERY way out, first error kept (matShade's rule)
+	int end() {
+		int rc = 0;
+		for(int n = 0; n < SNAIL_MAX_LIGHTS; n++)
+			if(relWhich[n] >= 0) { const int urc = relUsed(s, relWhich[n], st); if(!rc) rc = urc; }
+		return rc;
 	}
-	if(!W.done) HIP_TRY(hipEventCreateWithFlags(&W.done, hipEventDisableTiming));
-	if(W.used) HIP_TRY(hipStreamWaitEvent(st, W.done, 0));
-	*out = &W;
-	return 0;
-}
-// after the set's user has enqueued its stages (rc: how that went)
-int matSetDone(SnailMaterials::Set &W, const char *fn, int rc, hipStream_t st) {
-	// also when a stage failed after earlier ones were enqueued: they may still be running on these buffers, and the set's next user (on any
-	// stream) must come after them.  Should the record itself fail, the set is marked grown-from-scratch: its next user synchronises the device.
-	if(hipEventRecord(W.done, st) == hipSuccess) W.used = true;
-	else {
-		W.packets = 0; W.bouncePackets = 0; W.tilesPackets = 0; W.transpBytes = 0; W.pstatsPackets = 0; W.used = false;
-		if(!rc) { snail_set_error("%s: hipEventRecord failed", fn); return 1; }
+	int primary(const float cam[13], int resx, int resy, const int32_t *dXY, const Bufs &W, uint64_t *dStats) {
+		return launchPrimary(s, cam, resx, resy, 0, 0, 0, 0, dXY, np, W.hitT, W.hitU, W.hitV, W.hitId, dStats, st, nullptr, false, nullptr, nullptr, nullptr, nullptr, 0, pstats);
 	}
-	return rc;
-}
-
-int matShadeDev(SnailMaterials *m, const char *fn, const float cam[13], int resx, int resy, const int32_t *dXY, int np, const float *lights7, int nLights,
-				const float ambient[3], uint8_t *frame, int pitch, uint8_t *bgrPackets, uint64_t *dStats, hipStream_t st, bool refl = false) {
-	if(!dXY) { if(int rc = matFrameList(m, resx, resy, &dXY, &np)) return rc; }
-	SnailMaterials::Set *Wp = nullptr;
-	if(int rc = matNextSet(m, np, nLights, refl, false, st, &Wp)) return rc;
-	SnailMaterials::Set &W = *Wp;
-	SnailMaterials::Bufs B;
-	B.carve(W.base, (size_t)np);
-	SnailMaterials::BounceBufs RB;
-	if(refl) RB.carve(W.bounce, (size_t)np, nLights);
-	const int rc = matShade(m, fn, cam, resx, resy, dXY, np, lights7, nLights, ambient, frame, pitch, bgrPackets, B, refl ? &RB : nullptr, dStats, st);
-	return matSetDone(W, fn, rc, st);
-}
+	dev::MatArgs &frameArgs(dev::TreeArgs &G, const float cam[13], int resx, int resy, const int32_t *dXY, const Bufs &W) {
+		dev::MatArgs &A = G.t.m;
+		matFillArgs(m, A, cam, resx, resy, dXY, np);
+		A.s.hitId = W.hitId;
+		return A;
+	}
+	static int *object(const BounceBufs &R) { return R.rObj; }
+	void level(dev::TreeArgs &G, const BounceBufs &R, const int32_t *, bool) { G.t.m.s.rObj = R.rObj; }
+	int walk(const BounceBufs &R, const int32_t *order, uint64_t *dStats) {
+		// the walk reads the barycentrics it was given and writes them back for lanes without a hit: zeros, not what the buffer last held
+		const hipError_t e = hipMemsetAsync(R.bary, 0, (size_t)np * 256 * 8, st);
+		if(e != hipSuccess) return failed("hipMemsetAsync", e);
+		return launchRays(s, false, np, 64, 0, R.rOrg, R.rDir, R.rIDir, R.rMask, R.rDist, R.rObj, R.bary, dStats, st, order, nullptr, order ? np : 0, nullptr, 0, pstats);
+	}
+	int samplePrimary(dev::TreeArgs &G, float *opacity, unsigned char *sel) {
+		G.t.opacity = opacity; G.t.sel = sel;
+		SNAIL_LAUNCH(sse, TranspArgs, grid, dim3(64), 0, st, G.t, k_mat_sample_transp);
+		return launched("k_mat_sample_transp");
+	}
+	int sampleRays(dev::TreeArgs &G, float *opacity, unsigned char *sel) {
+		G.t.opacity = opacity; G.t.sel = sel;
+		SNAIL_LAUNCH(sse, TranspArgs, grid, dim3(64), 0, st, G.t, k_mat_sample_transp_rays);
+		return launched("k_mat_sample_transp_rays");
+	}
+	// (the lights of every level of both chains walk from the same origins: the same copies)
+	int lightsBegin(dev::MatArgs &A, int nLights) {
+		int rc = 0;
+		if(nLights && A.s.pack && !deep)
+			for(int n = 0; n < nLights && !rc; n++) rc = relFor(s, A.s.lights[n], st, &A.s.relLight[n], &relWhich[n]);
+		return rc;
+	}
+	int nestedLights(dev::TreeArgs &G) {
+		SNAIL_LEVELS_LAUNCH_DEEP(TranspArgs, lgrid, G.t, k_mat_light_transp);
+		return launched("k_mat_light_transp");
+	}
+	int lights(dev::TreeArgs &G) {
+		SNAIL_LEVELS_LAUNCH_DEEP(MatArgs, lgrid, G.t.m, k_mat_light);
+		return launched("k_mat_light");
+	}
+	// the handle's part of the frame bodies, of levelsStore and of the host calls
+	static int opaque(SnailMaterials *m, const char *fn, const float cam[13], int resx, int resy, const int32_t *dXY, int np, const float *lights7, int nLights,
+					  const float ambient[3], uint8_t *frame, int pitch, uint8_t *bgrPackets, const Bufs &W, const BounceBufs *R, uint64_t *dStats, hipStream_t st) {
+		return matShade(m, fn, cam, resx, resy, dXY, np, lights7, nLights, ambient, frame, pitch, bgrPackets, W, R, dStats, st);
+	}
+	static int depthStore(SnailMaterials *m, const char *fn, const float cam[13], int resx, int resy, const int32_t *dXY, int np, const float *lights7, int nLights,
+						  const float ambient[3], int flags, const float *tint, uint8_t *bgrPackets, const InstTileJob *J, uint64_t *dStats, hipStream_t st) {
+		return matShadeStore(m, fn, cam, resx, resy, dXY, np, lights7, nLights, ambient, flags, tint, bgrPackets, J, dStats, st);
+	}
+	static SnailScene *scene(SnailMaterials *m) { return m->scene; }
+	static std::mutex &mu(SnailMaterials *m) { return m->scene->mu; }
+};
 
 } // namespace
 
@@ -510,16 +485,7 @@ void snail_materials_destroy(SnailMaterials *m) {
 	if(!m) return;
 	DeviceGuard guard(m->device);
 	(void)hipDeviceSynchronize();
-	for(auto &W : m->set) {
-		if(W.base) (void)hipFree(W.base);
-		if(W.bounce) (void)hipFree(W.bounce);
-		if(W.tiles) (void)hipFree(W.tiles);
-		if(W.transp) (void)hipFree(W.transp);
-		if(W.pstats) (void)hipFree(W.pstats);
-		if(W.done) (void)hipEventDestroy(W.done);
-	}
-	freeInstTileJob(m->tileJob);
-	for(auto &f : m->frameLists) (void)hipFree(f.d);
+	m->release();
 	if(m->dBase) (void)hipFree(m->dBase);
 	dynFree(m->dyn);
 	delete m;
@@ -548,58 +514,6 @@ int snail_materials_shade_packets_dev(SnailMaterials *m, const float cam[13], in
 
 } // extern "C"
 
-// the three frame functions after their flags have been judged (refl: the one mirrored bounce)
-static int matFrameDev(const char *fn, SnailMaterials *m, const float cam[13], int resx, int resy, const float *lights7, int nLights, const float ambient[3], bool refl,
-					   uint8_t *frame, int pitch, uint64_t *dStats, void *stream) {
-	if(int rc = checkMaterials(m, fn)) return rc;
-	if(!frame || pitch < resx * 3) { snail_set_error("%s: null frame or a pitch below 3 * resx", fn); return 1; }
-	DeviceGuard guard(m->device);
-	SNAIL_LOCK(m->scene);
-	return matShadeDev(m, fn, cam, resx, resy, nullptr, 0, lights7, nLights, ambient, frame, pitch, nullptr, dStats, (hipStream_t)stream, refl);
-}
-
-static int matFramePacketsDev(const char *fn, SnailMaterials *m, const float cam[13], int resx, int resy, const int32_t *dPacketXY, int nPackets, const float *lights7,
-							  int nLights, const float ambient[3], bool refl, uint8_t *bgrPackets, uint64_t *dStats, void *stream) {
-	if(int rc = checkMaterials(m, fn)) return rc;
-	if(!dPacketXY && nPackets > 0) { snail_set_error("%s: null packet list", fn); return 1; }
-	if(nPackets <= 0) return 0;
-	if(!bgrPackets || ((unsigned long long)bgrPackets & 3)) { snail_set_error("%s: null or unaligned output", fn); return 1; }
-	DeviceGuard guard(m->device);
-	SNAIL_LOCK(m->scene);
-	return matShadeDev(m, fn, cam, resx, resy, dPacketXY, nPackets, lights7, nLights, ambient, nullptr, 0, bgrPackets, dStats, (hipStream_t)stream, refl);
-}
-
-static int matFrameImage(const char *fn, SnailMaterials *m, const float cam[13], int resx, int resy, const float *lights7, int nLights, const float ambient[3], bool refl,
-						 uint8_t *image, int pitch, uint64_t stats[4]) {
-	if(int rc = checkMaterials(m, fn)) return rc;
-	if(!image || pitch < resx * 3) { snail_set_error("%s: null image or a pitch below 3 * resx", fn); return 1; }
-	DeviceGuard guard(m->device);
-	HostCallScope hc(m->scene, fn);
-	if(hc.rc) return hc.rc;
-	if(int rc = hc.zeroStats()) return rc;
-	const int pw = (resx + 15) / 16, ph = (resy + 15) / 16, np = pw * ph;
-	std::vector<int32_t> xy((size_t)np * 2);
-	for(int y = 0; y < ph; y++)
-		for(int x = 0; x < pw; x++) { xy[((size_t)y * pw + x) * 2] = x * 16; xy[((size_t)y * pw + x) * 2 + 1] = y * 16; }
-	typedef HostCallScope H;
-	const size_t imgBytes = (size_t)pitch * resy, bufBytes = SnailMaterials::Bufs::bytes((size_t)np, nLights),
-				 bounceBytes = refl ? SnailMaterials::BounceBufs::bytes((size_t)np, nLights) : 0;
-	if(int rc = hc.reserve(H::pad(xy.size() * 4) + H::pad(bufBytes) + (refl ? H::pad(bounceBytes) : 0) + H::pad(imgBytes + 4))) return rc;
-	void *dXY = nullptr;
-	if(int rc = hc.put(&dXY, xy.data(), xy.size() * 4)) return rc;
-	SnailMaterials::Bufs W;
-	W.carve((char *)hc.carve(bufBytes), (size_t)np);
-	SnailMaterials::BounceBufs RB;
-	if(refl) RB.carve((char *)hc.carve(bounceBytes), (size_t)np, nLights);
-	uint8_t *dImg = (uint8_t *)hc.carve(imgBytes + 4);
-	{
-		SNAIL_LOCK(m->scene);
-		if(int rc = matShade(m, fn, cam, resx, resy, (const int32_t *)dXY, np, lights7, nLights, ambient, dImg, pitch, nullptr, W, refl ? &RB : nullptr, hc.stats(), hc.stream())) return rc;
-	}
-	HIP_TRY(hipMemcpy2DAsync(image, (size_t)pitch, dImg, (size_t)pitch, (size_t)resx * 3, (size_t)resy, hipMemcpyDeviceToHost, hc.stream()));
-	return hc.finish(stats);
-}
-
 // include/snail_materials_bounce.h: flags = 0 or SNAIL_RENDER_REFLECTIONS, judged before anything else
 static int checkBounceFrameArgs(const char *fn, const float cam[13], int resx, int resy, const float *lights7, int nLights, const float ambient[3], int flags) {
 	if(flags & ~SNAIL_RENDER_REFLECTIONS) {
@@ -615,21 +529,29 @@ int snail_render_materials_dev(SnailMaterials *m, const float cam[13], int resx,
 							   uint8_t *frame, int pitch, uint64_t *dStats, void *stream) {
 	const char *fn = "snail_render_materials_dev";
 	if(int rc = checkMatFrameArgs(fn, cam, resx, resy, lights7, nLights, ambient, flags)) return rc;
-	return matFrameDev(fn, m, cam, resx, resy, lights7, nLights, ambient, false, frame, pitch, dStats, stream);
+	if(int rc = checkMaterials(m, fn)) return rc;
+	if(!frame || pitch < resx * 3) { snail_set_error("%s: null frame or a pitch below 3 * resx", fn); return 1; }
+	return frameDev<MatLevels>(m, fn, cam, resx, resy, lights7, nLights, ambient, false, 0, frame, pitch, nullptr, dStats, stream);
 }
 
 int snail_render_materials_packets_dev(SnailMaterials *m, const float cam[13], int resx, int resy, const int32_t *dPacketXY, int nPackets, const float *lights7,
 									   int nLights, const float ambient[3], int flags, uint8_t *bgrPackets, uint64_t *dStats, void *stream) {
 	const char *fn = "snail_render_materials_packets_dev";
 	if(int rc = checkMatFrameArgs(fn, cam, resx, resy, lights7, nLights, ambient, flags)) return rc;
-	return matFramePacketsDev(fn, m, cam, resx, resy, dPacketXY, nPackets, lights7, nLights, ambient, false, bgrPackets, dStats, stream);
+	if(int rc = checkMaterials(m, fn)) return rc;
+	if(!dPacketXY && nPackets > 0) { snail_set_error("%s: null packet list", fn); return 1; }
+	if(nPackets <= 0) return 0;
+	if(!bgrPackets || ((unsigned long long)bgrPackets & 3)) { snail_set_error("%s: null or unaligned output", fn); return 1; }
+	return framePacketsDev<MatLevels>(m, fn, cam, resx, resy, dPacketXY, nPackets, lights7, nLights, ambient, false, 0, bgrPackets, nullptr, dStats, stream);
 }
 
 int snail_render_materials_image(SnailMaterials *m, const float cam[13], int resx, int resy, const float *lights7, int nLights, const float ambient[3], int flags,
 								 uint8_t *image, int pitch, uint64_t stats[4]) {
 	const char *fn = "snail_render_materials_image";
 	if(int rc = checkMatFrameArgs(fn, cam, resx, resy, lights7, nLights, ambient, flags)) return rc;
-	return matFrameImage(fn, m, cam, resx, resy, lights7, nLights, ambient, false, image, pitch, stats);
+	if(int rc = checkMaterials(m, fn)) return rc;
+	if(!image || pitch < resx * 3) { snail_set_error("%s: null image or a pitch below 3 * resx", fn); return 1; }
+	return frameImage<MatLevels>(m, fn, cam, resx, resy, lights7, nLights, ambient, false, 0, image, pitch, nullptr, stats);
 }
 
 // ---- include/snail_materials_bounce.h ----
@@ -637,21 +559,29 @@ int snail_materials_bounce_dev(SnailMaterials *m, const float cam[13], int resx,
 							   uint8_t *frame, int pitch, uint64_t *dStats, void *stream) {
 	const char *fn = "snail_materials_bounce_dev";
 	if(int rc = checkBounceFrameArgs(fn, cam, resx, resy, lights7, nLights, ambient, flags)) return rc;
-	return matFrameDev(fn, m, cam, resx, resy, lights7, nLights, ambient, (flags & SNAIL_RENDER_REFLECTIONS) != 0, frame, pitch, dStats, stream);
+	if(int rc = checkMaterials(m, fn)) return rc;
+	if(!frame || pitch < resx * 3) { snail_set_error("%s: null frame or a pitch below 3 * resx", fn); return 1; }
+	return frameDev<MatLevels>(m, fn, cam, resx, resy, lights7, nLights, ambient, (flags & SNAIL_RENDER_REFLECTIONS) != 0, 0, frame, pitch, nullptr, dStats, stream);
 }
 
 int snail_materials_bounce_packets_dev(SnailMaterials *m, const float cam[13], int resx, int resy, const int32_t *dPacketXY, int nPackets, const float *lights7,
 									   int nLights, const float ambient[3], int flags, uint8_t *bgrPackets, uint64_t *dStats, void *stream) {
 	const char *fn = "snail_materials_bounce_packets_dev";
 	if(int rc = checkBounceFrameArgs(fn, cam, resx, resy, lights7, nLights, ambient, flags)) return rc;
-	return matFramePacketsDev(fn, m, cam, resx, resy, dPacketXY, nPackets, lights7, nLights, ambient, (flags & SNAIL_RENDER_REFLECTIONS) != 0, bgrPackets, dStats, stream);
+	if(int rc = checkMaterials(m, fn)) return rc;
+	if(!dPacketXY && nPackets > 0) { snail_set_error("%s: null packet list", fn); return 1; }
+	if(nPackets <= 0) return 0;
+	if(!bgrPackets || ((unsigned long long)bgrPackets & 3)) { snail_set_error("%s: null or unaligned output", fn); return 1; }
+	return framePacketsDev<MatLevels>(m, fn, cam, resx, resy, dPacketXY, nPackets, lights7, nLights, ambient, (flags & SNAIL_RENDER_REFLECTIONS) != 0, 0, bgrPackets, nullptr, dStats, stream);
 }
 
 int snail_materials_bounce_image(SnailMaterials *m, const float cam[13], int resx, int resy, const float *lights7, int nLights, const float ambient[3], int flags,
 								 uint8_t *image, int pitch, uint64_t stats[4]) {
 	const char *fn = "snail_materials_bounce_image";
 	if(int rc = checkBounceFrameArgs(fn, cam, resx, resy, lights7, nLights, ambient, flags)) return rc;
-	return matFrameImage(fn, m, cam, resx, resy, lights7, nLights, ambient, (flags & SNAIL_RENDER_REFLECTIONS) != 0, image, pitch, stats);
+	if(int rc = checkMaterials(m, fn)) return rc;
+	if(!image || pitch < resx * 3) { snail_set_error("%s: null image or a pitch below 3 * resx", fn); return 1; }
+	return frameImage<MatLevels>(m, fn, cam, resx, resy, lights7, nLights, ambient, (flags & SNAIL_RENDER_REFLECTIONS) != 0, 0, image, pitch, nullptr, stats);
 }
 
 int snail_materials_mirror_packets_dev(SnailMaterials *m, const float cam[13], int resx, int resy, const int32_t *dPacketXY, int nPackets, const float *dT,

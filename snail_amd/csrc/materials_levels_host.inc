@@ -1,14 +1,17 @@
-// materials_levels_host.inc -- the level driver of full shading, once for plain and instanced scenes; included by snail_hip.hip after
-// materials_tiles_host.inc, ahead of its users (materials_*_host.inc and instances_materials_*_host.inc from the transparency files on).
-//   shadeLevels      the stages of one frame: the way down of chain A, then for k = D .. 0 the B chain of A_k (mirror, walk, sample, generator /
-//                    walk / sample down to level D, truncation count, way back up), the reflection blend into A_k, its transparency blend, lights
-//                    and colour.  Without refl: the transparency continuation alone.
-//   levelsStore      runs it over a packet list in slices that keep the levels within the set's budget, and hands the float colours to k_inst_store.
-//   renderTilesHost, renderFrameHost   the host calls around levelsStore: a stream, counters and staging of the call's own, the copy back.
-// Each is a template over a scene kind: MatLevels (materials_transparency_host.inc) for SnailMaterials, IMatLevels
-// (instances_materials_transparency_host.inc) for SnailInstancesMaterials.  A kind holds what differs between the two: how a launch is ordered
-// against rebuilds and updates (begin / end), the walks, the stages that read the scene's shading records (samples and lights) with their
-// argument records, and the handle's sets, lock and frame lists.  The scene-free stages are launched here.
+// materials_levels_host.inc -- the frames of full shading, once for plain and instanced scenes; included by snail_hip.hip ahead of
+// materials_host.inc and instances_materials_host.inc, which define the two scene kinds next to their handles.
+//   shadeLevels      the stages of one transparent frame: the way down of chain A, then for k = D .. 0 the B chain of A_k (mirror, walk, sample,
+//                    generator / walk / sample down to level D, truncation count, way back up), the reflection blend into A_k, its transparency
+//                    blend, lights and colour.  Without refl: the transparency continuation alone.
+//   frameStages      one frame's stages by depth: 0 = the kind's opaque stages (matShade, imatShade), otherwise shadeLevels.
+//   frameDev, framePacketsDev, frameImage   the bodies of every _dev, _packets_dev and _image entry point from DeviceGuard on: the first two over
+//                    the handle's next set of intermediates (frameSet), the last over a stream, counters and staging of the call's own.
+//   levelsStore      runs shadeLevels over a packet list in slices that keep the levels within the set's budget, and hands the float colours to k_inst_store.
+//   renderTilesHost, renderFrameHost   the host calls around a store step (levelsStore, or matStoreStep of materials_tiles_host.inc: matShadeStore).
+// Each is a template over a scene kind: MatLevels (materials_host.inc) for SnailMaterials, IMatLevels (instances_materials_host.inc) for
+// SnailInstancesMaterials.  A kind holds what differs between the two: how a launch is ordered against rebuilds and updates (begin / end), the
+// walks, the stages that read the scene's shading records (samples and lights) with their argument records, the opaque stages, and the handle's
+// lock and lender.  The scene-free stages are launched here; the sets of intermediates are the handles' ShadeSets (shading_sets_host.inc).
 #include "../../include/snail_materials_tree.h"
 
 namespace {
@@ -249,15 +252,92 @@ int shadeLevels(typename K::Handle *m, const char *fn, const float cam[13], int 
 	return rc ? rc : erc;
 }
 
-// a part of a group of intermediates grown under the next-set rule (matNextSet, imatNextSet): its previous user may still be running
-template <class Set, class Part>
-int levelsGrow(Set &W, Part *&part, size_t &have, size_t want, size_t bytes) {
-	if(part && have >= want) return 0;
-	HIP_TRY(hipDeviceSynchronize());
-	if(part) (void)hipFree(part);
-	part = nullptr; have = 0; W.used = false;
-	HIP_TRY(hipMalloc((void **)&part, bytes));
-	have = want;
+// One frame's stages into `frame` or packet-major `bgrPackets` (the kind's lock held).  maxDepth 0: the kind's opaque stages, with the one
+// mirrored bounce in R (or null); otherwise the levels at `arena`, chain B with refl.
+template <class K>
+int frameStages(typename K::Handle *m, const char *fn, const float cam[13], int resx, int resy, const int32_t *dXY, int np, const float *lights7, int nLights,
+				const float ambient[3], uint8_t *frame, int pitch, uint8_t *bgrPackets, const typename K::Bufs &W, const typename K::BounceBufs *R, char *arena, bool refl,
+				int maxDepth, uint64_t *dTrunc, uint64_t *dStats, hipStream_t st) {
+	if(!maxDepth) return K::opaque(m, fn, cam, resx, resy, dXY, np, lights7, nLights, ambient, frame, pitch, bgrPackets, W, R, dStats, st);
+	return shadeLevels<K>(m, fn, cam, resx, resy, dXY, np, lights7, nLights, ambient, frame, pitch, bgrPackets, nullptr, W, arena, maxDepth, refl, dTrunc, dStats, st);
+}
+
+// ... over the handle's next set of intermediates, grown if need be (the kind's lock held); dXY null: the whole frame's cached packet list
+template <class K>
+int frameSet(typename K::Handle *m, const char *fn, const float cam[13], int resx, int resy, const int32_t *dXY, int np, const float *lights7, int nLights,
+			 const float ambient[3], uint8_t *frame, int pitch, uint8_t *bgrPackets, bool refl, int maxDepth, uint64_t *dTrunc, uint64_t *dStats, hipStream_t st) {
+	if(!dXY) { if(int rc = m->frameLists.get(resx, resy, &dXY, &np)) return rc; }
+	const bool bounce = refl && !maxDepth;
+	ShadeSets::Set *Wp = nullptr;
+	if(int rc = setsNext(m, np, nLights, bounce, false, st, &Wp)) return rc;
+	ShadeSets::Set &W = *Wp;
+	if(maxDepth) {
+		const size_t want = levelsBytes<typename K::BounceBufs>((size_t)np, nLights, maxDepth, refl);
+		if(int rc = levelsGrow(W, W.transp, W.transpBytes, want, want)) return rc;
+	}
+	typename K::Bufs B;
+	B.carve(W.base, (size_t)np);
+	typename K::BounceBufs RB;
+	if(bounce) RB.carve(W.bounce, (size_t)np, nLights);
+	const int rc = frameStages<K>(m, fn, cam, resx, resy, dXY, np, lights7, nLights, ambient, frame, pitch, bgrPackets, B, bounce ? &RB : nullptr, W.transp, refl, maxDepth, dTrunc, dStats, st);
+	return setDone(W, fn, rc, st);
+}
+
+// The bodies of the _dev and _packets_dev entry points once their arguments and the handle have been judged
+template <class K>
+int frameDev(typename K::Handle *m, const char *fn, const float cam[13], int resx, int resy, const float *lights7, int nLights, const float ambient[3], bool refl,
+			 int maxDepth, uint8_t *frame, int pitch, uint64_t *dTrunc, uint64_t *dStats, void *stream) {
+	DeviceGuard guard(m->device);
+	std::lock_guard<std::mutex> lock(K::mu(m));
+	return frameSet<K>(m, fn, cam, resx, resy, nullptr, 0, lights7, nLights, ambient, frame, pitch, nullptr, refl, maxDepth, dTrunc, dStats, (hipStream_t)stream);
+}
+template <class K>
+int framePacketsDev(typename K::Handle *m, const char *fn, const float cam[13], int resx, int resy, const int32_t *dPacketXY, int nPackets, const float *lights7,
+					int nLights, const float ambient[3], bool refl, int maxDepth, uint8_t *bgrPackets, uint64_t *dTrunc, uint64_t *dStats, void *stream) {
+	DeviceGuard guard(m->device);
+	std::lock_guard<std::mutex> lock(K::mu(m));
+	return frameSet<K>(m, fn, cam, resx, resy, dPacketXY, nPackets, lights7, nLights, ambient, nullptr, 0, bgrPackets, refl, maxDepth, dTrunc, dStats, (hipStream_t)stream);
+}
+
+// ... and of the _image ones: a whole frame into the caller's pitched host memory.  The arena holds, in this order, the packet list, the kind's
+// Bufs, its BounceBufs, the levels, the image and the truncation counter (truncated null: none).
+template <class K>
+int frameImage(typename K::Handle *m, const char *fn, const float cam[13], int resx, int resy, const float *lights7, int nLights, const float ambient[3], bool refl,
+			   int maxDepth, uint8_t *image, int pitch, uint64_t *truncated, uint64_t stats[4]) {
+	DeviceGuard guard(m->device);
+	HostCallScope hc(K::scene(m), fn);   // (a stream, counters and staging arena of the call's own; the scene handle only lends its free list)
+	if(hc.rc) return hc.rc;
+	if(int rc = hc.zeroStats()) return rc;
+	const int pw = (resx + 15) / 16, ph = (resy + 15) / 16, np = pw * ph;
+	const std::vector<int32_t> xy = frameGrid(pw, ph);
+	typedef HostCallScope H;
+	const bool bounce = refl && !maxDepth;
+	const size_t imgBytes = (size_t)pitch * resy, bufBytes = K::Bufs::bytes((size_t)np, nLights), bounceBytes = bounce ? K::BounceBufs::bytes((size_t)np, nLights) : 0,
+				 levelBytes = maxDepth ? levelsBytes<typename K::BounceBufs>((size_t)np, nLights, maxDepth, refl) : 0;
+	if(int rc = hc.reserve(H::pad(xy.size() * 4) + H::pad(bufBytes) + (bounce ? H::pad(bounceBytes) : 0) + (maxDepth ? H::pad(levelBytes) : 0) + H::pad(imgBytes + 4) +
+						   (truncated ? H::pad(8) : 0)))
+		return rc;
+	void *dXY = nullptr;
+	if(int rc = hc.put(&dXY, xy.data(), xy.size() * 4)) return rc;
+	typename K::Bufs W;
+	W.carve((char *)hc.carve(bufBytes), (size_t)np);
+	typename K::BounceBufs RB;
+	if(bounce) RB.carve((char *)hc.carve(bounceBytes), (size_t)np, nLights);
+	char *arena = maxDepth ? (char *)hc.carve(levelBytes) : nullptr;
+	uint8_t *dImg = (uint8_t *)hc.carve(imgBytes + 4);
+	uint64_t *dTrunc = truncated ? (uint64_t *)hc.carve(8) : nullptr;
+	if(dTrunc) HIP_TRY(hipMemsetAsync(dTrunc, 0, 8, hc.stream()));
+	{
+		std::lock_guard<std::mutex> lock(K::mu(m));
+		if(int rc = frameStages<K>(m, fn, cam, resx, resy, (const int32_t *)dXY, np, lights7, nLights, ambient, dImg, pitch, nullptr, W, bounce ? &RB : nullptr, arena, refl, maxDepth,
+								   dTrunc, hc.stats(), hc.stream()))
+			return rc;
+	}
+	HIP_TRY(hipMemcpy2DAsync(image, (size_t)pitch, dImg, (size_t)pitch, (size_t)resx * 3, (size_t)resy, hipMemcpyDeviceToHost, hc.stream()));
+	uint64_t got = 0;
+	if(truncated) { if(int rc = hc.get(&got, dTrunc, 8)) return rc; }
+	if(int rc = hc.finish(stats)) return rc;
+	if(truncated) *truncated += got;
 	return 0;
 }
 
@@ -293,12 +373,13 @@ int levelsStore(typename K::Handle *m, const char *fn, const float cam[13], int 
 	const uint64_t budget = std::max(m->levelBudget ? m->levelBudget : (uint64_t)SNAIL_MAT_LEVEL_BUDGET, one);
 	const int slice = (int)std::min<uint64_t>(budget / one, (uint64_t)np);   // output packets per slice
 	const size_t ns = (size_t)slice * q, n = (size_t)np * q;
-	typename K::Set *Wp = nullptr;
-	if(int rc = K::nextSet(m, (int)ns, nLights, st, &Wp)) return rc;
-	typename K::Set &W = *Wp;
+	typedef typename K::Handle::TileBufs TileBufs;
+	ShadeSets::Set *Wp = nullptr;
+	if(int rc = setsNext(m, (int)ns, nLights, false, false, st, &Wp)) return rc;
+	ShadeSets::Set &W = *Wp;
 	if(tiles) {   // the tile renderer's part for the WHOLE list
 		const size_t packets = std::max(W.tilesPackets, n);
-		if(int rc = levelsGrow(W, W.tiles, W.tilesPackets, packets, SnailMaterials::TileBufs::bytes(packets))) return rc;
+		if(int rc = levelsGrow(W, W.tiles, W.tilesPackets, packets, TileBufs::bytes(packets))) return rc;
 	}
 	{
 		const size_t want = std::max(W.transpBytes, levelsBytes<typename K::BounceBufs>(ns, nLights, maxDepth, refl));
@@ -311,7 +392,7 @@ int levelsStore(typename K::Handle *m, const char *fn, const float cam[13], int 
 	uint32_t *pst = !heat ? nullptr : dPacketStats ? dPacketStats : W.pstats;
 	typename K::Bufs B;
 	B.carve(W.base, ns);
-	SnailMaterials::TileBufs T;
+	TileBufs T;
 	if(tiles) T.carve(W.tiles, n);
 	int rc = 0;
 	const int32_t *list = dXY;
@@ -359,7 +440,7 @@ int levelsStore(typename K::Handle *m, const char *fn, const float cam[13], int 
 		const hipError_t e = hipGetLastError();
 		if(e != hipSuccess) { snail_set_error("%s: k_inst_store: %s", fn, hipGetErrorString(e)); rc = 100 + (int)e; }
 	}
-	return K::setDone(W, fn, rc, st);
+	return setDone(W, fn, rc, st);
 }
 #undef SNAIL_LEVELS_STORE
 
@@ -375,11 +456,12 @@ int tileRectsOk(const char *fn, const int32_t *coords, int nTiles) {
 	return 0;
 }
 
-// a tile list (nTiles > 0, rects judged) into the caller's `data` at `offsets`, through the set's ONE cached tile job
-template <class K>
+// a tile list (nTiles > 0, rects judged) into the caller's `data` at `offsets`, through the set's ONE cached tile job.  `store`: levelsStore<K>, or
+// matStoreStep (matShadeStore, the opaque stages), called with levelsStore's arguments; truncated null: a call without a truncation counter.
+template <class K, class Store>
 int renderTilesHost(typename K::Handle *m, const char *fn, const float cam[13], int resx, int resy, const int32_t *coords, const int64_t *offsets, int nTiles,
 					const float *lights7, int nLights, const float ambient[3], int flags, const float *tint, uint8_t *data, int maxDepth, uint64_t *truncated,
-					uint64_t stats[4], bool heat) {
+					uint64_t stats[4], bool heat, Store store) {
 	std::lock_guard<std::mutex> renderLock(m->renderMu);   // one cached tile job per set: its calls take turns
 	DeviceGuard guard(m->device);
 	HostCallScope hc(K::scene(m), fn);   // (a stream, counters and staging arena of the call's own; the scene handle only lends its free list)
@@ -388,29 +470,32 @@ int renderTilesHost(typename K::Handle *m, const char *fn, const float cam[13], 
 	InstTileJob &J = *m->tileJob;
 	if(int rc = buildInstTileJob(J, resx, resy, coords, nTiles)) return rc;
 	if(stats) { if(int rc = hc.zeroStats()) return rc; }
-	if(int rc = hc.reserve(HostCallScope::pad(8))) return rc;
-	uint64_t *dTrunc = (uint64_t *)hc.carve(8);
-	HIP_TRY(hipMemsetAsync(dTrunc, 0, 8, hc.stream()));
+	uint64_t *dTrunc = nullptr;
+	if(truncated) {
+		if(int rc = hc.reserve(HostCallScope::pad(8))) return rc;
+		dTrunc = (uint64_t *)hc.carve(8);
+		HIP_TRY(hipMemsetAsync(dTrunc, 0, 8, hc.stream()));
+	}
 	{
 		std::lock_guard<std::mutex> lock(K::mu(m));
-		if(int rc = levelsStore<K>(m, fn, cam, resx, resy, J.dXY, J.nPackets, lights7, nLights, ambient, flags, tint, nullptr, &J, maxDepth, dTrunc, stats ? hc.stats() : nullptr,
-								   hc.stream(), heat))
+		if(int rc = store(m, fn, cam, resx, resy, J.dXY, J.nPackets, lights7, nLights, ambient, flags, tint, nullptr, &J, maxDepth, dTrunc, stats ? hc.stats() : nullptr, hc.stream(),
+						  heat, nullptr))
 			return rc;
 	}
 	HIP_TRY(hipMemcpyAsync(J.hPinned, J.dOut, J.planarBytes, hipMemcpyDeviceToHost, hc.stream()));
 	uint64_t got = 0;
-	if(int rc = hc.get(&got, dTrunc, 8)) return rc;
+	if(truncated) { if(int rc = hc.get(&got, dTrunc, 8)) return rc; }
 	if(int rc = hc.finish(stats)) return rc;
-	*truncated += got;
+	if(truncated) *truncated += got;
 	for(int k = 0; k < nTiles; k++)
 		memcpy(data + offsets[k], J.hPinned + J.compactOff[(size_t)k], (size_t)3 * coords[(size_t)k * 4 + 2] * coords[(size_t)k * 4 + 3]);
 	return 0;
 }
 
-// a whole frame into the caller's pitched `image`
-template <class K>
+// a whole frame into the caller's pitched `image`, packet-major bytes from `store` first
+template <class K, class Store>
 int renderFrameHost(typename K::Handle *m, const char *fn, const float cam[13], int resx, int resy, const float *lights7, int nLights, const float ambient[3], int flags,
-					uint8_t *image, int pitch, int maxDepth, uint64_t *truncated, uint64_t stats[4], bool heat) {
+					uint8_t *image, int pitch, int maxDepth, uint64_t *truncated, uint64_t stats[4], bool heat, Store store) {
 	DeviceGuard guard(m->device);
 	HostCallScope hc(K::scene(m), fn);
 	if(hc.rc) return hc.rc;
@@ -418,26 +503,26 @@ int renderFrameHost(typename K::Handle *m, const char *fn, const float cam[13], 
 	const int np = ((resx + 15) / 16) * ((resy + 15) / 16);
 	const size_t row = (size_t)resx * 3;
 	typedef HostCallScope H;
-	if(int rc = hc.reserve(H::pad((size_t)np * 768) + H::pad(row * resy + 4) + H::pad(8))) return rc;
+	if(int rc = hc.reserve(H::pad((size_t)np * 768) + H::pad(row * resy + 4) + (truncated ? H::pad(8) : 0))) return rc;
 	uint8_t *bgr = (uint8_t *)hc.carve((size_t)np * 768), *dImg = (uint8_t *)hc.carve(row * resy + 4);
-	uint64_t *dTrunc = (uint64_t *)hc.carve(8);
-	HIP_TRY(hipMemsetAsync(dTrunc, 0, 8, hc.stream()));
+	uint64_t *dTrunc = truncated ? (uint64_t *)hc.carve(8) : nullptr;
+	if(dTrunc) HIP_TRY(hipMemsetAsync(dTrunc, 0, 8, hc.stream()));
 	{
 		std::lock_guard<std::mutex> lock(K::mu(m));
 		const int32_t *dXY = nullptr;
 		int n = 0;
-		if(int rc = K::frameList(m, resx, resy, &dXY, &n)) return rc;
+		if(int rc = m->frameLists.get(resx, resy, &dXY, &n)) return rc;
 		// (a heat frame's packets carry no tint and no planes: their bytes come from k_heat_store, which k_heat_colours + k_inst_store equal byte for byte)
-		if(int rc = levelsStore<K>(m, fn, cam, resx, resy, dXY, np, lights7, nLights, ambient, flags, nullptr, bgr, nullptr, maxDepth, dTrunc, stats ? hc.stats() : nullptr, hc.stream(), heat))
+		if(int rc = store(m, fn, cam, resx, resy, dXY, np, lights7, nLights, ambient, flags, nullptr, bgr, nullptr, maxDepth, dTrunc, stats ? hc.stats() : nullptr, hc.stream(), heat, nullptr))
 			return rc;
 		// (under the lock: the cached frame list may be dropped by a later call, which first waits for everything enqueued)
 		if(int rc = snail_packets_bgr_to_frame_dev(dXY, np, resx, resy, bgr, dImg, (int)row, hc.stream())) return rc;
 	}
 	HIP_TRY(hipMemcpy2DAsync(image, (size_t)pitch, dImg, row, row, (size_t)resy, hipMemcpyDeviceToHost, hc.stream()));
 	uint64_t got = 0;
-	if(int rc = hc.get(&got, dTrunc, 8)) return rc;
+	if(truncated) { if(int rc = hc.get(&got, dTrunc, 8)) return rc; }
 	if(int rc = hc.finish(stats)) return rc;
-	*truncated += got;
+	if(truncated) *truncated += got;
 	return 0;
 }
 

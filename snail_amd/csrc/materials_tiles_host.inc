@@ -1,5 +1,6 @@
 // materials_tiles_host.inc -- host side of the tile renderer of full-shaded plain scenes (include/snail_materials_tiles.h); included by
-// snail_hip.hip after materials_host.inc.  RenderTask::Work (src/render.cpp:47-211) around the staged pipeline of materials_host.inc:
+// snail_hip.hip after materials_host.inc.  The host calls are renderTilesHost / renderFrameHost of materials_levels_host.inc with matShadeStore as
+// their store step (matStoreStep).  RenderTask::Work (src/render.cpp:47-211) around the staged pipeline of materials_host.inc:
 //   [k_inst_aa_packets: the four double-resolution packets of every packet]  ->  the scene's primary walk into hit distances (depth shading) or
 //   matShade with float colours (k_mat_colour / k_mat_colour_blend)  ->  k_inst_store: reduction, tint, ConvColor, packet-major bytes or the
 //   tiles' planes.
@@ -36,9 +37,9 @@ int matShadeStore(SnailMaterials *m, const char *fn, const float cam[13], int re
 	const size_t n = aa ? (size_t)np * 4 : (size_t)np;
 	const int rx = aa ? resx * 2 : resx, ry = aa ? resy * 2 : resy;
 	const int nl = depth ? 0 : nLights;
-	SnailMaterials::Set *Wp = nullptr;
-	if(int rc = matNextSet(m, (int)n, nl, refl, true, st, &Wp)) return rc;
-	SnailMaterials::Set &W = *Wp;
+	ShadeSets::Set *Wp = nullptr;
+	if(int rc = setsNext(m, (int)n, nl, refl, true, st, &Wp)) return rc;
+	ShadeSets::Set &W = *Wp;
 	SnailMaterials::Bufs B;
 	B.carve(W.base, n);
 	SnailMaterials::BounceBufs RB;
@@ -87,9 +88,15 @@ int matShadeStore(SnailMaterials *m, const char *fn, const float cam[13], int re
 		const hipError_t e = hipGetLastError();
 		if(e != hipSuccess) { snail_set_error("%s: k_inst_store: %s", fn, hipGetErrorString(e)); rc = 100 + (int)e; }
 	}
-	return matSetDone(W, fn, rc, st);
+	return setDone(W, fn, rc, st);
 }
 #undef SNAIL_MAT_STORE
+
+// ... as the store step of renderTilesHost / renderFrameHost (materials_levels_host.inc), which hand it levelsStore's arguments: the opaque stages
+// have no levels, truncation counter, heat mode or per-packet counters
+const auto matStoreStep = [](SnailMaterials *m, const char *fn, const float cam[13], int resx, int resy, const int32_t *dXY, int np, const float *lights7, int nLights,
+							 const float ambient[3], int flags, const float *tint, uint8_t *bgrPackets, const InstTileJob *J, int, uint64_t *, uint64_t *dStats, hipStream_t st,
+							 bool, uint32_t *) { return matShadeStore(m, fn, cam, resx, resy, dXY, np, lights7, nLights, ambient, flags, tint, bgrPackets, J, dStats, st); };
 
 } // namespace
 
@@ -104,11 +111,10 @@ int snail_materials_frame_packets_dev(SnailMaterials *m, const float cam[13], in
 	if(nPackets > 0 && (!bgrPackets || ((unsigned long long)bgrPackets & 3))) { snail_set_error("%s: null or unaligned output", fn); return 1; }
 	if(int rc = checkMaterials(m, fn)) return rc;
 	if(nPackets <= 0) return 0;
+	if(!tint && !(flags & (SNAIL_RENDER_DEPTH | SNAIL_RENDER_AA4)))   // the lit packets as they are: the merged path, bytes from k_mat_final / k_mat_final_blend
+		return framePacketsDev<MatLevels>(m, fn, cam, resx, resy, dPacketXY, nPackets, lights7, nLights, ambient, (flags & SNAIL_RENDER_REFLECTIONS) != 0, 0, bgrPackets, nullptr, dStats, stream);
 	DeviceGuard guard(m->device);
 	SNAIL_LOCK(m->scene);
-	if(!tint && !(flags & (SNAIL_RENDER_DEPTH | SNAIL_RENDER_AA4)))   // the lit packets as they are: the merged path, bytes from k_mat_final / k_mat_final_blend
-		return matShadeDev(m, fn, cam, resx, resy, dPacketXY, nPackets, lights7, nLights, ambient, nullptr, 0, bgrPackets, dStats, (hipStream_t)stream,
-						   (flags & SNAIL_RENDER_REFLECTIONS) != 0);
 	return matShadeStore(m, fn, cam, resx, resy, dPacketXY, nPackets, lights7, nLights, ambient, flags, tint, bgrPackets, nullptr, dStats, (hipStream_t)stream);
 }
 
@@ -117,33 +123,10 @@ int snail_materials_render_tiles(SnailMaterials *m, const float cam[13], int res
 	const char *fn = "snail_materials_render_tiles";
 	if(int rc = matTilesArgsOk(fn, cam, resx, resy, lights7, nLights, ambient, flags, tint)) return rc;
 	if(nTiles > 0 && (!coords || !offsets || !data)) { snail_set_error("%s: null buffer", fn); return 1; }
-	for(int k = 0; k < nTiles; k++) {
-		const long long x = coords[(size_t)k * 4 + 0], y = coords[(size_t)k * 4 + 1], w = coords[(size_t)k * 4 + 2], hh = coords[(size_t)k * 4 + 3];
-		if(w <= 0 || hh <= 0 || x < 0 || y < 0 || x + w > (1 << 24) || y + hh > (1 << 24)) {
-			snail_set_error("%s: tile %d: bad rect %lld,%lld %lldx%lld", fn, k, x, y, w, hh);
-			return 1;
-		}
-	}
+	if(int rc = tileRectsOk(fn, coords, nTiles)) return rc;
 	if(int rc = checkMaterials(m, fn)) return rc;
 	if(nTiles <= 0) return 0;
-	std::lock_guard<std::mutex> renderLock(m->renderMu);   // one cached tile job per set: its calls take turns
-	DeviceGuard guard(m->device);
-	HostCallScope hc(m->scene, fn);
-	if(hc.rc) return hc.rc;
-	if(!m->tileJob) m->tileJob = new InstTileJob();
-	InstTileJob &J = *m->tileJob;
-	if(int rc = buildInstTileJob(J, resx, resy, coords, nTiles)) return rc;
-	if(stats) { if(int rc = hc.zeroStats()) return rc; }
-	{
-		SNAIL_LOCK(m->scene);
-		if(int rc = matShadeStore(m, fn, cam, resx, resy, J.dXY, J.nPackets, lights7, nLights, ambient, flags, tint, nullptr, &J, stats ? hc.stats() : nullptr, hc.stream()))
-			return rc;
-	}
-	HIP_TRY(hipMemcpyAsync(J.hPinned, J.dOut, J.planarBytes, hipMemcpyDeviceToHost, hc.stream()));
-	if(int rc = hc.finish(stats)) return rc;
-	for(int k = 0; k < nTiles; k++)
-		memcpy(data + offsets[k], J.hPinned + J.compactOff[(size_t)k], (size_t)3 * coords[(size_t)k * 4 + 2] * coords[(size_t)k * 4 + 3]);
-	return 0;
+	return renderTilesHost<MatLevels>(m, fn, cam, resx, resy, coords, offsets, nTiles, lights7, nLights, ambient, flags, tint, data, 0, nullptr, stats, false, matStoreStep);
 }
 
 int snail_materials_render_frame(SnailMaterials *m, const float cam[13], int resx, int resy, const float *lights7, int nLights, const float ambient[3], int flags,
@@ -151,29 +134,10 @@ int snail_materials_render_frame(SnailMaterials *m, const float cam[13], int res
 	const char *fn = "snail_materials_render_frame";
 	if(int rc = matTilesArgsOk(fn, cam, resx, resy, lights7, nLights, ambient, flags, nullptr)) return rc;
 	if(!image || pitch < resx * 3) { snail_set_error("%s: null image or a pitch below 3 * resx", fn); return 1; }
-	if(!(flags & (SNAIL_RENDER_AA4 | SNAIL_RENDER_DEPTH)))   // exactly snail_materials_bounce_image
-		return matFrameImage(fn, m, cam, resx, resy, lights7, nLights, ambient, (flags & SNAIL_RENDER_REFLECTIONS) != 0, image, pitch, stats);
 	if(int rc = checkMaterials(m, fn)) return rc;
-	DeviceGuard guard(m->device);
-	HostCallScope hc(m->scene, fn);
-	if(hc.rc) return hc.rc;
-	if(stats) { if(int rc = hc.zeroStats()) return rc; }
-	const int np = ((resx + 15) / 16) * ((resy + 15) / 16);
-	const size_t row = (size_t)resx * 3;
-	typedef HostCallScope H;
-	if(int rc = hc.reserve(H::pad((size_t)np * 768) + H::pad(row * resy + 4))) return rc;
-	uint8_t *bgr = (uint8_t *)hc.carve((size_t)np * 768), *dImg = (uint8_t *)hc.carve(row * resy + 4);
-	{
-		SNAIL_LOCK(m->scene);
-		const int32_t *dXY = nullptr;
-		int n = 0;
-		if(int rc = matFrameList(m, resx, resy, &dXY, &n)) return rc;
-		if(int rc = matShadeStore(m, fn, cam, resx, resy, dXY, np, lights7, nLights, ambient, flags, nullptr, bgr, nullptr, stats ? hc.stats() : nullptr, hc.stream())) return rc;
-		// (under mu: the cached frame list may be dropped by a later call, which first waits for everything enqueued)
-		if(int rc = snail_packets_bgr_to_frame_dev(dXY, np, resx, resy, bgr, dImg, (int)row, hc.stream())) return rc;
-	}
-	HIP_TRY(hipMemcpy2DAsync(image, (size_t)pitch, dImg, row, row, (size_t)resy, hipMemcpyDeviceToHost, hc.stream()));
-	return hc.finish(stats);
+	if(!(flags & (SNAIL_RENDER_AA4 | SNAIL_RENDER_DEPTH)))   // exactly snail_materials_bounce_image
+		return frameImage<MatLevels>(m, fn, cam, resx, resy, lights7, nLights, ambient, (flags & SNAIL_RENDER_REFLECTIONS) != 0, 0, image, pitch, nullptr, stats);
+	return renderFrameHost<MatLevels>(m, fn, cam, resx, resy, lights7, nLights, ambient, flags, image, pitch, 0, nullptr, stats, false, matStoreStep);
 }
 
 } // extern "C"

@@ -128,7 +128,7 @@ __global__ __launch_bounds__(64) void k_mat_colour_transp(TranspArgs T) {
 	matFinal<SRC_MIRROR, false>(T.m);
 }
 // (this stage and k_mat_truncated index the level's buffers by the list position li, as matPacket<SRC_MIRROR> does: the frames always run over a
-// packet list -- matTranspDev makes the whole frame's when the caller brings none -- so the primary level's P.pidx is li as well)
+// packet list -- frameSet takes the whole frame's when the caller brings none -- so the primary level's P.pidx is li as well)
 __global__ __launch_bounds__(64) void k_mat_blend_transp(TranspArgs T) {
 	const int lane = threadIdx.x & 63;
 	const int li = (int)blockIdx.x;

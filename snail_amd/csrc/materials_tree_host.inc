@@ -1,6 +1,6 @@
 // materials_tree_host.inc -- the C-ABI of include/snail_materials_tree.h: the transparency continuation together with the mirrored bounce, the
 // tile renderer, 4x antialiasing, depth shading and the tint; included by snail_hip.hip after materials_transparency_host.inc.  The frames are
-// the level driver's (materials_levels_host.inc) for a plain scene (MatLevels, materials_transparency_host.inc): shadeLevels with chain B under
+// the level driver's (materials_levels_host.inc) for a plain scene (MatLevels, materials_host.inc): shadeLevels with chain B under
 // SNAIL_RENDER_REFLECTIONS, run by levelsStore over a packet list in slices that keep the levels within the set's budget.
 
 namespace {
@@ -77,7 +77,7 @@ int snail_materials_tree_render_tiles(SnailMaterials *m, const float cam[13], in
 	if(int rc = tileRectsOk(fn, coords, nTiles)) return rc;
 	if(int rc = checkMaterialsAny(m, fn)) return rc;
 	if(nTiles <= 0) return 0;
-	return renderTilesHost<MatLevels>(m, fn, cam, resx, resy, coords, offsets, nTiles, lights7, nLights, ambient, flags, tint, data, maxDepth, truncated, stats, false);
+	return renderTilesHost<MatLevels>(m, fn, cam, resx, resy, coords, offsets, nTiles, lights7, nLights, ambient, flags, tint, data, maxDepth, truncated, stats, false, levelsStore<MatLevels>);
 }
 
 int snail_materials_tree_render_frame(SnailMaterials *m, const float cam[13], int resx, int resy, const float *lights7, int nLights, const float ambient[3], int flags,
@@ -86,7 +86,7 @@ int snail_materials_tree_render_frame(SnailMaterials *m, const float cam[13], in
 	if(int rc = matTreeArgsOk(fn, cam, resx, resy, lights7, nLights, ambient, flags, nullptr, maxDepth, truncated)) return rc;
 	if(!image || pitch < resx * 3) { snail_set_error("%s: null image or a pitch below 3 * resx", fn); return 1; }
 	if(int rc = checkMaterialsAny(m, fn)) return rc;
-	return renderFrameHost<MatLevels>(m, fn, cam, resx, resy, lights7, nLights, ambient, flags, image, pitch, maxDepth, truncated, stats, false);
+	return renderFrameHost<MatLevels>(m, fn, cam, resx, resy, lights7, nLights, ambient, flags, image, pitch, maxDepth, truncated, stats, false, levelsStore<MatLevels>);
 }
 
 int snail_materials_set_level_budget(SnailMaterials *m, uint64_t bytes) {

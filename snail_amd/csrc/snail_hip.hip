@@ -1826,12 +1826,13 @@ int snail_account_primary(SnailScene *s, const float cam[13], int resx, int resy
 #include "bvh_fast_batch.inc"
 #include "wide_host.inc"
 #include "render_host.inc"
+#include "shading_sets_host.inc"
 #include "instances_host.inc"
 #include "instances_tiles_host.inc"
 #include "heatmap_host.inc"
+#include "materials_levels_host.inc"
 #include "materials_host.inc"
 #include "materials_tiles_host.inc"
-#include "materials_levels_host.inc"
 #include "materials_transparency_host.inc"
 #include "materials_tree_host.inc"
 #include "materials_heat_host.inc"
