@@ -80,7 +80,22 @@ void snail_scene_destroy(SnailScene *);
  * triangles collapsed into leaves -- in the reference's node / triangle record formats, built and kept on `device`; the traversal
  * entry points below work on it unchanged.  Triangle order (triId) and tree shape differ from BVH::Construct: hit distances agree
  * with the SAH tree's except where the reference's order-dependent packet culls differ; perm (optional, nTris) maps triId ->
- * input triangle; *build_ms (optional) = device time of the build.  tri_verts: host, nTris x (v0,v1,v2). */
+ * input triangle; *build_ms (optional) = device time of the build.  tri_verts: host, nTris x (v0,v1,v2).
+ * The tree is a function of the input alone (tests/lbvh_ref.py restates it, byte for byte):
+ *   key    10 bits per axis of the triangle's box centre, q = min(t * 1024, 1023) with t = (centre - scene min) / scene extent clamped
+ *          to [0, 1] (0 on an axis without extent), interleaved x, y, z from the top; ties -- one cell, identical triangles -- are
+ *          broken by the input index, so triId order within a cell is input order;
+ *   slots  2 * nTris - 1 node records, the root in slot 0; Karras' internal node i (the root is 0) puts its children in slots 1 + 2i
+ *          and 2 + 2i; a range of <= maxLeafTris triangles is one leaf (the root itself when nTris <= maxLeafTris), and the slots below
+ *          it stay unused: empty leaves (zero box, no triangles) that no walk reaches, so that a download is a valid input of
+ *          snail_scene_create; a node's axis is that of the larger separation of its children's box centres, firstNode = 0 when the
+ *          child in slot 1 + 2i comes first along +axis, else 1;
+ *   flags  snail_scene_flags reports what snail_scene_create reports for the downloaded arrays (fastOK = 0 for a zero-area triangle,
+ *          a record or a box bound beyond its magnitude limit -- on every path, a scene that is a single leaf included; nestedOK = 1);
+ *   a non-finite vertex is not refused: fminf / fmaxf keep a NaN out of every box and bound (the triangle's record keeps it), an
+ *          infinite coordinate gives the boxes above it an infinite bound and puts every centre into cell 0 on that axis; either way
+ *          a handle comes back with fastOK = 0 and its frames are the exact walk's of that tree.
+ * NULL tri_verts, nTris <= 0 or maxLeafTris outside 1..64: NULL and an error text, before any device work. */
 SnailScene *snail_scene_create_lbvh(const float *tri_verts, int nTris, int device, int maxLeafTris, int32_t *perm, float *build_ms);
 /* Copy a scene's node (nNodes x 32 B) and / or triangle (nTris x 64 B) records back to the host (either may be NULL). */
 int snail_scene_download(const SnailScene *, void *nodes32, void *tris64);

@@ -159,7 +159,7 @@ __global__ void k_refit(int n, const int2 *children, const int *parentInt, const
 	}
 }
 
-// every slot starts as an empty leaf (no triangles, inverted box): the slots below a collapsed subtree are never referenced, but the
+// every slot starts as an empty leaf (no triangles, the zero box): the slots below a collapsed subtree are never referenced, but the
 // array stays a valid input for snail_scene_create should a caller download and re-upload it
 __global__ void k_fill_empty(float *nodes, int nSlots) {
 	const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
@@ -167,6 +167,13 @@ __global__ void k_fill_empty(float *nodes, int nSlots) {
 	float4 *o = (float4 *)(nodes + (size_t)i * 8);
 	o[0] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
 	o[1] = make_float4(0.0f, 0.0f, __uint_as_float(0x80000000u), __int_as_float(0));
+}
+
+// the conditions snail_scene_create puts on a node's box before it allows the fast arithmetic modes: every emitted record passes through here
+__host__ __device__ __forceinline__ bool boxSane(const Box &b) {
+	bool ok = true;
+	for(int k = 0; k < 3; k++) ok = ok && fabsf(b.mn[k]) <= 1.0e9f && fabsf(b.mx[k]) <= 1.0e9f && b.mn[k] <= b.mx[k];
+	return ok;
 }
 
 __device__ __forceinline__ void writeNode(float *nodes, int slot, const Box &b, unsigned sub, int aux) {
@@ -184,7 +191,10 @@ __global__ void k_emit(int n, int maxLeaf, const int2 *children, const int2 *ran
 	const int2 r = range[i];
 	const int size = r.y - r.x + 1;
 	if(size <= maxLeaf) {
-		if(i == 0) { writeNode(nodes, 0, intBox[0], 0x80000000u | (unsigned)r.x, size); *depthOut = 0; }
+		if(i == 0) { // the whole scene is one leaf
+			writeNode(nodes, 0, intBox[0], 0x80000000u | (unsigned)r.x, size); *depthOut = 0;
+			if(!boxSane(intBox[0])) atomicAnd(flags, 0);
+		}
 		return;
 	}
 	// slot and depth of this node: walk up (inner ancestors only by construction)
@@ -203,8 +213,7 @@ __global__ void k_emit(int n, int maxLeaf, const int2 *children, const int2 *ran
 	const int firstNode = sep[axis] >= 0.0f ? 0 : 1;
 	const Box &bi = intBox[i];
 	writeNode(nodes, slot, bi, (unsigned)(1 + 2 * i), axis | (firstNode << 16));
-	bool ok = true;
-	for(int k = 0; k < 3; k++) ok = ok && fabsf(bi.mn[k]) <= 1.0e9f && fabsf(bi.mx[k]) <= 1.0e9f && bi.mn[k] <= bi.mx[k];
+	bool ok = boxSane(bi);
 	for(int side = 0; side < 2; side++) {
 		const int ch = side ? c.y : c.x;
 		const Box &cb = side ? br : bl;
@@ -216,7 +225,7 @@ __global__ void k_emit(int n, int maxLeaf, const int2 *children, const int2 *ran
 		}
 		if(leaf) {
 			writeNode(nodes, 1 + 2 * i + side, cb, 0x80000000u | (unsigned)first, count);
-			for(int k = 0; k < 3; k++) ok = ok && fabsf(cb.mn[k]) <= 1.0e9f && fabsf(cb.mx[k]) <= 1.0e9f && cb.mn[k] <= cb.mx[k];
+			ok = ok && boxSane(cb);
 			atomicMax(depthOut, depth + 1);
 		}
 	}
@@ -282,9 +291,11 @@ int buildLbvhDevice(const float *hostVerts, int n, int maxLeaf, uint4 **outNodes
 	if(S.get(&dTmp, tmpBytes)) { snail_set_error("snail_scene_create_lbvh: device allocation failed"); return fail(2); }
 	LBVH_TRY(rocprim::radix_sort_keys(dTmp, tmpBytes, dKeys, dKeysSorted, (size_t)n, 0, 64, 0));
 	hipLaunchKernelGGL(k_records, dim3(B), dim3(T), 0, 0, dVerts, n, dKeysSorted, (float *)dTris, dPerm, dLeafBox, dFlags);
+	bool rootOK = true;
 	if(n == 1) { // a single leaf
 		Box b;
 		LBVH_TRY(hipMemcpy(&b, dLeafBox, sizeof(Box), hipMemcpyDeviceToHost));
+		rootOK = boxSane(b);
 		float node[8] = {b.mn[0], b.mn[1], b.mn[2], b.mx[0], b.mx[1], b.mx[2], 0.0f, 0.0f};
 		const unsigned sub = 0x80000000u; const int aux = 1;
 		memcpy(&node[6], &sub, 4); memcpy(&node[7], &aux, 4);
@@ -305,7 +316,7 @@ int buildLbvhDevice(const float *hostVerts, int n, int maxLeaf, uint4 **outNodes
 	LBVH_TRY(hipMemcpy(flags, dFlags, sizeof(flags), hipMemcpyDeviceToHost));
 	if(permHost) LBVH_TRY(hipMemcpy(permHost, dPerm, (size_t)n * 4, hipMemcpyDeviceToHost));
 #undef LBVH_TRY
-	*outNodes = dNodes; *outTris = dTris; *fastOK = flags[0]; *depth = flags[1];
+	*outNodes = dNodes; *outTris = dTris; *fastOK = flags[0] && rootOK; *depth = flags[1];
 	if(buildMs) *buildMs = ms;
 	return 0;
 }

@@ -1172,26 +1172,9 @@ def test_gpu_lbvh_builder_option(torch_mod, name, max_leaf):
     want_tris = HostBVH.triangles(np.asarray(tv, dtype=np.float32).reshape(-1, 3, 3)[perm])
     for f in ("a", "ba", "ca", "t0", "it0", "plane"):
         util.assert_bit_equal(tris[f], want_tris[f], "triangle record field " + f)
-    # (1) topology
-    covered = np.zeros(n, dtype=np.int32)
-    stack, max_depth, n_leaves = [(0, 0)], 0, 0
-    while stack:
-        i, d = stack.pop()
-        nd = nodes[i]
-        if nd["sub"] & 0x80000000:
-            first, count = int(nd["sub"] & 0x7fffffff), int(nd["aux"])
-            assert 1 <= count <= max_leaf and first + count <= n
-            covered[first:first + count] += 1
-            tb = np.asarray(tv, dtype=np.float32).reshape(-1, 3, 3)[perm[first:first + count]].reshape(-1, 3)
-            assert (tb.min(axis=0) >= nd["bmin"]).all() and (tb.max(axis=0) <= nd["bmax"]).all()
-            max_depth = max(max_depth, d); n_leaves += 1
-        else:
-            c = int(nd["sub"])
-            assert 0 < c and c + 1 < len(nodes) and (nd["aux"] & 0xffff) <= 2 and (nd["aux"] >> 16) <= 1
-            for k in (0, 1):
-                assert (nodes[c + k]["bmin"] >= nd["bmin"]).all() and (nodes[c + k]["bmax"] <= nd["bmax"]).all()
-                stack.append((c + k, d + 1))
-    assert (covered == 1).all() and max_depth == sc.bvh.depth
+    # (1) topology: the validity walk of tests/lbvh_ref.py (it also holds the records to its own restatement of ComputeData)
+    from tests import lbvh_ref
+    lbvh_ref.check_tree(nodes, tris, perm, tv, max_leaf, sc.bvh.depth)
     # (2) the oracle walks the same tree
     osc2 = O.OracleScene.__new__(O.OracleScene)
     osc2.tris = np.ascontiguousarray(tris.view(O.TRI_DTYPE)); osc2.nodes = np.ascontiguousarray(nodes.view(O.NODE_DTYPE)); osc2.depth = sc.bvh.depth; osc2.perm = perm
